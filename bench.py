@@ -19,9 +19,20 @@ RCCL sum-reduce of sufficient statistics per step (values_amd.dist.ensemble_unce
 --config C4: HRNet-W18 at 1024x512, 8 TTA views per image (BASELINE config 4), images sharded over the ranks.
 --config C5: 128^3 images through the sliding-window path (64^3 patches, overlap 0.5, T = 20; BASELINE config 5).
 
-Rank 0 prints ONE JSON line; it carries `roofline` (dominant kernel, live HIP-event timing, algorithmic FLOPs and
-bytes, the binding roof named by max(flops / peak, bytes / bandwidth)) and, at N=1, `cpu_baseline` (the oracle =
-PyTorch-CPU restatement of test_3D.py's float64 loop, timed on this host on a bounded sample).
+A plain run sets up, warms up (W steps), times ONE region of exactly K steps, writes the last step's outputs if
+--dump-outputs is given, and prints the line: `value` = units per second over those K steps, `ms_per_step` = the region's
+time / K.  `roofline` and `cpu_baseline` are null there.
+
+--full adds everything else the bench measures, after the timed steps: the K-step region repeated (--repeats, default 5;
+--min-gpu-seconds, default 4; `value` = the median region), `roofline` (dominant kernel, live HIP-event timing, algorithmic
+FLOPs and bytes, the binding roof named by max(flops / peak, bytes / bandwidth)), at N=1 `cpu_baseline` (the oracle =
+PyTorch-CPU restatement of test_3D.py's float64 loop, timed on this host on a bounded sample), and the side objects of
+each config (C2: storage16, value_at_64, latency_single_volume, no_gather at N > 1; C4: eager).  The --no-* options
+switch single legs of --full off.
+
+--dump-outputs DIR: rank 0 writes the arrays its last timed step returned (the dict a caller of the timed path receives)
+as DIR/<name>.npy, float32 (float64 stays float64), at most 64 MB in all: an array over its share is written as a fixed
+sample (seeded indices, the same for the same arguments), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -441,9 +452,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C2", choices=("C2", "C3", "C4", "C5"))
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = their median")
-    ap.add_argument("--min-gpu-seconds", type=float, default=4.0,
-                    help="C2: keep adding timed regions of --steps steps until they add up to this much GPU time")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (repeated regions, roofline, CPU baseline, the configs' side objects); "
+                         "off: set up, warm up, time --steps steps, dump, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; value = their median (default 1, with --full 5)")
+    ap.add_argument("--min-gpu-seconds", type=float, default=None,
+                    help="C2: keep adding timed regions of --steps steps until they add up to this much GPU time (default 0, "
+                         "with --full 4)")
     ap.add_argument("--volumes", type=int, default=None, help="units per GPU per step (C2: 32 volumes, C3: 16, C4: 4 images)")
     ap.add_argument("--T", type=int, default=10)
     ap.add_argument("--size", type=int, default=64)
@@ -472,8 +490,14 @@ def main():
     ap.add_argument("--roofline-reps", type=int, default=8, help="C4 --roofline-only: timed forwards (a second profile with another count "
                     "shows which kernels of the trace belong to the model's one-off setup: their call counts do not move)")
     ap.add_argument("--pcie", action="store_true", help="also time the host-inclusive variant (pinned host input, maps copied back)")
-    ap.add_argument("--detail", type=str, default=None, help="write the per-kernel breakdown JSON here")
+    ap.add_argument("--detail", type=str, default=None, help="(--full) write the per-kernel breakdown JSON of the roofline leg here")
     args = ap.parse_args()
+    if args.detail and not (args.full and not args.no_roofline):
+        ap.error("--detail comes from the roofline leg: add --full (and drop --no-roofline)")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.min_gpu_seconds is None:
+        args.min_gpu_seconds = 4.0 if args.full else 0.0
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -548,6 +572,47 @@ def summarise(times, units_per_region, steps):
                         "value_first_region": round(units_per_region / times[0], 3)}}
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6       # under 64 MB in either unit
+DUMP_SEED = 20240613
+
+
+def dump_outputs(args, rank, out):
+    """--dump-outputs: the arrays of `out` (what the last timed step returned: a dict of device tensors, nested dicts / lists
+    walked with '.'-joined names) as <dir>/<name>.npy on rank 0.  float64 stays float64, everything else is written as
+    float32.  Each array gets an equal share of DUMP_BUDGET_BYTES; a larger one is written as the flat elements at sorted indices
+    drawn without replacement by numpy's generator seeded with (DUMP_SEED, element count): the same sample in every run."""
+    if not args.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            arrays[name] = v
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{name}.{k}" if name else str(k), x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{name}.{i}" if name else str(i), x)
+    walk("", out)
+    if not arrays:
+        raise SystemExit("bench.py --dump-outputs: the timed step returned no arrays")
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // len(arrays)     # 4 KB per file covers the .npy header
+    for name, t in sorted(arrays.items()):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        n = share // (8 if dt == torch.float64 else 4)
+        flat = t.detach().reshape(-1)
+        if flat.numel() > n:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, flat.numel()]).choice(flat.numel(), size=n, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].to(dt).cpu().numpy()
+        else:
+            a = t.detach().to(dt).cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, name.replace("/", "_") + ".npy"), a)
+
+
 def run_c2(args, world, rank, dev, barrier, reduce_max):
     import torch
     from values_amd import UNet3D, predict_uncertainty
@@ -572,14 +637,18 @@ def run_c2(args, world, rank, dev, barrier, reduce_max):
         from values_amd import GraphedPredictor
         gp = GraphedPredictor([model], tuple(x.shape), n_pred=T)
 
+    last = {}
+
     def step(i):
         out = gp(x, seed=i) if gp is not None else predict_uncertainty([model], x, n_pred=T, seeds=[i], range_check="off")
+        last["out"] = out
         return pipe.submit(out)
 
     times = timed_regions(step, pipe.flush, barrier, args.steps, args.warmup, max(1, args.repeats), reduce_max,
                           min_seconds=args.min_gpu_seconds)
+    dump_outputs(args, rank, last.pop("out", None))
     side = None
-    if gather:
+    if gather and args.full:
         # side number: the same steps with the maps left on their ranks (what the gather costs is value vs this)
         local = MapGatherPipeline(1, rank, depth=2)
 
@@ -589,7 +658,7 @@ def run_c2(args, world, rank, dev, barrier, reduce_max):
     model.check_range()      # the fp16-range word keeps the running maximum over every step above
 
     st16 = None
-    if (args.storage16 or world == 1) and not args.no_storage16 and not args.graph:
+    if args.full and (args.storage16 or world == 1) and not args.no_storage16 and not args.graph:
         try:
             # opt-in reduced-storage throughput mode: never `value` (it cannot meet the 1e-4 parity of the maps); what it buys and
             # what it costs, measured on the same volumes and dropout seeds as the default path
@@ -656,7 +725,7 @@ def run_c2(args, world, rank, dev, barrier, reduce_max):
     # volumes per GPU -- the 8^3 / 4^3 layers' launches amortise over twice the samples.  Workspace 47 MB per sample:
     # 640 samples = 30 GB + 1.3 GB of logits, of the 288 GB.
     at64 = None
-    if world == 1 and V == 32 and not args.no_batch64 and gp is None:
+    if args.full and world == 1 and V == 32 and not args.no_batch64 and gp is None:
         g64 = torch.Generator(device="cpu").manual_seed(777)
         x64 = torch.randn((64, 1, S, S, S), generator=g64).to(dev)
         loc64 = MapGatherPipeline(1, rank, depth=2)
@@ -671,14 +740,14 @@ def run_c2(args, world, rank, dev, barrier, reduce_max):
         model.check_range()
 
     roof, detail, cpu, lat = None, None, None, None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roof, detail = roofline_leg(model, x, T)
         if args.detail:
             os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
             json.dump(detail, open(args.detail, "w"), indent=1)
-    if rank == 0 and not args.no_latency:
+    if rank == 0 and args.full and not args.no_latency:
         lat = latency_leg(model, x[:1], T)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg(model.state_dict(), T)
     line = {"metric": "uncertainty-volumes/sec (64^3, T=10 MC-dropout)", "unit": "volumes/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "scaling": "weak",
@@ -759,19 +828,23 @@ def run_c3(args, world, rank, dev, barrier, reduce_max):
     g = torch.Generator(device="cpu").manual_seed(123)
     x = torch.randn((V, 1, S, S, S), generator=g).to(dev)      # the same volumes on every rank
 
+    last = {}
+
     def step(i):
-        return ensemble_uncertainty_sharded(members, x, world, rank, n_pred=1)
+        last["out"] = ensemble_uncertainty_sharded(members, x, world, rank, n_pred=1)
+        return last["out"]
 
     times = timed_regions(step, lambda: None, barrier, args.steps, args.warmup, max(1, args.repeats), reduce_max)
+    dump_outputs(args, rank, last.pop("out", None))
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # one member's forward over this rank's volumes (n_pred = 1, no dropout): the launches a step issues M times
         from values_amd.dist import ensemble_work_items
         vb = max(1, max((v1 - v0) for _, v0, v1 in ensemble_work_items(M, V, world)[rank]))
         roof, _ = roofline_leg(members[0], x[:vb], 1, chunks=[(0, vb)])
         roof["note"] = f"one member's forward over a {vb}-volume block; a step launches it once per (member, block) item"
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg_passes([m.state_dict() for m in members], M, M, False, "volumes/s",
                                       f"one volume ({M} members, no dropout)")
     line = {"metric": "uncertainty-volumes/sec (64^3, 5-member deep ensemble)", "unit": "volumes/s", "n_gpus": world,
@@ -799,22 +872,26 @@ def run_c5(args, world, rank, dev, barrier, reduce_max):
     g = torch.Generator(device="cpu").manual_seed(123 + rank)
     imgs = [torch.randn((S, S, S), generator=g).to(dev) for _ in range(B)]
 
+    last = {}
+
     def step(i):
-        out = None
+        outs = []
         for b, im in enumerate(imgs):
-            out = predict_image_sliding([model], im, patch_size=P, patch_overlap=0.5, n_pred=T, patch_batch=16,
-                                        seeds=[1000 * i + b])
-        return out
+            outs.append(predict_image_sliding([model], im, patch_size=P, patch_overlap=0.5, n_pred=T, patch_batch=16,
+                                              seeds=[1000 * i + b]))
+        last["out"] = outs          # every image's maps: what a caller of the step receives
+        return outs[-1]
 
     times = timed_regions(step, lambda: None, barrier, args.steps, args.warmup, max(1, args.repeats), reduce_max)
+    dump_outputs(args, rank, last.pop("out", None))
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # the forwards of one patch batch (16 patches x T = 320 samples, the launch geometry predict_image_sliding uses)
         xp = torch.stack([im[:P, :P, :P] for im in imgs[:1]] * 16)[:, None].contiguous()
         roof, _ = roofline_leg(model, xp, T, chunks=[(0, 16)])
         roof["note"] = "one patch batch (16 patches of 64^3 x T = 20 samples per launch), as predict_image_sliding issues them"
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg_passes([model.state_dict()], 27 * T, T, True, "images/s",
                                       f"one 128^3 image (27 patches x T={T})", reduce_vox_scale=8)
     line = {"metric": "uncertainty-images/sec (128^3 sliding window, T=20 MC-dropout)", "unit": "images/s", "n_gpus": world,
@@ -876,22 +953,27 @@ def run_c4(args, world, rank, dev, barrier, reduce_max):
     # the product path for a fixed image geometry: the step captured once as a hipGraph (the eager walk is ~950 launches
     # from Python and host-bound), replayed per step with the views copied into the graph's inputs
     eager = None
-    if not args.eager and rank == 0:     # the eager walk first (side number), its cached blocks returned before the capture
+    if args.full and not args.eager and rank == 0:     # the eager walk first (side number), its cached blocks returned before the capture
         et = timed_regions(step_eager, lambda: None, torch.cuda.synchronize, max(2, args.steps // 2), 1, 1, lambda v: v)
         eager = summarise(et, B * max(2, args.steps // 2), max(2, args.steps // 2))
         model._hold_last = None
         torch.cuda.empty_cache()
     gp = None if args.eager else GraphedPredictor2D([model], views, tta=True, keep_logits=False)
 
+    last = {}
+
     def step(i):
         if gp is None:
-            return step_eager(i)
+            last["out"] = step_eager(i)
+            return last["out"]
         tta_views_8_device(x, noisy, out=gp.x[0])      # this step's views straight into the graph's input
-        return gp()
+        last["out"] = gp()
+        return last["out"]
 
     times = timed_regions(step, lambda: None, barrier, args.steps, args.warmup, max(1, args.repeats), reduce_max)
+    dump_outputs(args, rank, last.pop("out", None))
     roof = None
-    if rank == 0 and not args.no_roofline and hasattr(model, "profile_forward"):
+    if rank == 0 and args.full and not args.no_roofline and hasattr(model, "profile_forward"):
         roof = model.profile_forward(views.t.view(-1, H, W, 4), peak_tflops=PEAK_SPLIT16_TFLOPS, hbm_gbs=PEAK_HBM_GBS, groups=8,
                                      nhwc=True)
         # HBM-side bytes per launch (PMC passes around `--config C4 --roofline-only`: the same single-stream launches)
@@ -899,7 +981,7 @@ def run_c4(args, world, rank, dev, barrier, reduce_max):
         # shape the object names -- quoted beside it, `traffic` stays null
         roof["instance_traffic_mean"] = pmc_traffic(roof["kernel"], f"traffic_c4w{args.hrnet_width}.json")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_leg_2d(extra, model.state_dict(), H, W)
     line = {"metric": f"uncertainty-images/sec (HRNet-W{args.hrnet_width}, 1024x512, 8-view TTA)", "unit": "images/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "scaling": "weak",

@@ -136,7 +136,7 @@ def test_bench_ranks_emulated_on_one_gpu(extra, world, units, workload):
     env = dict(os.environ, VX_BENCH_EMULATE_RANKS="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world)] + extra + ["--steps", "2", "--warmup", "1", "--repeats", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--full"] + extra + ["--steps", "2", "--warmup", "1", "--repeats", "1",
            "--min-gpu-seconds", "0", "--no-cpu-baseline", "--no-roofline", "--no-latency", "--no-batch64", "--no-storage16"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
