@@ -82,18 +82,9 @@ typedef struct vx_config {
                               the three full-resolution launches run ONE fp16 product per fp32 product (vx_conv3d_args.products):
                               what BASELINE config 2 calls "bf16".  Maps then differ from the float64 reference by ~1e-3:
                               bench.py --storage16 reports the measured differences of both */
-  int32_t s16_no_dbplain;  /* plain (not x-pair) single-chunk tile layers whose tile is 16 x 4 x 4: ONE LDS image with two barriers
-                              per item instead of two staggered images with one (same tile, same statistics layout, same bits) */
   int32_t s16_generic;     /* the tile kernel's GENERIC instance (run-time epilogue, one LDS image, two barriers per item) wherever a
                               specialised one (compile-time epilogue, double-buffered staggered schedule) would run: the reference
                               of tests/test_gpu_kernels.py::test_conv3d_k3_specialised_instances_equal_generic (bit for bit) */
-  int32_t s16_no_upcompose; /* the fused up-convolution evaluated per step by the staging waves (round 2) instead of composed into
-                               expand_1_1's weights (round 4, vx_conv3d_args.up_fused) */
-  int32_t s16_no_upsplit;  /* expand_2_2 stores plain floats and the fused up-convolution splits them per step (round 2) */
-  int32_t s16_no_presplit; /* MC-dropout batches: contr_1_2 normalises the shared first-layer tensor on load for every sample
-                              instead of reading the once-per-volume output of vx_prenorm_split */
-  int32_t s16_no_poolfin;  /* a separate vx_pool_finish pass over contr_1_2's window maxima instead of contr_2_1 finishing them while it
-                              stages its tiles (round 4, vx_conv3d_args.in_pool_flags) */
   int32_t s16_no_zc16;     /* the general tile kernels instead of the role-split z-column kernel (round 5, conv3d_zc16.hip) on the
                               Cout == 16 layers with Cin in {8, 16} and W % 32 == 0; with it the forward also keeps the separate
                               normalise + pool pass of the second contract block */

@@ -94,15 +94,21 @@ def test_config_surface_is_the_documented_one(lib):
     for decl in re.findall(r"int32_t\s+([^;]+);", body):
         names += [n.strip() for n in decl.split(",")]
     assert names == [n for n, _ in _lib.Config._fields_]
-    assert len(names) <= 20, names      # (round 6: + s16_no_l1dma, a data-flow switch the parity tests run)
+    assert len(names) <= 15, names      # (0.7.0: the five superseded data-flow switches below are gone)
     gone = {"conv_no_c8", "conv_no_xcd", "conv_per_cu", "s16_per_cu", "c8_per_cu", "convt_wgs", "s16_no_xp", "s16_no_db",
             "s16_no_db3", "s16_no_epi", "s16_no_ty8", "s16_no_wall", "c2s_no_nt5", "convt_no_mfma", "s16_range_check", "s16_pw",
-            "s16_prio"}
+            "s16_prio", "s16_no_upcompose", "s16_no_upsplit", "s16_no_poolfin", "s16_no_presplit", "s16_no_dbplain"}
     assert not (set(names) & gone)
+    c = _lib.get_config()             # the Python mirror keeps the retired switches at their only value
+    for f in _lib.Config.RETIRED:
+        assert f in gone and getattr(c, f) == 0
+        setattr(c, f, 0)
+        with pytest.raises(ValueError):
+            setattr(c, f, 1)
     blob = open(os.path.join(ROOT, "values_amd", "libvalues_amd.so"), "rb").read()
     for f in gone:
         assert ("VX_" + f.upper()).encode() + b"\0" not in blob, f
-    assert lib.vx_version() >= 600
+    assert lib.vx_version() >= 700
 
 
 def test_host_only_queries(lib, vxcfg):
@@ -194,6 +200,7 @@ def test_round6_host_queries_and_arg_checks_without_a_gpu(lib, vxcfg):
         return a
     refused = [args(16, 16, 16, 16, 16, in_planar=1, act=_lib.VX_ACT_RELU),                 # a shape the z-column kernel does not take
                args(8, 16, 32, 32, 32, in_planar=1, act=_lib.VX_ACT_RELU),                   # Cin = 8
+               args(8, 8, 64, 64, 64, in_planar=1, act=_lib.VX_ACT_RELU),                    # a launch the full-resolution kernel takes
                args(16, 16, 32, 32, 32, out_planar=1, stats_partial=0x10000),               # statistics epilogue
                args(16, 16, 32, 32, 32, out_planar=1, act=_lib.VX_ACT_RELU, out_pitch=32),  # not a dense 16-channel output
                args(32, 32, 16, 16, 16, products=1, act=_lib.VX_ACT_RELU),                   # one-product mode away from the full-resolution kernels

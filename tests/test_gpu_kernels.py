@@ -869,7 +869,7 @@ def test_conv3d_xp8_fused_upconvolution_matches_oracle(shape, xblk, pitch, pmode
     # Round 4: the up-convolution COMPOSED into the conv's weights (vx_pack_conv3d_upfused -> vx_conv3d_args.up_fused): per
     # output parity class a 2 x 2 x 3-tap convolution over the 16 coarse channels, the up bias through a table of the 27
     # border classes.  Same function, the same oracle, the same tolerance; with and without dropout, the coarse tensor as
-    # plain floats and as the fp16 pairs expand_2_2's epilogue hands over; and the knob that switches it off
+    # plain floats and as the fp16 pairs expand_2_2's epilogue hands over; and without the composed weights
     got, _, _, mx = _xp8_conv(xd, 16, wt, b, n, d, h, w, act=_lib.VX_ACT_LRELU, drop=_lib.VX_DROP_HASH, seed=93, layer=15,
                               xblk=xblk, in_pitch=8 if not xblk else None, pre=pre, up=(cd, uw, ub), compose=True)
     assert lib.vx_last_kernel_name().decode().startswith("conv3d_xp8w_kernel<2,1,%d,2," % (0 if pre is None else 1))
@@ -881,11 +881,9 @@ def test_conv3d_xp8_fused_upconvolution_matches_oracle(shape, xblk, pitch, pmode
     got1, _, _, _ = _xp8_conv(xd, 16, wt, b, n, d, h, w, act=_lib.VX_ACT_LRELU, xblk=xblk, in_pitch=8 if not xblk else None,
                               pre=pre, up=(cd, uw, ub), up_split=True)           # per-step evaluation on the pre-split tensor
     assert (got1.double() - F.leaky_relu(ref, 0.01)).abs().max().item() < 4e-5
-    vxcfg.set(s16_no_upcompose=1)
     _xp8_conv(xd, 16, wt, b, n, d, h, w, act=_lib.VX_ACT_LRELU, xblk=xblk, in_pitch=8 if not xblk else None, pre=pre,
-              up=(cd, uw, ub), compose=True)
+              up=(cd, uw, ub), compose=False)                                    # no up_fused: the per-step evaluation
     assert lib.vx_last_kernel_name().decode().startswith("conv3d_xp8w_kernel<2,3,%d,1," % (0 if pre is None else 1))
-    vxcfg.set(s16_no_upcompose=0)
     # refused, not silently ignored, where the column kernel does not run
     vxcfg.set(s16_no_upfuse=1)
     with pytest.raises(_lib.VxError):

@@ -872,14 +872,17 @@ def test_graphed_predictor_replays_equal_eager_and_draw_fresh_dropout():
     assert torch.equal(gd(x2)["logits"], predict_uncertainty([det], x2, n_pred=1)["logits"])
 
 
-@pytest.mark.parametrize("knobs", [dict(s16_skip_raw=0), dict(s16_no_prenorm=1), dict(s16_no_xp8=1), dict(s16_no_upfuse=1), dict(s16_no_upcompose=1), dict(no_head_fusion=1), dict(s16_no_poolfuse=1), dict(s16_no_poolfin=1), dict(s16_no_presplit=1), dict(s16_no_dbplain=1), dict(s16_no_upsplit=1), dict(s16_no_deep=1), dict(s16_no_l1dma=1)])
+# (ids as before vx_version 700: knobs4 and knobs7 - knobs10 were the cases of the switches it retired)
+_LEVEL0_KNOBS = {0: dict(s16_skip_raw=0), 1: dict(s16_no_prenorm=1), 2: dict(s16_no_xp8=1), 3: dict(s16_no_upfuse=1), 5: dict(no_head_fusion=1),
+                 6: dict(s16_no_poolfuse=1), 11: dict(s16_no_deep=1), 12: dict(s16_no_l1dma=1)}
+
+
+@pytest.mark.parametrize("knobs", list(_LEVEL0_KNOBS.values()), ids=[f"knobs{i}" for i in _LEVEL0_KNOBS])
 def test_level0_fusion_variants_vs_oracle_32(knobs, vxcfg):
     """The level-0 data-flow variants behind vx_config: a separate normalise pass for the skip half instead of expand_1_1
     normalising the raw tensor on load (s16_skip_raw=0), no normalise-on-load at all (s16_no_prenorm), the general tile
     kernels instead of the z-column kernel (s16_no_xp8), a separate upscale2 launch (s16_no_upfuse), the 1x1x1 head as its own
-    launch (no_head_fusion), every sample normalising the shared first-layer tensor itself instead of masking the
-    once-per-volume output of vx_prenorm_split (s16_no_presplit), a separate
-    pooling pass instead of the window maxima from contr_1_2's epilogue (s16_no_poolfuse) -- each
+    launch (no_head_fusion), a separate pooling pass instead of the window maxima from contr_1_2's epilogue (s16_no_poolfuse) -- each
     against the float64 oracle with the exported hash masks, MC-dropout (shared first layer) and TTA-style (src / flip)
     batches."""
     from values_amd import predict_uncertainty
@@ -896,7 +899,7 @@ def test_level0_fusion_variants_vs_oracle_32(knobs, vxcfg):
     # the un-shared first layer (per-sample src / flip: the TTA path) with dropout off
     det = make_model(do_dropout=False)
     a = predict_uncertainty([det], x.float().cuda(), tta=True, x_noise=x.float().cuda() * 1.01)
-    vxcfg.set(s16_skip_raw=1, s16_no_prenorm=0, s16_no_xp8=0, s16_no_upfuse=0, s16_no_upcompose=0, no_head_fusion=0, s16_no_poolfuse=0, s16_no_poolfin=0, s16_no_presplit=0, s16_no_dbplain=0, s16_no_upsplit=0, s16_no_deep=0, s16_no_l1dma=0)     # the defaults
+    vxcfg.set(s16_skip_raw=1, s16_no_prenorm=0, s16_no_xp8=0, s16_no_upfuse=0, no_head_fusion=0, s16_no_poolfuse=0, s16_no_deep=0, s16_no_l1dma=0)     # the defaults
     b = predict_uncertainty([det], x.float().cuda(), tta=True, x_noise=x.float().cuda() * 1.01)
     assert (a["logits"] - b["logits"]).abs().max().item() < 2e-5
 

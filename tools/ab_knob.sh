@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of one vx_config knob through the bench (base = knob set, new = default; base, new, base, new):
-#   tools/ab_knob.sh VX_S16_NO_UPCOMPOSE [layer-name-regex]
+#   tools/ab_knob.sh VX_S16_NO_UPFUSE [layer-name-regex]
 knob=${1:?knob}; pat=${2:-.}
 cd "$(dirname "$0")/.."
 OUT=${OUT:-bench_out}      # results folder, relative to the repository root

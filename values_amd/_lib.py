@@ -90,7 +90,21 @@ class Config(C.Structure):
     """vx_config (include/values_amd.h): kernel-family selection and tuning knobs, read once from VX_* variables."""
     _fields_ = [(n, _i32) for n in (
         "conv_fp32", "s16_no_prenorm", "s16_no_xp8", "s16_skip_raw", "no_head_fusion", "s16_no_upfuse", "s16_no_poolfuse",
-        "storage16", "s16_no_dbplain", "s16_generic", "s16_no_upcompose", "s16_no_upsplit", "s16_no_presplit", "s16_no_poolfin", "s16_no_zc16", "s16_no_halves", "s16_no_deep", "s16_no_l1dma", "c2s_no_wide", "c2s_no_oct")]
+        "storage16", "s16_generic", "s16_no_zc16", "s16_no_halves", "s16_no_deep", "s16_no_l1dma", "c2s_no_wide", "c2s_no_oct")]
+    # switches vx_version 700 retired (their launch sequences were measured slower; the default is the only path left): they
+    # read as 0 and take 0, so code that resets them keeps working, and asking for the retired path is an error
+    RETIRED = ("s16_no_upcompose", "s16_no_upsplit", "s16_no_poolfin", "s16_no_presplit", "s16_no_dbplain")
+
+
+def _retired_field(name):
+    def put(self, v):
+        if v:
+            raise ValueError(f"vx_config.{name} was retired in 0.7.0: the default data flow is the only one")
+    return property(lambda self: 0, put)
+
+
+for _n in Config.RETIRED:
+    setattr(Config, _n, _retired_field(_n))
 
 
 class UncOutputs(C.Structure):

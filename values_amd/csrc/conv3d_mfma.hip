@@ -746,6 +746,11 @@ extern "C" int vx_conv3d_k3(const vx_conv3d_args* ap, vx_stream_t stream) {
                            a.drop_mode != VX_DROP_MASK && a.in_drop_mode != VX_DROP_MASK))
     VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: products = 1 is taken by the full-resolution z-column kernel only (got %dx%dx%d, %d -> %d)",
             a.D, a.H, a.W, a.Cin, a.Cout);
+  // the planar hand-over only exists in the 16 -> 16 instances of the z-column kernel: refused before any other kernel can take
+  // the launch and ignore the flags
+  if ((a.in_planar || a.out_planar) && !vx_conv3d_k3_planar_ok(a.D, a.H, a.W, a.Cin, a.Cout))
+    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the planar pre-split hand-over (in_planar / out_planar) is taken where vx_conv3d_k3_planar_ok "
+            "(got %dx%dx%d, %d -> %d)", a.D, a.H, a.W, a.Cin, a.Cout);
   if (a.up_in) {
     if (!a.up_w || !a.up_b) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: fused up-convolution without weights");
     if (!vx_conv3d_k3_upfuse_ok(a.D, a.H, a.W, a.Cin, a.Cout) || a.drop_mode == VX_DROP_MASK || a.stats_partial || a.head_out)
@@ -826,8 +831,8 @@ extern "C" int vx_conv3d_k3(const vx_conv3d_args* ap, vx_stream_t stream) {
     if (rc != 1) return rc;
   }
   if (a.in_planar || a.out_planar)
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the planar pre-split hand-over (in_planar / out_planar) is taken where vx_conv3d_k3_planar_ok "
-            "(got %dx%dx%d, %d -> %d)", a.D, a.H, a.W, a.Cin, a.Cout);
+    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the z-column kernel does not take this planar launch (%dx%dx%d, %d -> %d)", a.D, a.H, a.W,
+            a.Cin, a.Cout);
   if (c.S16 && vx_conv3d_deep_applies(a.N, a.D, a.H, a.W, a.Cin, a.Cout)) {
     // the deep layers (Cout % 32 == 0 on small volumes): role-split tile kernel (conv3d_deep.hip); its weights follow the tile
     // kernel's in the packed block (family 7)

@@ -969,8 +969,6 @@ static int launch_s16(const ConvSArgs& ka_in, hipStream_t s) {
   return VX_OK;
 }
 
-static inline bool s16_dbplain() { return !vx_cfg().s16_no_dbplain && !vx_cfg().s16_generic; }
-
 template <int CB, int NT, int XP>
 static int dispatch_s16(const ConvSArgs& ka, int tx, hipStream_t s) {
   // epilogue specialisation of the large-tile instances (EPI in the kernel's header)
@@ -998,7 +996,7 @@ static int dispatch_s16(const ConvSArgs& ka, int tx, hipStream_t s) {
     // TWICE: -11 % on 16 -> 32 at 16^3.  Shrinking the tile to make room loses more than the stagger wins: the 16-channel
     // chunks at 32^3 on 16 x 4 x 4 instead of 16 x 8 x 4 were 14-15 % SLOWER double-buffered, and 8 -> 16 at 32^3 (whose large
     // tile does fit twice) measured neutral (same-process A/B)
-    if (tx == 16 && ka.nchunks == 1 && s16_dbplain()) {
+    if (tx == 16 && ka.nchunks == 1 && !generic) {
       if (!ka.ty8) {                             // 16 x 4 x 4 tile (two row tiles, or H < 32)
         if (epi == 0) return launch_s16<CB, NT, 16, 4, 4, 8, XP, 2, 0>(ka, s);
         if (epi == 1) return launch_s16<CB, NT, 16, 4, 4, 8, XP, 2, 1>(ka, s);

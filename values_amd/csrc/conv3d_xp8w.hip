@@ -1264,7 +1264,7 @@ int vx_conv3d_k3_xp8(const vx_conv3d_args& a, int stat_tiles, hipStream_t s) {
   if (epi == 2 && !(a.act == VX_ACT_LRELU && a.drop_mode == VX_DROP_HASH)) return 1;   // other heads: general kernel
   if (epi == 1 && a.act != VX_ACT_LRELU) return 1;
   // 2: the up-convolution composed into the weights (vx_pack_conv3d_upfused), 1: evaluated per step by the staging waves
-  const int up = a.up_in ? ((a.up_fused && !vx_cfg().s16_no_upcompose) ? 2 : 1) : 0;
+  const int up = a.up_in ? (a.up_fused ? 2 : 1) : 0;
   // producer waves: 8 (two per SIMD) for the two-chunk layers, whose staging is the heavy side; 4 for the one-chunk layers:
   // their consumers hold R = 4 image rows + accumulators (134-161 VGPRs) and at 16 waves per workgroup (128-VGPR cap) EVERY
   // one-chunk instance spilled 5-30 VGPRs into its item loop (round-3 verdict; tools/check_spills.sh now fails the build on any
