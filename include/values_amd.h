@@ -672,6 +672,61 @@ int vx_box_max(const float* map, int D, int H, int W, int pd, int ph, int pw, do
                void* workspace, size_t workspace_bytes, vx_stream_t stream);
 int vx_sum_thr(const void* map, int dtype, int64_t n, double thr, double* sums, vx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Device results writer (data_carrier_3D.py:208-371, DataCarrier3D.save_data; host mirror: values_amd/results.py
+ * save_case).  The NIfTI payloads of a case are assembled on the device (vx_nifti_payload), compressed to gzip members
+ * on the device (vx_gzip_encode), and the host only copies the members back and writes the files.
+ * These two entry points upload a small descriptor table from their own host copy and wait for that copy on the stream
+ * (hipStreamSynchronize) before they launch: they are not capturable into a hipGraph.
+ *
+ * vx_nifti_payload: one launch writes every item's payload at dst + dst_off: the 352-byte header (348 bytes + 4 zero
+ *   extension bytes, built by the caller: values_amd.nifti.header_bytes) and the voxels in Fortran order -- element
+ *   src[x][y][z] of a C-order (X, Y, Z) volume at index (z * Y + y) * X + x.  kind:
+ *     COPY        src (X, Y, Z) of esize (1/2/4/8) bytes per element, copied as it is
+ *     PROB        src (T, C, X, Y, Z) VX_F32 / VX_F64 probabilities -> float64 src[t][c] / float64(clip(count, 1))
+ *                 (count: optional (X, Y, Z) float64 divisor; null = none)
+ *     MEAN_PROB   float64 sum of PROB over t = 0..T-1 added in that order, divided by T
+ *     ARGMAX      uint8 first index of the maximum over c of PROB[t] (a NaN is the maximum: np.argmax)
+ *     ARGMAX_MEAN the same over MEAN_PROB
+ *   dst 16-byte aligned, dst_off a multiple of 16, every payload within dst_bytes; workspace: vx_nifti_workspace_bytes.
+ *   vx_nifti_payload_bytes: 352 + voxels * output element size (host only).
+ * vx_gzip_encode: one complete gzip member (RFC 1952: 10-byte header with MTIME 0, DEFLATE stream, CRC-32, ISIZE) of
+ *   each item's n bytes at dst + dst_off (the slot needs vx_gzip_bound(n) bytes within dst_bytes); the member's size goes
+ *   to out_sizes[i] (device).  stride_hint: distances (element, row, slice bytes; 0 = none, each <= 32768) the match
+ *   finder tries besides its hash table.  The output is deterministic.  workspace: vx_gzip_workspace_bytes(sizes, n).
+ * vx_gzip_bound: worst-case member size of n input bytes (n + 5 per 32 KiB chunk + 18; <= n + n/1000 + 64 from
+ *   n >= 1 MiB); host only.
+ * vx_crc32: out[0] = CRC-32 (ISO-HDLC, zlib.crc32) of n bytes at x (any alignment). */
+enum { VX_NIFTI_COPY = 0, VX_NIFTI_PROB = 1, VX_NIFTI_MEAN_PROB = 2, VX_NIFTI_ARGMAX = 3, VX_NIFTI_ARGMAX_MEAN = 4 };
+typedef struct vx_nifti_item {
+  const void* src;
+  const double* count;   /* PROB kinds: optional (X, Y, Z) float64 divisor */
+  int64_t dst_off;
+  int32_t kind;
+  int32_t src_dtype;     /* PROB kinds: VX_F32 / VX_F64 */
+  int32_t esize;         /* COPY: bytes per element */
+  int32_t T, C, t, c;
+  int32_t X, Y, Z;
+  uint8_t header[352];
+} vx_nifti_item;
+size_t vx_nifti_workspace_bytes(int n_items);
+int64_t vx_nifti_payload_bytes(const vx_nifti_item* item);
+int vx_nifti_payload(const vx_nifti_item* items /* host array */, int n_items, uint8_t* dst, int64_t dst_bytes, void* workspace,
+                     size_t ws_bytes, vx_stream_t stream);
+
+typedef struct vx_gz_item {
+  const void* src;
+  int64_t n;
+  int64_t dst_off;
+  int32_t stride_hint[3];
+  int32_t pad;
+} vx_gz_item;
+int64_t vx_gzip_bound(int64_t n);
+size_t vx_gzip_workspace_bytes(const int64_t* sizes /* host array */, int n_items);
+int vx_gzip_encode(const vx_gz_item* items /* host array */, int n_items, uint8_t* dst, int64_t dst_bytes,
+                   int64_t* out_sizes /* device */, void* workspace, size_t ws_bytes, vx_stream_t stream);
+int vx_crc32(const void* x, int64_t n, uint32_t* out /* device */, vx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

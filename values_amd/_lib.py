@@ -125,6 +125,21 @@ class UNet3DRun(C.Structure):
                 ("range_flag", _p), ("seed_dev", _p)]
 
 
+VX_NIFTI_COPY, VX_NIFTI_PROB, VX_NIFTI_MEAN_PROB, VX_NIFTI_ARGMAX, VX_NIFTI_ARGMAX_MEAN = 0, 1, 2, 3, 4
+
+
+class NiftiItem(C.Structure):
+    """vx_nifti_item: one NIfTI payload (header + Fortran-order voxels) of the device results writer."""
+    _fields_ = [("src", _p), ("count", _p), ("dst_off", _i64), ("kind", _i32), ("src_dtype", _i32), ("esize", _i32),
+                ("T", _i32), ("C", _i32), ("t", _i32), ("c", _i32), ("X", _i32), ("Y", _i32), ("Z", _i32),
+                ("header", C.c_uint8 * 352)]
+
+
+class GzItem(C.Structure):
+    """vx_gz_item: one gzip member to encode (device source, n bytes, slot offset in dst, match-finder stride hints)."""
+    _fields_ = [("src", _p), ("n", _i64), ("dst_off", _i64), ("stride_hint", _i32 * 3), ("pad", _i32)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -212,6 +227,13 @@ SIGNATURES = {
     "vx_calib_bins": (_i, [_p, _i, _p, _p, _i, _i64, _i, C.c_double, C.c_double, C.POINTER(C.c_double), _p, _p, _p]),
     "vx_box_max": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
     "vx_sum_thr": (_i, [_p, _i, _i64, C.c_double, _p, _p]),
+    "vx_nifti_workspace_bytes": (C.c_size_t, [_i]),
+    "vx_nifti_payload_bytes": (_i64, [C.POINTER(NiftiItem)]),
+    "vx_nifti_payload": (_i, [C.POINTER(NiftiItem), _i, _p, _i64, _p, C.c_size_t, _p]),
+    "vx_gzip_bound": (_i64, [_i64]),
+    "vx_gzip_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i]),
+    "vx_gzip_encode": (_i, [C.POINTER(GzItem), _i, _p, _i64, _p, _p, C.c_size_t, _p]),
+    "vx_crc32": (_i, [_p, _i64, _p, _p]),
 }
 
 _lib = None

@@ -20,20 +20,24 @@ _DT = {np.dtype("uint8"): (2, 8), np.dtype("int16"): (4, 16), np.dtype("int32"):
 _CODE = {v[0]: k for k, v in _DT.items()}
 
 
-def save(arr, path: str, header=None) -> None:
-    """arr: numpy array (or anything np.asarray accepts) indexed [x, y(, z, ...)].  `header` (a dict with optional
-    "pixdim" and "affine") plays the role of medpy's header argument; False / None = identity geometry."""
-    a = np.asarray(arr)
-    if a.dtype == np.bool_:
-        a = a.astype(np.uint8)
-    if a.dtype.newbyteorder("<") not in _DT and a.dtype not in _DT:
-        a = a.astype(np.float64)
-    a = a.astype(a.dtype.newbyteorder("<"), copy=False)
-    code, bitpix = _DT[np.dtype(a.dtype.name)]
-    nd = a.ndim
+def file_dtype(dtype) -> np.dtype:
+    """The dtype `save` stores an array of `dtype` as: bool -> uint8, anything outside the NIfTI table -> float64."""
+    dt = np.dtype(dtype)
+    if dt == np.bool_:
+        return np.dtype("uint8")
+    if dt.newbyteorder("<") not in _DT and dt not in _DT:
+        return np.dtype("float64")
+    return np.dtype(dt.name)
+
+
+def header_bytes(shape, dtype, header=None) -> bytes:
+    """The 352 bytes in front of the voxels of a file `save` writes: the 348-byte header of an array of `shape` and
+    `dtype` (already one of the table's, see file_dtype) plus the 4 zero extension bytes."""
+    code, bitpix = _DT[np.dtype(np.dtype(dtype).name)]
+    nd = len(shape)
     if not 1 <= nd <= 7:
         raise ValueError("NIfTI-1 stores 1..7 dimensions")
-    dim = [nd] + list(a.shape) + [1] * (7 - nd)
+    dim = [nd] + [int(v) for v in shape] + [1] * (7 - nd)
     pixdim = [1.0] * 8
     affine = np.eye(4)
     if isinstance(header, dict):
@@ -57,7 +61,15 @@ def save(arr, path: str, header=None) -> None:
     struct.pack_into("<4f", h, 296, *affine[1])
     struct.pack_into("<4f", h, 312, *affine[2])
     h[344:348] = b"n+1\0"
-    payload = bytes(h) + b"\0\0\0\0" + np.asfortranarray(a).tobytes(order="F")
+    return bytes(h) + b"\0\0\0\0"
+
+
+def save(arr, path: str, header=None) -> None:
+    """arr: numpy array (or anything np.asarray accepts) indexed [x, y(, z, ...)].  `header` (a dict with optional
+    "pixdim" and "affine") plays the role of medpy's header argument; False / None = identity geometry."""
+    a = np.asarray(arr)
+    a = a.astype(file_dtype(a.dtype).newbyteorder("<"), copy=False)
+    payload = header_bytes(a.shape, a.dtype, header) + np.asfortranarray(a).tobytes(order="F")
     if str(path).endswith(".gz"):
         with gzip.open(path, "wb", compresslevel=1) as f:
             f.write(payload)

@@ -10,9 +10,12 @@
 """
 from __future__ import annotations
 
+import ctypes as C
 import json
 import os
-from typing import Dict, Optional
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -54,6 +57,292 @@ def save_case(save_dir: str, image_id: str, softmax_pred, maps: Optional[Dict] =
         if maps and k in maps:
             os.makedirs(os.path.join(save_dir, k), exist_ok=True)
             nifti.save(_np(maps[k]), os.path.join(save_dir, k, f"{image_id}.nii.gz"), header)
+
+
+class PlannedFile(NamedTuple):
+    """One file of a case's results tree: path relative to save_dir, payload kind (vx_nifti_item kinds: "COPY", "PROB",
+    "MEAN_PROB", "ARGMAX", "ARGMAX_MEAN"), source (("input",), ("gt_seg", r), ("prob", t, c), ("mean", c), ("seg", t),
+    ("seg_mean",), ("map", name)), voxel shape and the numpy dtype the file stores."""
+    path: str
+    kind: str
+    source: tuple
+    shape: tuple
+    dtype: np.dtype
+
+
+def _shape_dtype(a):
+    """(shape, dtype name) of a numpy array or a torch tensor without copying it"""
+    if hasattr(a, "detach"):
+        return tuple(a.shape), str(a.dtype).replace("torch.", "")
+    a = np.asarray(a)
+    return a.shape, a.dtype
+
+
+def _np_dtype(d) -> np.dtype:
+    return np.dtype("bool" if d == "bool" else d) if isinstance(d, str) else np.dtype(d)
+
+
+def plan_case(image_id: str, softmax_pred, maps: Optional[Dict] = None, data=None, gt_seg=None) -> List[PlannedFile]:
+    """The files save_case writes for these arguments, in its order: same names, the same T > 1 rule for the mean files,
+    the same dtypes.  Host logic only: nothing is read but shapes and dtypes."""
+    out = []
+    if data is not None:
+        shp, dt = _shape_dtype(data)
+        out.append(PlannedFile(os.path.join("input", f"{image_id}.nii.gz"), "COPY", ("input",), shp, _file_dtype(dt)))
+    if gt_seg is not None:
+        shp, dt = _shape_dtype(gt_seg)
+        for r in range(shp[0]):
+            out.append(PlannedFile(os.path.join("gt_seg", f"{image_id}_{str(r).zfill(2)}.nii.gz"), "COPY", ("gt_seg", r),
+                                   tuple(shp[1:]), _file_dtype(dt)))
+    shp, _ = _shape_dtype(softmax_pred)
+    T, C = shp[:2]
+    vol = tuple(shp[2:])
+    f64, u8 = np.dtype("float64"), np.dtype("uint8")
+    if T > 1:
+        out.append(PlannedFile(os.path.join("pred_seg", f"{image_id}_mean.nii.gz"), "ARGMAX_MEAN", ("seg_mean",), vol, u8))
+        for c in range(C):
+            out.append(PlannedFile(os.path.join("pred_prob", f"{image_id}_mean_{str(c + 1).zfill(2)}.nii.gz"), "MEAN_PROB",
+                                   ("mean", c), vol, f64))
+    for t in range(T):
+        tag = str(t + 1).zfill(2)
+        out.append(PlannedFile(os.path.join("pred_seg", f"{image_id}_{tag}.nii.gz"), "ARGMAX", ("seg", t), vol, u8))
+        for c in range(C):
+            out.append(PlannedFile(os.path.join("pred_prob", f"{image_id}_{tag}_{str(c + 1).zfill(2)}.nii.gz"), "PROB",
+                                   ("prob", t, c), vol, f64))
+    for k in ("pred_entropy", "aleatoric_uncertainty", "epistemic_uncertainty"):
+        if maps and k in maps:
+            shp, dt = _shape_dtype(maps[k])
+            out.append(PlannedFile(os.path.join(k, f"{image_id}.nii.gz"), "COPY", ("map", k), shp, _file_dtype(dt)))
+    return out
+
+
+def _file_dtype(d) -> np.dtype:
+    try:
+        return nifti.file_dtype(_np_dtype(d))
+    except TypeError:   # a torch dtype numpy has no name for (bfloat16, ...): not in the table
+        return np.dtype("float64")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# device results writer
+
+_TORCH_OK = ("uint8", "int8", "int16", "int32", "int64", "float32", "float64", "uint16", "uint32", "uint64")
+
+
+def _to_device(a, dev):
+    """a torch tensor on `dev` holding the array (numpy, CPU or device tensor); numpy inputs go up as native-order bytes"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        return a.detach().to(dev)
+    a = np.asarray(a)
+    if not a.dtype.isnative:
+        a = a.astype(a.dtype.newbyteorder("="))
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    if a.dtype.name in ("uint16", "uint32", "uint64"):
+        a = a.view(a.dtype.name[1:])    # same bytes; the file dtype is decided from the plan
+    if a.dtype.name not in _TORCH_OK:
+        a = a.astype(np.float64)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _copy_source(t, dtype: np.dtype):
+    """(contiguous device tensor of the file's dtype with the voxels in an order the COPY kernel turns into Fortran
+    order, X, Y, Z)"""
+    import torch
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    name = str(t.dtype).replace("torch.", "")
+    if name != dtype.name and not (dtype.name in ("uint16", "uint32", "uint64") and name == dtype.name[1:]):
+        t = t.double()    # outside the NIfTI table (float16, bfloat16, ...): stored as float64 like nifti.save
+    shp = tuple(t.shape)
+    if len(shp) <= 3:
+        X, Y, Z = (1,) * (3 - len(shp)) + shp
+        return t.contiguous(), X, Y, Z
+    # more than three axes: reverse them on the device; the kernel then copies in order
+    return t.permute(*reversed(range(len(shp)))).contiguous(), 1, 1, int(np.prod(shp))
+
+
+class _Buffers:
+    """device payload / member / workspace buffers and the pinned host buffer of one case in flight (grown, never shrunk)"""
+
+    def __init__(self):
+        self.t = {}
+
+    def get(self, name, nbytes, dev, pinned=False):
+        import torch
+        b = self.t.get(name)
+        if b is None or b.numel() < nbytes:
+            n = max(int(nbytes * 1.25), 1 << 16)
+            b = torch.empty(n, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(n, dtype=torch.uint8, device=dev)
+            self.t[name] = b
+        return b
+
+
+def _encode_case(bufs: _Buffers, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header, timing=None):
+    """payload launch + encode launch + one D2H copy: -> (plan, host uint8 array, [(offset, size)])"""
+    import torch
+    from . import _lib, gz
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    plan = plan_case(image_id, softmax_pred, maps, data, gt_seg)
+    sm = _to_device(softmax_pred, dev)
+    if sm.dtype not in (torch.float32, torch.float64):
+        sm = sm.double()
+    sm = sm.contiguous()
+    T, Cn = int(sm.shape[0]), int(sm.shape[1])
+    vol = tuple(int(v) for v in sm.shape[2:])
+    if len(vol) != 3:
+        raise _lib.VxError(f"save_case_device: softmax_pred (T, C, X, Y, Z) expected, got {tuple(sm.shape)}")
+    cnt = None
+    if num_predictions is not None:
+        cnt = _to_device(num_predictions, dev).double()
+        while cnt.dim() > 3 and cnt.shape[0] == 1:
+            cnt = cnt[0]
+        try:
+            cnt = torch.broadcast_to(cnt, vol)
+        except RuntimeError:
+            raise _lib.VxError(f"save_case_device: num_predictions {tuple(cnt.shape)} does not broadcast to {vol}")
+        cnt = cnt.contiguous()
+    keep = [sm, cnt]
+    items = (_lib.NiftiItem * len(plan))()
+    gz_items, off = [], 0
+    kinds = {"COPY": _lib.VX_NIFTI_COPY, "PROB": _lib.VX_NIFTI_PROB, "MEAN_PROB": _lib.VX_NIFTI_MEAN_PROB,
+             "ARGMAX": _lib.VX_NIFTI_ARGMAX, "ARGMAX_MEAN": _lib.VX_NIFTI_ARGMAX_MEAN}
+    dsrc = _to_device(data, dev) if data is not None else None
+    gsrc = _to_device(gt_seg, dev) if gt_seg is not None else None
+    for i, f in enumerate(plan):
+        it = items[i]
+        it.kind = kinds[f.kind]
+        if f.kind == "COPY":
+            src = dsrc if f.source[0] == "input" else gsrc[f.source[1]] if f.source[0] == "gt_seg" else \
+                _to_device(maps[f.source[1]], dev)
+            src, X, Y, Z = _copy_source(src, f.dtype)
+            keep.append(src)
+            it.src = src.data_ptr() if src.numel() else None
+            it.esize = f.dtype.itemsize
+        else:
+            X, Y, Z = vol
+            it.src = sm.data_ptr()
+            it.count = cnt.data_ptr() if cnt is not None else None
+            it.src_dtype = _lib.VX_F64 if sm.dtype == torch.float64 else _lib.VX_F32
+            it.T, it.C = T, Cn
+            it.t = f.source[1] if f.kind in ("PROB", "ARGMAX") else 0
+            it.c = f.source[-1] if f.kind in ("PROB", "MEAN_PROB") else 0
+        it.X, it.Y, it.Z = X, Y, Z
+        it.dst_off = off
+        C.memmove(it.header, nifti.header_bytes(f.shape, f.dtype, header), 352)
+        n = int(_lib.load().vx_nifti_payload_bytes(C.byref(it)))
+        gz_items.append((off, n, gz.hints_for(f.dtype.itemsize, f.shape)))
+        off += (n + 15) // 16 * 16
+    lib = _lib.load()
+    payload = bufs.get("payload", off, dev)
+    nws = bufs.get("nifti_ws", int(lib.vx_nifti_workspace_bytes(len(plan))), dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
+    if ev:
+        ev[0].record()
+    _lib.check(lib.vx_nifti_payload(items, len(plan), _lib.ptr(payload), payload.numel(), _lib.ptr(nws), nws.numel(),
+                                    _lib.stream_ptr()), "vx_nifti_payload")
+    if ev:
+        ev[1].record()
+    slots, goff = [], 0
+    for _, n, _h in gz_items:
+        slots.append(goff)
+        goff += gz.bound(n)
+    dst = bufs.get("members", goff, dev)
+    sizes = bufs.get("sizes", 8 * len(plan), dev)[:8 * len(plan)].view(torch.int64)
+    gws = bufs.get("gzip_ws", gz.workspace_bytes([n for _, n, _h in gz_items]), dev)
+    base = payload.data_ptr()
+    gz.encode_into([(base + o, n, s, h) for (o, n, h), s in zip(gz_items, slots)], dst, sizes, gws)
+    if ev:
+        ev[2].record()
+    host_sizes = sizes.cpu().tolist()      # synchronises the stream
+    used = max(s + n for s, n in zip(slots, host_sizes))
+    host = bufs.get("host", used, dev, pinned=True)
+    host[:used].copy_(dst[:used])
+    if ev:
+        timing["payload_ms"] = timing.get("payload_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timing["encode_ms"] = timing.get("encode_ms", 0.0) + ev[1].elapsed_time(ev[2])
+        timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(n for _, n, _h in gz_items)
+    del keep
+    return plan, host.numpy(), list(zip(slots, host_sizes))
+
+
+def _make_dirs(save_dir, plan):
+    for d in ("input", "gt_seg", "pred_seg", "pred_prob"):   # save_case creates these four whatever it writes
+        os.makedirs(os.path.join(save_dir, d), exist_ok=True)
+    for f in plan:
+        os.makedirs(os.path.join(save_dir, os.path.dirname(f.path)), exist_ok=True)
+
+
+def _write(path, buf, off, n):
+    with open(path, "wb") as fh:
+        fh.write(memoryview(buf)[off:off + n])
+
+
+_shared_bufs = _Buffers()
+_shared_lock = threading.Lock()
+
+
+def save_case_device(save_dir: str, image_id: str, softmax_pred, maps: Optional[Dict] = None, data=None, gt_seg=None,
+                     num_predictions=None, header=False, _timing=None) -> None:
+    """save_case on the device: the same arguments, the same tree, the same decoded bytes in every file.  Device tensors
+    are used where they are; numpy arrays and CPU tensors are uploaded.  One vx_nifti_payload launch assembles every
+    payload, one vx_gzip_encode compresses them, one copy brings the members back into reused pinned memory, and the
+    host writes the files."""
+    with _shared_lock:
+        plan, host, spans = _encode_case(_shared_bufs, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header,
+                                         _timing)
+        _make_dirs(save_dir, plan)
+        for f, (o, n) in zip(plan, spans):
+            _write(os.path.join(save_dir, f.path), host, o, n)
+
+
+class ResultsWriter:
+    """Pipelined save_case_device: submit() encodes a case on the GPU and hands its files to a small thread pool, so the
+    files of case i are written while case i + 1 is encoded.  Two buffer sets alternate; a set is reused only once its
+    files are written.  close() (or leaving the `with` block) waits and re-raises the first write error."""
+
+    def __init__(self, workers: int = 4):
+        if workers < 1:
+            raise ValueError("ResultsWriter: workers >= 1")
+        self._pool = ThreadPoolExecutor(max_workers=int(workers))
+        self._bufs = [_Buffers(), _Buffers()]
+        self._pending = [[], []]
+        self._all = []
+        self._n = 0
+        self._closed = False
+
+    def submit(self, save_dir: str, image_id: str, softmax_pred, maps: Optional[Dict] = None, data=None, gt_seg=None,
+               num_predictions=None, header=False) -> None:
+        if self._closed:
+            raise RuntimeError("ResultsWriter is closed")
+        k = self._n % 2
+        self._n += 1
+        for f in self._pending[k]:   # the buffer set's previous case must be on disk before it is overwritten
+            f.exception()
+        plan, host, spans = _encode_case(self._bufs[k], image_id, softmax_pred, maps, data, gt_seg, num_predictions, header)
+        _make_dirs(save_dir, plan)
+        futs = [self._pool.submit(_write, os.path.join(save_dir, f.path), host, o, n) for f, (o, n) in zip(plan, spans)]
+        self._pending[k] = futs
+        self._all.extend(futs)
+
+    def close(self) -> None:
+        if self._closed:
+            return
+        self._closed = True
+        self._pool.shutdown(wait=True)
+        for f in self._all:
+            e = f.exception()
+            if e is not None:
+                raise e
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def results_dir(root_dir: str, exp_name: str, version, test_split: str = "id") -> str:
