@@ -727,6 +727,29 @@ int vx_gzip_encode(const vx_gz_item* items /* host array */, int n_items, uint8_
                    int64_t* out_sizes /* device */, void* workspace, size_t ws_bytes, vx_stream_t stream);
 int vx_crc32(const void* x, int64_t n, uint32_t* out /* device */, vx_stream_t stream);
 
+/* The 2D results tree (Tester.save_prediction, test_2D.py:116-141; host mirror: values_amd/results2d.py save_prediction).
+ * vx_png_encode: one complete 8-bit RGB PNG file (signature, IHDR, one IDAT holding a zlib stream -- header 78 01, raw
+ *   DEFLATE, Adler-32 -- and IEND) per item, colouring each label through lut (device, 256 x 3 RGB bytes); pixels
+ *   whose ignore byte is non-zero take lut[unlabeled].  Every scanline has filter 0: the inflated IDAT is exactly the
+ *   raw stream image_io.write_png compresses.  labels / ignore: device (H, W) uint8, C order; ignore may be null.  The
+ *   files are written back to back in item order from dst + 0; out_offsets[i] / out_sizes[i] (device) receive file i's
+ *   place.  dst_bytes must cover the sum of vx_png_bound over the items, the workspace (16-byte aligned) at least
+ *   vx_png_workspace_bytes(items, n) bytes.  H * (3 W + 1) < 2^31.  The output is deterministic.  Like vx_gzip_encode it
+ *   uploads its descriptor table and synchronises the stream before it launches: not capturable into a hipGraph.
+ * vx_png_bound: worst-case file size of an H x W item: n = H * (3 W + 1) scanline bytes as stored blocks
+ *   (n + 5 per 32 KiB chunk) plus 63 bytes of PNG and zlib framing; host only, -1 for H or W < 1.
+ * vx_png_workspace_bytes: 0 for a null table, n < 1 or an item with H or W < 1. */
+typedef struct vx_png_item {
+  const uint8_t* labels;
+  const uint8_t* ignore;
+  int32_t H, W;
+} vx_png_item;
+int64_t vx_png_bound(int H, int W);
+size_t vx_png_workspace_bytes(const vx_png_item* items /* host array */, int n);
+int vx_png_encode(const vx_png_item* items /* host array */, int n, const uint8_t* lut, int unlabeled, uint8_t* dst,
+                  int64_t dst_bytes, int64_t* out_offsets /* device */, int64_t* out_sizes /* device */, void* workspace,
+                  size_t ws_bytes, vx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,11 @@ class GzItem(C.Structure):
     _fields_ = [("src", _p), ("n", _i64), ("dst_off", _i64), ("stride_hint", _i32 * 3), ("pad", _i32)]
 
 
+class PngItem(C.Structure):
+    """vx_png_item: one (H, W) uint8 label mask to encode as an RGB PNG (device labels, optional device ignore map)."""
+    _fields_ = [("labels", _p), ("ignore", _p), ("H", _i32), ("W", _i32)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -234,6 +239,9 @@ SIGNATURES = {
     "vx_gzip_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i]),
     "vx_gzip_encode": (_i, [C.POINTER(GzItem), _i, _p, _i64, _p, _p, C.c_size_t, _p]),
     "vx_crc32": (_i, [_p, _i64, _p, _p]),
+    "vx_png_bound": (_i64, [_i, _i]),
+    "vx_png_workspace_bytes": (C.c_size_t, [C.POINTER(PngItem), _i]),
+    "vx_png_encode": (_i, [C.POINTER(PngItem), _i, _p, _i, _p, _i64, _p, _p, _p, C.c_size_t, _p]),
 }
 
 _lib = None

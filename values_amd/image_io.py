@@ -86,29 +86,37 @@ def read_png(path) -> np.ndarray:
 
 
 # ----------------------------------------------------------------------------------------------- TIFF
-def write_tiff_f32(path, img: np.ndarray) -> None:
-    """img (H, W) float32 -> baseline little-endian TIFF: one strip, uncompressed, SampleFormat = IEEE float."""
-    a = np.ascontiguousarray(img, dtype="<f4")
-    if a.ndim != 2:
-        raise ValueError("write_tiff_f32: (H, W) expected")
-    h, w = a.shape
-    data = a.tobytes()
+def tiff_f32_parts(h: int, w: int):
+    """(head, tail) of write_tiff_f32's file for an (h, w) float32 map: the file is head + the map's 4 h w little-endian
+    bytes + tail (8-byte header, the pixel strip, then the IFD).  The 2D device writer (results2d.save_images_device)
+    wraps the map bytes it copies back from the device in these."""
+    nbytes = 4 * h * w
     tags = [  # (tag, type, count, value)   type 3 = SHORT, 4 = LONG
         (256, 4, 1, w), (257, 4, 1, h), (258, 3, 1, 32), (259, 3, 1, 1), (262, 3, 1, 1), (273, 4, 1, 8),
-        (277, 3, 1, 1), (278, 4, 1, h), (279, 4, 1, len(data)), (284, 3, 1, 1), (339, 3, 1, 3),
+        (277, 3, 1, 1), (278, 4, 1, h), (279, 4, 1, nbytes), (284, 3, 1, 1), (339, 3, 1, 3),
     ]
-    ifd_off = 8 + len(data)
+    ifd_off = 8 + nbytes
+    pad = b""
     if ifd_off % 2:
-        data += b"\x00"
+        pad = b"\x00"
         ifd_off += 1
     ifd = struct.pack("<H", len(tags))
     for tag, typ, cnt, val in tags:
         ifd += struct.pack("<HHI", tag, typ, cnt) + (struct.pack("<HH", val, 0) if typ == 3 else struct.pack("<I", val))
     ifd += struct.pack("<I", 0)
+    return b"II*\x00" + struct.pack("<I", ifd_off), pad + ifd
+
+
+def write_tiff_f32(path, img: np.ndarray) -> None:
+    """img (H, W) float32 -> baseline little-endian TIFF: one strip, uncompressed, SampleFormat = IEEE float."""
+    a = np.ascontiguousarray(img, dtype="<f4")
+    if a.ndim != 2:
+        raise ValueError("write_tiff_f32: (H, W) expected")
+    head, tail = tiff_f32_parts(*a.shape)
     with open(path, "wb") as f:
-        f.write(b"II*\x00" + struct.pack("<I", ifd_off))
-        f.write(data)
-        f.write(ifd)
+        f.write(head)
+        f.write(a.tobytes())
+        f.write(tail)
 
 
 def read_tiff_f32(path) -> np.ndarray:

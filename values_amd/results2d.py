@@ -7,17 +7,23 @@ The label -> colour table is the Cityscapes train-id palette extended by the fiv
 GTA/Cityscapes setup (uncertainty_modeling/data/cityscapes_labels.py:59-102, trainId2color; 255 = unlabeled = black).
 Arg-max and colour lookup run on the device (vx_unc_reduce's sample_argmax, vx_colorize_u8); the files are written
 with values_amd.image_io.
+
+save_images_device / ResultsWriter2D write the same tree from the device: one vx_png_encode call builds every PNG file of a
+batch (colour lookup, scanlines, DEFLATE, zlib and PNG framing) and the host only copies the finished bytes back.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
-from .image_io import write_png, write_tiff_f32
+from .image_io import tiff_f32_parts, write_png, write_tiff_f32
+from .results import _Buffers
 
 UNLABELED = 255  # cs_labels.name2trainId["unlabeled"]
 TRAINID2COLOR = {
@@ -82,3 +88,246 @@ def save_uncertainty(save_dir: str, image_id: str, uncertainty_dict: Dict[str, t
         os.makedirs(d, exist_ok=True)
         m = unc_map.detach().cpu().numpy() if isinstance(unc_map, torch.Tensor) else np.asarray(unc_map)
         write_tiff_f32(os.path.join(d, f"{image_id}.tif"), m.astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# device results writer (2D)
+
+class PlannedImage(NamedTuple):
+    """One file of the 2D results tree: path relative to save_dir, kind ("png" / "tif") and source: ("mean", b),
+    ("pred", b, t) with t 0-based, or ("unc", name, b)."""
+    path: str
+    kind: str
+    source: tuple
+
+
+def plan_images(image_ids: Sequence[str], n_pred: int, unc_types: Sequence[str]) -> List[PlannedImage]:
+    """The files save_prediction(<save_dir>/pred_seg, ...) and save_uncertainty(<save_dir>, ...) write for each image, in
+    that order: `<id>_mean.png` then `<id>_01.png`... with several predictions, `<id>_01.png` alone with one; then
+    `<unc_type>/<id>.tif` per uncertainty type."""
+    out = []
+    for b, iid in enumerate(image_ids):
+        if n_pred > 1:
+            out.append(PlannedImage(os.path.join("pred_seg", f"{iid}_mean.png"), "png", ("mean", b)))
+        for t in range(n_pred):
+            out.append(PlannedImage(os.path.join("pred_seg", f"{iid}_{str(t + 1).zfill(2)}.png"), "png", ("pred", b, t)))
+        for name in unc_types:
+            out.append(PlannedImage(os.path.join(name, f"{iid}.tif"), "tif", ("unc", name, b)))
+    return out
+
+
+_luts: Dict[int, torch.Tensor] = {}
+
+
+def _device_lut(dev) -> torch.Tensor:
+    k = dev.index if dev.index is not None else torch.cuda.current_device()
+    if k not in _luts:
+        _luts[k] = torch.from_numpy(_lut()).to(dev)
+    return _luts[k]
+
+
+def _as_device(a, dev, dtype=None):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    t = t.detach().to(dev)
+    return t if dtype is None else t.to(dtype)
+
+
+def png_encode(masks: Sequence[torch.Tensor], ignores: Optional[Sequence] = None) -> List[bytes]:
+    """One RGB PNG file per device (H, W) label mask, coloured like colorize (ignored pixels unlabeled), all in one
+    vx_png_encode call; the shapes may differ.  ignores: per mask an (H, W) map or None."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    labs = [_as_device(m, dev, torch.uint8).contiguous() for m in masks]
+    if not labs:
+        return []
+    igs = [None if g is None else (_as_device(g, dev) != 0).to(torch.uint8).contiguous() for g in (ignores or [None] * len(labs))]
+    items = (_lib.PngItem * len(labs))()
+    bound = 0
+    for i, (lab, ig) in enumerate(zip(labs, igs)):
+        if lab.dim() != 2 or (ig is not None and ig.shape != lab.shape):
+            raise ValueError("png_encode: (H, W) masks and ignore maps of the same shape expected")
+        items[i].labels, items[i].ignore = lab.data_ptr(), None if ig is None else ig.data_ptr()
+        items[i].H, items[i].W = int(lab.shape[0]), int(lab.shape[1])
+        bound += int(lib.vx_png_bound(items[i].H, items[i].W))
+    n = len(labs)
+    dst = torch.empty(bound, dtype=torch.uint8, device=dev)
+    place = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.vx_png_workspace_bytes(items, n)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.vx_png_encode(items, n, _device_lut(dev).data_ptr(), UNLABELED, dst.data_ptr(), dst.numel(),
+                                 place.data_ptr(), place[n:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               "vx_png_encode")
+    pl = place.cpu().tolist()
+    host = dst[:pl[n - 1] + pl[2 * n - 1]].cpu().numpy()
+    return [host[o:o + k].tobytes() for o, k in zip(pl[:n], pl[n:])]
+
+
+def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, timing=None):
+    """vx_png_encode over every mask of the batch + one small read of the file sizes + one copy of the PNG bytes and one
+    of the uncertainty maps into pinned memory: -> (plan, host uint8 array, [(offset, size)] per planned file)"""
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pm = _as_device(pred_masks, dev, torch.uint8)
+    if pm.dim() != 4:
+        raise ValueError(f"save_images_device: pred_masks (B, N, H, W) expected, got {tuple(pm.shape)}")
+    B, N, H, W = (int(v) for v in pm.shape)
+    ids = list(image_ids)
+    if len(ids) != B:
+        raise ValueError(f"save_images_device: {len(ids)} image ids for {B} images")
+    pm = pm.contiguous()
+    mm = None
+    if N > 1:
+        if mean_masks is None:
+            raise ValueError("save_images_device: several predictions need mean_masks")
+        mm = _as_device(mean_masks, dev, torch.uint8).reshape(B, H, W).contiguous()
+    ign = None
+    if ignore_index_map is not None:
+        ign = (_as_device(ignore_index_map, dev) != 0).to(torch.uint8)
+        ign = (ign.expand(B, H, W) if ign.dim() == 2 else ign.reshape(B, H, W)).contiguous()
+    unc = {k: _as_device(v, dev, torch.float32) for k, v in (uncertainty or {}).items()}
+    plan = plan_images(ids, N, list(unc))
+
+    pngs = [f for f in plan if f.kind == "png"]
+    items = (_lib.PngItem * len(pngs))()
+    bound = 0
+    for i, f in enumerate(pngs):
+        b = f.source[1]
+        lab = mm[b] if f.source[0] == "mean" else pm[b, f.source[2]]
+        items[i].labels = lab.data_ptr()
+        items[i].ignore = ign[b].data_ptr() if ign is not None else None
+        items[i].H, items[i].W = H, W
+        bound += int(lib.vx_png_bound(H, W))
+    n = len(pngs)
+    dst = bufs.get("png", bound, dev)
+    place = bufs.get("place", 16 * n, dev)[:16 * n].view(torch.int64)
+    ws = bufs.get("png_ws", int(lib.vx_png_workspace_bytes(items, n)), dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing is not None else None
+    if ev:
+        ev[0].record()
+    _lib.check(lib.vx_png_encode(items, n, _device_lut(dev).data_ptr(), UNLABELED, dst.data_ptr(), dst.numel(),
+                                 place.data_ptr(), place[n:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               "vx_png_encode")
+    if ev:
+        ev[1].record()
+    flat = torch.cat([unc[k][b].reshape(-1) for b in range(B) for k in unc]) if unc else None
+    pl = place.cpu().tolist()              # the one small read: synchronises the stream
+    offs, sizes = pl[:n], pl[n:]
+    png_bytes = offs[-1] + sizes[-1]
+    unc0 = (png_bytes + 15) // 16 * 16
+    total = unc0 + (4 * flat.numel() if flat is not None else 0)
+    host = bufs.get("host", total, dev, pinned=True)
+    host[:png_bytes].copy_(dst[:png_bytes])
+    if flat is not None:
+        host[unc0:total].copy_(flat.view(torch.uint8))
+    if ev:
+        timing["encode_ms"] = timing.get("encode_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timing["raw_bytes"] = timing.get("raw_bytes", 0) + n * H * (3 * W + 1)
+        timing["png_bytes"] = timing.get("png_bytes", 0) + png_bytes
+    spans, k, u = [], 0, unc0
+    for f in plan:
+        if f.kind == "png":
+            spans.append((offs[k], sizes[k]))
+            k += 1
+        else:
+            m = unc[f.source[1]]
+            nb = 4 * int(m[f.source[2]].numel())
+            spans.append((u, nb, tuple(int(v) for v in m.shape[1:])))
+            u += nb
+    return plan, host.numpy(), spans
+
+
+def _make_dirs(save_dir, plan):
+    os.makedirs(os.path.join(save_dir, "pred_seg"), exist_ok=True)
+    for f in plan:
+        os.makedirs(os.path.join(save_dir, os.path.dirname(f.path)), exist_ok=True)
+
+
+def _write_file(path, buf, span):
+    with open(path, "wb") as fh:
+        if len(span) == 2:
+            o, n = span
+            fh.write(memoryview(buf)[o:o + n])
+        else:   # TIFF: host-built header + the map's bytes + IFD
+            o, n, (h, w) = span
+            head, tail = tiff_f32_parts(h, w)
+            fh.write(head)
+            fh.write(memoryview(buf)[o:o + n])
+            fh.write(tail)
+
+
+_shared_bufs = _Buffers()
+_shared_lock = threading.Lock()
+
+
+def save_images_device(save_dir: str, image_ids: Sequence[str], pred_masks, mean_masks, uncertainty: Optional[Dict] = None,
+                       ignore_index_map=None, _timing=None) -> None:
+    """Writes the tree save_prediction(<save_dir>/pred_seg, id, pred_masks[b], mean_masks[b], ignore) and
+    save_uncertainty(<save_dir>, id, {name: map[b]}) write for every image b of a batch, with the same names, the same
+    decoded PNG pixels and byte-identical TIFFs.
+
+    pred_masks (B, N, H, W) uint8 arg-max per prediction, mean_masks (B, H, W) arg-max of the mean prediction (needed when
+    N > 1), uncertainty {name: (B, H, W) float32}, ignore_index_map (B, H, W) or (H, W) (non-zero: unlabeled).  From
+    predict2d, per batch:
+
+        out = process_output_2d(logits)                   # pred_seg (B, H, W): arg-max of the mean; the three maps
+        pm = uncertainty_maps(out["softmax_pred"], want_sample_argmax=True)["sample_argmax"]   # (B, N, H, W)
+        save_images_device(save_dir, ids, pm, out["pred_seg"],
+                           {k: out[k] for k in ("pred_entropy", "aleatoric_uncertainty", "epistemic_uncertainty") if k in out})
+
+    One vx_png_encode call encodes all B (N + 1) masks (B N with one prediction); one small read brings back the file
+    sizes, then the PNG bytes and the uncertainty maps come back in one copy each into reused pinned memory."""
+    with _shared_lock:
+        plan, host, spans = _encode_images(_shared_bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map,
+                                           _timing)
+        _make_dirs(save_dir, plan)
+        for f, sp in zip(plan, spans):
+            _write_file(os.path.join(save_dir, f.path), host, sp)
+
+
+class ResultsWriter2D:
+    """Pipelined save_images_device: submit() encodes a batch on the GPU and hands its files to a small thread pool, so
+    the files of batch i are written while batch i + 1 is encoded.  Two buffer sets alternate; a set is reused only once
+    its files are written.  close() (or leaving the `with` block) waits and re-raises the first write error."""
+
+    def __init__(self, workers: int = 4):
+        if workers < 1:
+            raise ValueError("ResultsWriter2D: workers >= 1")
+        self._pool = ThreadPoolExecutor(max_workers=int(workers))
+        self._bufs = [_Buffers(), _Buffers()]
+        self._pending = [[], []]
+        self._all = []
+        self._n = 0
+        self._closed = False
+
+    def submit(self, save_dir: str, image_ids: Sequence[str], pred_masks, mean_masks, uncertainty: Optional[Dict] = None,
+               ignore_index_map=None, _timing=None) -> None:
+        if self._closed:
+            raise RuntimeError("ResultsWriter2D is closed")
+        k = self._n % 2
+        self._n += 1
+        for f in self._pending[k]:   # the buffer set's previous batch must be on disk before it is overwritten
+            f.exception()
+        plan, host, spans = _encode_images(self._bufs[k], image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map,
+                                           _timing)
+        _make_dirs(save_dir, plan)
+        futs = [self._pool.submit(_write_file, os.path.join(save_dir, f.path), host, sp) for f, sp in zip(plan, spans)]
+        self._pending[k] = futs
+        self._all.extend(futs)
+
+    def close(self) -> None:
+        if self._closed:
+            return
+        self._closed = True
+        self._pool.shutdown(wait=True)
+        for f in self._all:
+            e = f.exception()
+            if e is not None:
+                raise e
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
