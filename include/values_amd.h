@@ -750,6 +750,75 @@ int vx_png_encode(const vx_png_item* items /* host array */, int n, const uint8_
                   int64_t dst_bytes, int64_t* out_offsets /* device */, int64_t* out_sizes /* device */, void* workspace,
                   size_t ws_bytes, vx_stream_t stream);
 
+/* Reading the results tree back (ExperimentDataloader, aggregate_uncertainties, find_threshold: every consumer of
+ * nifti.load; Python: values_amd.gz.gunzip, values_amd.nifti.load_device).
+ *
+ * vx_inflate: decodes each item's compressed bytes (src, src_n: device) into dst[dst_off, dst_off + dst_cap).  format:
+ *   GZIP  RFC 1952, every header flag (FTEXT, FHCRC, FEXTRA, FNAME, FCOMMENT); several members decode to their
+ *         concatenation, zero padding between or after members is skipped (gzip.decompress); each member's CRC-32 and
+ *         ISIZE are checked;
+ *   ZLIB  RFC 1950 with the Adler-32 checked; a preset dictionary is VX_INFLATE_DICT;
+ *   RAW   a bare RFC 1951 stream.
+ *   Statuses are per item: out_status[i] (device) is VX_INFLATE_OK or one of the codes below, out_sizes[i] (device) the
+ *   bytes written into the item's window, also on error.  The return value is reserved for argument errors (refused
+ *   before any launch) and hipError_t.  No input reads outside [src, src + src_n) or writes outside the item's window,
+ *   and every loop of the decoder makes progress on input or output.  The windows must not overlap each other or any
+ *   source.  workspace: vx_inflate_workspace_bytes(n_items) bytes, 16-byte aligned.  Like vx_gzip_encode it uploads its
+ *   descriptor table and synchronises the stream before it launches: not capturable into a hipGraph.
+ * vx_nifti_decode: the inverse of vx_nifti_payload.  Per item, the voxels of a decoded NIfTI-1 payload (src: header +
+ *   voxels in Fortran order at vox_offset, src_n bytes) go to dst as the C-order array nifti.load returns, indexed
+ *   [x, y, z, ...] (ndim 1..7, dims[0..ndim)): byte-swapped when big_endian, and when scaled, v * slope + inter computed
+ *   in the output type (out_dtype VX_F32: float32 operands; VX_F64: float64) as numpy promotes a * slope + inter;
+ *   unscaled, out_dtype is -1 and the elements keep the file's type.  code: the NIfTI datatype (2, 4, 8, 16, 64, 256, 512,
+ *   768, 1024, 1280).  src_n must cover vox_offset + voxels * element size, dst_n the output.  workspace:
+ *   vx_nifti_decode_workspace_bytes(n_items).  Uploads its table and synchronises the stream, as vx_inflate. */
+enum { VX_INFLATE_GZIP = 0, VX_INFLATE_ZLIB = 1, VX_INFLATE_RAW = 2 };
+enum {
+  VX_INFLATE_OK = 0,
+  VX_INFLATE_TRUNCATED = 1,     /* the input ends inside the stream, its header or its trailer */
+  VX_INFLATE_BAD_HEADER = 2,    /* gzip magic / method / reserved flags, zlib method / window / check bits */
+  VX_INFLATE_BAD_BLOCK = 3,     /* block type 3 */
+  VX_INFLATE_BAD_LENGTHS = 4,   /* invalid, over-subscribed or incomplete code lengths; HLIT > 286, HDIST > 30 */
+  VX_INFLATE_BAD_SYMBOL = 5,    /* bits that are no code, literal/length 286 / 287, distance 30 / 31 */
+  VX_INFLATE_BAD_DISTANCE = 6,  /* a distance reaching before the start of the member's output */
+  VX_INFLATE_CAPACITY = 7,      /* the output window is full and the stream has more */
+  VX_INFLATE_BAD_CHECK = 8,     /* CRC-32 (gzip) or Adler-32 (zlib) mismatch */
+  VX_INFLATE_BAD_ISIZE = 9,     /* gzip ISIZE mismatch */
+  VX_INFLATE_TRAILING = 10,     /* bytes after the stream (after zero padding for gzip) */
+  VX_INFLATE_BAD_STORED = 11,   /* stored block whose NLEN is not the complement of LEN */
+  VX_INFLATE_DICT = 12          /* zlib preset dictionary */
+};
+typedef struct vx_inflate_item {
+  const uint8_t* src;
+  int64_t src_n;
+  int64_t dst_off;
+  int64_t dst_cap;
+  int32_t format;
+  int32_t pad;
+} vx_inflate_item;
+int64_t vx_inflate_workspace_bytes(int n_items);
+int vx_inflate(const vx_inflate_item* items /* host array */, int n_items, uint8_t* dst, int64_t dst_n,
+               int64_t* out_sizes /* device */, int32_t* out_status /* device */, void* workspace,
+               int64_t workspace_bytes, vx_stream_t stream);
+
+typedef struct vx_nifti_dec_item {
+  const uint8_t* src;
+  int64_t src_n;
+  int64_t vox_offset;
+  void* dst;
+  int64_t dst_n;
+  int32_t ndim;
+  int32_t dims[7];
+  int32_t code;
+  int32_t big_endian;
+  int32_t out_dtype;   /* -1: the file's type; VX_F32 / VX_F64: scaled */
+  int32_t pad;
+  double slope, inter;
+} vx_nifti_dec_item;
+int64_t vx_nifti_decode_workspace_bytes(int n_items);
+int vx_nifti_decode(const vx_nifti_dec_item* items /* host array */, int n_items, void* workspace,
+                    int64_t workspace_bytes, vx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

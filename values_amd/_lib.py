@@ -145,6 +145,25 @@ class PngItem(C.Structure):
     _fields_ = [("labels", _p), ("ignore", _p), ("H", _i32), ("W", _i32)]
 
 
+class InflateItem(C.Structure):
+    """vx_inflate_item: one compressed stream (device src, src_n bytes) and its output window dst[dst_off, +dst_cap)."""
+    _fields_ = [("src", _p), ("src_n", _i64), ("dst_off", _i64), ("dst_cap", _i64), ("format", _i32), ("pad", _i32)]
+
+
+VX_INFLATE_GZIP, VX_INFLATE_ZLIB, VX_INFLATE_RAW = 0, 1, 2
+INFLATE_STATUS = ("ok", "truncated", "bad header", "bad block type", "invalid code lengths", "bad symbol",
+                  "distance beyond the output start", "output capacity reached", "checksum mismatch", "ISIZE mismatch",
+                  "trailing bytes", "stored block length mismatch", "preset dictionary")
+VX_INFLATE_CAPACITY = 7
+
+
+class NiftiDecItem(C.Structure):
+    """vx_nifti_dec_item: the voxels of one decoded NIfTI payload to a C-order array (out_dtype -1: the file's type)."""
+    _fields_ = [("src", _p), ("src_n", _i64), ("vox_offset", _i64), ("dst", _p), ("dst_n", _i64), ("ndim", _i32),
+                ("dims", _i32 * 7), ("code", _i32), ("big_endian", _i32), ("out_dtype", _i32), ("pad", _i32),
+                ("slope", C.c_double), ("inter", C.c_double)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -242,6 +261,10 @@ SIGNATURES = {
     "vx_png_bound": (_i64, [_i, _i]),
     "vx_png_workspace_bytes": (C.c_size_t, [C.POINTER(PngItem), _i]),
     "vx_png_encode": (_i, [C.POINTER(PngItem), _i, _p, _i, _p, _i64, _p, _p, _p, C.c_size_t, _p]),
+    "vx_inflate_workspace_bytes": (_i64, [_i]),
+    "vx_inflate": (_i, [C.POINTER(InflateItem), _i, _p, _i64, _p, _p, _p, _i64, _p]),
+    "vx_nifti_decode_workspace_bytes": (_i64, [_i]),
+    "vx_nifti_decode": (_i, [C.POINTER(NiftiDecItem), _i, _p, _i64, _p]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 // The container-independent half of the DEFLATE encoder, shared by gzip.hip (gzip members) and png.hip (zlib streams
 // inside PNG files): the chunk kernel that turns 32 KiB of an item into a byte-aligned raw DEFLATE fragment, its
-// shared-memory layout and descriptor structs, and the CRC-32 tables and joins.  gzip.hip's header comment describes
+// shared-memory layout and descriptor structs (the CRC-32 tables and joins are in checksum.h).  gzip.hip's header comment describes
 // the chunk kernel step by step.
 //
 // Everything here has internal linkage (an anonymous namespace): each including file compiles its own copy of the
@@ -9,7 +9,7 @@
 //
 // Every store in this file is a plain C++ store of a vector register.
 #pragma once
-#include "common.h"
+#include "checksum.h"
 
 namespace {
 
@@ -19,7 +19,6 @@ constexpr int GZ_SLICE = GZ_CHUNK / GZ_LANES;   // 128 bytes parsed by each lane
 constexpr int GZ_HBITS = 12;
 constexpr int GZ_HSIZE = 1 << GZ_HBITS;
 constexpr int GZ_SLOT = GZ_CHUNK + 256;   // workspace bytes per chunk output (stored worst case: 5 + 32768)
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
 
 struct GzItemDev {
   const uint8_t* src;
@@ -38,80 +37,6 @@ struct GzChunkMeta {
   uint32_t bytes;
   uint32_t crc;
 };
-
-__host__ __device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
-struct CrcTables {
-  uint32_t byte[256];
-  uint32_t x2n[32];   // x^(2^k) mod P, reflected
-};
-
-constexpr uint32_t crc_multmodp_c(uint32_t a, uint32_t b) {
-  uint32_t m = 1u << 31, p = 0;
-  for (;;) {
-    if (a & m) {
-      p ^= b;
-      if ((a & (m - 1)) == 0) break;
-    }
-    m >>= 1;
-    b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
-  }
-  return p;
-}
-
-constexpr CrcTables make_crc_tables() {
-  CrcTables t{};
-  for (uint32_t i = 0; i < 256; ++i) {
-    uint32_t c = i;
-    for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ CRC_POLY : c >> 1;
-    t.byte[i] = c;
-  }
-  uint32_t p = 1u << 30;   // x^1
-  t.x2n[0] = p;
-  for (int n = 1; n < 32; ++n) t.x2n[n] = p = crc_multmodp_c(p, p);
-  return t;
-}
-
-__constant__ CrcTables kCrc = make_crc_tables();
-
-__device__ uint32_t crc_multmodp(uint32_t a, uint32_t b) {
-  uint32_t m = 1u << 31, p = 0;
-  for (int i = 0; i < 32; ++i) {
-    if (a & m) p ^= b;
-    m >>= 1;
-    b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
-  }
-  return p;
-}
-// x^(8 n) mod P: the operator that shifts a CRC over n zero bytes
-__device__ uint32_t crc_shift_op(uint64_t n) {
-  uint32_t p = 1u << 31;
-  int k = 3;
-  while (n) {
-    if (n & 1) p = crc_multmodp(kCrc.x2n[k & 31], p);
-    n >>= 1;
-    ++k;
-  }
-  return p;
-}
-// crc32(A || B) from crc32(A), crc32(B) and |B|
-__device__ uint32_t crc_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
-  return len_b ? crc_multmodp(crc_shift_op(len_b), crc_a) ^ crc_b : crc_a;
-}
-
-// tree join of the per-lane CRCs of consecutive slices (crc[], len[] in LDS; all lanes of the block call it)
-template <int N>
-__device__ void crc_join_block(uint32_t* crc, uint32_t* len) {
-  const int l = threadIdx.x;
-  for (int stride = 1; stride < N; stride <<= 1) {
-    __syncthreads();
-    if ((l % (2 * stride)) == 0 && l + stride < N) {
-      crc[l] = crc_combine(crc[l], crc[l + stride], len[l + stride]);
-      len[l] += len[l + stride];
-    }
-  }
-  __syncthreads();
-}
 
 // ---------------------------------------------------------------------------------------------
 // Huffman code lengths.  sortkey/sortsym: scratch for n symbols.  Called by one whole wave (64 lanes): the rank sort is

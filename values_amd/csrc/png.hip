@@ -30,7 +30,6 @@ namespace {
 
 constexpr int PNG_FRAME = 63;     // bytes of a file outside its DEFLATE stream
 constexpr int PNG_STREAM0 = 43;   // offset of the DEFLATE stream in the file
-constexpr uint32_t ADLER_BASE = 65521u;
 constexpr int PNG_FRAME_LANES = 1024;
 constexpr int PNG_SCAN_LANES = 1024;
 
@@ -42,16 +41,6 @@ struct PngItemDev {
   int32_t n;               // H * (3 W + 1) < 2^31
   int32_t first_chunk, nchunks, pad;
 };
-
-__device__ __forceinline__ uint32_t adler_combine(uint32_t a1, uint32_t a2, uint64_t len2) {
-  // adler32(A || B): s1 = s1A + s1B - 1, s2 = s2A + s2B + |B| (s1A - 1), mod 65521 (zlib's adler32_combine)
-  const uint64_t B = ADLER_BASE;
-  const uint64_t s1a = a1 & 0xFFFFu, s2a = a1 >> 16, s1b = a2 & 0xFFFFu, s2b = a2 >> 16;
-  const uint64_t r = len2 % B;
-  const uint64_t s1 = (s1a + s1b + B - 1) % B;
-  const uint64_t s2 = (s2a + s2b + r * ((s1a + B - 1) % B)) % B;
-  return (uint32_t)((s2 << 16) | s1);
-}
 
 __global__ __launch_bounds__(256) void png_scanline_kernel(const PngItemDev* __restrict__ items, int n_items,
                                                            const uint8_t* __restrict__ lut, int unlabeled) {

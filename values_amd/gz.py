@@ -86,3 +86,96 @@ def gzip_encode(tensors, stride_hints: Optional[Sequence] = None) -> List[bytes]
     encode_into([(_lib.ptr(v) if v.numel() else None, v.numel(), o, h) for v, o, h in zip(views, offs, hints)], dst, sizes, ws)
     host = dst.cpu().numpy()
     return [host[o:o + int(n)].tobytes() for o, n in zip(offs, sizes.cpu().tolist())]
+
+
+# ---------------------------------------------------------------------------------------------
+# Decoding (values_amd/csrc/inflate.hip: vx_inflate)
+
+FORMATS = {"gzip": _lib.VX_INFLATE_GZIP, "zlib": _lib.VX_INFLATE_ZLIB, "raw": _lib.VX_INFLATE_RAW}
+MAX_RATIO = 1032   # DEFLATE expands at most 1032:1 (258-byte matches of 2 bits); a capacity that always suffices
+ALIGN = 256
+
+
+def _align(n: int) -> int:
+    return (int(n) + ALIGN - 1) // ALIGN * ALIGN
+
+
+def inflate_into(items: List[tuple], device):
+    """items: (device pointer, src_n, format, capacity) -> (dst, offsets, sizes, statuses): one vx_inflate call, item i
+    decoded into dst[offsets[i]:offsets[i] + sizes[i]] (dst: a device uint8 tensor; sizes / statuses: host lists)."""
+    import torch
+    offs, off = [], 0
+    for _, _, _, cap in items:
+        offs.append(off)
+        off += _align(max(int(cap), 1))
+    dst = torch.empty(max(off, 1), dtype=torch.uint8, device=device)
+    if not items:
+        return dst, offs, [], []
+    arr = (_lib.InflateItem * len(items))()
+    for i, (ptr, n, fmt, cap) in enumerate(items):
+        arr[i].src, arr[i].src_n, arr[i].dst_off, arr[i].dst_cap, arr[i].format = ptr, int(n), offs[i], int(cap), int(fmt)
+    res = torch.empty(len(items) * 3, dtype=torch.int32, device=device)   # [sizes (int64) | statuses]
+    sizes = res[:2 * len(items)].view(torch.int64)
+    status = res[2 * len(items):]
+    ws = torch.empty(int(_lib.load().vx_inflate_workspace_bytes(len(items))), dtype=torch.uint8, device=device)
+    _lib.check(_lib.load().vx_inflate(arr, len(items), _lib.ptr(dst), dst.numel(), _lib.ptr(sizes), _lib.ptr(status),
+                                      _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "vx_inflate")
+    host = res.cpu()
+    return dst, offs, host[:2 * len(items)].view(torch.int64).tolist(), host[2 * len(items):].tolist()
+
+
+def status_name(st: int) -> str:
+    return _lib.INFLATE_STATUS[st] if 0 <= st < len(_lib.INFLATE_STATUS) else f"status {st}"
+
+
+def gunzip(blobs, fmt: str = "gzip", sizes: Optional[Sequence[int]] = None, device=None) -> list:
+    """One device uint8 tensor per compressed blob (bytes or a device uint8 tensor), all in one vx_inflate call --
+    the counterpart of gzip_encode.  fmt: "gzip" (several members decode to their concatenation), "zlib" or "raw".
+    sizes: the decoded sizes if known; otherwise a gzip blob's ISIZE trailer, else 4x the input, and an item that
+    fills its window is decoded again with the DEFLATE bound.  A bad stream raises VxError naming the item and the
+    status."""
+    import torch
+    _lib.require_gpu()
+    if fmt not in FORMATS:
+        raise ValueError(f"gunzip: format {fmt!r} (gzip, zlib or raw)")
+    f = FORMATS[fmt]
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    srcs, keep = [], []
+    for b in blobs:
+        if isinstance(b, torch.Tensor):
+            t = _bytes_view(b)
+            srcs.append((t, t[-4:].cpu().numpy().tobytes() if t.numel() >= 4 else b""))
+        else:
+            mv = bytes(b)
+            t = torch.frombuffer(bytearray(mv), dtype=torch.uint8).to(dev) if mv else torch.empty(0, dtype=torch.uint8, device=dev)
+            srcs.append((t, mv[-4:]))
+        keep.append(srcs[-1][0])
+    if not srcs:
+        return []
+    caps = []
+    for i, (t, tail) in enumerate(srcs):
+        if sizes is not None:
+            caps.append(int(sizes[i]))
+        elif f == _lib.VX_INFLATE_GZIP and len(tail) == 4:
+            caps.append(int.from_bytes(tail, "little"))
+        else:
+            caps.append(4 * t.numel() + 1024)
+    items = [(_lib.ptr(t) if t.numel() else None, t.numel(), f, c) for (t, _), c in zip(srcs, caps)]
+    dst, offs, out_n, st = inflate_into(items, dev)
+    out = [None] * len(items)
+    retry = []
+    for i, s in enumerate(st):
+        if s == _lib.VX_INFLATE_CAPACITY and sizes is None:
+            retry.append(i)
+        elif s != 0:
+            raise _lib.VxError(f"gunzip: item {i}: {status_name(s)} (status {s}, {out_n[i]} bytes decoded)")
+        else:
+            out[i] = dst[offs[i]:offs[i] + out_n[i]]
+    if retry:
+        items2 = [(items[i][0], items[i][1], f, MAX_RATIO * items[i][1] + 64) for i in retry]
+        dst2, offs2, n2, st2 = inflate_into(items2, dev)
+        for k, i in enumerate(retry):
+            if st2[k] != 0:
+                raise _lib.VxError(f"gunzip: item {i}: {status_name(st2[k])} (status {st2[k]}, {n2[k]} bytes decoded)")
+            out[i] = dst2[offs2[k]:offs2[k] + n2[k]].clone()
+    return out

@@ -88,7 +88,8 @@ def get_foreground_quantile(exp_dataloader) -> Dict:
     all_quantiles = []
     for image_id in exp_dataloader.image_ids:
         for pred_seg in exp_dataloader.get_pred_segs(image_id):
-            all_quantiles.append(calculate_foreground_quantile_image(np.asarray(pred_seg)))
+            img = pred_seg if isinstance(pred_seg, torch.Tensor) else np.asarray(pred_seg)   # device tensors: DeviceExperimentDataloader
+            all_quantiles.append(calculate_foreground_quantile_image(img))
     return {exp_dataloader.exp_version.pred_model: {exp_dataloader.exp_version.version_name: all_quantiles}}
 
 
@@ -125,9 +126,12 @@ def calculate_threshold_image(quantile_path, image, method: str) -> float:
     return quantile(t, all_quantiles[method])
 
 
-def find_threshold(results_dict: Dict, quantile_path, save_path, loader=None) -> Dict:
+def find_threshold(results_dict: Dict, quantile_path, save_path, loader=None, device_io: bool = False,
+                   batch: int = 64) -> Dict:
     """find_threshold.py:69-117.  results_dict: {pred_model: {version: {unc_type: [paths]}}} (threshold_images_paths,
-    merged over versions).  Maps are read with the package's NIfTI reader unless `loader(path) -> array` is given."""
+    merged over versions).  Maps are read with the package's NIfTI reader unless `loader(path) -> array` is given;
+    device_io=True reads them with nifti.load_device (`batch` files per call), casts them to float32 and joins them on
+    the device: the same thresholds."""
     if not os.path.isfile(quantile_path):
         quantile_path = Path(quantile_path) / "quantile_analysis.json"
     if not os.path.isfile(save_path):
@@ -143,7 +147,11 @@ def find_threshold(results_dict: Dict, quantile_path, save_path, loader=None) ->
     for pred_model, uncs in per_model.items():
         threshold_dict[pred_model] = {}
         for unc, paths in uncs.items():
-            maps = [np.asarray(load(p), dtype=np.float32) for p in paths]
+            if device_io and loader is None:
+                maps = torch.cat([t.reshape(-1).to(torch.float32) for i in range(0, len(paths), batch)
+                                  for t, _ in nifti.load_device(paths[i:i + batch])])
+            else:
+                maps = [np.asarray(load(p), dtype=np.float32) for p in paths]
             thr = calculate_threshold_image(quantile_path, maps, pred_model)
             threshold_dict[pred_model][f"Mean {unc.split('_')[0]} threshold"] = thr
     al, ep, pr = [], [], []
