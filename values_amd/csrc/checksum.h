@@ -1,4 +1,4 @@
-// Checksums of the DEFLATE containers, shared by the encoders (deflate_chunk.h: gzip.hip, png.hip) and the decoder
+// Checksums of the DEFLATE containers, shared by the encoders (deflate_chunk.hip, gzip.hip, png.hip) and the decoder
 // (inflate.hip): CRC-32 (gzip members, PNG chunks) with its GF(2) shift and join operators, and the Adler-32 join (zlib
 // streams).  Internal linkage: each including file compiles its own copy.
 #pragma once

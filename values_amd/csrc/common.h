@@ -33,6 +33,17 @@ const char* vx_kname(const char* fmt, ...);   // lib.cpp: the environment is rea
   } while (0)
 
 static inline bool vx_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+static inline size_t vx_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Copies a launcher's host-built table into (the head of) its workspace.  The table is the launcher's own host copy,
+// freed when it returns, and hipMemcpyAsync from pageable memory may return before the bytes have left it: wait for the
+// copy.  `who` is the launcher's name, `what` the word its message uses ("descriptor upload" / "table upload").
+static inline int vx_upload_table(const char* who, const char* what, void* dst, const void* table, size_t bytes, hipStream_t s) {
+  hipError_t e = hipMemcpyAsync(dst, table, bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) VX_FAIL((int)e, "%s: %s: %s", who, what, hipGetErrorString(e));
+  return VX_OK;
+}
 
 // compute units of the current device (256 on a whole MI355X; a compute partition has fewer): the persistent kernels launch one
 // workgroup per CU.  One process drives one device, so the first answer is kept.

@@ -20,8 +20,8 @@
 //     before it; it copies its bytes behind the 10-byte header, the first chunk writes the header and the last the
 //     CRC-32 / ISIZE trailer and the member's size.
 //
-// The chunk kernel, its structs and the CRC-32 helpers live in deflate_chunk.h (shared with png.hip); this file keeps
-// the gzip framing: the pack kernel, vx_crc32 and the launchers.
+// The chunk kernel is compiled in deflate_chunk.hip and launched through deflate_chunk.h (shared with png.hip), the CRC-32
+// helpers live in checksum.h; this file keeps the gzip framing: the pack kernel, vx_crc32 and the launchers.
 //
 // Every store in this file is a plain C++ store of a vector register.
 #include <vector>
@@ -118,7 +118,7 @@ extern "C" size_t vx_gzip_workspace_bytes(const int64_t* sizes, int n_items) {
     if (sizes[i] < 0) return 0;
     nch += gz_nchunks(sizes[i]);
   }
-  return align256(sizeof(GzItemDev) * n_items) + align256(sizeof(GzChunkDev) * nch) + align256(sizeof(GzChunkMeta) * nch) +
+  return vx_align256(sizeof(GzItemDev) * n_items) + vx_align256(sizeof(GzChunkDev) * nch) + vx_align256(sizeof(GzChunkMeta) * nch) +
          (size_t)nch * GZ_SLOT;
 }
 
@@ -142,43 +142,21 @@ extern "C" int vx_gzip_encode(const vx_gz_item* items, int n_items, uint8_t* dst
   }
   const size_t need = vx_gzip_workspace_bytes(sizes.data(), n_items);
   if (ws_bytes < need) VX_FAIL(VX_E_WORKSPACE, "vx_gzip_encode: workspace %zu < %zu bytes", ws_bytes, need);
-  // descriptor tables: built here, uploaded into the head of the workspace (pageable source: the copy is staged before
-  // hipMemcpyAsync returns)
-  std::vector<GzItemDev> di(n_items);
-  std::vector<GzChunkDev> dc;
-  for (int i = 0; i < n_items; ++i) {
-    const vx_gz_item& g = items[i];
-    di[i].src = (const uint8_t*)g.src;
-    di[i].n = g.n;
-    di[i].dst_off = g.dst_off;
-    for (int k = 0; k < 3; ++k) di[i].hint[k] = g.stride_hint[k];
-    di[i].first_chunk = (int32_t)dc.size();
-    di[i].nchunks = (int32_t)gz_nchunks(g.n);
-    di[i].pad = 0;
-    for (int k = 0; k < di[i].nchunks; ++k) dc.push_back(GzChunkDev{i, k});
-  }
-  const size_t nch = dc.size();
+  // descriptor tables, built in one host block laid out like the head of the workspace and uploaded in one copy
+  int64_t nch = 0;
+  for (int i = 0; i < n_items; ++i) nch += gz_nchunks(items[i].n);
+  const size_t chunks_at = vx_align256(sizeof(GzItemDev) * n_items);
+  std::vector<uint8_t> head(chunks_at + sizeof(GzChunkDev) * nch, 0);
+  gz_fill_tables(items, n_items, (GzItemDev*)head.data(), (GzChunkDev*)(head.data() + chunks_at));
   uint8_t* ws = (uint8_t*)workspace;
   GzItemDev* d_items = (GzItemDev*)ws;
-  ws += align256(sizeof(GzItemDev) * n_items);
-  GzChunkDev* d_chunks = (GzChunkDev*)ws;
-  ws += align256(sizeof(GzChunkDev) * nch);
+  GzChunkDev* d_chunks = (GzChunkDev*)(ws + chunks_at);
+  ws += chunks_at + vx_align256(sizeof(GzChunkDev) * nch);
   GzChunkMeta* d_meta = (GzChunkMeta*)ws;
-  ws += align256(sizeof(GzChunkMeta) * nch);
-  uint8_t* d_slots = ws;
+  uint8_t* d_slots = ws + vx_align256(sizeof(GzChunkMeta) * nch);
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(d_items, di.data(), sizeof(GzItemDev) * n_items, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_chunks, dc.data(), sizeof(GzChunkDev) * nch, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);   // the host tables are freed on return
-  if (e != hipSuccess) VX_FAIL((int)e, "vx_gzip_encode: descriptor upload: %s", hipGetErrorString(e));
-  static bool attr_set = false;
-  if (!attr_set) {
-    e = hipFuncSetAttribute((const void*)gz_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GzShared));
-    if (e != hipSuccess) VX_FAIL((int)e, "vx_gzip_encode: LDS attribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gz_chunk_kernel, dim3((unsigned)nch), dim3(GZ_LANES), sizeof(GzShared), s, d_items, d_chunks, d_meta, d_slots);
-  VX_CHECK_LAUNCH("vx_gzip_encode: chunks");
+  if (int rc = vx_upload_table("vx_gzip_encode", "descriptor upload", workspace, head.data(), head.size(), s)) return rc;
+  if (int rc = gz_launch_chunks("vx_gzip_encode", d_items, d_chunks, d_meta, d_slots, nch, s)) return rc;
   hipLaunchKernelGGL(gz_pack_kernel, dim3((unsigned)nch), dim3(256), 0, s, d_items, d_chunks, d_meta, d_slots, dst, out_sizes);
   VX_CHECK_LAUNCH("vx_gzip_encode: pack");
   return VX_OK;

@@ -310,13 +310,11 @@ __global__ __launch_bounds__(IF_LANES) void inflate_kernel(const InfItemDev* __r
   }
 }
 
-size_t if_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int64_t vx_inflate_workspace_bytes(int n_items) {
   if (n_items < 0) return -1;
-  return 256 + (int64_t)if_align256(sizeof(InfItemDev) * (size_t)(n_items > 0 ? n_items : 1));
+  return 256 + (int64_t)vx_align256(sizeof(InfItemDev) * (size_t)(n_items > 0 ? n_items : 1));
 }
 
 extern "C" int vx_inflate(const vx_inflate_item* items, int n_items, uint8_t* dst, int64_t dst_n, int64_t* out_sizes,
@@ -355,10 +353,7 @@ extern "C" int vx_inflate(const vx_inflate_item* items, int n_items, uint8_t* ds
   std::vector<uint8_t> table(256 + sizeof(InfItemDev) * n_items, 0);   // [counter | items]
   memcpy(table.data() + 256, di.data(), sizeof(InfItemDev) * n_items);
   hipStream_t s = (hipStream_t)stream;
-  // the table is uploaded from this function's own host copy, which is freed on return: wait for the copy
-  hipError_t e = hipMemcpyAsync(workspace, table.data(), table.size(), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) VX_FAIL((int)e, "vx_inflate: table upload: %s", hipGetErrorString(e));
+  if (int rc = vx_upload_table("vx_inflate", "table upload", workspace, table.data(), table.size(), s)) return rc;
   const int grid = std::min(n_items, vx_cu_count() * IF_WAVES_PER_CU);
   hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)grid), dim3(IF_LANES), 0, s,
                      (const InfItemDev*)((uint8_t*)workspace + 256), n_items, (int*)workspace, dst, out_sizes, out_status);

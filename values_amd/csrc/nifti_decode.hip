@@ -205,10 +205,7 @@ extern "C" int vx_nifti_decode(const vx_nifti_dec_item* items, int n_items, void
   if (blocks > 0x7FFFFFFF) VX_FAIL(VX_E_SHAPE, "vx_nifti_decode: %lld workgroups", (long long)blocks);
   if (blocks == 0) return VX_OK;
   hipStream_t s = (hipStream_t)stream;
-  // the table is uploaded from this function's own host copy, which is freed on return: wait for the copy
-  hipError_t e = hipMemcpyAsync(workspace, di.data(), sizeof(NdItemDev) * n_items, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) VX_FAIL((int)e, "vx_nifti_decode: table upload: %s", hipGetErrorString(e));
+  if (int rc = vx_upload_table("vx_nifti_decode", "table upload", workspace, di.data(), sizeof(NdItemDev) * n_items, s)) return rc;
   hipLaunchKernelGGL(nifti_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const NdItemDev*)workspace, n_items);
   VX_CHECK_LAUNCH("vx_nifti_decode");
   return VX_OK;

@@ -178,10 +178,7 @@ extern "C" int vx_nifti_payload(const vx_nifti_item* items, int n_items, uint8_t
   if (ws_bytes < need) VX_FAIL(VX_E_WORKSPACE, "vx_nifti_payload: workspace %zu < %zu bytes", ws_bytes, need);
   NpItemDev* d_items = (NpItemDev*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  // the table is uploaded from this function's own host copy, which is freed on return: wait for the copy
-  hipError_t e = hipMemcpyAsync(d_items, di.data(), need, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) VX_FAIL((int)e, "vx_nifti_payload: table upload: %s", hipGetErrorString(e));
+  if (int rc = vx_upload_table("vx_nifti_payload", "table upload", d_items, di.data(), need, s)) return rc;
   hipLaunchKernelGGL(nifti_payload_kernel, dim3((unsigned)tiles), dim3(256), 0, s, d_items, n_items, dst);
   VX_CHECK_LAUNCH("vx_nifti_payload");
   return VX_OK;

@@ -8,7 +8,7 @@
 //     exactly the bytes write_png hands to zlib.  HBM-bound.
 //   png_adler_kernel    (one workgroup per 32 KiB chunk): Adler-32 of the chunk's raw bytes -- 128-byte lane slices,
 //     then a tree join with adler_combine.
-//   gz_chunk_kernel     (deflate_chunk.h, shared with gzip.hip, unchanged): one byte-aligned raw DEFLATE fragment per
+//   gz_chunk_kernel     (deflate_chunk.hip, shared with gzip.hip): one byte-aligned raw DEFLATE fragment per
 //     chunk, stride hints (3, 3W + 1, 0): the previous pixel and the previous scanline.
 //   png_scan_kernel     (one workgroup): exclusive scan of the fragments' sizes over the whole batch.  File i starts at
 //     the sum of the streams before it plus 63 bytes of framing per earlier file; out_offsets / out_sizes are written.
@@ -240,16 +240,16 @@ struct PngLayout {
 PngLayout png_layout(const vx_png_item* items, int n, int64_t nch) {
   PngLayout L{};
   size_t o = 0;
-  L.items = o; o += align256(sizeof(PngItemDev) * n);
-  L.gz_items = o; o += align256(sizeof(GzItemDev) * n);
-  L.chunks = o; o += align256(sizeof(GzChunkDev) * nch);
+  L.items = o; o += vx_align256(sizeof(PngItemDev) * n);
+  L.gz_items = o; o += vx_align256(sizeof(GzItemDev) * n);
+  L.chunks = o; o += vx_align256(sizeof(GzChunkDev) * nch);
   L.head = o;
-  L.meta = o; o += align256(sizeof(GzChunkMeta) * nch);
-  L.adler = o; o += align256(sizeof(uint32_t) * nch);
-  L.chunk_off = o; o += align256(sizeof(int64_t) * nch);
+  L.meta = o; o += vx_align256(sizeof(GzChunkMeta) * nch);
+  L.adler = o; o += vx_align256(sizeof(uint32_t) * nch);
+  L.chunk_off = o; o += vx_align256(sizeof(int64_t) * nch);
   L.slots = o; o += (size_t)nch * GZ_SLOT;
   L.raw = o;
-  for (int i = 0; i < n; ++i) o += align256((size_t)png_raw_bytes(items[i].H, items[i].W));
+  for (int i = 0; i < n; ++i) o += vx_align256((size_t)png_raw_bytes(items[i].H, items[i].W));
   L.total = o;
   return L;
 }
@@ -296,13 +296,10 @@ extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut
   if (ws_bytes < L.total) VX_FAIL(VX_E_WORKSPACE, "vx_png_encode: workspace %zu < %zu bytes", ws_bytes, L.total);
 
   // descriptor tables, built in one host block laid out like the head of the workspace and uploaded in one copy
-  // (pageable source: the copy is staged before hipMemcpyAsync returns; the stream is synchronised before the block is
-  // freed)
   uint8_t* ws = (uint8_t*)workspace;
   std::vector<uint8_t> head(L.head, 0);
   PngItemDev* pi = reinterpret_cast<PngItemDev*>(head.data() + L.items);
-  GzItemDev* gi = reinterpret_cast<GzItemDev*>(head.data() + L.gz_items);
-  GzChunkDev* gc = reinterpret_cast<GzChunkDev*>(head.data() + L.chunks);
+  std::vector<vx_gz_item> recs(n);   // each item's scanline buffer as the chunk kernel's input
   size_t raw = L.raw;
   int32_t c = 0, max_words = 1;
   for (int i = 0; i < n; ++i) {
@@ -311,30 +308,16 @@ extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut
     const int32_t k = (int32_t)gz_nchunks(nb);
     pi[i] = PngItemDev{g.labels, g.ignore, ws + raw, g.H, g.W, nb, c, k, 0};
     const int64_t row = 3 * (int64_t)g.W + 1;
-    gi[i].src = ws + raw;
-    gi[i].n = nb;
-    gi[i].dst_off = 0;
-    gi[i].hint[0] = 3;
-    gi[i].hint[1] = row <= GZ_CHUNK ? (int32_t)row : 0;   // the previous scanline, while within the window
-    gi[i].hint[2] = 0;
-    gi[i].first_chunk = c;
-    gi[i].nchunks = k;
-    gi[i].pad = 0;
-    for (int j = 0; j < k; ++j) gc[c + j] = GzChunkDev{i, j};
+    // stride hints: the previous pixel and, while within the window, the previous scanline
+    recs[i] = vx_gz_item{ws + raw, nb, 0, {3, row <= GZ_CHUNK ? (int32_t)row : 0, 0}, 0};
     c += k;
-    raw += align256((size_t)nb);
+    raw += vx_align256((size_t)nb);
     max_words = max(max_words, (nb + 3) / 4);
   }
+  gz_fill_tables(recs.data(), n, reinterpret_cast<GzItemDev*>(head.data() + L.gz_items),
+                 reinterpret_cast<GzChunkDev*>(head.data() + L.chunks));
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemcpyAsync(ws, head.data(), L.head, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) VX_FAIL((int)e, "vx_png_encode: descriptor upload: %s", hipGetErrorString(e));
-  static bool attr_set = false;   // this file's copy of the chunk kernel
-  if (!attr_set) {
-    e = hipFuncSetAttribute((const void*)gz_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GzShared));
-    if (e != hipSuccess) VX_FAIL((int)e, "vx_png_encode: LDS attribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  if (int rc = vx_upload_table("vx_png_encode", "descriptor upload", ws, head.data(), L.head, s)) return rc;
   const PngItemDev* d_items = (const PngItemDev*)(ws + L.items);
   const GzItemDev* d_gz = (const GzItemDev*)(ws + L.gz_items);
   const GzChunkDev* d_chunks = (const GzChunkDev*)(ws + L.chunks);
@@ -348,8 +331,7 @@ extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut
   VX_CHECK_LAUNCH("vx_png_encode: scanlines");
   hipLaunchKernelGGL(png_adler_kernel, dim3((unsigned)nch), dim3(GZ_LANES), 0, s, d_gz, d_chunks, d_adler);
   VX_CHECK_LAUNCH("vx_png_encode: adler");
-  hipLaunchKernelGGL(gz_chunk_kernel, dim3((unsigned)nch), dim3(GZ_LANES), sizeof(GzShared), s, d_gz, d_chunks, d_meta, d_slots);
-  VX_CHECK_LAUNCH("vx_png_encode: chunks");
+  if (int rc = gz_launch_chunks("vx_png_encode", d_gz, d_chunks, d_meta, d_slots, nch, s)) return rc;
   hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(PNG_SCAN_LANES), 0, s, d_items, n, d_chunks, d_meta, nch, d_off,
                      out_offsets, out_sizes);
   VX_CHECK_LAUNCH("vx_png_encode: scan");

@@ -146,10 +146,10 @@ class ExperimentDataloader:
         return nifti.load(self.unc_path_dict[unc_type] / f"{image_id}{self.exp_version.unc_ending}")[0]
 
 
-def aggregate_uncertainties(exp_dataloader: ExperimentDataloader, aggregations):
-    """aggregate_uncertainties.py:70-95: for every uncertainty type, image and aggregation config
-    ({"_target_": ..., **params}) -> aggregated_<unc>.json.  `_target_`s naming the reference's functions are
-    re-pointed to values_amd.aggregation (GPU)."""
+def _aggregate(exp_dataloader, aggregations, images_of):
+    """aggregated_<unc>.json for every uncertainty type; images_of(unc_path, keys) yields the (key, image) pairs of a type's
+    files, each image loaded once (the reference reloads per aggregation).  `_target_`s naming the reference's functions
+    are re-pointed to values_amd.aggregation (GPU)."""
     from .io import TARGET_MAP
     ref = "evaluation.uncertainty_aggregation.aggregate_uncertainties."
     for fn in ("patch_level_aggregation", "image_level_aggregation", "threshold_aggregation"):
@@ -158,15 +158,19 @@ def aggregate_uncertainties(exp_dataloader: ExperimentDataloader, aggregations):
     ending = exp_dataloader.exp_version.unc_ending
     for unc, unc_path in exp_dataloader.unc_path_dict.items():
         all_uncs = {}
-        for image_id in exp_dataloader.image_ids:
-            key = f"{image_id}{ending}"
+        for key, unc_image in images_of(unc_path, [f"{image_id}{ending}" for image_id in exp_dataloader.image_ids]):
             all_uncs[key] = {}
-            unc_image, _ = nifti.load(unc_path / key)  # loaded once per image (the reference reloads per aggregation)
             for name, cfg in aggregations.items():
                 all_uncs[key][name] = instantiate(dict(cfg), image=unc_image,
                                                   pred_model=exp_dataloader.exp_version.pred_model, unc_type=unc)
         with open(exp_dataloader.dataset_path / f"aggregated_{unc}.json", "w") as f:
             json.dump(all_uncs, f, indent=4)
+
+
+def aggregate_uncertainties(exp_dataloader: ExperimentDataloader, aggregations):
+    """aggregate_uncertainties.py:70-95: for every uncertainty type, image and aggregation config
+    ({"_target_": ..., **params}) -> aggregated_<unc>.json."""
+    _aggregate(exp_dataloader, aggregations, lambda unc_path, keys: ((k, nifti.load(unc_path / k)[0]) for k in keys))
 
 
 class DeviceExperimentDataloader(ExperimentDataloader):
@@ -246,22 +250,11 @@ def aggregate_uncertainties_device(exp_dataloader: ExperimentDataloader, aggrega
     """aggregate_uncertainties with the maps read on the device: every map of a type is read with nifti.NiftiReader,
     `batch` files per call, and handed to the aggregations as a device tensor.  Writes the same aggregated_<unc>.json,
     byte for byte."""
-    from .io import TARGET_MAP
-    ref = "evaluation.uncertainty_aggregation.aggregate_uncertainties."
-    for fn in ("patch_level_aggregation", "image_level_aggregation", "threshold_aggregation"):
-        TARGET_MAP.setdefault(ref + fn, "values_amd.aggregation." + fn)
-        TARGET_MAP.setdefault("uncertainty_aggregation.aggregate_uncertainties." + fn, "values_amd.aggregation." + fn)
-    ending = exp_dataloader.exp_version.unc_ending
     with nifti.NiftiReader() as reader:
-        for unc, unc_path in exp_dataloader.unc_path_dict.items():
-            keys = [f"{image_id}{ending}" for image_id in exp_dataloader.image_ids]
+        def images_of(unc_path, keys):
             chunks = _chunks(keys, batch)
-            all_uncs = {}
             for chunk, res in zip(chunks, reader.read([[unc_path / k for k in c] for c in chunks])):
                 for key, (unc_image, _) in zip(chunk, res):
-                    all_uncs[key] = {}
-                    for name, cfg in aggregations.items():
-                        all_uncs[key][name] = instantiate(dict(cfg), image=unc_image,
-                                                          pred_model=exp_dataloader.exp_version.pred_model, unc_type=unc)
-            with open(exp_dataloader.dataset_path / f"aggregated_{unc}.json", "w") as f:
-                json.dump(all_uncs, f, indent=4)
+                    yield key, unc_image
+
+        _aggregate(exp_dataloader, aggregations, images_of)

@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import gzip
 import struct
+import threading
 
 import numpy as np
 
@@ -276,16 +277,8 @@ def _decode(names, raws, device, staging, timing=None):
     return [(o, h.header) for o, h in zip(outs, heads)]
 
 
-_POOL = None
-_STAGING = None
-
-
-def _pool():
-    global _POOL
-    if _POOL is None:
-        from concurrent.futures import ThreadPoolExecutor
-        _POOL = ThreadPoolExecutor(max_workers=8)
-    return _POOL
+_shared = None   # load_device's reader: its thread pool and pinned staging buffer, used by one call at a time
+_shared_lock = threading.Lock()
 
 
 def load_device(paths, device=None, _timing=None):
@@ -295,16 +288,17 @@ def load_device(paths, device=None, _timing=None):
     ISIZE trailers), the voxels decoded in one vx_nifti_decode call."""
     import torch
     from . import _lib
-    global _STAGING
+    global _shared
     _lib.require_gpu()
     paths = [str(p) for p in paths]
     if not paths:
         return []
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    raws = list(_pool().map(_read, paths))
-    if _STAGING is None:
-        _STAGING = _Staging()
-    return _decode(paths, raws, dev, _STAGING, _timing)
+    with _shared_lock:
+        if _shared is None:
+            _shared = NiftiReader()
+        raws = list(_shared._pool.map(_read, paths))
+        return _decode(paths, raws, dev, _shared._staging, _timing)
 
 
 class NiftiReader:

@@ -13,13 +13,11 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
-import threading
-from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 
-from . import nifti
+from . import _devio, nifti
 
 
 def _np(t):
@@ -163,23 +161,7 @@ def _copy_source(t, dtype: np.dtype):
     return t.permute(*reversed(range(len(shp)))).contiguous(), 1, 1, int(np.prod(shp))
 
 
-class _Buffers:
-    """device payload / member / workspace buffers and the pinned host buffer of one case in flight (grown, never shrunk)"""
-
-    def __init__(self):
-        self.t = {}
-
-    def get(self, name, nbytes, dev, pinned=False):
-        import torch
-        b = self.t.get(name)
-        if b is None or b.numel() < nbytes:
-            n = max(int(nbytes * 1.25), 1 << 16)
-            b = torch.empty(n, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(n, dtype=torch.uint8, device=dev)
-            self.t[name] = b
-        return b
-
-
-def _encode_case(bufs: _Buffers, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header, timing=None):
+def _encode_case(bufs, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header, timing=None):
     """payload launch + encode launch + one D2H copy: -> (plan, host uint8 array, [(offset, size)])"""
     import torch
     from . import _lib, gz
@@ -268,20 +250,7 @@ def _encode_case(bufs: _Buffers, image_id, softmax_pred, maps, data, gt_seg, num
     return plan, host.numpy(), list(zip(slots, host_sizes))
 
 
-def _make_dirs(save_dir, plan):
-    for d in ("input", "gt_seg", "pred_seg", "pred_prob"):   # save_case creates these four whatever it writes
-        os.makedirs(os.path.join(save_dir, d), exist_ok=True)
-    for f in plan:
-        os.makedirs(os.path.join(save_dir, os.path.dirname(f.path)), exist_ok=True)
-
-
-def _write(path, buf, off, n):
-    with open(path, "wb") as fh:
-        fh.write(memoryview(buf)[off:off + n])
-
-
-_shared_bufs = _Buffers()
-_shared_lock = threading.Lock()
+_DIRS = ("input", "gt_seg", "pred_seg", "pred_prob")   # save_case creates these four whatever it writes
 
 
 def save_case_device(save_dir: str, image_id: str, softmax_pred, maps: Optional[Dict] = None, data=None, gt_seg=None,
@@ -290,59 +259,21 @@ def save_case_device(save_dir: str, image_id: str, softmax_pred, maps: Optional[
     are used where they are; numpy arrays and CPU tensors are uploaded.  One vx_nifti_payload launch assembles every
     payload, one vx_gzip_encode compresses them, one copy brings the members back into reused pinned memory, and the
     host writes the files."""
-    with _shared_lock:
-        plan, host, spans = _encode_case(_shared_bufs, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header,
-                                         _timing)
-        _make_dirs(save_dir, plan)
-        for f, (o, n) in zip(plan, spans):
-            _write(os.path.join(save_dir, f.path), host, o, n)
+    _devio.save_once(save_dir, _DIRS, _encode_case, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header,
+                     _timing)
 
 
-class ResultsWriter:
+class ResultsWriter(_devio.PipelinedWriter):
     """Pipelined save_case_device: submit() encodes a case on the GPU and hands its files to a small thread pool, so the
     files of case i are written while case i + 1 is encoded.  Two buffer sets alternate; a set is reused only once its
     files are written.  close() (or leaving the `with` block) waits and re-raises the first write error."""
 
-    def __init__(self, workers: int = 4):
-        if workers < 1:
-            raise ValueError("ResultsWriter: workers >= 1")
-        self._pool = ThreadPoolExecutor(max_workers=int(workers))
-        self._bufs = [_Buffers(), _Buffers()]
-        self._pending = [[], []]
-        self._all = []
-        self._n = 0
-        self._closed = False
+    _encode = staticmethod(_encode_case)
+    _dirs = _DIRS
 
     def submit(self, save_dir: str, image_id: str, softmax_pred, maps: Optional[Dict] = None, data=None, gt_seg=None,
                num_predictions=None, header=False) -> None:
-        if self._closed:
-            raise RuntimeError("ResultsWriter is closed")
-        k = self._n % 2
-        self._n += 1
-        for f in self._pending[k]:   # the buffer set's previous case must be on disk before it is overwritten
-            f.exception()
-        plan, host, spans = _encode_case(self._bufs[k], image_id, softmax_pred, maps, data, gt_seg, num_predictions, header)
-        _make_dirs(save_dir, plan)
-        futs = [self._pool.submit(_write, os.path.join(save_dir, f.path), host, o, n) for f, (o, n) in zip(plan, spans)]
-        self._pending[k] = futs
-        self._all.extend(futs)
-
-    def close(self) -> None:
-        if self._closed:
-            return
-        self._closed = True
-        self._pool.shutdown(wait=True)
-        for f in self._all:
-            e = f.exception()
-            if e is not None:
-                raise e
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+        self._submit(save_dir, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header)
 
 
 def results_dir(root_dir: str, exp_name: str, version, test_split: str = "id") -> str:

@@ -14,16 +14,13 @@ batch (colour lookup, scanlines, DEFLATE, zlib and PNG framing) and the host onl
 from __future__ import annotations
 
 import os
-import threading
-from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _devio, _lib
 from .image_io import tiff_f32_parts, write_png, write_tiff_f32
-from .results import _Buffers
 
 UNLABELED = 255  # cs_labels.name2trainId["unlabeled"]
 TRAINID2COLOR = {
@@ -132,31 +129,45 @@ def _as_device(a, dev, dtype=None):
     return t if dtype is None else t.to(dtype)
 
 
+def _png_table(entries):
+    """the vx_png_item table of (labels_ptr, ignore_ptr or None, H, W) entries -> (table, sum of vx_png_bound, workspace bytes)"""
+    lib = _lib.load()
+    items = (_lib.PngItem * len(entries))()
+    bound = 0
+    for it, (lab, ig, H, W) in zip(items, entries):
+        it.labels, it.ignore, it.H, it.W = lab, ig, H, W
+        bound += int(lib.vx_png_bound(H, W))
+    return items, bound, int(lib.vx_png_workspace_bytes(items, len(entries)))
+
+
+def _png_launch(items, dst, place, ws):
+    """vx_png_encode of a _png_table into dst (uint8); place (int64, two per item) receives the files' offsets, then their
+    sizes; ws: the workspace.  All three are device tensors, freshly made or cut from a buffer set."""
+    n = len(items)
+    _lib.check(_lib.load().vx_png_encode(items, n, _device_lut(dst.device).data_ptr(), UNLABELED, dst.data_ptr(), dst.numel(),
+                                         place.data_ptr(), place[n:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               "vx_png_encode")
+
+
 def png_encode(masks: Sequence[torch.Tensor], ignores: Optional[Sequence] = None) -> List[bytes]:
     """One RGB PNG file per device (H, W) label mask, coloured like colorize (ignored pixels unlabeled), all in one
     vx_png_encode call; the shapes may differ.  ignores: per mask an (H, W) map or None."""
     _lib.require_gpu()
-    lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device())
     labs = [_as_device(m, dev, torch.uint8).contiguous() for m in masks]
     if not labs:
         return []
     igs = [None if g is None else (_as_device(g, dev) != 0).to(torch.uint8).contiguous() for g in (ignores or [None] * len(labs))]
-    items = (_lib.PngItem * len(labs))()
-    bound = 0
-    for i, (lab, ig) in enumerate(zip(labs, igs)):
+    entries = []
+    for lab, ig in zip(labs, igs):
         if lab.dim() != 2 or (ig is not None and ig.shape != lab.shape):
             raise ValueError("png_encode: (H, W) masks and ignore maps of the same shape expected")
-        items[i].labels, items[i].ignore = lab.data_ptr(), None if ig is None else ig.data_ptr()
-        items[i].H, items[i].W = int(lab.shape[0]), int(lab.shape[1])
-        bound += int(lib.vx_png_bound(items[i].H, items[i].W))
+        entries.append((lab.data_ptr(), None if ig is None else ig.data_ptr(), int(lab.shape[0]), int(lab.shape[1])))
+    items, bound, ws_bytes = _png_table(entries)
     n = len(labs)
     dst = torch.empty(bound, dtype=torch.uint8, device=dev)
     place = torch.empty(2 * n, dtype=torch.int64, device=dev)
-    ws = torch.empty(int(lib.vx_png_workspace_bytes(items, n)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.vx_png_encode(items, n, _device_lut(dev).data_ptr(), UNLABELED, dst.data_ptr(), dst.numel(),
-                                 place.data_ptr(), place[n:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-               "vx_png_encode")
+    _png_launch(items, dst, place, torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
     pl = place.cpu().tolist()
     host = dst[:pl[n - 1] + pl[2 * n - 1]].cpu().numpy()
     return [host[o:o + k].tobytes() for o, k in zip(pl[:n], pl[n:])]
@@ -164,9 +175,9 @@ def png_encode(masks: Sequence[torch.Tensor], ignores: Optional[Sequence] = None
 
 def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, timing=None):
     """vx_png_encode over every mask of the batch + one small read of the file sizes + one copy of the PNG bytes and one
-    of the uncertainty maps into pinned memory: -> (plan, host uint8 array, [(offset, size)] per planned file)"""
+    of the uncertainty maps into pinned memory: -> (plan, host uint8 array, [(offset, size)] per planned PNG file,
+    [(offset, size, head, tail)] per TIFF)"""
     _lib.require_gpu()
-    lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device())
     pm = _as_device(pred_masks, dev, torch.uint8)
     if pm.dim() != 4:
@@ -189,25 +200,20 @@ def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_
     plan = plan_images(ids, N, list(unc))
 
     pngs = [f for f in plan if f.kind == "png"]
-    items = (_lib.PngItem * len(pngs))()
-    bound = 0
-    for i, f in enumerate(pngs):
+    entries = []
+    for f in pngs:
         b = f.source[1]
         lab = mm[b] if f.source[0] == "mean" else pm[b, f.source[2]]
-        items[i].labels = lab.data_ptr()
-        items[i].ignore = ign[b].data_ptr() if ign is not None else None
-        items[i].H, items[i].W = H, W
-        bound += int(lib.vx_png_bound(H, W))
+        entries.append((lab.data_ptr(), ign[b].data_ptr() if ign is not None else None, H, W))
+    items, bound, ws_bytes = _png_table(entries)
     n = len(pngs)
     dst = bufs.get("png", bound, dev)
     place = bufs.get("place", 16 * n, dev)[:16 * n].view(torch.int64)
-    ws = bufs.get("png_ws", int(lib.vx_png_workspace_bytes(items, n)), dev)
+    ws = bufs.get("png_ws", ws_bytes, dev)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing is not None else None
     if ev:
         ev[0].record()
-    _lib.check(lib.vx_png_encode(items, n, _device_lut(dev).data_ptr(), UNLABELED, dst.data_ptr(), dst.numel(),
-                                 place.data_ptr(), place[n:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-               "vx_png_encode")
+    _png_launch(items, dst, place, ws)
     if ev:
         ev[1].record()
     flat = torch.cat([unc[k][b].reshape(-1) for b in range(B) for k in unc]) if unc else None
@@ -232,32 +238,10 @@ def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_
         else:
             m = unc[f.source[1]]
             nb = 4 * int(m[f.source[2]].numel())
-            spans.append((u, nb, tuple(int(v) for v in m.shape[1:])))
+            h, w = (int(v) for v in m.shape[1:])
+            spans.append((u, nb) + tiff_f32_parts(h, w))   # TIFF: host-built header + the map's bytes + IFD
             u += nb
     return plan, host.numpy(), spans
-
-
-def _make_dirs(save_dir, plan):
-    os.makedirs(os.path.join(save_dir, "pred_seg"), exist_ok=True)
-    for f in plan:
-        os.makedirs(os.path.join(save_dir, os.path.dirname(f.path)), exist_ok=True)
-
-
-def _write_file(path, buf, span):
-    with open(path, "wb") as fh:
-        if len(span) == 2:
-            o, n = span
-            fh.write(memoryview(buf)[o:o + n])
-        else:   # TIFF: host-built header + the map's bytes + IFD
-            o, n, (h, w) = span
-            head, tail = tiff_f32_parts(h, w)
-            fh.write(head)
-            fh.write(memoryview(buf)[o:o + n])
-            fh.write(tail)
-
-
-_shared_bufs = _Buffers()
-_shared_lock = threading.Lock()
 
 
 def save_images_device(save_dir: str, image_ids: Sequence[str], pred_masks, mean_masks, uncertainty: Optional[Dict] = None,
@@ -277,57 +261,18 @@ def save_images_device(save_dir: str, image_ids: Sequence[str], pred_masks, mean
 
     One vx_png_encode call encodes all B (N + 1) masks (B N with one prediction); one small read brings back the file
     sizes, then the PNG bytes and the uncertainty maps come back in one copy each into reused pinned memory."""
-    with _shared_lock:
-        plan, host, spans = _encode_images(_shared_bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map,
-                                           _timing)
-        _make_dirs(save_dir, plan)
-        for f, sp in zip(plan, spans):
-            _write_file(os.path.join(save_dir, f.path), host, sp)
+    _devio.save_once(save_dir, ("pred_seg",), _encode_images, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map,
+                     _timing)
 
 
-class ResultsWriter2D:
+class ResultsWriter2D(_devio.PipelinedWriter):
     """Pipelined save_images_device: submit() encodes a batch on the GPU and hands its files to a small thread pool, so
     the files of batch i are written while batch i + 1 is encoded.  Two buffer sets alternate; a set is reused only once
     its files are written.  close() (or leaving the `with` block) waits and re-raises the first write error."""
 
-    def __init__(self, workers: int = 4):
-        if workers < 1:
-            raise ValueError("ResultsWriter2D: workers >= 1")
-        self._pool = ThreadPoolExecutor(max_workers=int(workers))
-        self._bufs = [_Buffers(), _Buffers()]
-        self._pending = [[], []]
-        self._all = []
-        self._n = 0
-        self._closed = False
+    _encode = staticmethod(_encode_images)
+    _dirs = ("pred_seg",)
 
     def submit(self, save_dir: str, image_ids: Sequence[str], pred_masks, mean_masks, uncertainty: Optional[Dict] = None,
                ignore_index_map=None, _timing=None) -> None:
-        if self._closed:
-            raise RuntimeError("ResultsWriter2D is closed")
-        k = self._n % 2
-        self._n += 1
-        for f in self._pending[k]:   # the buffer set's previous batch must be on disk before it is overwritten
-            f.exception()
-        plan, host, spans = _encode_images(self._bufs[k], image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map,
-                                           _timing)
-        _make_dirs(save_dir, plan)
-        futs = [self._pool.submit(_write_file, os.path.join(save_dir, f.path), host, sp) for f, sp in zip(plan, spans)]
-        self._pending[k] = futs
-        self._all.extend(futs)
-
-    def close(self) -> None:
-        if self._closed:
-            return
-        self._closed = True
-        self._pool.shutdown(wait=True)
-        for f in self._all:
-            e = f.exception()
-            if e is not None:
-                raise e
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+        self._submit(save_dir, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, _timing)
