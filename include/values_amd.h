@@ -819,6 +819,38 @@ int64_t vx_nifti_decode_workspace_bytes(int n_items);
 int vx_nifti_decode(const vx_nifti_dec_item* items /* host array */, int n_items, void* workspace,
                     int64_t workspace_bytes, vx_stream_t stream);
 
+/* Reading the 2D results tree back (values_amd/images.py: load_png_device; values_amd/gta.py: pred_seg_loading_device) --
+ * what follows vx_inflate(format = ZLIB) of a PNG's joined IDAT chunks.
+ *
+ * vx_png_unfilter: per item, the inflated scanline stream of an 8-bit non-interlaced PNG (src, src_n bytes: device; H rows
+ *   of one filter byte and W * bpp pixel bytes; bpp 1 / 3 / 4 = grey / RGB / RGBA) is reconstructed into dst (device,
+ *   H * W * bpp bytes, C order).  All five filters as RFC 2083 section 6: Paeth ties resolve a, then b, then c; Average
+ *   is (a + b) >> 1 on the unclamped 9-bit sum; the row above the first and the pixel left of the first are zero.
+ *   Statuses are per item: out_status[i] (device) is VX_PNG_OK, VX_PNG_BAD_FILTER (a filter byte above 4) or
+ *   VX_PNG_BAD_SIZE (src_n != H * (1 + W * bpp)); such an item's dst is left as it was, the others decode.  The return
+ *   value is reserved for argument errors (refused before any launch: a null table or pointer, bpp other than 1 / 3 / 4,
+ *   H or W < 1, a row of more than 65536 pixel bytes, H * (1 + W * bpp) >= 2^31) and hipError_t.  No read outside
+ *   [src, src + src_n), no write outside dst; src and dst may have any alignment.  workspace:
+ *   vx_png_unfilter_workspace_bytes(n_items) bytes, 16-byte aligned.  Like vx_inflate it uploads its table and
+ *   synchronises the stream before it launches: not capturable into a hipGraph.
+ * vx_rgb_to_trainid: out[i] = the id of the table entry whose key is pixel i's 0x00RRGGBB (rgb: n pixels at pitch 3), else
+ *   default_id -- color2trainId.get(tuple(x), 128) of evaluation/utils/gta.py:9-11.  table: device, n_table <= 256 pairs
+ *   (key, id) of uint32; of two entries with one key the later one counts.  Plain launch: capturable. */
+enum { VX_PNG_OK = 0, VX_PNG_BAD_FILTER = 1, VX_PNG_BAD_SIZE = 2 };
+typedef struct vx_png_unfilter_item {
+  const uint8_t* src;
+  int64_t src_n;
+  uint8_t* dst;
+  int32_t H, W;
+  int32_t bpp;
+  int32_t pad;
+} vx_png_unfilter_item;
+int64_t vx_png_unfilter_workspace_bytes(int n_items);
+int vx_png_unfilter(const vx_png_unfilter_item* items /* host array */, int n_items, int32_t* out_status /* device */,
+                    void* workspace, int64_t workspace_bytes, vx_stream_t stream);
+int vx_rgb_to_trainid(const uint8_t* rgb, int64_t n, const uint32_t* table /* device */, int n_table, int default_id,
+                      uint8_t* out, vx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

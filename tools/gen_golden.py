@@ -681,8 +681,41 @@ def gen_hrnet():
           sum(int(np.prod(s)) for s in shapes.values()), "logit range", float(logits.min()), float(logits.max()))
 
 
+# ----------------------------------------------------------------------------- 2D results tree, read back
+def gen_color2trainid():
+    """cityscapes_labels.color2trainId (the table evaluation/utils/gta.py:9-11 looks colours up in) and the train ids of
+    the five label-switch classes of gt_unc_map (gta.py:20-28)"""
+    import uncertainty_modeling.data.cityscapes_labels as cs
+    res = {"color2trainId": [[int(c[0]), int(c[1]), int(c[2]), int(i)] for c, i in cs.color2trainId.items()],
+           "default": 128,
+           "name2trainId": {n: int(cs.name2trainId[n]) for n in ("sidewalk", "person", "car", "vegetation", "road")}}
+    with open(os.path.join(OUT, "cityscapes_color2trainid.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print("cityscapes_color2trainid.json", len(res["color2trainId"]), "colours")
+
+
+def gen_images2d():
+    """three small PNG files from a foreign encoder (PIL, adaptive filters) with their decoded arrays: RGB, grey, RGBA"""
+    from PIL import Image
+    d = os.path.join(OUT, "images2d")
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(7)
+    yy, xx = np.mgrid[0:44, 0:37]
+    base = (2 * xx + 3 * yy) % 256
+    base[12:18] = rng.integers(0, 256, (6, 37))         # a noise band
+    base[30:36] = 77                                    # a flat band
+    rgb = np.stack([base, (base * 3 + 11) % 256, 255 - base], -1).astype(np.uint8)
+    grey = base.astype(np.uint8)
+    rgba = np.concatenate([rgb, ((xx * 5) % 256).astype(np.uint8)[..., None]], -1)
+    for name, a, mode in (("rgb", rgb, "RGB"), ("grey", grey, "L"), ("rgba", rgba, "RGBA")):
+        Image.fromarray(a, mode).save(os.path.join(d, f"pil_{name}.png"), optimize=True)
+        np.save(os.path.join(d, f"pil_{name}.npy"), a)
+        print("images2d", name, os.path.getsize(os.path.join(d, f"pil_{name}.png")), "bytes")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["unc", "unet16", "unet32", "tta", "patch", "agg", "hrnet", "ssn", "metrics", "hrnet_ssn", "hrnet_w18", "hrnet_w18_full", "evalmetrics"]
+    which = sys.argv[1:] or ["unc", "unet16", "unet32", "tta", "patch", "agg", "hrnet", "ssn", "metrics", "hrnet_ssn", "hrnet_w18", "hrnet_w18_full", "evalmetrics",
+                             "color2trainid", "images2d"]
     if "unc" in which:
         gen_unc_kat()
     if "unet16" in which:
@@ -709,3 +742,7 @@ if __name__ == "__main__":
         gen_hrnet_w18_full()
     if "evalmetrics" in which:
         gen_evalmetrics()
+    if "color2trainid" in which:
+        gen_color2trainid()
+    if "images2d" in which:
+        gen_images2d()

@@ -164,6 +164,15 @@ class NiftiDecItem(C.Structure):
                 ("slope", C.c_double), ("inter", C.c_double)]
 
 
+class PngUnfilterItem(C.Structure):
+    """vx_png_unfilter_item: one inflated PNG scanline stream (device src, src_n bytes) to reconstruct into dst."""
+    _fields_ = [("src", _p), ("src_n", _i64), ("dst", _p), ("H", _i32), ("W", _i32), ("bpp", _i32), ("pad", _i32)]
+
+
+VX_PNG_OK, VX_PNG_BAD_FILTER, VX_PNG_BAD_SIZE = 0, 1, 2
+PNG_STATUS = ("ok", "filter byte above 4", "stream size is not H (1 + W bpp)")
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -265,6 +274,9 @@ SIGNATURES = {
     "vx_inflate": (_i, [C.POINTER(InflateItem), _i, _p, _i64, _p, _p, _p, _i64, _p]),
     "vx_nifti_decode_workspace_bytes": (_i64, [_i]),
     "vx_nifti_decode": (_i, [C.POINTER(NiftiDecItem), _i, _p, _i64, _p]),
+    "vx_png_unfilter_workspace_bytes": (_i64, [_i]),
+    "vx_png_unfilter": (_i, [C.POINTER(PngUnfilterItem), _i, _p, _p, _i64, _p]),
+    "vx_rgb_to_trainid": (_i, [_p, _i64, _p, _i, _i, _p, _p]),
 }
 
 _lib = None

@@ -4,8 +4,15 @@
 evaluation/experiment_dataloader.py:11-169: same constructor arguments, attributes, method names and path scheme
     <base_path>/<naming_scheme_pred_model>/test_results/<version_name>/<split>/{pred_seg,pred_prob,pred_entropy,
     aleatoric_uncertainty,epistemic_uncertainty,gt_seg}/<id>...<ending>
-so evaluation code written against the reference classes runs unchanged.  Volumes are read with
-`values_amd.nifti`; the two arithmetic methods (1 - max softmax, aggregation) run on the GPU.
+so evaluation code written against the reference classes runs unchanged.  Files are read by their ending (`_load_file`):
+volumes with `values_amd.nifti`, the 2D tree's PNG masks and TIFF maps with `values_amd.image_io`; the two arithmetic
+methods (1 - max softmax, aggregation) run on the GPU.
+
+Axis order of 2D files: UNPINNED.  The reference reads every file with medpy.io.load, MedPy is absent here, and for an
+image file its axis order is not documented; evaluation/utils/gta.py:34 swaps the axes of the ground-truth map it builds
+from a numpy label (`np.swapaxes(unc_map, 0, 1)`) to match what the loader hands back, so the loader returns [x, y].
+A PNG / TIFF file is therefore returned with its first two axes swapped ((W, H) or (W, H, 3)).  The hooks are the
+exception: `pred_seg_loading` / `gt_unc_map_loading` return what the hook returns.
 `aggregate_uncertainties` mirrors evaluation/uncertainty_aggregation/aggregate_uncertainties.py:70-95.
 """
 from __future__ import annotations
@@ -18,6 +25,80 @@ import numpy as np
 
 from . import nifti
 from .io import instantiate
+
+
+NIFTI_ENDINGS, PNG_ENDINGS, TIFF_ENDINGS = (".nii", ".nii.gz"), (".png",), (".tif", ".tiff")
+
+
+def _kind(path) -> str:
+    p = str(path).lower()
+    for kind, ends in (("nifti", NIFTI_ENDINGS), ("png", PNG_ENDINGS), ("tiff", TIFF_ENDINGS)):
+        if p.endswith(ends):
+            return kind
+    raise ValueError(f"{path}: not a results file (.nii, .nii.gz, .png, .tif, .tiff)")
+
+
+def _load_file(path):
+    """One file of a results tree as a numpy array: a volume indexed [x, y, z] (nifti.load), a 2D image with its first
+    two axes swapped (module docstring: unpinned)."""
+    kind = _kind(path)
+    if kind == "nifti":
+        return nifti.load(path)[0]
+    from .image_io import read_png, read_tiff_f32
+    return np.swapaxes(read_png(path) if kind == "png" else read_tiff_f32(path), 0, 1)
+
+
+def _save_file(arr, path):
+    """The inverse of _load_file for the files the dataloader itself writes (pred_entropy of a Softmax model)."""
+    if _kind(path) == "tiff":
+        from .image_io import write_tiff_f32
+        write_tiff_f32(path, np.ascontiguousarray(np.swapaxes(np.asarray(arr, dtype=np.float32), 0, 1)))
+    else:
+        nifti.save(arr, path)
+
+
+def _load_files_device(paths):
+    """_load_file for a batch of paths, as device tensors: one load_device / load_png_device / load_tiff_device call per
+    kind of file in the batch"""
+    from . import images
+    paths = [str(p) for p in paths]
+    kinds = [_kind(p) for p in paths]
+    out = [None] * len(paths)
+    for kind in ("nifti", "png", "tiff"):
+        sel = [i for i, k in enumerate(kinds) if k == kind]
+        if not sel:
+            continue
+        if kind == "nifti":
+            got = [t for t, _ in nifti.load_device([paths[i] for i in sel])]
+        else:
+            fn = images.load_png_device if kind == "png" else images.load_tiff_device
+            got = [t.transpose(0, 1) for t in fn([paths[i] for i in sel])]
+        for i, t in zip(sel, got):
+            out[i] = t
+    return out
+
+
+PREFETCH_BATCH_2D = 256   # files per device call for PNG / TIFF files (DESIGN 5j)
+
+
+def _read_batches_device(paths, batch, batch_2d=None):
+    """(path, device tensor) for every path, read with the pipelined readers: the volumes `batch` files per
+    nifti.NiftiReader call, then the 2D files `batch_2d` (default: batch) per images.ImageReader call"""
+    from . import images
+    paths = [str(p) for p in paths]
+    vols = [p for p in paths if _kind(p) == "nifti"]
+    imgs = [p for p in paths if _kind(p) != "nifti"]
+    if vols:
+        with nifti.NiftiReader() as r:
+            for chunk, res in zip(_chunks(vols, batch), r.read(_chunks(vols, batch))):
+                for p, (t, _) in zip(chunk, res):
+                    yield p, t
+    if imgs:
+        n2 = batch if batch_2d is None else batch_2d
+        with images.ImageReader() as r:
+            for chunk, res in zip(_chunks(imgs, n2), r.read(_chunks(imgs, n2))):
+                for p, t in zip(chunk, res):
+                    yield p, t.transpose(0, 1)
 
 
 class ExperimentVersion:
@@ -85,7 +166,7 @@ class ExperimentDataloader:
         probs = []
         for c in range(self.exp_version.n_classes):
             f = os.path.join(self.pred_prob_dir, f"{image_id}_01_{str(c + 1).zfill(2)}{self.exp_version.unc_ending}")
-            probs.append(nifti.load(f)[0])
+            probs.append(_load_file(f))
         return calculate_one_minus_msr(torch.from_numpy(np.array(probs)))["pred_entropy"].numpy()
 
     def _setup_pred_entropy_softmax(self):
@@ -93,7 +174,7 @@ class ExperimentDataloader:
         if not os.path.exists(target):
             os.makedirs(target)
             for image_id in self.image_ids:
-                nifti.save(self.get_max_softmax_pred(image_id), target / f"{image_id}{self.exp_version.unc_ending}")
+                _save_file(self.get_max_softmax_pred(image_id), target / f"{image_id}{self.exp_version.unc_ending}")
 
     def _setup_unc_path_dict(self):
         return {u: self.dataset_path / ("pred_entropy" if u == "predictive_uncertainty" else u)
@@ -108,7 +189,7 @@ class ExperimentDataloader:
         return [self.pred_seg_dir / n for n in os.listdir(self.pred_seg_dir) if n.startswith(image_id) and n.endswith(end)]
 
     def get_pred_segs(self, image_id):
-        return [nifti.load(p)[0] for p in self.get_pred_seg_paths(image_id)]
+        return [_load_file(p) for p in self.get_pred_seg_paths(image_id)]
 
     def get_aggregated_unc_files_dict(self):
         return {u: self.dataset_path / f"aggregated_{u}.json" for u in self.unc_path_dict
@@ -121,7 +202,7 @@ class ExperimentDataloader:
 
     def _reference_segs(self, image_id):
         end = self.exp_version.image_ending
-        return np.array([nifti.load(self.ref_seg_dir / f"{image_id}_{i:02d}{end}")[0]
+        return np.array([_load_file(self.ref_seg_dir / f"{image_id}_{i:02d}{end}")
                          for i in range(self.exp_version.n_reference_segs)])
 
     def get_reference_segs(self, image_id):
@@ -139,11 +220,11 @@ class ExperimentDataloader:
         tag = "mean" if self.exp_version.pred_model != "Softmax" else "01"
         p = self.pred_seg_dir / f"{image_id}_{tag}{self.exp_version.image_ending}"
         if self.exp_version.pred_seg_loading is None:
-            return nifti.load(p)[0]
+            return _load_file(p)
         return instantiate(dict(self.exp_version.pred_seg_loading), pred_seg_path=p)
 
     def get_unc_map(self, image_id, unc_type):
-        return nifti.load(self.unc_path_dict[unc_type] / f"{image_id}{self.exp_version.unc_ending}")[0]
+        return _load_file(self.unc_path_dict[unc_type] / f"{image_id}{self.exp_version.unc_ending}")
 
 
 def _aggregate(exp_dataloader, aggregations, images_of):
@@ -170,13 +251,14 @@ def _aggregate(exp_dataloader, aggregations, images_of):
 def aggregate_uncertainties(exp_dataloader: ExperimentDataloader, aggregations):
     """aggregate_uncertainties.py:70-95: for every uncertainty type, image and aggregation config
     ({"_target_": ..., **params}) -> aggregated_<unc>.json."""
-    _aggregate(exp_dataloader, aggregations, lambda unc_path, keys: ((k, nifti.load(unc_path / k)[0]) for k in keys))
+    _aggregate(exp_dataloader, aggregations, lambda unc_path, keys: ((k, _load_file(unc_path / k)) for k in keys))
 
 
 class DeviceExperimentDataloader(ExperimentDataloader):
-    """ExperimentDataloader whose file getters return device tensors read with nifti.load_device (same constructor,
-    same paths).  get_reference_segs returns the stacked reference segmentations as one device tensor in the
-    file branch; get_gt_unc_map and the datamodule branch are inherited unchanged.  prefetch() reads a split's files in
+    """ExperimentDataloader whose file getters return device tensors read with nifti.load_device, or for a 2D tree with
+    images.load_png_device / load_tiff_device (same constructor, same paths, same axis order as the host getters).  get_reference_segs returns the stacked reference segmentations as one device tensor in the
+    file branch; the GTA hooks (values_amd.gta) run in their device forms, any other hook, get_gt_unc_map without a hook
+    and the datamodule branch are inherited unchanged.  prefetch() reads a split's files in
     batches ahead of the getters, under a byte budget."""
 
     def __init__(self, exp_version: ExperimentVersion, dataset_split):
@@ -187,12 +269,12 @@ class DeviceExperimentDataloader(ExperimentDataloader):
         p = str(path)
         if p in self._cache:
             return self._cache.pop(p)
-        return nifti.load_device([p])[0][0]
+        return _load_files_device([p])[0]
 
     def _load_many(self, paths):
         paths = [str(p) for p in paths]
         missing = [p for p in paths if p not in self._cache]
-        got = dict(zip(missing, (t for t, _ in nifti.load_device(missing)))) if missing else {}
+        got = dict(zip(missing, _load_files_device(missing))) if missing else {}
         return [self._cache.pop(p) if p in self._cache else got[p] for p in paths]
 
     def _files_of(self, image_id):
@@ -203,22 +285,21 @@ class DeviceExperimentDataloader(ExperimentDataloader):
             out += [str(self.ref_seg_dir / f"{image_id}_{i:02d}{end}") for i in range(self.exp_version.n_reference_segs)]
         return [p for p in dict.fromkeys(out) if os.path.isfile(p)]
 
-    def prefetch(self, image_ids=None, budget_bytes: int = 1 << 30, batch: int = 64) -> int:
-        """Read the files of `image_ids` (default: the split) the getters read, `batch` files per load_device call,
-        until the decoded tensors reach `budget_bytes`; the getters then take them from the cache (once each).
-        Returns the number of files cached."""
+    def prefetch(self, image_ids=None, budget_bytes: int = 1 << 30, batch: int = 64, batch_2d: int = PREFETCH_BATCH_2D) -> int:
+        """Read the files of `image_ids` (default: the split) the getters read, `batch` volumes per load_device call
+        (`batch_2d` PNG / TIFF files per call for a 2D tree: a device call costs about its slowest stream, so the small
+        2D files want many in flight), until the decoded tensors reach `budget_bytes`; the getters then take them from
+        the cache (once each).  Returns the number of files cached."""
         paths = [p for i in (self.image_ids if image_ids is None else image_ids) for p in self._files_of(i)]
         paths = [p for p in paths if p not in self._cache]
         used = sum(t.numel() * t.element_size() for t in self._cache.values())
         n = 0
-        with nifti.NiftiReader() as r:
-            for chunk, res in zip(_chunks(paths, batch), r.read(_chunks(paths, batch))):
-                for p, (t, _) in zip(chunk, res):
-                    if used + t.numel() * t.element_size() > budget_bytes:
-                        return n
-                    self._cache[p] = t
-                    used += t.numel() * t.element_size()
-                    n += 1
+        for p, t in _read_batches_device(paths, batch, batch_2d):
+            if used + t.numel() * t.element_size() > budget_bytes:
+                return n
+            self._cache[p] = t
+            used += t.numel() * t.element_size()
+            n += 1
         return n
 
     def get_pred_segs(self, image_id):
@@ -232,11 +313,28 @@ class DeviceExperimentDataloader(ExperimentDataloader):
         return torch.stack(self._load_many([self.ref_seg_dir / f"{image_id}_{i:02d}{end}"
                                             for i in range(self.exp_version.n_reference_segs)]))
 
+    @staticmethod
+    def _device_hook(cfg):
+        """a hook config with the GTA hooks (values_amd.gta, under any of their spellings) re-pointed to their device
+        forms; any other hook runs as it is"""
+        from .io import TARGET_MAP
+        cfg = dict(cfg)
+        target = TARGET_MAP.get(cfg["_target_"], cfg["_target_"])
+        if target in ("values_amd.gta.pred_seg_loading", "values_amd.gta.gt_unc_map"):
+            cfg["_target_"] = target + "_device"
+        return cfg
+
+    def get_gt_unc_map(self, image_id):
+        if self.exp_version.gt_unc_map_loading is None:
+            return super().get_gt_unc_map(image_id)
+        return instantiate(self._device_hook(self.exp_version.gt_unc_map_loading), image_id=image_id, dataloader=self.dataloader)
+
     def get_mean_pred_seg(self, image_id):
-        if self.exp_version.pred_seg_loading is not None:
-            return super().get_mean_pred_seg(image_id)
         tag = "mean" if self.exp_version.pred_model != "Softmax" else "01"
-        return self._load(self.pred_seg_dir / f"{image_id}_{tag}{self.exp_version.image_ending}")
+        p = self.pred_seg_dir / f"{image_id}_{tag}{self.exp_version.image_ending}"
+        if self.exp_version.pred_seg_loading is not None:
+            return instantiate(self._device_hook(self.exp_version.pred_seg_loading), pred_seg_path=p)
+        return self._load(p)
 
     def get_unc_map(self, image_id, unc_type):
         return self._load(self.unc_path_dict[unc_type] / f"{image_id}{self.exp_version.unc_ending}")
@@ -247,14 +345,11 @@ def _chunks(seq, n):
 
 
 def aggregate_uncertainties_device(exp_dataloader: ExperimentDataloader, aggregations, batch: int = 32):
-    """aggregate_uncertainties with the maps read on the device: every map of a type is read with nifti.NiftiReader,
-    `batch` files per call, and handed to the aggregations as a device tensor.  Writes the same aggregated_<unc>.json,
-    byte for byte."""
-    with nifti.NiftiReader() as reader:
-        def images_of(unc_path, keys):
-            chunks = _chunks(keys, batch)
-            for chunk, res in zip(chunks, reader.read([[unc_path / k for k in c] for c in chunks])):
-                for key, (unc_image, _) in zip(chunk, res):
-                    yield key, unc_image
+    """aggregate_uncertainties with the maps read on the device: every map of a type is read with nifti.NiftiReader (or,
+    for a 2D tree's TIFF maps, images.ImageReader), `batch` files per call, and handed to the aggregations as a device
+    tensor.  Writes the same aggregated_<unc>.json, byte for byte."""
+    def images_of(unc_path, keys):
+        for key, (_, unc_image) in zip(keys, _read_batches_device([unc_path / k for k in keys], batch)):
+            yield key, unc_image
 
-        _aggregate(exp_dataloader, aggregations, images_of)
+    _aggregate(exp_dataloader, aggregations, images_of)

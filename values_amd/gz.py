@@ -100,15 +100,20 @@ def _align(n: int) -> int:
     return (int(n) + ALIGN - 1) // ALIGN * ALIGN
 
 
-def inflate_into(items: List[tuple], device):
+def inflate_into(items: List[tuple], device, dst=None, offsets: Optional[Sequence[int]] = None):
     """items: (device pointer, src_n, format, capacity) -> (dst, offsets, sizes, statuses): one vx_inflate call, item i
-    decoded into dst[offsets[i]:offsets[i] + sizes[i]] (dst: a device uint8 tensor; sizes / statuses: host lists)."""
+    decoded into dst[offsets[i]:offsets[i] + sizes[i]] (dst: a device uint8 tensor; sizes / statuses: host lists).
+    With dst and offsets given, item i is decoded into the caller's dst at offsets[i] (windows of `capacity` bytes that
+    do not overlap); otherwise dst is allocated here, the windows back to back at 256-byte boundaries."""
     import torch
-    offs, off = [], 0
-    for _, _, _, cap in items:
-        offs.append(off)
-        off += _align(max(int(cap), 1))
-    dst = torch.empty(max(off, 1), dtype=torch.uint8, device=device)
+    if dst is None:
+        offs, off = [], 0
+        for _, _, _, cap in items:
+            offs.append(off)
+            off += _align(max(int(cap), 1))
+        dst = torch.empty(max(off, 1), dtype=torch.uint8, device=device)
+    else:
+        offs = [int(o) for o in offsets]
     if not items:
         return dst, offs, [], []
     arr = (_lib.InflateItem * len(items))()

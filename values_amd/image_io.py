@@ -35,51 +35,64 @@ def write_png(path, img: np.ndarray, level: int = 3) -> None:
         f.write(_chunk(b"IEND", b""))
 
 
-def read_png(path) -> np.ndarray:
-    """8-bit grey / RGB / RGBA, non-interlaced (all five scanline filters)."""
-    with open(path, "rb") as f:
-        buf = f.read()
-    if buf[:8] != b"\x89PNG\r\n\x1a\n":
+def png_parse(buf):
+    """The layout of an 8-bit non-interlaced grey / RGB / RGBA PNG file held in `buf`:
+    -> (w, h, ctype, bpp, [(offset, size) of every IDAT chunk's data]).  The chunks' data joined in order are one zlib
+    stream; inflated, it is h rows of one filter byte and w * bpp pixel bytes.  Shared by read_png and the device reader
+    (values_amd.images.load_png_device).  Not read: interlaced, palette, 16-bit and 1/2/4-bit files (ValueError)."""
+    if bytes(buf[:8]) != b"\x89PNG\r\n\x1a\n":
         raise ValueError("not a PNG file")
     pos, idat, hdr = 8, [], None
-    while pos < len(buf):
+    while pos + 8 <= len(buf):
         n, tag = struct.unpack(">I4s", buf[pos:pos + 8])
-        data = buf[pos + 8:pos + 8 + n]
-        pos += 12 + n
         if tag == b"IHDR":
-            hdr = struct.unpack(">IIBBBBB", data)
+            hdr = struct.unpack(">IIBBBBB", buf[pos + 8:pos + 8 + n])
         elif tag == b"IDAT":
-            idat.append(data)
+            idat.append((pos + 8, min(n, len(buf) - pos - 8)))
         elif tag == b"IEND":
             break
+        pos += 12 + n
+    if hdr is None:
+        raise ValueError("not a PNG file: no IHDR chunk")
     w, h, depth, ctype, _, _, interlace = hdr
     if depth != 8 or interlace != 0 or ctype not in (0, 2, 6):
         raise ValueError("read_png: only 8-bit non-interlaced grey/RGB/RGBA")
-    bpp = {0: 1, 2: 3, 6: 4}[ctype]
-    raw = np.frombuffer(zlib.decompress(b"".join(idat)), dtype=np.uint8).reshape(h, 1 + w * bpp)
+    return w, h, ctype, {0: 1, 2: 3, 6: 4}[ctype], idat
+
+
+def read_png(path) -> np.ndarray:
+    """8-bit grey / RGB / RGBA, non-interlaced (all five scanline filters).  None, Sub and Up rows are numpy row
+    operations (Sub: a wrapping running sum per byte lane -- what OpenCV writes for every row of a mask); Average and Paeth
+    rows run byte by byte."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    w, h, _, bpp, spans = png_parse(buf)
+    raw = np.frombuffer(zlib.decompress(b"".join(buf[o:o + n] for o, n in spans)), dtype=np.uint8).reshape(h, 1 + w * bpp)
     out = np.zeros((h, w * bpp), dtype=np.uint8)
     prev = np.zeros(w * bpp, dtype=np.int32)
     for y in range(h):
         ft, line = int(raw[y, 0]), raw[y, 1:].astype(np.int32)
         if ft == 0:
             cur = line
+        elif ft == 1:
+            cur = np.cumsum(raw[y, 1:].reshape(w, bpp), axis=0, dtype=np.uint8).reshape(-1).astype(np.int32)
         elif ft == 2:
             cur = (line + prev) & 0xFF
-        else:  # 1 (sub), 3 (average), 4 (Paeth): sequential along the scanline
+        elif ft in (3, 4):  # average, Paeth: sequential along the scanline
             cur = np.zeros_like(line)
             for i in range(w * bpp):
                 a = cur[i - bpp] if i >= bpp else 0
                 b = prev[i]
                 c = prev[i - bpp] if i >= bpp else 0
-                if ft == 1:
-                    pred = a
-                elif ft == 3:
+                if ft == 3:
                     pred = (a + b) >> 1
                 else:
                     p = a + b - c
                     pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
                     pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
                 cur[i] = (line[i] + pred) & 0xFF
+        else:
+            raise ValueError(f"read_png: {path}: row {y}: filter type {ft}")
         out[y] = cur
         prev = cur
     return out.reshape(h, w) if bpp == 1 else out.reshape(h, w, bpp)
@@ -119,13 +132,26 @@ def write_tiff_f32(path, img: np.ndarray) -> None:
         f.write(tail)
 
 
-def read_tiff_f32(path) -> np.ndarray:
-    """Reads what write_tiff_f32 writes (and any uncompressed single-channel float32 strip TIFF, either byte order)."""
-    with open(path, "rb") as f:
-        buf = f.read()
-    bo = {b"II": "<", b"MM": ">"}[buf[:2]]
-    if struct.unpack(bo + "H", buf[2:4])[0] != 42:
-        raise ValueError("not a TIFF file")
+class TiffLayout:
+    """What tiff_parse reads from a single-channel float32 strip TIFF: w, h, endian ("<" / ">"), deflate (the strips are
+    zlib streams) and strips: [(first row, rows, offset, size)] in row order."""
+
+    __slots__ = ("w", "h", "endian", "deflate", "strips")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def tiff_parse(buf, name: str = "") -> TiffLayout:
+    """The layout of a single-channel 32-bit float strip TIFF held in `buf` (either byte order; any RowsPerStrip;
+    Compression 1 = none or 8 / 32946 = Deflate, Predictor 1).  Shared by read_tiff_f32 and the device reader
+    (values_amd.images.load_tiff_device).  LZW (Compression 5, OpenCV's default) and the floating-point predictor
+    (Predictor 3) are not decoded: ValueError naming the tag and its value."""
+    pre = f"{name}: " if name else ""
+    bo = {b"II": "<", b"MM": ">"}.get(bytes(buf[:2]))
+    if bo is None or len(buf) < 8 or struct.unpack(bo + "H", buf[2:4])[0] != 42:
+        raise ValueError(f"{pre}not a TIFF file")
     off = struct.unpack(bo + "I", buf[4:8])[0]
     n = struct.unpack(bo + "H", buf[off:off + 2])[0]
     tags = {}
@@ -143,7 +169,41 @@ def read_tiff_f32(path) -> np.ndarray:
             vals = struct.unpack(bo + fmt * cnt, buf[p:p + size * cnt])
         tags[tag] = vals
     w, h = tags[256][0], tags[257][0]
-    if tags.get(259, (1,))[0] != 1 or tags.get(258, (0,))[0] != 32 or tags.get(339, (1,))[0] != 3 or tags.get(277, (1,))[0] != 1:
-        raise ValueError("read_tiff_f32: only uncompressed single-channel 32-bit float")
-    chunks = [buf[o:o + c] for o, c in zip(tags[273], tags[279])]
-    return np.frombuffer(b"".join(chunks), dtype=bo + "f4").reshape(h, w).astype(np.float32)
+    comp, pred = tags.get(259, (1,))[0], tags.get(317, (1,))[0]
+    if comp not in (1, 8, 32946):
+        what = " (LZW)" if comp == 5 else ""
+        raise ValueError(f"{pre}read_tiff_f32: Compression (tag 259) = {comp}{what}: only 1 (none) and 8 / 32946 (Deflate)")
+    if pred != 1:
+        what = " (floating point)" if pred == 3 else ""
+        raise ValueError(f"{pre}read_tiff_f32: Predictor (tag 317) = {pred}{what}: only 1 (none)")
+    if tags.get(258, (0,))[0] != 32 or tags.get(339, (1,))[0] != 3 or tags.get(277, (1,))[0] != 1:
+        raise ValueError(f"{pre}read_tiff_f32: only single-channel 32-bit float")
+    rps = min(tags.get(278, (h,))[0], h) or h
+    offs, counts = tags[273], tags[279]
+    if len(offs) != len(counts) or len(offs) != -(-h // rps):
+        raise ValueError(f"{pre}read_tiff_f32: {len(offs)} strip offsets, {len(counts)} byte counts for {h} rows of {rps} per strip")
+    strips = []
+    for k, (o, c) in enumerate(zip(offs, counts)):
+        if o + c > len(buf):
+            raise ValueError(f"{pre}read_tiff_f32: strip {k} [{o}, +{c}) beyond the file's {len(buf)} bytes")
+        strips.append((k * rps, min(rps, h - k * rps), o, c))
+    return TiffLayout(w=w, h=h, endian=bo, deflate=comp != 1, strips=strips)
+
+
+def tiff_decode(buf, t: TiffLayout, name: str = "") -> np.ndarray:
+    """The (h, w) float32 map of a file held in `buf` whose layout tiff_parse read."""
+    out = np.empty((t.h, t.w), dtype=np.float32)
+    for r0, rows, o, c in t.strips:
+        data = zlib.decompress(buf[o:o + c]) if t.deflate else buf[o:o + c]
+        if len(data) < 4 * rows * t.w:
+            raise ValueError(f"{name}: read_tiff_f32: strip at row {r0} holds {len(data)} bytes, {4 * rows * t.w} expected")
+        out[r0:r0 + rows] = np.frombuffer(data, dtype=t.endian + "f4", count=rows * t.w).reshape(rows, t.w)
+    return out
+
+
+def read_tiff_f32(path) -> np.ndarray:
+    """Reads what write_tiff_f32 writes and any single-channel float32 strip TIFF tiff_parse accepts: either byte order,
+    several strips of any RowsPerStrip, uncompressed or Deflate without predictor."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    return tiff_decode(buf, tiff_parse(buf, str(path)), str(path))

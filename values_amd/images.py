@@ -1,0 +1,269 @@
+"""Reading the 2D results tree on the device: the PNG masks and float32 TIFF maps results2d.py writes (and any file
+image_io.read_png / read_tiff_f32 read) as device tensors -- the 2D counterpart of nifti.load_device / NiftiReader.
+
+    PNG    files read on a thread pool, png_parse on the host, the IDAT chunks' bytes joined in a pinned staging
+           buffer and uploaded in one copy; one vx_inflate call (zlib) for the batch, then one vx_png_unfilter call
+           reconstructs every image's scanlines into its own tensor.
+    TIFF   tiff_parse on the host; every Deflate strip is one vx_inflate item that decodes straight into its rows of
+           the map, an uncompressed strip is copied into place.  The maps of a batch are views of one device buffer.
+           A big-endian file is decoded on the host and uploaded.
+
+The arrays are the ones the host readers return: (H, W) or (H, W, 3 | 4) uint8, (H, W) float32.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+
+import numpy as np
+
+from . import _lib
+from .image_io import png_parse, tiff_decode, tiff_parse
+from .nifti import MAX_FILE, _read
+
+PNG_ENDINGS, TIFF_ENDINGS = (".png",), (".tif", ".tiff")
+
+
+def kind_of(path) -> str:
+    """"png" / "tiff" by the file's ending, else ValueError."""
+    p = str(path).lower()
+    if p.endswith(PNG_ENDINGS):
+        return "png"
+    if p.endswith(TIFF_ENDINGS):
+        return "tiff"
+    raise ValueError(f"{path}: neither a .png nor a .tif / .tiff file")
+
+
+class _Staging:
+    """a pinned host buffer reused across batches (grown when a batch needs more): spans of the files' bytes are joined
+    in it and uploaded in one copy; that copy is waited for before the buffer is written again"""
+
+    def __init__(self):
+        self.buf = None
+        self.event = None
+
+    def upload(self, pieces, device):
+        """pieces: per item (bytes, [(offset, size)]) -> (device uint8 tensor, item offsets, item sizes)"""
+        import torch
+        from .gz import _align
+        offs, sizes, off = [], [], 0
+        for _, spans in pieces:
+            n = sum(s for _, s in spans)
+            offs.append(off)
+            sizes.append(n)
+            off += _align(max(n, 1))
+        if self.event is not None:
+            self.event.synchronize()
+        if self.buf is None or self.buf.numel() < off:
+            self.buf = torch.empty(max(off, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        host = self.buf.numpy()
+        for (raw, spans), o in zip(pieces, offs):
+            view = np.frombuffer(raw, np.uint8)
+            for so, sn in spans:
+                host[o:o + sn] = view[so:so + sn]
+                o += sn
+        dev = self.buf[:max(off, 1)].to(device, non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
+        return dev, offs, sizes
+
+
+def _events(timing):
+    import torch
+    return [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
+
+
+def png_unfilter(entries, device):
+    """entries: (src pointer, src_n, H, W, bpp, dst pointer) -> the items' statuses (host list): one vx_png_unfilter call."""
+    import torch
+    if not entries:
+        return []
+    lib = _lib.load()
+    arr = (_lib.PngUnfilterItem * len(entries))()
+    for it, (src, n, h, w, bpp, dst) in zip(arr, entries):
+        it.src, it.src_n, it.dst, it.H, it.W, it.bpp = src, int(n), dst, int(h), int(w), int(bpp)
+    status = torch.empty(len(entries), dtype=torch.int32, device=device)
+    ws = torch.empty(int(lib.vx_png_unfilter_workspace_bytes(len(entries))), dtype=torch.uint8, device=device)
+    _lib.check(lib.vx_png_unfilter(arr, len(entries), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "vx_png_unfilter")
+    return status.cpu().tolist()
+
+
+def _decode_png(names, raws, device, staging, timing=None):
+    import torch
+    from .gz import inflate_into, status_name
+    heads = []
+    for nm, r in zip(names, raws):
+        if len(r) >= MAX_FILE:
+            raise ValueError(f"{nm}: {len(r)} bytes: files of 4 GiB or more are not read on the device")
+        try:
+            heads.append(png_parse(r))
+        except ValueError as e:
+            raise ValueError(f"{nm}: {e}") from None
+    src, soffs, sizes = staging.upload([(r, h[4]) for r, h in zip(raws, heads)], device)
+    ev = _events(timing)
+    if ev:
+        ev[0].record()
+    need = [h * (1 + w * bpp) for w, h, _, bpp, _ in heads]
+    items = [(C.c_void_p(src.data_ptr() + o) if n else None, n, _lib.VX_INFLATE_ZLIB, cap)
+             for o, n, cap in zip(soffs, sizes, need)]
+    lines, loffs, ln, st = inflate_into(items, device)
+    for nm, s, n in zip(names, st, ln):
+        if s != 0:
+            raise _lib.VxError(f"{nm}: IDAT: {status_name(s)} (status {s}, {n} bytes decoded)")
+    if ev:
+        ev[1].record()
+    outs = [torch.empty((h, w) if bpp == 1 else (h, w, bpp), dtype=torch.uint8, device=device) for w, h, _, bpp, _ in heads]
+    st = png_unfilter([(C.c_void_p(lines.data_ptr() + lo), n, h, w, bpp, C.c_void_p(out.data_ptr()))
+                       for lo, n, (w, h, _, bpp, _), out in zip(loffs, ln, heads, outs)], device)
+    for nm, s in zip(names, st):
+        if s != 0:
+            what = _lib.PNG_STATUS[s] if 0 <= s < len(_lib.PNG_STATUS) else "?"
+            raise _lib.VxError(f"{nm}: scanlines: {what} (status {s})")
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        timing["inflate_ms"] = timing.get("inflate_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timing["unfilter_ms"] = timing.get("unfilter_ms", 0.0) + ev[1].elapsed_time(ev[2])
+        timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(need)
+    return outs
+
+
+def _decode_tiff(names, raws, device, staging, timing=None):
+    import torch
+    from .gz import _align, inflate_into, status_name
+    lay = [tiff_parse(r, str(nm)) for nm, r in zip(names, raws)]
+    on_dev = [i for i, t in enumerate(lay) if t.endian == "<"]
+    # the maps of the batch: one buffer, every map at a 256-byte boundary
+    moffs, off = {}, 0
+    for i in on_dev:
+        moffs[i] = off
+        off += _align(max(4 * lay[i].h * lay[i].w, 1))
+    maps = torch.empty(max(off, 1), dtype=torch.uint8, device=device)
+    strips = [(i, s) for i in on_dev for s in lay[i].strips]
+    src, soffs, sizes = staging.upload([(raws[i], [(s[2], s[3])]) for i, s in strips], device)
+    ev = _events(timing)
+    if ev:
+        ev[0].record()
+    items, at, who = [], [], []
+    for (i, (r0, rows, _, _)), so, n in zip(strips, soffs, sizes):
+        w = lay[i].w
+        d0, nb = moffs[i] + 4 * r0 * w, 4 * rows * w
+        if lay[i].deflate:
+            items.append((C.c_void_p(src.data_ptr() + so) if n else None, n, _lib.VX_INFLATE_ZLIB, nb))
+            at.append(d0)
+            who.append((i, r0, nb))
+        else:
+            if n < nb:
+                raise ValueError(f"{names[i]}: strip at row {r0} holds {n} bytes, {nb} expected")
+            maps[d0:d0 + nb].copy_(src[so:so + nb])
+    if items:
+        _, _, dn, st = inflate_into(items, device, dst=maps, offsets=at)
+        for (i, r0, nb), s, n in zip(who, st, dn):
+            if s != 0 or n != nb:
+                raise _lib.VxError(f"{names[i]}: strip at row {r0}: {status_name(s)} (status {s}, {n} of {nb} bytes decoded)")
+    if ev:
+        ev[1].record()
+        ev[1].synchronize()
+        timing["inflate_ms"] = timing.get("inflate_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(4 * t.h * t.w for t in lay)
+    outs = []
+    for i, t in enumerate(lay):
+        if i in moffs:
+            outs.append(maps[moffs[i]:moffs[i] + 4 * t.h * t.w].view(torch.float32).reshape(t.h, t.w))
+        else:   # big endian: the host reader's array, uploaded
+            out = tiff_decode(raws[i], t, str(names[i]))
+            outs.append(torch.from_numpy(out).to(device))
+    return outs
+
+
+def _decode(names, raws, device, staging, timing=None):
+    """the device half of one batch of file contents, PNG and TIFF files mixed: -> tensors in the order of `names`"""
+    kinds = [kind_of(nm) for nm in names]
+    outs = [None] * len(names)
+    for kind, fn in (("png", _decode_png), ("tiff", _decode_tiff)):
+        sel = [i for i, k in enumerate(kinds) if k == kind]
+        if sel:
+            for i, t in zip(sel, fn([names[i] for i in sel], [raws[i] for i in sel], device, staging, timing)):
+                outs[i] = t
+    return outs
+
+
+def _device(device):
+    import torch
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+_shared = None   # the one-shot loaders' reader: its thread pool and pinned staging buffer, used by one call at a time
+_shared_lock = threading.Lock()
+
+
+def _load(paths, device, timing, kind):
+    global _shared
+    _lib.require_gpu()
+    paths = [str(p) for p in paths]
+    for p in paths:
+        if kind_of(p) != kind:
+            raise ValueError(f"{p}: not a {kind} file")
+    if not paths:
+        return []
+    dev = _device(device)
+    with _shared_lock:
+        if _shared is None:
+            _shared = ImageReader()
+        raws = list(_shared._pool.map(_read, paths))
+        return _decode(paths, raws, dev, _shared._staging, timing)
+
+
+def load_png_device(paths, device=None, _timing=None):
+    """-> [uint8 device tensor (H, W) or (H, W, 3 | 4)] for a batch of 8-bit non-interlaced PNG files: the arrays
+    image_io.read_png returns, on `device` (default: the current device).  One vx_inflate call and one vx_png_unfilter
+    call per batch; a bad stream raises VxError naming the file and the status."""
+    return _load(paths, device, _timing, "png")
+
+
+def load_tiff_device(paths, device=None, _timing=None):
+    """-> [float32 device tensor (H, W)] for a batch of single-channel float32 strip TIFF files: the arrays
+    image_io.read_tiff_f32 returns.  The tensors of a batch are views of one device buffer."""
+    return _load(paths, device, _timing, "tiff")
+
+
+class ImageReader:
+    """Pipelined load_png_device / load_tiff_device over batches of files (PNG and TIFF may be mixed): the files of batch
+    i + 1 are read from disk on a thread pool while batch i is decoded on the device.  read(batches) yields one list of
+    tensors per batch, in order -- nifti.NiftiReader for the 2D tree."""
+
+    def __init__(self, device=None, workers: int = 8, _timing=None):
+        if workers < 1:
+            raise ValueError("ImageReader: workers >= 1")
+        from concurrent.futures import ThreadPoolExecutor
+        self.device = device
+        self._pool = ThreadPoolExecutor(max_workers=int(workers))
+        self._staging = _Staging()
+        self._timing = _timing
+
+    def _submit(self, batch):
+        return [str(p) for p in batch], [self._pool.submit(_read, str(p)) for p in batch]
+
+    def read(self, batches):
+        _lib.require_gpu()
+        dev = _device(self.device)
+        it = iter(batches)
+        nxt = next(it, None)
+        pending = self._submit(nxt) if nxt is not None else None
+        while pending is not None:
+            names, futs = pending
+            nxt = next(it, None)
+            raws = [f.result() for f in futs]
+            pending = self._submit(nxt) if nxt is not None else None
+            yield _decode(names, raws, dev, self._staging, self._timing) if names else []
+
+    def close(self):
+        self._pool.shutdown(wait=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

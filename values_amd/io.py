@@ -20,6 +20,11 @@ TARGET_MAP = {
     "models.unet3D_module.UNet3D": "values_amd.unet3d.UNet3D",
     "uncertainty_modeling.models.ssn_unet3D_module.SsnUNet3D": "values_amd.ssn.SsnUNet3D",
     "models.ssn_unet3D_module.SsnUNet3D": "values_amd.ssn.SsnUNet3D",
+    # the 2D experiments' evaluation hooks (evaluation/utils/gta.py), under both spellings the reference configs use
+    "evaluation.utils.gta.pred_seg_loading": "values_amd.gta.pred_seg_loading",
+    "utils.gta.pred_seg_loading": "values_amd.gta.pred_seg_loading",
+    "evaluation.utils.gta.gt_unc_map": "values_amd.gta.gt_unc_map",
+    "utils.gta.gt_unc_map": "values_amd.gta.gt_unc_map",
 }
 
 
