@@ -618,10 +618,18 @@ int vx_count_nonzero_u8(const uint8_t* x, int64_t n, uint64_t* out, vx_stream_t 
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),
  *   counts[i][j][c] = #{v: mask_i(v) == c and mask_j(v) == c}.  M <= 32, C <= 8.
+ * vx_mask_agreement_batched (the metrics half of process_output, test_2D.py:205-244): the same counts for the B images of
+ *   a 2D inference step at once.  masks [B][M][nvox] uint8, counts [B][M][M][C] uint64 (zeroed here, the full array, not a
+ *   triangle).  1 <= M <= 32, 1 <= C <= 32, B >= 1, 0 <= nvox <= 2^39; anything else is VX_E_SHAPE before any launch.
+ *   A label equal to remap_from counts as class C - 1 (the reference's gt[gt == 255] = C - 1 for the appended "ignore"
+ *   class, done on load; remap_from outside 0..255: none); any other label >= C counts for no class.  One memset + one
+ *   launch on the stream, no synchronisation, no descriptor upload: capturable into a hipGraph.
  * vx_soft_metric_sums: prob [C][nvox] float32 (mean softmax), gt [R][nvox] uint8; sums [R][3*C+1] float64:
  *   for each class (sum p_c [gt==c], sum [gt==c], sum p_c), then sum_v log p_{gt(v)}(v);
  *   workspace of vx_soft_metric_workspace_bytes(C, R). */
 int vx_mask_agreement(const uint8_t* masks, int M, int C, int64_t nvox, uint64_t* counts, vx_stream_t stream);
+int vx_mask_agreement_batched(const uint8_t* masks, int B, int M, int C, int64_t nvox, int remap_from, uint64_t* counts,
+                              vx_stream_t stream);
 int64_t vx_soft_metric_workspace_bytes(int C, int R);
 int vx_soft_metric_sums(const float* prob, const uint8_t* gt, int C, int R, int64_t nvox, double* sums, void* workspace,
                         vx_stream_t stream);

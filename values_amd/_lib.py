@@ -239,6 +239,7 @@ SIGNATURES = {
     "vx_select_kth": (_i, [_p, _i64, _i64, _p, _p, _p]),
     "vx_count_nonzero_u8": (_i, [_p, _i64, _p, _p]),
     "vx_mask_agreement": (_i, [_p, _i, _i, _i64, _p, _p]),
+    "vx_mask_agreement_batched": (_i, [_p, _i, _i, _i, _i64, _i, _p, _p]),
     "vx_soft_metric_workspace_bytes": (_i64, [_i, _i]),
     "vx_soft_metric_sums": (_i, [_p, _p, _i, _i, _i64, _p, _p, _p]),
     "vx_ssn2d_lowres": (_i, [_p, _i, _p, _i, _p, _u32, _i, _i64, _i, _i, _i, _p, _p, _p]),

@@ -30,6 +30,22 @@ def mask_agreement(masks: torch.Tensor, num_classes: int) -> np.ndarray:
     return out.cpu().numpy()
 
 
+def mask_agreement_batched(masks: torch.Tensor, num_classes: int, remap_from: Optional[int] = None) -> np.ndarray:
+    """masks (B, M, *spatial) integer labels on the device -> counts (B, M, M, C) int64 (host): `mask_agreement` of every
+    image of a batch with ONE launch (`vx_mask_agreement_batched`: C <= 32) and one device-to-host copy.  A label equal
+    to remap_from counts as class C - 1 (the 2D ground truth's ignore label 255 -> the appended class, on load)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    if masks.dim() < 2:
+        raise ValueError("mask_agreement_batched: masks (B, M, *spatial) expected")
+    B, M = int(masks.shape[0]), int(masks.shape[1])
+    m = masks.reshape(B, M, -1).to(torch.uint8).contiguous()
+    out = torch.empty((B, M, M, num_classes), dtype=torch.int64, device=m.device)
+    _lib.check(lib.vx_mask_agreement_batched(m.data_ptr(), B, M, num_classes, m.shape[2], -1 if remap_from is None else int(remap_from),
+                                             out.data_ptr(), _lib.stream_ptr()), "vx_mask_agreement_batched")
+    return out.cpu().numpy()
+
+
 def _micro_dice(I: np.ndarray, a_idx, b_idx, classes) -> float:
     """torchmetrics dice(average='micro', mdmc_average='global', zero_division=0) pooled over the listed (a, b) pairs."""
     tp = fp = fn = 0
@@ -105,9 +121,15 @@ def calculate_ged(output_softmax: torch.Tensor, ground_truth: torch.Tensor, igno
                                       want_sample_argmax=True)["sample_argmax"].reshape(T, nvox)
     pm = _to_dev(pred_masks, dev).reshape(T, -1).to(torch.uint8)
     g8 = gt.reshape(R, -1).to(torch.uint8)
-    I = mask_agreement(torch.cat([pm, g8], 0), C)
-    P = list(range(T))
-    G = [T + r for r in range(R)]
+    stack = torch.cat([pm, g8], 0)
+    # up to 8 classes: the one-image kernel, as ever (same integers either way); more (2D: 19 + 1): the batched one with B = 1
+    I = mask_agreement(stack, C) if C <= 8 else mask_agreement_batched(stack[None], C)[0]
+    return _ged_from_counts(I, list(range(T)), [T + r for r in range(R)], C, ignore_index, ged_only)
+
+
+def _ged_from_counts(I: np.ndarray, P, G, C: int, ignore_index, ged_only: bool) -> Dict:
+    """calculate_ged's ratios from one image's agreement counts I (M, M, C); P / G: the rows of the predictions / raters"""
+    T, R = len(P), len(G)
     cls = _classes(C, ignore_index)
     # pooled distances over the repeated tensors of :290-320 (order of a pair does not change pooled tp / fp+fn)
     d_gp = 1.0 - _micro_dice(I, [p for _ in G for p in P], [g for g in G for _ in P], cls)
@@ -124,3 +146,85 @@ def calculate_ged(output_softmax: torch.Tensor, ground_truth: torch.Tensor, igno
             out["max dice rater {}".format(r)] = float(max(np.float32(0), pair[:, r].max()))
         out["max dice pred"] = float(np.float32(sum(max(np.float32(0), pair[p].max()) for p in range(T))) / np.float32(T))
     return out
+
+
+def _extended_gt(ground_truth, dev, ignore_label):
+    """(R, *spatial) labels -> (R, nvox) uint8 on the device; ignore_label must survive the cast to be remapped on load"""
+    if ignore_label is not None and not 0 <= int(ignore_label) <= 255:
+        raise ValueError(f"ignore_label {ignore_label} is no uint8 label")
+    gt = _to_dev(ground_truth, dev)
+    return gt.reshape(gt.shape[0], -1).to(torch.uint8)
+
+
+def calculate_test_metrics_2d(mean_softmax: torch.Tensor, ground_truth: torch.Tensor, ignore_label: Optional[int] = None,
+                              pred_seg: Optional[torch.Tensor] = None) -> Dict:
+    """Tester.calculate_test_metrics of test_2D.py:161-173: mean_softmax (C_ext, H, W), the mean prediction WITH the
+    appended zero channel; ground_truth (R, H, W) integer -> {"dice"}: per rater the Dice of the arg-max of the mean
+    prediction with ignore_index = C_ext - 1 (the appended class), averaged over raters.  ignore_label: ground-truth
+    pixels carrying it count as class C_ext - 1 (what process_output does to the tensor beforehand; None: already done).
+    pred_seg (H, W): the arg-max when the caller has it (process_output_2d's "pred_seg")."""
+    _lib.require_gpu()
+    dev = mean_softmax.device if mean_softmax.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    p = _to_dev(mean_softmax, dev)
+    C = int(p.shape[0])
+    if pred_seg is None:
+        from .uncertainty import uncertainty_maps
+        nvox = p[0].numel()
+        pred_seg = uncertainty_maps(p.reshape(1, 1, C, nvox).to(torch.float32), from_logits=False)["argmax"]
+    am = _to_dev(pred_seg, dev).reshape(1, -1).to(torch.uint8)
+    g8 = _extended_gt(ground_truth, dev, ignore_label)
+    I = mask_agreement_batched(torch.cat([am, g8], 0)[None], C, ignore_label)[0]
+    return _test_metrics_2d_from_counts(I, 0, range(1, 1 + g8.shape[0]), C)
+
+
+def _test_metrics_2d_from_counts(I, p, G, C):
+    cls = _classes(C, C - 1)
+    return {"dice": float(np.mean(np.array([_micro_dice(I, [p], [g], cls) for g in G])))}
+
+
+def process_metrics_2d(out: Dict, gt: torch.Tensor, ignore_label: int = 255, ged_only: bool = True, image_ids=None,
+                       sample_argmax: Optional[torch.Tensor] = None):
+    """The metrics half of Tester.process_output (test_2D.py:205-244) for a whole batch: per image
+    calculate_test_metrics ("dice") and calculate_ged(ignore_index = C, ged_only) ("ged", and with ged_only=False and
+    several raters the "max dice ..." keys of process_image_prediction).
+
+    out: what process_output_2d returns -- softmax_pred (B, T, C, H, W), pred_seg (B, H, W); gt (B, R, H, W) integer
+    labels that still carry ignore_label.  sample_argmax (B, T, H, W): the per-sample arg-max masks when the caller has
+    them (uncertainty_maps(..., want_sample_argmax=True), which also feeds the results writer), else taken from
+    softmax_pred.  Returns a list of metric dicts in batch order, or {image_id: dict} with image_ids.
+
+    The reference appends a zero channel to the softmax so that class C exists for the ignored pixels.  It is never
+    materialised here: a softmax is > 0 everywhere, so the zero channel never wins an arg-max, and the arg-max masks of
+    the C-channel tensor ARE those of the extended one; only the ground truth sees class C (ignore_label is mapped to
+    it on load).  One vx_mask_agreement_batched call over the stacked [mean arg-max, T sample arg-maxes, R raters]
+    (M = 1 + T + R <= 32) and one host copy; every ratio is formed on the host from the integers."""
+    _lib.require_gpu()
+    sm = out["softmax_pred"]
+    dev = sm.device if sm.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    B, T, C = (int(v) for v in sm.shape[:3])
+    g = _to_dev(gt, dev)
+    if g.dim() < 3 or g.shape[0] != B:
+        raise ValueError(f"process_metrics_2d: gt (B, R, H, W) expected for {B} images, got {tuple(g.shape)}")
+    R = int(g.shape[1])
+    if 1 + T + R > 32:
+        raise ValueError(f"process_metrics_2d: 1 + T + R = {1 + T + R} masks per image (at most 32)")
+    if ignore_label is not None and not 0 <= int(ignore_label) <= 255:
+        raise ValueError(f"ignore_label {ignore_label} is no uint8 label")
+    if image_ids is not None and len(image_ids) != B:
+        raise ValueError(f"process_metrics_2d: {len(image_ids)} image ids for {B} images")
+    if sample_argmax is None:
+        from .uncertainty import uncertainty_maps
+        smd = _to_dev(sm, dev).to(torch.float32)
+        sample_argmax = uncertainty_maps(smd.reshape(B, T, C, -1), from_logits=False, want_sample_argmax=True)["sample_argmax"]
+    stack = torch.cat([_to_dev(out["pred_seg"], dev).reshape(B, 1, -1).to(torch.uint8),
+                       _to_dev(sample_argmax, dev).reshape(B, T, -1).to(torch.uint8),
+                       g.reshape(B, R, -1).to(torch.uint8)], 1)
+    Ce = C + 1
+    I = mask_agreement_batched(stack, Ce, ignore_label)
+    P, G = list(range(1, 1 + T)), list(range(1 + T, 1 + T + R))
+    res = []
+    for b in range(B):
+        m = _test_metrics_2d_from_counts(I[b], 0, G, Ce)
+        m.update(_ged_from_counts(I[b], P, G, Ce, Ce - 1, ged_only))
+        res.append(m)
+    return res if image_ids is None else dict(zip(image_ids, res))

@@ -13,6 +13,7 @@ batch (colour lookup, scanlines, DEFLATE, zlib and PNG framing) and the host onl
 """
 from __future__ import annotations
 
+import json
 import os
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
@@ -85,6 +86,23 @@ def save_uncertainty(save_dir: str, image_id: str, uncertainty_dict: Dict[str, t
         os.makedirs(d, exist_ok=True)
         m = unc_map.detach().cpu().numpy() if isinstance(unc_map, torch.Tensor) else np.asarray(unc_map)
         write_tiff_f32(os.path.join(d, f"{image_id}.tif"), m.astype(np.float32))
+
+
+def save_results_dict(save_dir: str, results_dict: Dict[str, Dict]) -> Dict[str, Dict]:
+    """Tester.save_results_dict (test_2D.py:258-271): <save_dir>/metrics.json with one {"dataset": ..., "metrics": {...}}
+    entry per image id (values_amd.metrics.process_metrics_2d gives the metrics) plus "mean": {"metrics": {...}}, the plain
+    mean of every metric over the images that carry it; indent=2.  Returns the written dict (the argument is left as it
+    was).  This is the file evalmetrics.get_dice / failure_detection read."""
+    scores: Dict[str, List[float]] = {}
+    for image_id, value in results_dict.items():
+        for metric, score in value["metrics"].items():
+            scores.setdefault(metric, []).append(score)
+    full = dict(results_dict)
+    full["mean"] = {"metrics": {metric: float(np.asarray(v).mean()) for metric, v in scores.items()}}
+    os.makedirs(save_dir, exist_ok=True)
+    with open(os.path.join(save_dir, "metrics.json"), "w") as f:
+        json.dump(full, f, indent=2)
+    return full
 
 
 # ---------------------------------------------------------------------------------------------------------------------
