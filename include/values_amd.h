@@ -626,13 +626,24 @@ int vx_count_nonzero_u8(const uint8_t* x, int64_t n, uint64_t* out, vx_stream_t 
  *   launch on the stream, no synchronisation, no descriptor upload: capturable into a hipGraph.
  * vx_soft_metric_sums: prob [C][nvox] float32 (mean softmax), gt [R][nvox] uint8; sums [R][3*C+1] float64:
  *   for each class (sum p_c [gt==c], sum [gt==c], sum p_c), then sum_v log p_{gt(v)}(v);
- *   workspace of vx_soft_metric_workspace_bytes(C, R). */
+ *   workspace of vx_soft_metric_workspace_bytes(C, R).
+ * vx_soft_metric_sums_batched (the SoftDice + NLL half of calculate_metrics, test_3D.py:537-575, for a whole step): the sums of
+ *   vx_soft_metric_sums for B images in one pass over the data.  prob [B][C][nvox] float32, gt [B][R][nvox] uint8,
+ *   sums [B][R][3*C+1] float64 in the one-image layout.  1 <= C <= 32, 1 <= R <= 31, B >= 1, 1 <= nvox <= 2^39; anything
+ *   else is VX_E_SHAPE, a null pointer VX_E_NULL, both before any device call.  A label >= C counts for no class and takes no
+ *   log term.  Deterministic: fixed summation order, no atomics, and an image's sums do not depend on B or on its batch
+ *   mates (bit-equal to the same image submitted alone).  workspace of vx_soft_metric_batched_workspace_bytes(B, C, R, nvox)
+ *   (0 for arguments the call refuses; B times the value for one image).  Two launches on the stream, no synchronisation:
+ *   capturable into a hipGraph. */
 int vx_mask_agreement(const uint8_t* masks, int M, int C, int64_t nvox, uint64_t* counts, vx_stream_t stream);
 int vx_mask_agreement_batched(const uint8_t* masks, int B, int M, int C, int64_t nvox, int remap_from, uint64_t* counts,
                               vx_stream_t stream);
 int64_t vx_soft_metric_workspace_bytes(int C, int R);
 int vx_soft_metric_sums(const float* prob, const uint8_t* gt, int C, int R, int64_t nvox, double* sums, void* workspace,
                         vx_stream_t stream);
+int64_t vx_soft_metric_batched_workspace_bytes(int B, int C, int R, int64_t nvox);
+int vx_soft_metric_sums_batched(const float* prob, const uint8_t* gt, int B, int C, int R, int64_t nvox, double* sums,
+                                void* workspace, vx_stream_t stream);
 
 /* 2D SSN head (HighResolutionNet.hrnet_ssn, hrnet_module.py:559-595), see accumulate.hip:
  * vx_ssn2d_lowres: channels-last head outputs at the head's resolution -- mean [B*pix][mean_pitch] (C used),

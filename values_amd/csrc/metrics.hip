@@ -244,3 +244,190 @@ extern "C" int vx_soft_metric_sums(const float* prob, const uint8_t* gt, int C, 
   VX_CHECK_LAUNCH("vx_soft_metric_sums");
   return VX_OK;
 }
+
+// ---- vx_soft_metric_sums_batched: the same sums for the B volumes of a 3D inference step in ONE pass over the data ----------------
+// (calculate_metrics of test_3D.py:537-575 runs calculate_test_metrics per case; the one-image kernel above walks the volume once
+// per output scalar)
+// An image is cut into spans of SMB_SPAN = 4096 voxels (a rule of nvox alone: image b of a batch is cut, summed and combined exactly
+// as the same image submitted alone); a workgroup owns a span, a lane 4 tiles x 4 consecutive voxels of it:
+//   1. the lane's labels of all R raters are loaded once, four to a register (one 32-bit load per rater and tile);
+//   2. per class c the lane's 16 probabilities are loaded once (16-byte loads) and every sum that involves p_c is formed from those
+//      registers: sum p_c (rater-independent: once), and per rater sum p_c [g_r = c] (float64), #[g_r = c] (an integer, counted as
+//      one) and this class's share of sum logf(p_{g_r}) -- logf is taken once per (voxel, class) and selected per rater;
+//   3. the lane partials of a class go down a fixed __shfl_down tree per wave, the four wave totals are added in wave order by one
+//      thread per scalar, and the workgroup's partial lands in the workspace [B][spans][R][3C + 1] (sum p_c in rater 0's slot only);
+//   4. a finalize launch adds an image's span partials in span order and replicates sum p_c into every rater's row.
+// No atomics and no data-dependent order: bit-reproducible, and independent of B.  Labels >= C (255 included: also what a lane sees
+// past the end of the image) match no class and take no log term.  Where nvox % 4 != 0 (or a base pointer is not aligned) the same
+// lanes take the same voxels with scalar loads: the sums do not depend on which loads were used.
+// Registers: RT = 4 holds the raters of the 3D data sets (R <= 4); RT = 31 is the general instance (one wave per SIMD).
+constexpr int SMB_MAXC = 32, SMB_MAXR = 31;
+constexpr int SMB_TILES = 4;
+constexpr int SMB_SPAN = 256 * 4 * SMB_TILES;
+constexpr int64_t SMB_MAXWG = 65536;   // workgroups of a launch; more spans than that: a workgroup takes every SMB_MAXWG-th
+
+__device__ __forceinline__ f32x4 smb_load_p(const float* __restrict__ p, int64_t v, int64_t nvox, bool vec) {
+  f32x4 q = {0.f, 0.f, 0.f, 0.f};
+  if (vec) {
+    if (v < nvox) q = *reinterpret_cast<const f32x4*>(p + v);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (v + j < nvox) q[j] = p[v + j];
+  }
+  return q;
+}
+
+__device__ __forceinline__ unsigned smb_load_g(const uint8_t* __restrict__ g, int64_t v, int64_t nvox, bool vec) {
+  unsigned w = 0xffffffffu;
+  if (vec) {
+    if (v < nvox) w = *reinterpret_cast<const unsigned*>(g + v);
+  } else {
+    w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w |= (v + j < nvox ? (unsigned)g[v + j] : 255u) << (8 * j);
+  }
+  return w;
+}
+
+// lane 0 ends with the wave's total; the tree is the same for every call
+__device__ __forceinline__ double smb_wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;
+}
+__device__ __forceinline__ int smb_wave_sum(int x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;
+}
+
+template <int RT>
+__global__ __launch_bounds__(256, RT <= 4 ? 4 : 1) void soft_metric_batched_kernel(const float* __restrict__ prob, const uint8_t* __restrict__ gt, int C,
+                                                                  int R, int64_t nvox, int64_t nwg, int64_t nspan, int vec,
+                                                                  double* __restrict__ part) {
+  __shared__ double red[2][4][2 * RT + 1];   // [class parity][wave][sum p_c | sum p_c [g_r = c] | #[g_r = c]]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int per = 3 * C + 1;
+  for (int64_t sp = blockIdx.x; sp < nspan; sp += gridDim.x) {   // span sp = image b, span blk of it
+    const int64_t b = sp / nwg, blk = sp - b * nwg;
+    const float* p = prob + (size_t)b * C * nvox;
+    const uint8_t* g = gt + (size_t)b * R * nvox;
+    double* o = part + (size_t)sp * R * per;
+    const int64_t v0 = blk * SMB_SPAN + tid * 4;
+    unsigned lab[RT][SMB_TILES];
+    double nll[RT];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+      nll[r] = 0.0;
+#pragma unroll
+      for (int t = 0; t < SMB_TILES; ++t)
+        lab[r][t] = r < R ? smb_load_g(g + (size_t)r * nvox, v0 + t * 1024, nvox, vec) : 0xffffffffu;
+    }
+    for (int c = 0; c < C; ++c) {
+      f32x4 q[SMB_TILES], lq[SMB_TILES];
+#pragma unroll
+      for (int t = 0; t < SMB_TILES; ++t) q[t] = smb_load_p(p + (size_t)c * nvox, v0 + t * 1024, nvox, vec);
+      double ps = 0.0;
+#pragma unroll
+      for (int t = 0; t < SMB_TILES; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          ps += (double)q[t][j];
+          lq[t][j] = logf(q[t][j]);   // torch.log of the float32 probability (past the end: log 0, never selected)
+        }
+      double* rd = red[c & 1][wave];
+      ps = smb_wave_sum(ps);
+      if (lane == 0) rd[0] = ps;
+#pragma unroll
+      for (int r = 0; r < RT; ++r) {
+        if (r < R) {
+          double in = 0.0;
+          int cn = 0;
+#pragma unroll
+          for (int t = 0; t < SMB_TILES; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const bool m = ((lab[r][t] >> (8 * j)) & 255u) == (unsigned)c;
+              in += (double)(m ? q[t][j] : 0.f);
+              nll[r] += (double)(m ? lq[t][j] : 0.f);
+              cn += m ? 1 : 0;
+            }
+          in = smb_wave_sum(in);
+          cn = smb_wave_sum(cn);
+          if (lane == 0) {
+            rd[1 + r] = in;
+            rd[1 + RT + r] = (double)cn;
+          }
+        }
+      }
+      __syncthreads();
+      // (the other parity is written next: its readers passed this barrier's predecessor)
+      if (tid < 1 + 2 * RT) {
+        const int r = tid == 0 ? 0 : (tid - 1) % RT, which = tid == 0 ? 2 : (tid <= RT ? 0 : 1);
+        if (r < R) o[r * per + 3 * c + which] = ((red[c & 1][0][tid] + red[c & 1][1][tid]) + red[c & 1][2][tid]) + red[c & 1][3][tid];
+      }
+    }
+    double* rd = red[C & 1][wave];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+      if (r < R) {
+        const double s = smb_wave_sum(nll[r]);
+        if (lane == 0) rd[r] = s;
+      }
+    }
+    __syncthreads();
+    if (tid < R) o[tid * per + 3 * C] = ((red[C & 1][0][tid] + red[C & 1][1][tid]) + red[C & 1][2][tid]) + red[C & 1][3][tid];
+    __syncthreads();   // the next span's first class may write the parity just read
+  }
+}
+
+// sums[b][r][k] = the span partials of image b added in span order; sum p_c (k = 3c + 2) from rater 0's slot for every rater
+__global__ __launch_bounds__(256) void soft_metric_batched_final_kernel(const double* __restrict__ part, int64_t n, int K, int per,
+                                                                        int64_t nwg, double* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / K;
+    const int k = (int)(i - b * K), j = k % per;
+    const double* p = part + (size_t)b * nwg * K + ((j < per - 1 && j % 3 == 2) ? j : k);
+    double s = 0.0;
+    for (int64_t blk = 0; blk < nwg; ++blk) s += p[(size_t)blk * K];
+    out[i] = s;
+  }
+}
+
+static bool smb_shape_ok(int B, int C, int R, int64_t nvox) {
+  return B >= 1 && C >= 1 && C <= SMB_MAXC && R >= 1 && R <= SMB_MAXR && nvox >= 1 && nvox <= MAB_MAXVOX;
+}
+
+extern "C" int64_t vx_soft_metric_batched_workspace_bytes(int B, int C, int R, int64_t nvox) {
+  if (!smb_shape_ok(B, C, R, nvox)) return 0;
+  const int64_t nwg = (nvox + SMB_SPAN - 1) / SMB_SPAN;                     // <= 2^27
+  const int64_t row = (int64_t)R * (3 * C + 1) * (int64_t)sizeof(double);   // < 2^15
+  const int64_t nspan = (int64_t)B * nwg;                                   // < 2^58
+  return nspan > INT64_MAX / row ? 0 : nspan * row;                         // (no such batch fits a device: 0, refused below)
+}
+
+extern "C" int vx_soft_metric_sums_batched(const float* prob, const uint8_t* gt, int B, int C, int R, int64_t nvox, double* sums,
+                                           void* workspace, vx_stream_t stream) {
+  if (!smb_shape_ok(B, C, R, nvox))
+    VX_FAIL(VX_E_SHAPE, "vx_soft_metric_sums_batched: B=%d (>= 1) C=%d (1..%d) R=%d (1..%d) nvox=%lld (1..2^39)", B, C, SMB_MAXC, R,
+            SMB_MAXR, (long long)nvox);
+  if (vx_soft_metric_batched_workspace_bytes(B, C, R, nvox) == 0)
+    VX_FAIL(VX_E_SHAPE, "vx_soft_metric_sums_batched: B=%d images of %lld voxels", B, (long long)nvox);
+  if (!prob || !gt || !sums || !workspace) VX_FAIL(VX_E_NULL, "vx_soft_metric_sums_batched: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t nwg = (nvox + SMB_SPAN - 1) / SMB_SPAN, nspan = (int64_t)B * nwg;
+  const int vec = nvox % 4 == 0 && vx_aligned16(prob) && (((uintptr_t)gt) & 3u) == 0;
+  const dim3 grid((unsigned)(nspan < SMB_MAXWG ? nspan : SMB_MAXWG));
+  double* part = (double*)workspace;
+  if (R <= 4)
+    hipLaunchKernelGGL(soft_metric_batched_kernel<4>, grid, dim3(256), 0, s, prob, gt, C, R, nvox, nwg, nspan, vec, part);
+  else
+    hipLaunchKernelGGL(soft_metric_batched_kernel<SMB_MAXR>, grid, dim3(256), 0, s, prob, gt, C, R, nvox, nwg, nspan, vec, part);
+  const int K = R * (3 * C + 1);
+  const int64_t n = (int64_t)B * K, fb = (n + 255) / 256;
+  hipLaunchKernelGGL(soft_metric_batched_final_kernel, dim3((unsigned)(fb < SMB_MAXWG ? fb : SMB_MAXWG)), dim3(256), 0, s,
+                     (const double*)part, n, K, 3 * C + 1, nwg, sums);
+  VX_CHECK_LAUNCH("vx_soft_metric_sums_batched");
+  return VX_OK;
+}

@@ -8,6 +8,9 @@ masks, the voxels on which both carry class c; every Dice is then a ratio of sum
     tp = sum_c I[a][b][c],  fp = sum_c (I[a][a][c] - I[a][b][c]),  fn = sum_c (I[b][b][c] - I[a][b][c])
 with c running over the classes that survive `ignore_index` (torchmetrics deletes that one-hot column for micro
 averaging).  SoftDiceLoss + NLLLoss (loss_modules.py:7-97) come from `vx_soft_metric_sums`.
+
+Whole steps: `process_metrics_2d` (test_2D.py:205-244) and `process_metrics_3d` (calculate_metrics, test_3D.py:537-575)
+take the B images of an inference step through `vx_mask_agreement_batched` (and, 3D, `vx_soft_metric_sums_batched`) at once.
 """
 from __future__ import annotations
 
@@ -44,6 +47,28 @@ def mask_agreement_batched(masks: torch.Tensor, num_classes: int, remap_from: Op
     _lib.check(lib.vx_mask_agreement_batched(m.data_ptr(), B, M, num_classes, m.shape[2], -1 if remap_from is None else int(remap_from),
                                              out.data_ptr(), _lib.stream_ptr()), "vx_mask_agreement_batched")
     return out.cpu().numpy()
+
+
+def soft_metric_sums_batched(mean_softmax: torch.Tensor, gt: torch.Tensor) -> np.ndarray:
+    """mean_softmax (B, C, *spatial) float32 and gt (B, R, *spatial) integer labels on the device -> sums (B, R, 3C + 1)
+    float64 (host): per image, rater and class  sum p_c [g_r = c],  sum [g_r = c],  sum p_c,  then  sum log p_{g_r}  --
+    `vx_soft_metric_sums` of every image of a batch with one launch pair (`vx_soft_metric_sums_batched`: C <= 32,
+    R <= 31) and one device-to-host copy.  An image's row is bit-equal to what the same image gives when submitted alone."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    if mean_softmax.dim() < 2 or gt.dim() < 2 or gt.shape[0] != mean_softmax.shape[0]:
+        raise ValueError("soft_metric_sums_batched: mean_softmax (B, C, *spatial) and gt (B, R, *spatial) expected")
+    B, C, R = int(mean_softmax.shape[0]), int(mean_softmax.shape[1]), int(gt.shape[1])
+    p = mean_softmax.reshape(B, C, -1).to(torch.float32).contiguous()
+    g8 = gt.reshape(B, R, -1).to(torch.uint8).contiguous()
+    nvox = int(p.shape[2])
+    if g8.shape[2] != nvox:
+        raise ValueError(f"soft_metric_sums_batched: {nvox} voxels of probabilities, {g8.shape[2]} of labels")
+    sums = torch.empty((B, R, 3 * C + 1), dtype=torch.float64, device=p.device)
+    ws = torch.empty(max(int(lib.vx_soft_metric_batched_workspace_bytes(B, C, R, nvox)), 8), dtype=torch.uint8, device=p.device)
+    _lib.check(lib.vx_soft_metric_sums_batched(p.data_ptr(), g8.data_ptr(), B, C, R, nvox, sums.data_ptr(), ws.data_ptr(),
+                                               _lib.stream_ptr()), "vx_soft_metric_sums_batched")
+    return sums.cpu().numpy()
 
 
 def _micro_dice(I: np.ndarray, a_idx, b_idx, classes) -> float:
@@ -90,7 +115,16 @@ def calculate_test_metrics(output_softmax: torch.Tensor, ground_truth: torch.Ten
     from .uncertainty import uncertainty_maps
     am = uncertainty_maps(p.reshape(1, 1, C, nvox), from_logits=False)["argmax"].reshape(1, nvox)
     I = mask_agreement(torch.cat([am, g8], 0), C)
-    s = sums.cpu().numpy()
+    return _test_metrics_from_sums(sums.cpu().numpy(), I, C, nvox)
+
+
+def _test_metrics_from_sums(sums_row: np.ndarray, I: np.ndarray, C: int, nvox: int, pred: int = 0, raters=None) -> Dict:
+    """calculate_test_metrics' ratios for one image: sums_row (R, 3C + 1) the soft sums of its raters (vx_soft_metric_sums'
+    layout), I (M, M, C) its agreement counts; pred / raters: the rows of I that hold the arg-max of the mean prediction
+    and the R raters (default: row 0 and rows 1 .. R)."""
+    s = np.asarray(sums_row)
+    R = s.shape[0]
+    G = list(range(1, 1 + R)) if raters is None else list(raters)
     smooth = 1e-5
     losses, dices = [], []
     cls = _classes(C, 0)
@@ -99,7 +133,7 @@ def calculate_test_metrics(output_softmax: torch.Tensor, ground_truth: torch.Ten
         soft = np.mean(-((2.0 * inter + smooth) / ((psum + cnt) + smooth)))      # soft_dice, B = 1
         nll = -s[r, 3 * C] / nvox                                                 # NLLLoss mean reduction
         losses.append(soft + nll)
-        dices.append(_micro_dice(I, [0], [1 + r], cls))
+        dices.append(_micro_dice(I, [pred], [G[r]], cls))
     return {"loss": float(np.mean(np.array(losses))), "dice": float(np.mean(np.array(dices)))}
 
 
@@ -228,3 +262,94 @@ def process_metrics_2d(out: Dict, gt: torch.Tensor, ignore_label: int = 255, ged
         m.update(_ged_from_counts(I[b], P, G, Ce, Ce - 1, ged_only))
         res.append(m)
     return res if image_ids is None else dict(zip(image_ids, res))
+
+
+def _first(d: Dict, *keys):
+    for k in keys:
+        if d.get(k) is not None:
+            return d[k]
+    return None
+
+
+def process_metrics_3d(out: Dict, gt: torch.Tensor, image_ids=None, sample_argmax: Optional[torch.Tensor] = None,
+                       probs: Optional[torch.Tensor] = None):
+    """calculate_metrics of test_3D.py:537-575 for the B cases of a step: per case calculate_test_metrics ("loss": SoftDice +
+    NLL, "dice": Dice with ignore_index = 0, both averaged over the raters) and, when R > 1 or T > 1 (the reference's
+    condition), the keys of calculate_ged(..., ignore_index=0, ged_only=False).
+
+    out: what uncertainty_maps / predict_uncertainty return -- mean_softmax (B, C, *spatial), the arg-max of the mean
+    prediction ("argmax" or "pred_seg_mean", (B, *spatial); taken from mean_softmax when absent) and optionally the
+    per-sample arg-max masks ("sample_argmax" or "pred_seg", (B, T, *spatial)).  gt (B, R, *spatial) integer labels.
+    sample_argmax overrides out's; when neither is there the masks are taken from probs (B, T, C, *spatial) through
+    uncertainty_maps(want_sample_argmax=True); with none of the three T is unknown and only "loss" / "dice" are produced.
+    Returns a list of metric dicts in batch order, or {image_id: dict} with image_ids (what results.log_metrics takes).
+
+    One vx_soft_metric_sums_batched call, one vx_mask_agreement_batched call over the stacked [mean arg-max, T sample
+    arg-maxes, R raters] and two host copies; every ratio is formed on the host by the helpers the per-case functions use
+    (same integers, same float64 arithmetic).  The counts kernel takes at most 32 masks and 32 classes: with
+    1 + T + R > 32 or C > 32 the cases go through calculate_test_metrics / calculate_ged one at a time instead (same
+    results, the per-case launch count, and those functions' own limits)."""
+    _lib.require_gpu()
+    mean = out["mean_softmax"]
+    dev = mean.device if mean.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    mean = _to_dev(mean, dev).to(torch.float32)
+    if mean.dim() < 3:
+        raise ValueError("process_metrics_3d: out['mean_softmax'] (B, C, *spatial) expected")
+    B, C = int(mean.shape[0]), int(mean.shape[1])
+    g = _to_dev(gt, dev)
+    if g.dim() < 3 or g.shape[0] != B:
+        raise ValueError(f"process_metrics_3d: gt (B, R, *spatial) expected for {B} cases, got {tuple(g.shape)}")
+    R = int(g.shape[1])
+    if image_ids is not None and len(image_ids) != B:
+        raise ValueError(f"process_metrics_3d: {len(image_ids)} image ids for {B} cases")
+    nvox = mean[0, 0].numel()
+    from .uncertainty import uncertainty_maps
+    if sample_argmax is None:
+        sample_argmax = _first(out, "sample_argmax", "pred_seg")
+    if sample_argmax is None and probs is not None:
+        pd = _to_dev(probs, dev).to(torch.float32)
+        sample_argmax = uncertainty_maps(pd.reshape(B, pd.shape[1], C, nvox), from_logits=False, want_sample_argmax=True)["sample_argmax"]
+    T = None
+    if sample_argmax is not None:
+        sample_argmax = _to_dev(sample_argmax, dev)
+        T = int(sample_argmax.shape[1])
+    want_ged = _ged_due(T, R)
+    if 1 + (T or 0) + R > 32 or C > 32:
+        res = []
+        for b in range(B):
+            m = calculate_test_metrics(mean[b:b + 1], g[b])
+            if want_ged:
+                m.update(calculate_ged(mean[b:b + 1].expand((T,) + tuple(mean.shape[1:])), g[b], ignore_index=0,
+                                       pred_masks=sample_argmax[b]))   # (only T and C are read off the first argument)
+            res.append(m)
+        return res if image_ids is None else dict(zip(image_ids, res))
+    am = _first(out, "argmax", "pred_seg_mean")
+    if am is None:
+        am = uncertainty_maps(mean.reshape(B, 1, C, nvox), from_logits=False)["argmax"]
+    g8 = g.reshape(B, R, nvox).to(torch.uint8)
+    parts = [_to_dev(am, dev).reshape(B, 1, nvox).to(torch.uint8)]
+    if want_ged:
+        parts.append(sample_argmax.reshape(B, T, nvox).to(torch.uint8))
+    sums = soft_metric_sums_batched(mean, g8)
+    I = mask_agreement_batched(torch.cat(parts + [g8], 1), C)
+    res = _metrics_3d_from_reductions(sums, I, C, nvox, T, R)
+    return res if image_ids is None else dict(zip(image_ids, res))
+
+
+def _ged_due(T: Optional[int], R: int) -> bool:
+    """test_3D.py:554: the GED keys exist for several raters or several predictions (T None: no per-sample masks at all)"""
+    return T is not None and (R > 1 or T > 1)
+
+
+def _metrics_3d_from_reductions(sums: np.ndarray, I: np.ndarray, C: int, nvox: int, T: Optional[int], R: int):
+    """The host half of process_metrics_3d: sums (B, R, 3C + 1) and the counts I (B, M, M, C) of the stack
+    [mean arg-max, the T sample arg-maxes (only when the GED is due), R raters] -> the metric dicts in batch order."""
+    nP = T if _ged_due(T, R) else 0
+    P, G = list(range(1, 1 + nP)), list(range(1 + nP, 1 + nP + R))
+    res = []
+    for b in range(len(sums)):
+        m = _test_metrics_from_sums(sums[b], I[b], C, nvox, 0, G)
+        if nP:
+            m.update(_ged_from_counts(I[b], P, G, C, 0, False))
+        res.append(m)
+    return res
