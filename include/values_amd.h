@@ -691,6 +691,38 @@ int vx_box_max(const float* map, int D, int H, int W, int pd, int ph, int pw, do
                void* workspace, size_t workspace_bytes, vx_stream_t stream);
 int vx_sum_thr(const void* map, int dtype, int64_t n, double thr, double* sums, vx_stream_t stream);
 
+/* vx_aggregate_batched (K38): the three aggregations above for a batch of maps in one call, with the per-image kernels'
+ * float64 results bit for bit (every sum keeps their association; a map's results do not depend on its batch mates).
+ *   items  host array: a device map [D][H][W] (a 2D map: D = 1) of VX_F32 or VX_F64 each; shapes and dtypes may differ.
+ *   specs  host array, shared by all items.  kind IMAGE: sum of the map.  THRESHOLD: sum and count of the elements with
+ *          (double)x >= thr.  PATCH: maximum of the 'valid' (pd, ph, pw) box sums and its first C-order index with
+ *          |v - max| <= 1e-8 + 1e-5 |max| (np.isclose); a float64 map is narrowed to float32 first, as vx_box_max takes it.
+ *   out    device [n_items][n_specs][4] float64:  IMAGE {sum, 0, 0, 0};  THRESHOLD {sum, count, 0, 0};
+ *          PATCH {maximum, d, h, w} (the index as exact integers).
+ * 1 <= n_items <= 4096, 1 <= n_specs <= 8, a patch must fit every item's map (the message names the item), and a patch so
+ * large that no LDS tile holds its halo is refused: VX_E_SHAPE, before any device call.  All IMAGE / THRESHOLD specs of
+ * an item come from one read of its map (one workgroup per item); the box sums run on LDS tiles and keep two 8-byte
+ * words per tile in the workspace, never the box sums themselves.  At most four launches, whatever n_items and n_specs
+ * are.  The descriptor tables go up through a pinned staging buffer: the call does not wait for the stream (only, if
+ * it is still in flight, for the previous call's upload), and it is not capturable into a hipGraph.
+ * workspace of vx_aggregate_workspace_bytes(the same arguments), 0 for arguments the call refuses. */
+#define VX_AGG_IMAGE 0
+#define VX_AGG_THRESHOLD 1
+#define VX_AGG_PATCH 2
+typedef struct vx_agg_item {
+  const void* map;
+  int32_t dtype; /* VX_F32 | VX_F64 */
+  int32_t D, H, W;
+} vx_agg_item;
+typedef struct vx_agg_spec {
+  int32_t kind; /* VX_AGG_* */
+  int32_t pd, ph, pw;
+  double thr;
+} vx_agg_spec;
+size_t vx_aggregate_workspace_bytes(const vx_agg_item* items, int n_items, const vx_agg_spec* specs, int n_specs);
+int vx_aggregate_batched(const vx_agg_item* items /* host */, int n_items, const vx_agg_spec* specs /* host */, int n_specs,
+                         double* out /* device */, void* workspace, size_t workspace_bytes, vx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------
  * Device results writer (data_carrier_3D.py:208-371, DataCarrier3D.save_data; host mirror: values_amd/results.py
  * save_case).  The NIfTI payloads of a case are assembled on the device (vx_nifti_payload), compressed to gzip members

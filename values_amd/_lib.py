@@ -173,6 +173,20 @@ VX_PNG_OK, VX_PNG_BAD_FILTER, VX_PNG_BAD_SIZE = 0, 1, 2
 PNG_STATUS = ("ok", "filter byte above 4", "stream size is not H (1 + W bpp)")
 
 
+VX_AGG_IMAGE, VX_AGG_THRESHOLD, VX_AGG_PATCH = 0, 1, 2
+VX_AGG_MAX_SPECS, VX_AGG_MAX_ITEMS = 8, 4096
+
+
+class AggItem(C.Structure):
+    """vx_agg_item: one device map [D][H][W] (a 2D map: D = 1) of VX_F32 / VX_F64 for vx_aggregate_batched."""
+    _fields_ = [("map", _p), ("dtype", _i32), ("D", _i32), ("H", _i32), ("W", _i32)]
+
+
+class AggSpec(C.Structure):
+    """vx_agg_spec: one aggregation of a vx_aggregate_batched call (kind VX_AGG_*; patch for PATCH, thr for THRESHOLD)."""
+    _fields_ = [("kind", _i32), ("pd", _i32), ("ph", _i32), ("pw", _i32), ("thr", C.c_double)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -263,6 +277,8 @@ SIGNATURES = {
     "vx_calib_bins": (_i, [_p, _i, _p, _p, _i, _i64, _i, C.c_double, C.c_double, C.POINTER(C.c_double), _p, _p, _p]),
     "vx_box_max": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
     "vx_sum_thr": (_i, [_p, _i, _i64, C.c_double, _p, _p]),
+    "vx_aggregate_workspace_bytes": (C.c_size_t, [C.POINTER(AggItem), _i, C.POINTER(AggSpec), _i]),
+    "vx_aggregate_batched": (_i, [C.POINTER(AggItem), _i, C.POINTER(AggSpec), _i, _p, _p, C.c_size_t, _p]),
     "vx_nifti_workspace_bytes": (C.c_size_t, [_i]),
     "vx_nifti_payload_bytes": (_i64, [C.POINTER(NiftiItem)]),
     "vx_nifti_payload": (_i, [C.POINTER(NiftiItem), _i, _p, _i64, _p, C.c_size_t, _p]),

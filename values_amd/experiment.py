@@ -227,23 +227,36 @@ class ExperimentDataloader:
         return _load_file(self.unc_path_dict[unc_type] / f"{image_id}{self.exp_version.unc_ending}")
 
 
-def _aggregate(exp_dataloader, aggregations, images_of):
+def _aggregate(exp_dataloader, aggregations, images_of, batch=None):
     """aggregated_<unc>.json for every uncertainty type; images_of(unc_path, keys) yields the (key, image) pairs of a type's
     files, each image loaded once (the reference reloads per aggregation).  `_target_`s naming the reference's functions
-    are re-pointed to values_amd.aggregation (GPU)."""
-    from .io import TARGET_MAP
-    ref = "evaluation.uncertainty_aggregation.aggregate_uncertainties."
-    for fn in ("patch_level_aggregation", "image_level_aggregation", "threshold_aggregation"):
-        TARGET_MAP.setdefault(ref + fn, "values_amd.aggregation." + fn)
-        TARGET_MAP.setdefault("uncertainty_aggregation.aggregate_uncertainties." + fn, "values_amd.aggregation." + fn)
+    are re-pointed to values_amd.aggregation (GPU).  batch=None: every image and aggregation on its own (instantiate);
+    batch=n: n consecutive images per aggregation.aggregate_batch call, the same results in one device call each."""
+    from . import aggregation
+    aggregation.register_targets()
     ending = exp_dataloader.exp_version.unc_ending
+    pred_model = exp_dataloader.exp_version.pred_model
     for unc, unc_path in exp_dataloader.unc_path_dict.items():
         all_uncs = {}
-        for key, unc_image in images_of(unc_path, [f"{image_id}{ending}" for image_id in exp_dataloader.image_ids]):
-            all_uncs[key] = {}
-            for name, cfg in aggregations.items():
-                all_uncs[key][name] = instantiate(dict(cfg), image=unc_image,
-                                                  pred_model=exp_dataloader.exp_version.pred_model, unc_type=unc)
+        pairs = images_of(unc_path, [f"{image_id}{ending}" for image_id in exp_dataloader.image_ids])
+        if batch is None:
+            for key, unc_image in pairs:
+                all_uncs[key] = {}
+                for name, cfg in aggregations.items():
+                    all_uncs[key][name] = instantiate(dict(cfg), image=unc_image, pred_model=pred_model, unc_type=unc)
+        else:
+            pending = []
+
+            def flush():
+                got = aggregation.aggregate_batch([im for _, im in pending], aggregations, pred_model=pred_model, unc_type=unc)
+                all_uncs.update(zip((k for k, _ in pending), got))
+                pending.clear()
+            for pair in pairs:
+                pending.append(pair)
+                if len(pending) >= max(int(batch), 1):
+                    flush()
+            if pending:
+                flush()
         with open(exp_dataloader.dataset_path / f"aggregated_{unc}.json", "w") as f:
             json.dump(all_uncs, f, indent=4)
 
@@ -346,10 +359,10 @@ def _chunks(seq, n):
 
 def aggregate_uncertainties_device(exp_dataloader: ExperimentDataloader, aggregations, batch: int = 32):
     """aggregate_uncertainties with the maps read on the device: every map of a type is read with nifti.NiftiReader (or,
-    for a 2D tree's TIFF maps, images.ImageReader), `batch` files per call, and handed to the aggregations as a device
-    tensor.  Writes the same aggregated_<unc>.json, byte for byte."""
+    for a 2D tree's TIFF maps, images.ImageReader), `batch` files per call, and the maps of one reader batch are
+    aggregated by one aggregation.aggregate_batch call.  Writes the same aggregated_<unc>.json, byte for byte."""
     def images_of(unc_path, keys):
         for key, (_, unc_image) in zip(keys, _read_batches_device([unc_path / k for k in keys], batch)):
             yield key, unc_image
 
-    _aggregate(exp_dataloader, aggregations, images_of)
+    _aggregate(exp_dataloader, aggregations, images_of, batch=batch)
