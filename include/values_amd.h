@@ -678,6 +678,55 @@ int vx_calib_bins(const void* unc, int dtype, const int32_t* ref, const int32_t*
                   int ignore_value, double A, double B, const double* edges21, double* bins63, void* workspace,
                   vx_stream_t stream);
 
+/* The three reductions above for a batch of images in one call each (evalmetrics_batched.hip), with the per-image entry
+ * points' float64 results bit for bit: every sum keeps their association (thread t of block b adds elements
+ * b * 256 + t + k * 131072 in ascending k, a 64-lane shuffle tree, four waves in order, 512 block rows in index order),
+ * and an item's numbers do not depend on its batch mates or on n_items.  Items of a call may differ in size, R and dtype.
+ *   items      HOST array of descriptors of DEVICE buffers.  1 <= n_items <= VX_EM_MAX_ITEMS, R >= 1, nvox >= 1.
+ *   vx_ncc_batched         sums [n_items][5] (device) = sum gt, sum pred, sum (gt-mg)^2, sum (pred-mp)^2,
+ *                          sum (gt-mg)(pred-mp) with mg = sums[0] / (double)n, mp = sums[1] / (double)n formed on the
+ *                          device between the passes (the IEEE division the host does for vx_ncc_sums).  Four launches,
+ *                          no synchronisation.  The ground-truth side is a map (gt_R = 0, gt_dtype VX_F32 | VX_F64) or
+ *                          gt_R >= 1 int32 label volumes [gt_R][n]: then every voxel's value is np.var(labels, axis=0),
+ *                          evaluated on the fly in float64 in numpy's order (sum over raters in index order, / R, sum
+ *                          of (x - mean)^2 in index order, / R; no multiply-add is fused); the variance map is never
+ *                          written.  n_gt != n_pred is refused.
+ *   vx_rater_variance      that variance as a float64 map [nvox] of its own (one launch).
+ *   vx_platt_sums_batched  sums [n_items][8] (device), the eight numbers of vx_platt_sums; params: HOST [n_items][4] =
+ *                          (A, B, t_pos, t_neg) per item; one ignore_value for the call.  Two launches.
+ *   vx_calib_bins_batched  bins63 [n_items][63] (device), the numbers of vx_calib_bins; ab: HOST [n_items][2] = (A, B)
+ *                          per item; edges21: HOST.  Two launches.
+ * Every argument check (VX_E_NULL / VX_E_SHAPE / VX_E_DTYPE, the message names the item; VX_E_WORKSPACE / VX_E_ALIGN)
+ * returns before any device call.  workspace: caller-owned, of vx_*_batched_workspace_bytes(the same items) bytes --
+ * the descriptor table and 512 partial rows per item -- 0 for arguments the call refuses.  The descriptor table goes up
+ * through a pinned staging buffer: a call does not wait for the stream (only, if it is still in flight, for the previous
+ * call's upload), and it is not capturable into a hipGraph. */
+#define VX_EM_MAX_ITEMS 4096
+typedef struct vx_em_item {
+  const void* unc;     /* device [nvox], VX_F32 | VX_F64 */
+  const int32_t* ref;  /* device [R][nvox] reference segmentations */
+  const int32_t* pred; /* device [nvox] mean prediction */
+  int64_t nvox;
+  int32_t dtype, R;
+} vx_em_item;
+typedef struct vx_ncc_item {
+  const void* gt;       /* gt_R == 0: device map [n_gt] of gt_dtype;  gt_R >= 1: device int32 labels [gt_R][n_gt] */
+  const void* pred;     /* device map [n_pred] of pred_dtype */
+  int64_t n_gt, n_pred; /* must be equal */
+  int32_t gt_dtype, pred_dtype, gt_R, reserved;
+} vx_ncc_item;
+size_t vx_ncc_batched_workspace_bytes(const vx_ncc_item* items, int n_items);
+int vx_ncc_batched(const vx_ncc_item* items /* host */, int n_items, double* sums /* device */, void* workspace,
+                   size_t workspace_bytes, vx_stream_t stream);
+int vx_rater_variance(const int32_t* labels, int R, int64_t nvox, double* variance, vx_stream_t stream);
+size_t vx_platt_batched_workspace_bytes(const vx_em_item* items, int n_items);
+int vx_platt_sums_batched(const vx_em_item* items /* host */, int n_items, const double* params /* host */, int ignore_value,
+                          double* sums /* device */, void* workspace, size_t workspace_bytes, vx_stream_t stream);
+size_t vx_calib_batched_workspace_bytes(const vx_em_item* items, int n_items);
+int vx_calib_bins_batched(const vx_em_item* items /* host */, int n_items, const double* ab /* host */,
+                          const double* edges21 /* host */, int ignore_value, double* bins63 /* device */, void* workspace,
+                          size_t workspace_bytes, vx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------
  * K19/K20: map -> scalar aggregations (evaluation/uncertainty_aggregation/aggregate_uncertainties.py).
  *   vx_box_max : patch_level_aggregation (:13-31): box-sum 'valid' (pd,ph,pw) in float64, max and

@@ -1,0 +1,87 @@
+"""Inputs shared by tests/test_evalmetrics_batched_cpu.py and tests/test_gpu_evalmetrics_batched.py: a numpy stand-in for
+the Platt sums, images whose Platt fits finish in different rounds, rater label stacks, and a datamodule stub for a
+results tree whose reference segmentations come from a dataloader."""
+import os
+
+import numpy as np
+
+
+def platt_sums_numpy(unc, correct, A, B, t_pos, t_neg):
+    """numpy stand-in for vx_platt_sums (R = 1, nothing ignored): the same eight sums, numpy's summation order"""
+    F = -np.asarray(unc, dtype=np.float64)
+    T = np.where(correct, t_pos, t_neg)
+    z = A * F + B
+    e = np.exp(-np.abs(z))
+    P = np.where(z >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+    loss = np.where(z >= 0, T * z, (T - 1.0) * z) + np.log1p(e)
+    d, w = T - P, P * (1.0 - P)
+    return [float(len(F)), float(np.sum(correct)), float(loss.sum()), float((d * F).sum()), float(d.sum()),
+            float((w * F * F).sum()), float((w * F).sum()), float(w.sum())]
+
+
+def platt_items():
+    """(uncertainty, correct) of six one-rater images that finish in different rounds: one whose start point is already the
+    optimum (zero map, as many correct as wrong voxels), well and badly separated ones, and two heavy-tailed maps (a few
+    huge uncertainties among tiny ones) on which the full Newton step overshoots, so the line search halves it"""
+    items = [(np.zeros(40), np.arange(40) % 2 == 0)]
+    rng = np.random.default_rng(7)
+    for n, sep, flip in ((500, 0.0, 0.3), (257, 0.5, 0.0), (1031, 0.3, 0.02)):
+        correct = rng.random(n) < 0.7
+        unc = np.where(correct, rng.random(n) * 0.2, 0.2 + sep + rng.random(n) * 0.2)
+        items.append((unc, correct ^ (rng.random(n) < flip)))
+    for seed, n in ((27, 241), (7, 103)):
+        rng = np.random.default_rng(seed)
+        correct = rng.random(n) < 0.97
+        correct[:2] = (True, False)
+        items.append((np.exp(rng.normal(0.0, 3.0, n)) * np.where(correct, 0.1, 1.0), correct))
+    return items
+
+
+def rater_label_cases():
+    """label stacks (R, *spatial) for R in {1, 3, 4}, labels 0..3, a 3D and a 2D shape"""
+    rng = np.random.default_rng(21)
+    return [rng.integers(0, 4, (R,) + shape).astype(np.int32) for R in (1, 3, 4) for shape in ((5, 7, 3), (64, 48))]
+
+
+def rater_variance_restated(labels):
+    """np.var(labels, axis=0) in the order of the device function em_rater_var, one float64 operation at a time"""
+    R = labels.shape[0]
+    s = np.zeros(labels.shape[1:], dtype=np.float64)
+    for r in range(R):
+        s = s + labels[r].astype(np.float64)
+    mean = s / np.float64(R)
+    q = np.zeros_like(s)
+    for r in range(R):
+        d = labels[r].astype(np.float64) - mean
+        q = q + d * d
+    return q / np.float64(R)
+
+
+class StubDataModule:
+    """datamodule_config target of a test tree: <root>/<split>/<id>.npy is an image's (H, W) label (what gta.gt_unc_map
+    reads through dataset.masks), <id>_seg.npy its (R, H, W) reference segmentations"""
+
+    def __init__(self, root, test_split):
+        self.dir = os.path.join(root, test_split)
+
+    def setup(self, stage):
+        pass
+
+    def test_dataloader(self):
+        return _StubLoader(self.dir)
+
+
+class _StubDataset:
+    def __init__(self, d):
+        self.dir = d
+        self.image_ids = sorted(f[:-4] for f in os.listdir(d) if f.endswith(".npy") and not f.endswith("_seg.npy"))
+        self.masks = [os.path.join(d, f"{i}.npy") for i in self.image_ids]
+
+    def __getitem__(self, idx):
+        import torch
+        return {"seg": torch.from_numpy(np.load(os.path.join(self.dir, f"{self.image_ids[idx]}_seg.npy")))[None]}
+
+
+class _StubLoader:
+    def __init__(self, d):
+        self.dataset = _StubDataset(d)

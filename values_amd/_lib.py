@@ -187,6 +187,21 @@ class AggSpec(C.Structure):
     _fields_ = [("kind", _i32), ("pd", _i32), ("ph", _i32), ("pw", _i32), ("thr", C.c_double)]
 
 
+VX_EM_MAX_ITEMS = 4096
+
+
+class EmItem(C.Structure):
+    """vx_em_item: one image of vx_platt_sums_batched / vx_calib_bins_batched: device map [nvox] (VX_F32 / VX_F64), int32
+    reference segmentations [R][nvox] and mean prediction [nvox]."""
+    _fields_ = [("unc", _p), ("ref", _p), ("pred", _p), ("nvox", _i64), ("dtype", _i32), ("R", _i32)]
+
+
+class NccItem(C.Structure):
+    """vx_ncc_item: one map pair of vx_ncc_batched; gt is a map (gt_R = 0) or gt_R int32 label volumes [gt_R][n_gt]."""
+    _fields_ = [("gt", _p), ("pred", _p), ("n_gt", _i64), ("n_pred", _i64), ("gt_dtype", _i32), ("pred_dtype", _i32),
+                ("gt_R", _i32), ("reserved", _i32)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -275,6 +290,14 @@ SIGNATURES = {
     "vx_ncc_sums": (_i, [_p, _i, _p, _i, _i64, _i, C.c_double, C.c_double, _p, _p, _p]),
     "vx_platt_sums": (_i, [_p, _i, _p, _p, _i, _i64, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p]),
     "vx_calib_bins": (_i, [_p, _i, _p, _p, _i, _i64, _i, C.c_double, C.c_double, C.POINTER(C.c_double), _p, _p, _p]),
+    "vx_ncc_batched_workspace_bytes": (C.c_size_t, [C.POINTER(NccItem), _i]),
+    "vx_ncc_batched": (_i, [C.POINTER(NccItem), _i, _p, _p, C.c_size_t, _p]),
+    "vx_rater_variance": (_i, [_p, _i, _i64, _p, _p]),
+    "vx_platt_batched_workspace_bytes": (C.c_size_t, [C.POINTER(EmItem), _i]),
+    "vx_platt_sums_batched": (_i, [C.POINTER(EmItem), _i, C.POINTER(C.c_double), _i, _p, _p, C.c_size_t, _p]),
+    "vx_calib_batched_workspace_bytes": (C.c_size_t, [C.POINTER(EmItem), _i]),
+    "vx_calib_bins_batched": (_i, [C.POINTER(EmItem), _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _p, _p,
+                                   C.c_size_t, _p]),
     "vx_box_max": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
     "vx_sum_thr": (_i, [_p, _i, _i64, C.c_double, _p, _p]),
     "vx_aggregate_workspace_bytes": (C.c_size_t, [C.POINTER(AggItem), _i, C.POINTER(AggSpec), _i]),

@@ -6,10 +6,9 @@
 // Every value is a float64 formed with the association of the per-image kernels, so the results are theirs bit for bit
 // and do not depend on the batch, the tiling or the chunking.  At most four launches per call, whatever n_items and
 // n_specs are; no atomics; nothing but the descriptor upload touches the host.
-#include <mutex>
-
 #include "aggregate_plan.h"
 #include "common.h"
+#include "staging.h"
 
 // the IMAGE / THRESHOLD specs of a call, by value: thr[j] is the j-th distinct THRESHOLD spec, slot[s] its j for spec s
 struct agg_sum_specs {
@@ -250,51 +249,13 @@ __global__ __launch_bounds__(64) void agg_box_finish_kernel(const agg_pair* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Descriptor upload without a wait on the stream: the tables go through one pinned staging buffer, and a call waits
-// only for the event behind the PREVIOUS call's upload (long complete unless calls are issued back to back).
-namespace {
-struct agg_staging {
-  std::mutex mu;
-  void* host = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  int dev = -1;
-  bool pending = false;
-};
-agg_staging g_stage;
-}  // namespace
+// The two tables go up through the pinned staging buffer of staging.h: no wait on the stream.
+static vx_staging g_stage;
 
 static int agg_upload(const agg_plan& p, void* workspace, hipStream_t s) {
-  agg_staging& st = g_stage;
-  std::lock_guard<std::mutex> lock(st.mu);
-  hipError_t e = hipSuccess;
-  int dev = 0;
-  if ((e = hipGetDevice(&dev)) != hipSuccess) VX_FAIL((int)e, "vx_aggregate_batched: hipGetDevice: %s", hipGetErrorString(e));
-  if (st.pending && (e = hipEventSynchronize(st.ev)) != hipSuccess)
-    VX_FAIL((int)e, "vx_aggregate_batched: descriptor upload: %s", hipGetErrorString(e));
-  st.pending = false;
-  if (st.ev && st.dev != dev) { hipEventDestroy(st.ev); st.ev = nullptr; }
-  if (!st.ev) {
-    if ((e = hipEventCreateWithFlags(&st.ev, hipEventDisableTiming)) != hipSuccess)
-      VX_FAIL((int)e, "vx_aggregate_batched: hipEventCreate: %s", hipGetErrorString(e));
-    st.dev = dev;
-  }
-  const size_t bytes = p.off_tmax;
-  if (bytes > st.cap) {
-    if (st.host) hipHostFree(st.host);
-    st.host = nullptr; st.cap = 0;
-    const size_t cap = bytes < (64 << 10) ? (64 << 10) : bytes * 2;
-    if ((e = hipHostMalloc(&st.host, cap, hipHostMallocDefault)) != hipSuccess)
-      VX_FAIL((int)e, "vx_aggregate_batched: %zu bytes of pinned staging: %s", cap, hipGetErrorString(e));
-    st.cap = cap;
-  }
-  memcpy(st.host, p.sums.data(), p.sums.size() * sizeof(agg_sum_item));
-  memcpy((char*)st.host + p.off_pairs, p.pairs.data(), p.pairs.size() * sizeof(agg_pair));
-  if ((e = hipMemcpyAsync(workspace, st.host, bytes, hipMemcpyHostToDevice, s)) != hipSuccess ||
-      (e = hipEventRecord(st.ev, s)) != hipSuccess)
-    VX_FAIL((int)e, "vx_aggregate_batched: descriptor upload: %s", hipGetErrorString(e));
-  st.pending = true;
-  return VX_OK;
+  const vx_stage_part parts[2] = {{p.sums.data(), p.sums.size() * sizeof(agg_sum_item), 0},
+                                  {p.pairs.data(), p.pairs.size() * sizeof(agg_pair), p.off_pairs}};
+  return vx_staged_upload(g_stage, "vx_aggregate_batched", parts, 2, p.off_tmax, workspace, s);
 }
 
 extern "C" size_t vx_aggregate_workspace_bytes(const vx_agg_item* items, int n_items, const vx_agg_spec* specs, int n_specs) {

@@ -6,6 +6,10 @@ Where the work is per voxel it runs on the GPU in float64 (values_amd/csrc/evalm
   sigmoid_calibration      ace.py:13-41     Platt scaling of -uncertainty against "reference == prediction": loss,
                                             gradient and Hessian sums on the device, Newton steps on the host
   calc_ace                 ace.py:44-90     platt_scale_confid + the 20-bin statistics of calib_stats in one pass
+The same three scores for a whole batch of images per device call (values_amd/csrc/evalmetrics_batched.hip, the per-image
+results bit for bit): ncc_batch, sigmoid_calibration_batch (the Newton iterations of all images in lock step), calc_ace_batch,
+and the drivers ambiguity_modeling_device / platt_scale_params_device / calibration_error_device / calibration_device, which
+take a DeviceExperimentDataloader and write the same JSON files byte for byte.
 Where it is one scalar per IMAGE (AURC / E-AURC over (risk, confidence) pairs, AUROC over (OoD label, score) pairs:
 a few hundred numbers) it stays on the host, restated in numpy float64: aurc.py:14-67, and sklearn's roc_curve + auc
 as auroc.py:126-127 calls them.  scikit-learn itself is not needed.
@@ -29,6 +33,17 @@ def _workspace(dev):
     if key not in _ws:
         _ws[key] = torch.empty(_lib.load().vx_evalmetrics_workspace_bytes(), dtype=torch.uint8, device=dev)
     return _ws[key]
+
+
+def _workspace_batched(dev, need):
+    key = ("batched", str(dev))
+    if key not in _ws or _ws[key].numel() < need:
+        _ws[key] = torch.empty(max(int(need), 1 << 16), dtype=torch.uint8, device=dev)
+    return _ws[key]
+
+
+def _on_device(a):
+    return isinstance(a, torch.Tensor) and a.is_cuda
 
 
 def _dev():
@@ -153,10 +168,84 @@ def compute_ncc(gt_unc_map, pred_unc_map):
     s0 = sums.tolist()
     mg, mp = s0[0] / n, s0[1] / n
     _lib.check(lib.vx_ncc_sums(_lib.ptr(g), gd, _lib.ptr(p), pd, n, 1, mg, mp, _lib.ptr(sums), _lib.ptr(ws), st), "vx_ncc_sums")
-    vg, vp, prod = sums.tolist()
+    return _ncc_value(n, *sums.tolist())
+
+
+def _ncc_value(n, vg, vp, prod):
+    """ncc.py:21-25 from the three centred sums (Python floats) of a pair of n-element maps"""
     sg, sp = np.sqrt(vg / (n - 1)), np.sqrt(vp / (n - 1))
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.float64(1.0) / (np.float64(n) * sg * sp) * np.float64(prod)
+
+
+def _integer_dtype(a):
+    dt = a.dtype
+    return (not dt.is_floating_point and not dt.is_complex) if isinstance(dt, torch.dtype) else dt.kind in "biu"
+
+
+def _is_rater_stack(g, p):
+    """the ground-truth side of ncc_batch is a stack of label volumes (R, *spatial) when it has an integer / bool dtype
+    and one axis more than the predicted map; anything else is a map"""
+    return _integer_dtype(g) and g.ndim == p.ndim + 1 and tuple(g.shape[1:]) == tuple(p.shape)
+
+
+def _labels(a, dev):
+    """label volume(s) as a contiguous int32 device tensor; a device tensor is converted where it lies"""
+    if _on_device(a):
+        return a.detach().to(torch.int32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.int32)).to(dev)
+
+
+def rater_variance(reference_segs):
+    """np.var(reference_segs, axis=0) of integer label volumes (R, *spatial) as a float64 device map, bit for bit"""
+    dev = _dev()
+    lab = _labels(reference_segs, dev)
+    out = torch.empty(tuple(lab.shape[1:]), dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().vx_rater_variance(_lib.ptr(lab), int(lab.shape[0]), out.numel(), _lib.ptr(out), _lib.stream_ptr()),
+               "vx_rater_variance")
+    return out
+
+
+def _ncc_sums_batch(gts, preds):
+    """[(n, [sum g, sum p, sum (g-mg)^2, sum (p-mp)^2, sum (g-mg)(p-mp)])] per pair: one vx_ncc_batched call and ONE
+    device -> host copy per VX_EM_MAX_ITEMS pairs"""
+    lib, dev = _lib.load(), _dev()
+    rows = [None] * len(gts)
+    for lo in range(0, len(gts), _lib.VX_EM_MAX_ITEMS):
+        members = range(lo, min(lo + _lib.VX_EM_MAX_ITEMS, len(gts)))
+        keep, items = [], []
+        for i in members:
+            g, p = gts[i], preds[i]
+            pt, pdt = _float_map(p, dev)
+            if _is_rater_stack(g, p):
+                gt, gdt, R = _labels(g, dev), _lib.VX_F32, int(g.shape[0])
+                n_gt = gt.numel() // R
+            else:
+                gt, gdt = _float_map(g, dev)
+                R, n_gt = 0, gt.numel()
+            if n_gt != pt.numel():
+                raise ValueError(f"ncc_batch: pair {i}: maps of different size")
+            keep.append((gt, pt))
+            items.append(_lib.NccItem(gt.data_ptr(), pt.data_ptr(), n_gt, pt.numel(), gdt, pdt, R, 0))
+        arr = (_lib.NccItem * len(items))(*items)
+        ws = _workspace_batched(dev, int(lib.vx_ncc_batched_workspace_bytes(arr, len(items))))
+        sums = torch.empty((len(items), 5), dtype=torch.float64, device=dev)
+        _lib.check(lib.vx_ncc_batched(arr, len(items), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "vx_ncc_batched")
+        for i, it, row in zip(members, items, sums.cpu().tolist()):
+            rows[i] = (int(it.n_gt), row)
+    return rows
+
+
+def ncc_batch(gt_maps_or_rater_stacks, pred_maps):
+    """[compute_ncc(g, p)] for a list of pairs (arrays or tensors, host or device; sizes and dtypes may differ), bit for
+    bit, from one device call and one device -> host copy per batch (_ncc_sums_batch).  A ground-truth entry with an
+    integer dtype and shape (R, *pred.shape) is a stack of rater label volumes: the pair's value is
+    compute_ncc(np.var(stack, axis=0), p), the variance evaluated inside the kernel."""
+    gts, preds = list(gt_maps_or_rater_stacks), list(pred_maps)
+    if len(gts) != len(preds):
+        raise ValueError("ncc_batch: lists of different length")
+    return [_ncc_value(n, row[2], row[3], row[4]) for n, row in _ncc_sums_batch(gts, preds)]
 
 
 def ambiguity_modeling(exp_dataloader):
@@ -182,6 +271,22 @@ class _RaterInputs:
 
     def __init__(self, reference_segs, pred_seg, unc_map, ignore_value=None):
         dev = _dev()
+        self.ignore = -1 if ignore_value is None else int(ignore_value)
+        if ignore_value is not None and int(ignore_value) < 0:
+            raise ValueError("ignore_value must be a non-negative label")
+        self.dev = dev
+        if any(_on_device(a) for a in (reference_segs, pred_seg, unc_map)):
+            # device inputs stay on the device: labels converted where they lie, the 2D swap as a device transpose
+            ref, pred = _labels(reference_segs, dev), _labels(pred_seg, dev)
+            unc, self.dtype = _float_map(unc_map if isinstance(unc_map, (np.ndarray, torch.Tensor)) else np.asarray(unc_map), dev)
+            if tuple(pred.shape) != tuple(unc.shape):
+                unc = unc.transpose(0, 1).contiguous()
+            if tuple(ref.shape[1:]) != tuple(pred.shape) or tuple(unc.shape) != tuple(pred.shape):
+                raise ValueError(f"reference {tuple(ref.shape)}, prediction {tuple(pred.shape)} and map {tuple(unc.shape)} "
+                                 "do not fit together")
+            self.R, self.nvox = int(ref.shape[0]), int(pred.numel())
+            self.ref, self.pred, self.unc = ref, pred, unc
+            return
         ref = np.asarray(reference_segs)
         pred = np.asarray(pred_seg)
         unc = unc_map.detach().cpu().numpy() if isinstance(unc_map, torch.Tensor) else np.asarray(unc_map)
@@ -193,10 +298,6 @@ class _RaterInputs:
         self.ref = torch.from_numpy(np.ascontiguousarray(ref, dtype=np.int32)).to(dev)
         self.pred = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.int32)).to(dev)
         self.unc, self.dtype = _float_map(unc, dev)
-        self.ignore = -1 if ignore_value is None else int(ignore_value)
-        if ignore_value is not None and int(ignore_value) < 0:
-            raise ValueError("ignore_value must be a non-negative label")
-        self.dev = dev
 
 
 def _platt_sums(x: _RaterInputs, A, B, t_pos, t_neg):
@@ -207,6 +308,110 @@ def _platt_sums(x: _RaterInputs, A, B, t_pos, t_neg):
     return sums.tolist()
 
 
+def _em_items(xs):
+    return (_lib.EmItem * len(xs))(*[_lib.EmItem(x.unc.data_ptr(), x.ref.data_ptr(), x.pred.data_ptr(), x.nvox, x.dtype, x.R)
+                                     for x in xs])
+
+
+def _platt_sums_batch(xs, params):
+    """the eight sums of _platt_sums for every x of xs at its own (A, B, t_pos, t_neg): one vx_platt_sums_batched call
+    and one device -> host copy per VX_EM_MAX_ITEMS inputs"""
+    lib, rows = _lib.load(), []
+    for lo in range(0, len(xs), _lib.VX_EM_MAX_ITEMS):
+        part, par = xs[lo:lo + _lib.VX_EM_MAX_ITEMS], params[lo:lo + _lib.VX_EM_MAX_ITEMS]
+        dev, n = part[0].dev, len(part)
+        items = _em_items(part)
+        flat = (C.c_double * (4 * n))(*[float(v) for p in par for v in p])
+        ws = _workspace_batched(dev, int(lib.vx_platt_batched_workspace_bytes(items, n)))
+        sums = torch.empty((n, 8), dtype=torch.float64, device=dev)
+        _lib.check(lib.vx_platt_sums_batched(items, n, flat, part[0].ignore, _lib.ptr(sums), _lib.ptr(ws), ws.numel(),
+                                             _lib.stream_ptr()), "vx_platt_sums_batched")
+        rows += sums.cpu().tolist()
+    return rows
+
+
+class _PlattFit:
+    """The damped Newton iteration of sigmoid_calibration for ONE image as a state machine: `request` is the
+    (A, B, t_pos, t_neg) whose eight sums it wants next, feed(sums) takes them and moves on, until `done`.  Phases (the
+    evaluation that is outstanding): "counts" (valid / correct voxels), "start" (the start point), "newton" (the full
+    Newton step, t = 1), "line_search" (a halved step).  sigmoid_calibration feeds it one evaluation at a time,
+    sigmoid_calibration_batch feeds a whole batch of them per device call: the same arithmetic on the same sums, so the
+    same (A, B) sequence.  `visited` lists the (phase, A, B, t) evaluated."""
+
+    def __init__(self, max_iter=100):
+        self.max_iter, self.iters = max_iter, 0
+        self.phase, self.done, self.t = "counts", False, 1.0
+        self.request = (0.0, 0.0, 0.5, 0.5)
+        self.visited = []
+
+    def _ask(self, phase, A, B):
+        self.phase, self.request = phase, (float(A), float(B), self.t_pos, self.t_neg)
+
+    def feed(self, s):
+        self.visited.append((self.phase, self.request[0], self.request[1], self.t))
+        if self.phase == "counts":
+            self.n, n1 = s[0], s[1]
+            if self.n <= 0:
+                raise ValueError("sigmoid_calibration: no valid voxel")
+            prior1, prior0 = n1, self.n - n1
+            self.t_pos, self.t_neg = (prior1 + 1.0) / (prior1 + 2.0), 1.0 / (prior0 + 2.0)
+            self.A, self.B = 0.0, float(np.log((prior0 + 1.0) / (prior1 + 1.0)))
+            self._ask("start", self.A, self.B)
+        elif self.phase == "start":
+            self.s = s
+            self._newton()
+        else:
+            if s[2] <= self.loss + 1e-12 * abs(self.loss) or self.t < 1e-10:
+                self.A, self.B, self.s = self.trial[0], self.trial[1], s
+                self.iters += 1
+                self._newton()
+            else:
+                self.t *= 0.5
+                self._trial("line_search")
+
+    def _trial(self, phase):
+        self.trial = (self.A - self.t * self.step[0], self.B - self.t * self.step[1])
+        self._ask(phase, *self.trial)
+
+    def _newton(self):
+        s = self.s
+        self.loss, g, H = s[2], np.array([s[3], s[4]]), np.array([[s[5], s[6]], [s[6], s[7]]])
+        if self.iters >= self.max_iter or np.abs(g).max() < 1e-10 * max(1.0, self.n):
+            self.done, self.request = True, None
+            return
+        self.step = np.linalg.solve(H + 1e-12 * np.eye(2), g)
+        self.t = 1.0
+        self._trial("newton")
+
+    @property
+    def result(self):
+        return float(self.A), float(self.B)
+
+
+def _platt_fit_one(evaluate, max_iter=100):
+    """evaluate(A, B, t_pos, t_neg) -> the eight sums of one image"""
+    fit = _PlattFit(max_iter)
+    while not fit.done:
+        fit.feed(evaluate(*fit.request))
+    return fit
+
+
+def _platt_fit_lockstep(n_items, evaluate, max_iter=100):
+    """evaluate(indices, requests) -> the eight sums of every listed item at its request.  Every round evaluates all
+    unfinished items at once; a finished item drops out of the table."""
+    fits = [_PlattFit(max_iter) for _ in range(n_items)]
+    active = list(range(n_items))
+    while active:
+        rows = evaluate(active, [fits[i].request for i in active])
+        for i, s in zip(active, rows):
+            try:
+                fits[i].feed(s)
+            except ValueError as e:
+                raise ValueError(f"item {i}: {e}") from None
+        active = [i for i in active if not fits[i].done]
+    return fits
+
+
 def sigmoid_calibration(reference_segs, pred_seg, unc_map, ignore_value=None, max_iter=100):
     """(a, b) of sklearn.calibration._sigmoid_calibration(-unc, reference == prediction) as ace.py:30-36 calls it:
     Platt's regularised targets, P = 1 / (1 + exp(a F + b)).  The objective is convex in (a, b); every evaluation
@@ -214,27 +419,16 @@ def sigmoid_calibration(reference_segs, pred_seg, unc_map, ignore_value=None, ma
     optimum (|gradient| below 1e-10 per sample).  sklearn reaches the same optimum with BFGS (1.2.2, the reference's
     pin) or L-BFGS-B (>= 1.4) to ITS tolerance -- that difference is the only unpinned part."""
     x = _RaterInputs(reference_segs, pred_seg, unc_map, ignore_value)
-    s = _platt_sums(x, 0.0, 0.0, 0.5, 0.5)
-    n, n1 = s[0], s[1]
-    if n <= 0:
-        raise ValueError("sigmoid_calibration: no valid voxel")
-    prior1, prior0 = n1, n - n1
-    t_pos, t_neg = (prior1 + 1.0) / (prior1 + 2.0), 1.0 / (prior0 + 2.0)
-    A, B = 0.0, float(np.log((prior0 + 1.0) / (prior1 + 1.0)))
-    s = _platt_sums(x, A, B, t_pos, t_neg)
-    for _ in range(max_iter):
-        loss, g, H = s[2], np.array([s[3], s[4]]), np.array([[s[5], s[6]], [s[6], s[7]]])
-        if np.abs(g).max() < 1e-10 * max(1.0, n):
-            break
-        step = np.linalg.solve(H + 1e-12 * np.eye(2), g)
-        t = 1.0
-        while True:
-            s2 = _platt_sums(x, A - t * step[0], B - t * step[1], t_pos, t_neg)
-            if s2[2] <= loss + 1e-12 * abs(loss) or t < 1e-10:
-                break
-            t *= 0.5
-        A, B, s = A - t * step[0], B - t * step[1], s2
-    return float(A), float(B)
+    return _platt_fit_one(lambda A, B, t_pos, t_neg: _platt_sums(x, A, B, t_pos, t_neg), max_iter).result
+
+
+def sigmoid_calibration_batch(ref_list, pred_list, unc_list, ignore_value=None, max_iter=100):
+    """[sigmoid_calibration(ref, pred, unc, ignore_value, max_iter)] for lists of inputs (host or device), the same floats:
+    the Newton iterations of all images run in lock step, one vx_platt_sums_batched call and one device -> host copy
+    per round over the images that have not converged yet."""
+    xs = [_RaterInputs(r, p, u, ignore_value) for r, p, u in zip(ref_list, pred_list, unc_list)]
+    fits = _platt_fit_lockstep(len(xs), lambda idx, req: _platt_sums_batch([xs[i] for i in idx], req), max_iter)
+    return [f.result for f in fits]
 
 
 def platt_scale_confid(uncalib_confid, platt_scale_file, uncertainty):
@@ -254,7 +448,11 @@ def calib_stats(reference_segs, pred_seg, unc_map, a, b, ignore_value=None):
     _lib.check(_lib.load().vx_calib_bins(_lib.ptr(x.unc), x.dtype, _lib.ptr(x.ref), _lib.ptr(x.pred), x.R, x.nvox, x.ignore,
                                          float(a), float(b), e, _lib.ptr(out), _lib.ptr(_workspace(x.dev)),
                                          _lib.stream_ptr()), "vx_calib_bins")
-    h = out.cpu().numpy()
+    return _calib_from_bins(out.cpu().numpy())
+
+
+def _calib_from_bins(h):
+    """calib_stats' host part from the 63 numbers of one image"""
     bin_sums, bin_true, bin_total = h[:21], h[21:42], h[42:]
     n = bin_total.sum()
     if n <= 0:
@@ -268,10 +466,35 @@ def calib_stats(reference_segs, pred_seg, unc_map, a, b, ignore_value=None):
     return disc, bin_total[nz] / n, int(nz.sum())
 
 
+def calib_stats_batch(ref_list, pred_list, unc_list, a, b, ignore_value=None):
+    """[calib_stats(ref, pred, unc, a, b, ignore_value)] for lists of inputs (host or device), bit for bit: one
+    vx_calib_bins_batched call and one device -> host copy per VX_EM_MAX_ITEMS images"""
+    xs = [_RaterInputs(r, p, u, ignore_value) for r, p, u in zip(ref_list, pred_list, unc_list)]
+    lib = _lib.load()
+    e = (C.c_double * 21)(*np.linspace(0.0, 1.0 + 1e-8, 21).tolist())
+    res = []
+    for lo in range(0, len(xs), _lib.VX_EM_MAX_ITEMS):
+        part = xs[lo:lo + _lib.VX_EM_MAX_ITEMS]
+        dev, n = part[0].dev, len(part)
+        items = _em_items(part)
+        ab = (C.c_double * (2 * n))(*([float(a), float(b)] * n))
+        ws = _workspace_batched(dev, int(lib.vx_calib_batched_workspace_bytes(items, n)))
+        out = torch.empty((n, 63), dtype=torch.float64, device=dev)
+        _lib.check(lib.vx_calib_bins_batched(items, n, ab, e, part[0].ignore, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                             _lib.stream_ptr()), "vx_calib_bins_batched")
+        res += [_calib_from_bins(h) for h in out.cpu().numpy()]
+    return res
+
+
 def calc_ace(reference_segs, pred_seg, unc_map, a, b, ignore_value=None):
     """ace.py:85-87 on the device inputs: average calibration error over the non-empty bins"""
     disc, _, k = calib_stats(reference_segs, pred_seg, unc_map, a, b, ignore_value)
     return (1 / k) * np.sum(disc)
+
+
+def calc_ace_batch(ref_list, pred_list, unc_list, a, b, ignore_value=None):
+    """[calc_ace(ref, pred, unc, a, b, ignore_value)] from one calib_stats_batch call"""
+    return [(1 / k) * np.sum(disc) for disc, _, k in calib_stats_batch(ref_list, pred_list, unc_list, a, b, ignore_value)]
 
 
 def platt_scale_params(val_exp_dataloader, ignore_value=None):
@@ -317,6 +540,104 @@ def calibration(exp_dataloader, ignore_value=None):
         from .experiment import ExperimentDataloader
         platt_scale_params(ExperimentDataloader(exp_dataloader.exp_version, "val"), ignore_value=ignore_value)
     return calibration_error(exp_dataloader, ignore_value=ignore_value)
+
+
+# ------------------------------------------------------------------------------------------------ batched drivers
+def _image_chunks(exp_dataloader, batch):
+    """the split's image ids in chunks of `batch`; a DeviceExperimentDataloader reads each chunk's files ahead (prefetch,
+    under its byte budget) before the chunk is scored"""
+    from .experiment import _chunks
+    for chunk in _chunks(exp_dataloader.image_ids, batch):
+        if hasattr(exp_dataloader, "prefetch"):
+            exp_dataloader.prefetch(chunk)
+        yield chunk
+
+
+def _gt_side(exp_dataloader, image_id):
+    """what ncc_batch takes for an image's ground truth: the hook's map, or in the file branch the stack of reference
+    segmentations itself (a stack of a floating dtype, which numpy would not evaluate in float64, goes through
+    get_gt_unc_map as before)"""
+    if exp_dataloader.exp_version.gt_unc_map_loading is not None:
+        return exp_dataloader.get_gt_unc_map(image_id)
+    device_files = hasattr(exp_dataloader, "prefetch") and exp_dataloader.dataloader is None
+    stack = exp_dataloader.get_reference_segs(image_id) if device_files else exp_dataloader._reference_segs(image_id)
+    return stack if _integer_dtype(stack) else np.var(np.asarray(stack.cpu() if _on_device(stack) else stack), axis=0)
+
+
+def _rater_labels(exp_dataloader, chunk):
+    """int32 device reference segmentations and mean predictions of a chunk, converted once for all uncertainty types"""
+    dev = _dev()
+    return ([_labels(exp_dataloader.get_reference_segs(i), dev) for i in chunk],
+            [_labels(exp_dataloader.get_mean_pred_seg(i), dev) for i in chunk])
+
+
+def ambiguity_modeling_device(exp_dataloader, batch=32):
+    """ambiguity_modeling with `batch` images per ncc_batch call: the same ambiguity_modeling.json, byte for byte.  Takes
+    a DeviceExperimentDataloader (nothing but the five sums per image leaves the device) or a plain ExperimentDataloader
+    (its arrays go up once)."""
+    unc_types = exp_dataloader.exp_version.unc_types
+    res, vals = {"mean": {}}, {u: [] for u in unc_types}
+    for chunk in _image_chunks(exp_dataloader, batch):
+        gts = [_gt_side(exp_dataloader, i) for i in chunk]
+        for image_id in chunk:
+            res.setdefault(image_id, {})
+        for unc_type in unc_types:
+            nccs = ncc_batch(gts, [exp_dataloader.get_unc_map(i, unc_type) for i in chunk])
+            for image_id, ncc in zip(chunk, nccs):
+                res[image_id][unc_type] = {"metrics": {"ncc": float(ncc)}}
+                vals[unc_type].append(float(ncc))
+    for unc_type in unc_types:
+        res["mean"][unc_type] = {"metrics": {"ncc": float(np.mean(np.array(vals[unc_type])))}}
+    with open(exp_dataloader.dataset_path / "ambiguity_modeling.json", "w") as f:
+        json.dump(res, f, indent=2)
+    return res
+
+
+def platt_scale_params_device(val_exp_dataloader, ignore_value=None, batch=32):
+    """platt_scale_params with `batch` images per lock-step fit: the same platt_scale_params.json, byte for byte"""
+    unc_types = val_exp_dataloader.exp_version.unc_types
+    aa, bb = {u: [] for u in unc_types}, {u: [] for u in unc_types}
+    for chunk in _image_chunks(val_exp_dataloader, batch):
+        refs, preds = _rater_labels(val_exp_dataloader, chunk)
+        for unc_type in unc_types:
+            uncs = [val_exp_dataloader.get_unc_map(i, unc_type) for i in chunk]
+            for a, b in sigmoid_calibration_batch(refs, preds, uncs, ignore_value):
+                aa[unc_type].append(a)
+                bb[unc_type].append(b)
+    res = {u: {"a": float(np.mean(np.array(aa[u]))), "b": float(np.mean(np.array(bb[u])))} for u in unc_types}
+    with open(val_exp_dataloader.exp_version.exp_path / "platt_scale_params.json", "w") as f:
+        json.dump(res, f, indent=2)
+    return res
+
+
+def calibration_error_device(exp_dataloader, ignore_value=None, batch=32):
+    """calibration_error with `batch` images per calc_ace_batch call: the same calibration.json, byte for byte"""
+    with open(exp_dataloader.exp_version.exp_path / "platt_scale_params.json") as f:
+        params = json.load(f)
+    unc_types = exp_dataloader.exp_version.unc_types
+    res, vals = {"mean": {}}, {u: [] for u in unc_types}
+    for chunk in _image_chunks(exp_dataloader, batch):
+        refs, preds = _rater_labels(exp_dataloader, chunk)
+        for image_id in chunk:
+            res.setdefault(image_id, {})
+        for unc_type in unc_types:
+            uncs = [exp_dataloader.get_unc_map(i, unc_type) for i in chunk]
+            aces = calc_ace_batch(refs, preds, uncs, params[unc_type]["a"], params[unc_type]["b"], ignore_value)
+            for image_id, ace in zip(chunk, aces):
+                res[image_id][unc_type] = {"metrics": {"ace": float(ace)}}
+                vals[unc_type].append(float(ace))
+    for unc_type in unc_types:
+        res["mean"][unc_type] = {"metrics": {"ace": float(np.mean(np.array(vals[unc_type])))}}
+    with open(exp_dataloader.dataset_path / "calibration.json", "w") as f:
+        json.dump(res, f, indent=2)
+    return res
+
+
+def calibration_device(exp_dataloader, ignore_value=None, batch=32):
+    """calibration with the batched drivers; the validation split is read with the class of loader it was given"""
+    if not os.path.isfile(exp_dataloader.exp_version.exp_path / "platt_scale_params.json"):
+        platt_scale_params_device(type(exp_dataloader)(exp_dataloader.exp_version, "val"), ignore_value=ignore_value, batch=batch)
+    return calibration_error_device(exp_dataloader, ignore_value=ignore_value, batch=batch)
 
 
 # ------------------------------------------------------------------------------------------------ OoD detection

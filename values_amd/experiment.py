@@ -342,6 +342,17 @@ class DeviceExperimentDataloader(ExperimentDataloader):
             return super().get_gt_unc_map(image_id)
         return instantiate(self._device_hook(self.exp_version.gt_unc_map_loading), image_id=image_id, dataloader=self.dataloader)
 
+    def get_gt_unc_map_device(self, image_id):
+        """get_gt_unc_map without the host: in the file branch the variance over the device-read reference segmentations
+        (evalmetrics.rater_variance: np.var(..., axis=0) bit for bit, a float64 device map); with a hook, the hook's map.
+        get_gt_unc_map itself keeps returning the host array in the file branch."""
+        if self.exp_version.gt_unc_map_loading is None and self.dataloader is None:
+            from .evalmetrics import rater_variance
+            refs = self.get_reference_segs(image_id)
+            if not refs.dtype.is_floating_point:
+                return rater_variance(refs)
+        return self.get_gt_unc_map(image_id)
+
     def get_mean_pred_seg(self, image_id):
         tag = "mean" if self.exp_version.pred_model != "Softmax" else "01"
         p = self.pred_seg_dir / f"{image_id}_{tag}{self.exp_version.image_ending}"
