@@ -615,6 +615,52 @@ int64_t vx_select_workspace_bytes(void);
 int vx_select_kth(const float* x, int64_t n, int64_t k, float* out, void* workspace, vx_stream_t stream);
 int vx_count_nonzero_u8(const uint8_t* x, int64_t n, uint64_t* out, vx_stream_t stream);
 
+/* K40: the same two steps for a whole reader batch / a whole split in one call each (select_batched.hip).
+ * vx_count_nonzero_batched (calculate_foreground_quantile_image, find_threshold.py:11-13, for a batch of predicted masks):
+ *   counts[i] (device, zeroed here) = np.count_nonzero of item i.  An item is a device pointer, an element count n >= 0
+ *   and a kind: VX_COUNT_B1 / B2 / B4 / B8, an integer or bool of 1 / 2 / 4 / 8 bytes (non-zero: any bit set), or
+ *   VX_COUNT_F32 / F64 (non-zero: x != 0, so NaN counts and -0.0 does not).  An item with n = 0 yields 0 and its pointer
+ *   is not looked at; pointers need only the alignment of their elements.  One memset and ONE launch for all items: the
+ *   items are cut into work blocks of 16 KB that the workgroups take in turn, so thousands of small 2D masks and a few
+ *   large volumes share one grid.  0 <= n_items <= VX_SELECT_MAX_ITEMS.
+ * vx_select_segments (calculate_threshold_image, find_threshold.py:63-68: np.quantile over all validation maps):
+ *   out[0] = the k-th smallest (0-based), out[1] = the (k+1)-th smallest of the UNION of the items' elements, where the
+ *   maps lie: no concatenation and no cast copy.  k + 1 == n_total: out[1] = out[0].  An item is VX_F32, or VX_F64
+ *   narrowed to float32 on load (round to nearest even, as astype(float32)).  MSB-first radix select over the key of
+ *   vx_select_kth in passes of 11, 11 and 10 bits (LDS histograms folded into 64-bit bins); the second order statistic
+ *   needs no second select: the last pass knows whether another key equal to the k-th remains, and only if none does one
+ *   more pass takes the minimum key above it -- decided on the device, the host does not wait between passes.  At most
+ *   four reads of the data; a memset, the table upload and eight launches.  status (device) = VX_SELECT_NAN when any element is NaN (the outputs
+ *   are then unspecified), else VX_SELECT_OK; +-inf are ordinary values.  Integer arithmetic only: exact, independent of
+ *   order and grid size.  1 <= n_items <= VX_SELECT_MAX_ITEMS, element counts are 64-bit.
+ * Both refuse before any device call: a null table or a null pointer of a non-empty item (VX_E_NULL), n_items or an n out of
+ * range, for the selection n_total = 0 or k outside [0, n_total) (VX_E_SHAPE), an unknown kind / dtype (VX_E_DTYPE), a
+ * pointer off its element alignment or a workspace off 16 bytes (VX_E_ALIGN), a short workspace (VX_E_WORKSPACE).
+ * workspace: vx_*_workspace_bytes(n_items) bytes, 0 for an n_items the call refuses.  The item table goes up through a
+ * pinned staging buffer inside the call: no wait on the stream (only, if it is still in flight, for the previous call's
+ * upload), and neither call is capturable into a hipGraph. */
+#define VX_SELECT_MAX_ITEMS 65536
+enum { VX_COUNT_B1 = 0, VX_COUNT_B2 = 1, VX_COUNT_B4 = 2, VX_COUNT_B8 = 3, VX_COUNT_F32 = 4, VX_COUNT_F64 = 5 };
+enum { VX_SELECT_OK = 0, VX_SELECT_NAN = 1 };
+typedef struct vx_count_item {
+  const void* ptr; /* device, n elements */
+  int64_t n;
+  int32_t kind; /* VX_COUNT_* */
+  int32_t reserved;
+} vx_count_item;
+typedef struct vx_select_item {
+  const void* ptr; /* device, n elements */
+  int64_t n;
+  int32_t dtype; /* VX_F32 | VX_F64 */
+  int32_t reserved;
+} vx_select_item;
+int64_t vx_count_nonzero_batched_workspace_bytes(int n_items);
+int vx_count_nonzero_batched(const vx_count_item* items /* host */, int n_items, uint64_t* counts /* device [n_items] */,
+                             void* workspace, int64_t ws_bytes, vx_stream_t stream);
+int64_t vx_select_segments_workspace_bytes(int n_items);
+int vx_select_segments(const vx_select_item* items /* host */, int n_items, int64_t k, float* out /* device [2] */,
+                       int32_t* status /* device */, void* workspace, int64_t ws_bytes, vx_stream_t stream);
+
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),
  *   counts[i][j][c] = #{v: mask_i(v) == c and mask_j(v) == c}.  M <= 32, C <= 8.

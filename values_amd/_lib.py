@@ -202,6 +202,21 @@ class NccItem(C.Structure):
                 ("gt_R", _i32), ("reserved", _i32)]
 
 
+VX_SELECT_MAX_ITEMS = 65536
+VX_COUNT_B1, VX_COUNT_B2, VX_COUNT_B4, VX_COUNT_B8, VX_COUNT_F32, VX_COUNT_F64 = range(6)
+VX_SELECT_OK, VX_SELECT_NAN = 0, 1
+
+
+class CountItem(C.Structure):
+    """vx_count_item: one device array of n elements of kind VX_COUNT_* for vx_count_nonzero_batched."""
+    _fields_ = [("ptr", _p), ("n", _i64), ("kind", _i32), ("reserved", _i32)]
+
+
+class SelectItem(C.Structure):
+    """vx_select_item: one device array of n VX_F32 / VX_F64 elements for vx_select_segments."""
+    _fields_ = [("ptr", _p), ("n", _i64), ("dtype", _i32), ("reserved", _i32)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -267,6 +282,10 @@ SIGNATURES = {
     "vx_select_workspace_bytes": (_i64, []),
     "vx_select_kth": (_i, [_p, _i64, _i64, _p, _p, _p]),
     "vx_count_nonzero_u8": (_i, [_p, _i64, _p, _p]),
+    "vx_count_nonzero_batched_workspace_bytes": (_i64, [_i]),
+    "vx_count_nonzero_batched": (_i, [C.POINTER(CountItem), _i, _p, _p, _i64, _p]),
+    "vx_select_segments_workspace_bytes": (_i64, [_i]),
+    "vx_select_segments": (_i, [C.POINTER(SelectItem), _i, _i64, _p, _p, _p, _i64, _p]),
     "vx_mask_agreement": (_i, [_p, _i, _i, _i64, _p, _p]),
     "vx_mask_agreement_batched": (_i, [_p, _i, _i, _i, _i64, _i, _p, _p]),
     "vx_soft_metric_workspace_bytes": (_i64, [_i, _i]),
