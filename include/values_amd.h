@@ -607,15 +607,9 @@ int vx_tta_views_2d(const void* src, int src_u8, const float* noise0, const floa
 int vx_colorize_u8(const uint8_t* labels, const uint8_t* ignore, int64_t n, const uint8_t* lut, int unlabeled, uint8_t* rgb,
                    vx_stream_t stream);
 
-/* K21: threshold search (evaluation/uncertainty_aggregation/find_threshold.py).
- * vx_select_kth: out[0] = k-th smallest (0-based) of the n finite float32 values of x, by radix select
- *   (np.quantile(x, q) = lerp of the two order statistics around q*(n-1), done by the host in float64);
- *   workspace of vx_select_workspace_bytes().  vx_count_nonzero_u8: np.count_nonzero of a label mask. */
-int64_t vx_select_workspace_bytes(void);
-int vx_select_kth(const float* x, int64_t n, int64_t k, float* out, void* workspace, vx_stream_t stream);
-int vx_count_nonzero_u8(const uint8_t* x, int64_t n, uint64_t* out, vx_stream_t stream);
-
-/* K40: the same two steps for a whole reader batch / a whole split in one call each (select_batched.hip).
+/* K40: threshold search (evaluation/uncertainty_aggregation/find_threshold.py) for one array, a whole reader batch or a
+ * whole split in one call each (select.hip).  np.quantile(x, q) is the lerp of the two order statistics around
+ * q * (n - 1), done by the host in float64.
  * vx_count_nonzero_batched (calculate_foreground_quantile_image, find_threshold.py:11-13, for a batch of predicted masks):
  *   counts[i] (device, zeroed here) = np.count_nonzero of item i.  An item is a device pointer, an element count n >= 0
  *   and a kind: VX_COUNT_B1 / B2 / B4 / B8, an integer or bool of 1 / 2 / 4 / 8 bytes (non-zero: any bit set), or
@@ -626,8 +620,9 @@ int vx_count_nonzero_u8(const uint8_t* x, int64_t n, uint64_t* out, vx_stream_t 
  * vx_select_segments (calculate_threshold_image, find_threshold.py:63-68: np.quantile over all validation maps):
  *   out[0] = the k-th smallest (0-based), out[1] = the (k+1)-th smallest of the UNION of the items' elements, where the
  *   maps lie: no concatenation and no cast copy.  k + 1 == n_total: out[1] = out[0].  An item is VX_F32, or VX_F64
- *   narrowed to float32 on load (round to nearest even, as astype(float32)).  MSB-first radix select over the key of
- *   vx_select_kth in passes of 11, 11 and 10 bits (LDS histograms folded into 64-bit bins); the second order statistic
+ *   narrowed to float32 on load (round to nearest even, as astype(float32)).  MSB-first radix select over the usual
+ *   order-preserving map of IEEE float32 bits to unsigned keys (negative: all bits flipped, non-negative: sign bit set)
+ *   in passes of 11, 11 and 10 bits (LDS histograms folded into 64-bit bins); the second order statistic
  *   needs no second select: the last pass knows whether another key equal to the k-th remains, and only if none does one
  *   more pass takes the minimum key above it -- decided on the device, the host does not wait between passes.  At most
  *   four reads of the data; a memset, the table upload and eight launches.  status (device) = VX_SELECT_NAN when any element is NaN (the outputs
@@ -703,45 +698,34 @@ int vx_ssn2d_add_diag(float* out, const float* diag, const float* eps_d, uint32_
                       float epsilon, vx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
- * Downstream scalars of the evaluation stage (evaluation/metrics/{ncc,ace}.py): the per-voxel float64 reductions, all
- * deterministic (fixed grid of partial rows added in index order).  workspace: vx_evalmetrics_workspace_bytes().
- *   vx_ncc_sums  (ncc.py:9-25)  pass 0: sums[0..1] = sum gt, sum pred;  pass 1 (means given): sums[0..2] =
- *                sum (gt-mg)^2, sum (pred-mp)^2, sum (gt-mg)(pred-mp)  -- numpy's two-pass mean / std(ddof=1) / product.
- *   vx_platt_sums (ace.py:13-41, sklearn.calibration._sigmoid_calibration on (-unc, reference == prediction)):
- *                ref [R][nvox] int32 reference segmentations, pred [nvox] int32 mean prediction, unc [nvox] f32/f64;
- *                voxels with ref == ignore_value dropped (ignore_value < 0: none).  For the sigmoid parameters (A, B)
- *                and Platt's targets t_pos / t_neg: sums[0] = valid count, [1] = correct count, [2] = loss,
- *                [3..4] = gradient (dA, dB), [5..7] = Hessian (AA, AB, BB).  The host iterates (Newton).
- *   vx_calib_bins (ace.py:44-90) platt_scale_confid + calib_stats' 20-bin statistics: bins63 = bin_sums[21],
- *                bin_true[21], bin_total[21] for the bin edges edges21 (a HOST array: np.linspace(0, 1 + 1e-8, 21)). */
-int64_t vx_evalmetrics_workspace_bytes(void);
-int vx_ncc_sums(const void* gt, int gt_dtype, const void* pred, int pred_dtype, int64_t n, int pass, double mean_gt,
-                double mean_pred, double* sums, void* workspace, vx_stream_t stream);
-int vx_platt_sums(const void* unc, int dtype, const int32_t* ref, const int32_t* pred, int R, int64_t nvox,
-                  int ignore_value, double A, double B, double t_pos, double t_neg, double* sums, void* workspace,
-                  vx_stream_t stream);
-int vx_calib_bins(const void* unc, int dtype, const int32_t* ref, const int32_t* pred, int R, int64_t nvox,
-                  int ignore_value, double A, double B, const double* edges21, double* bins63, void* workspace,
-                  vx_stream_t stream);
-
-/* The three reductions above for a batch of images in one call each (evalmetrics_batched.hip), with the per-image entry
- * points' float64 results bit for bit: every sum keeps their association (thread t of block b adds elements
- * b * 256 + t + k * 131072 in ascending k, a 64-lane shuffle tree, four waves in order, 512 block rows in index order),
- * and an item's numbers do not depend on its batch mates or on n_items.  Items of a call may differ in size, R and dtype.
+ * Downstream scalars of the evaluation stage (evaluation/metrics/{ncc,ace}.py): the per-voxel float64 reductions for a
+ * batch of images in one call each (evalmetrics.hip); one image is a batch of one.  All sums are deterministic and formed
+ * with ONE association, which is the contract of these calls: thread t of block b adds elements
+ * b * 256 + t + k * 131072 in ascending k, a 64-lane shuffle tree, four waves in order, 512 block rows in index order; no
+ * multiply-add is fused.  An item's numbers do not depend on its batch mates or on n_items: they are bit-equal to the
+ * same item submitted alone.  Items of a call may differ in size, R and dtype.
  *   items      HOST array of descriptors of DEVICE buffers.  1 <= n_items <= VX_EM_MAX_ITEMS, R >= 1, nvox >= 1.
- *   vx_ncc_batched         sums [n_items][5] (device) = sum gt, sum pred, sum (gt-mg)^2, sum (pred-mp)^2,
- *                          sum (gt-mg)(pred-mp) with mg = sums[0] / (double)n, mp = sums[1] / (double)n formed on the
- *                          device between the passes (the IEEE division the host does for vx_ncc_sums).  Four launches,
- *                          no synchronisation.  The ground-truth side is a map (gt_R = 0, gt_dtype VX_F32 | VX_F64) or
+ *   vx_ncc_batched         (ncc.py:9-25: numpy's two-pass mean / std(ddof=1) / product)  sums [n_items][5] (device) =
+ *                          sum gt, sum pred, sum (gt-mg)^2, sum (pred-mp)^2, sum (gt-mg)(pred-mp) with
+ *                          mg = sums[0] / (double)n, mp = sums[1] / (double)n, one IEEE division each, formed on the
+ *                          device between the passes.  Four launches, no synchronisation.
+ *                          The ground-truth side is a map (gt_R = 0, gt_dtype VX_F32 | VX_F64) or
  *                          gt_R >= 1 int32 label volumes [gt_R][n]: then every voxel's value is np.var(labels, axis=0),
  *                          evaluated on the fly in float64 in numpy's order (sum over raters in index order, / R, sum
- *                          of (x - mean)^2 in index order, / R; no multiply-add is fused); the variance map is never
- *                          written.  n_gt != n_pred is refused.
+ *                          of (x - mean)^2 in index order, / R); the variance map is never written.  n_gt != n_pred is
+ *                          refused.
  *   vx_rater_variance      that variance as a float64 map [nvox] of its own (one launch).
- *   vx_platt_sums_batched  sums [n_items][8] (device), the eight numbers of vx_platt_sums; params: HOST [n_items][4] =
- *                          (A, B, t_pos, t_neg) per item; one ignore_value for the call.  Two launches.
- *   vx_calib_bins_batched  bins63 [n_items][63] (device), the numbers of vx_calib_bins; ab: HOST [n_items][2] = (A, B)
- *                          per item; edges21: HOST.  Two launches.
+ *   vx_platt_sums_batched  (ace.py:13-41, sklearn.calibration._sigmoid_calibration on (-unc, reference == prediction))
+ *                          per item: ref [R][nvox] int32 reference segmentations, pred [nvox] int32 mean prediction,
+ *                          unc [nvox] f32/f64; voxels with ref == ignore_value dropped (ignore_value < 0: none; one
+ *                          ignore_value for the call).  params: HOST [n_items][4] = the sigmoid parameters and Platt's
+ *                          targets (A, B, t_pos, t_neg) per item.  sums [n_items][8] (device): [0] = valid count,
+ *                          [1] = correct count, [2] = loss, [3..4] = gradient (dA, dB), [5..7] = Hessian (AA, AB, BB).
+ *                          The host iterates (Newton).  Two launches.
+ *   vx_calib_bins_batched  (ace.py:44-90) platt_scale_confid + calib_stats' 20-bin statistics: bins63 [n_items][63]
+ *                          (device) = bin_sums[21], bin_true[21], bin_total[21] per item for the bin edges edges21 (a
+ *                          HOST array: np.linspace(0, 1 + 1e-8, 21)); ab: HOST [n_items][2] = (A, B) per item.  Two
+ *                          launches.
  * Every argument check (VX_E_NULL / VX_E_SHAPE / VX_E_DTYPE, the message names the item; VX_E_WORKSPACE / VX_E_ALIGN)
  * returns before any device call.  workspace: caller-owned, of vx_*_batched_workspace_bytes(the same items) bytes --
  * the descriptor table and 512 partial rows per item -- 0 for arguments the call refuses.  The descriptor table goes up

@@ -1,13 +1,14 @@
 """Inputs shared by tests/test_evalmetrics_batched_cpu.py and tests/test_gpu_evalmetrics_batched.py: a numpy stand-in for
-the Platt sums, images whose Platt fits finish in different rounds, rater label stacks, and a datamodule stub for a
-results tree whose reference segmentations come from a dataloader."""
+the Platt sums, images whose Platt fits finish in different rounds, rater label stacks, host restatements of the device
+arithmetic (the rater variance, the five NCC sums in the documented association), and a datamodule stub for a results tree whose reference segmentations come from a dataloader."""
 import os
 
 import numpy as np
 
 
 def platt_sums_numpy(unc, correct, A, B, t_pos, t_neg):
-    """numpy stand-in for vx_platt_sums (R = 1, nothing ignored): the same eight sums, numpy's summation order"""
+    """numpy stand-in for one item of vx_platt_sums_batched (R = 1, nothing ignored): the same eight sums, numpy's
+    summation order"""
     F = -np.asarray(unc, dtype=np.float64)
     T = np.where(correct, t_pos, t_neg)
     z = A * F + B
@@ -55,6 +56,41 @@ def rater_variance_restated(labels):
         d = labels[r].astype(np.float64) - mean
         q = q + d * d
     return q / np.float64(R)
+
+
+EM_BLOCKS, EM_THREADS = 512, 256          # the grid of every reduction of evalmetrics.hip
+
+
+def _sum_in_device_order(x):
+    """the sum of the float64 vector x in the association include/values_amd.h documents: element i belongs to thread
+    i % 131072, which adds its elements in ascending i starting from 0.0 (elements past the end are never added); in every
+    wave of 64 threads the shuffle-down tree with offsets 32, 16, ..., 1, of which lane 0's value is kept; the four waves
+    of a block added in order from 0.0; the 512 block rows added in index order from 0.0"""
+    grid = EM_BLOCKS * EM_THREADS
+    acc = np.zeros(grid, dtype=np.float64)
+    for lo in range(0, len(x), grid):
+        part = x[lo:lo + grid]
+        acc[:len(part)] = acc[:len(part)] + part
+    lanes = acc.reshape(EM_BLOCKS, EM_THREADS // 64, 64).copy()
+    for off in (32, 16, 8, 4, 2, 1):          # lane l < off takes lane l + off; only those lanes reach lane 0
+        lanes[..., :off] = lanes[..., :off] + lanes[..., off:2 * off]
+    rows = np.zeros(EM_BLOCKS, dtype=np.float64)
+    for w in range(EM_THREADS // 64):
+        rows = rows + lanes[:, w, 0]
+    total = np.float64(0.0)
+    for b in range(EM_BLOCKS):
+        total = total + rows[b]
+    return float(total)
+
+
+def ncc_sums_restated(g, p):
+    """[sum g, sum p, sum (g-mg)^2, sum (p-mp)^2, sum (g-mg)(p-mp)] of a map pair as vx_ncc_batched forms them, one float64
+    operation at a time: pass 0, then mg = sum g / n and mp = sum p / n, then pass 1 with the products formed unfused"""
+    g, p = np.asarray(g).reshape(-1).astype(np.float64), np.asarray(p).reshape(-1).astype(np.float64)
+    n = len(g)
+    sg, sp = _sum_in_device_order(g), _sum_in_device_order(p)
+    da, db = g - np.float64(sg) / np.float64(n), p - np.float64(sp) / np.float64(n)
+    return [sg, sp, _sum_in_device_order(da * da), _sum_in_device_order(db * db), _sum_in_device_order(da * db)]
 
 
 class StubDataModule:

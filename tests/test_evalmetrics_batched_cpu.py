@@ -1,4 +1,4 @@
-"""CPU: the host half of the batched evaluation scores (values_amd/evalmetrics.py, csrc/evalmetrics_batched.hip): the ABI
+"""CPU: the host half of the batched evaluation scores (values_amd/evalmetrics.py, csrc/evalmetrics.hip): the ABI
 structs against the C header, the workspace queries and the refusals that happen before any device call, and the
 lock-step Platt controller driven by a numpy stand-in for the device sums.  No device call."""
 import ctypes
@@ -139,7 +139,7 @@ def test_lockstep_controller_visits_the_per_image_sequence():
 
 
 def test_rater_variance_restated_in_kernel_order_is_numpys():
-    """em_rater_var (evalmetrics_core.h) adds the raters in index order, divides by R, adds the squared deviations in index
+    """em_rater_var (evalmetrics.hip) adds the raters in index order, divides by R, adds the squared deviations in index
     order, divides by R, all in float64 with no fused multiply-add: restated in numpy, that is np.var(labels, axis=0) bit
     for bit on the cases the GPU test uses, for every label dtype a results tree holds"""
     from tests.em_inputs import rater_label_cases, rater_variance_restated
@@ -150,3 +150,51 @@ def test_rater_variance_restated_in_kernel_order_is_numpys():
             assert want.dtype == np.float64
             assert np.array_equal(rater_variance_restated(lab), want), (labels.shape, dt)
     assert np.var(rater_label_cases()[-1], axis=0).max() > 0
+
+
+def _wave_sum_scalar(x):
+    """one wave's share of the documented association, one Python float at a time: lane i holds 0.0 + x[i] (lanes past the
+    end hold 0.0), the shuffle-down tree, then the three idle waves and the 511 idle block rows, each 0.0"""
+    lanes = [0.0] * 64
+    for i, v in enumerate(x):
+        lanes[i] = 0.0 + float(v)
+    for off in (32, 16, 8, 4, 2, 1):
+        new = list(lanes)
+        for lane in range(64):
+            new[lane] = lanes[lane] + lanes[lane + off if lane + off < 64 else lane]   # (__shfl_down past the wave: own value)
+        lanes = new
+    block = 0.0
+    for w in range(4):
+        block += lanes[0] if w == 0 else 0.0
+    total = 0.0
+    for b in range(512):
+        total += block if b == 0 else 0.0
+    return total
+
+
+def test_ncc_sums_restated_follows_the_documented_association():
+    """tests/em_inputs.ncc_sums_restated, the host reference of the GPU test's `==` on the five NCC sums: numpy's own sums
+    to 1e-12 relative at a size below one wave row and at one element more than the grid has threads, and for at most 64
+    elements the explicit scalar loop over one wave's lanes, bit for bit"""
+    from tests.em_inputs import ncc_sums_restated
+    rng = np.random.default_rng(41)
+    for n, dg, dp in ((255, np.float32, np.float64), (131073, np.float64, np.float32)):
+        g = rng.random(n).astype(dg)
+        p = (0.6 * g + 0.4 * rng.random(n)).astype(dp)
+        got = ncc_sums_restated(g, p)
+        g64, p64 = g.astype(np.float64), p.astype(np.float64)
+        da, db = g64 - g64.sum() / n, p64 - p64.sum() / n
+        want = [g64.sum(), p64.sum(), (da * da).sum(), (db * db).sum(), (da * db).sum()]
+        assert len(got) == 5 and all(type(v) is float for v in got)
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert abs(a - b) <= 1e-12 * abs(b), (n, k, a, b)
+    for n in (1, 2, 37, 64):
+        g = rng.random(n).astype(np.float32)
+        p = rng.normal(size=n)
+        got = ncc_sums_restated(g, p)
+        g64, p64 = [float(v) for v in g], [float(v) for v in p]
+        sg, sp = _wave_sum_scalar(g64), _wave_sum_scalar(p64)
+        da, db = [v - sg / n for v in g64], [v - sp / n for v in p64]
+        want = [sg, sp, _wave_sum_scalar([a * a for a in da]), _wave_sum_scalar([b * b for b in db]),
+                _wave_sum_scalar([a * b for a, b in zip(da, db)])]
+        assert got == want, (n, got, want)

@@ -1,7 +1,8 @@
-"""GPU: the batched evaluation scores (values_amd/csrc/evalmetrics_batched.hip, evalmetrics.ncc_batch /
-sigmoid_calibration_batch / calc_ace_batch and the *_device drivers) against the per-image functions: every number equal
-with `==`, every JSON file byte for byte.  The sizes sit where the shared association could break (one element, one short
-of a wave row, exactly / one more than one element per thread of the 512 x 256 grid, several rounds of the grid)."""
+"""GPU: the batched evaluation scores (values_amd/csrc/evalmetrics.hip, evalmetrics.ncc_batch /
+sigmoid_calibration_batch / calc_ace_batch and the *_device drivers) against the per-image functions and a host
+restatement of the documented association: every number equal with `==`, every JSON file byte for byte.  The sizes sit
+where the shared association could break (one element, one short of a wave row, exactly / one more than one element per
+thread of the 512 x 256 grid, several rounds of the grid)."""
 import ctypes as C
 import json
 import os
@@ -11,28 +12,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests.em_inputs import platt_items, rater_label_cases
+from tests.em_inputs import ncc_sums_restated, platt_items, rater_label_cases
 from tests.helpers import load_npz
 
 pytestmark = pytest.mark.gpu
 
 NCC_SIZES = (1, 2, 255, 131072, 131073, 300001)
-
-
-def _ncc_sums_single(g, p):
-    """the five sums compute_ncc forms for one pair, through the per-image entry point as compute_ncc calls it"""
-    from values_amd import _lib, evalmetrics as vm
-    lib, dev = _lib.load(), vm._dev()
-    gt, gd = vm._float_map(g, dev)
-    pt, pd = vm._float_map(p, dev)
-    n = gt.numel()
-    sums = torch.empty(3, dtype=torch.float64, device=dev)
-    ws, st = vm._workspace(dev), _lib.stream_ptr()
-    _lib.check(lib.vx_ncc_sums(_lib.ptr(gt), gd, _lib.ptr(pt), pd, n, 0, 0.0, 0.0, _lib.ptr(sums), _lib.ptr(ws), st), "vx_ncc_sums")
-    s0 = sums.tolist()
-    _lib.check(lib.vx_ncc_sums(_lib.ptr(gt), gd, _lib.ptr(pt), pd, n, 1, s0[0] / n, s0[1] / n, _lib.ptr(sums), _lib.ptr(ws), st),
-               "vx_ncc_sums")
-    return s0[:2] + sums.tolist()
 
 
 @pytest.fixture(scope="module")
@@ -45,7 +30,7 @@ def ncc_pairs():
         g = rng.random(n).astype(dg)
         pairs.append((g, (0.6 * g + 0.4 * rng.random(n)).astype(dp)))
     pairs.append((np.full(255, 0.25, dtype=np.float32), rng.random(255)))          # a constant map: the host path gives nan
-    single = [_ncc_sums_single(g, p) for g, p in pairs]
+    single = [ncc_sums_restated(g, p) for g, p in pairs]
     return pairs, single
 
 
@@ -136,12 +121,14 @@ def test_platt_sums_and_bins_batched_equal_the_per_image_calls(ignore):
     edges = (C.c_double * 21)(*np.linspace(0.0, 1.0 + 1e-8, 21).tolist())
     ign = -1 if ignore is None else ignore
     single = torch.empty((len(xs), 63), dtype=torch.float64, device=dev)
-    for i, (x, p) in enumerate(zip(xs, params)):
-        _lib.check(lib.vx_calib_bins(_lib.ptr(x.unc), x.dtype, _lib.ptr(x.ref), _lib.ptr(x.pred), x.R, x.nvox, ign, p[0], p[1], edges,
-                                     _lib.ptr(single[i]), _lib.ptr(vm._workspace(dev)), st), "vx_calib_bins")
+    for i, (x, p) in enumerate(zip(xs, params)):               # every item as a call of its own
+        one = vm._em_items([x])
+        ws = _lib.workspace(dev, lib.vx_calib_batched_workspace_bytes(one, 1))
+        _lib.check(lib.vx_calib_bins_batched(one, 1, (C.c_double * 2)(p[0], p[1]), edges, ign, _lib.ptr(single[i]), _lib.ptr(ws),
+                                             ws.numel(), st), "vx_calib_bins_batched")
     items = vm._em_items(xs)
     ab = (C.c_double * 12)(*[v for p in params for v in p[:2]])
-    ws = vm._workspace_batched(dev, lib.vx_calib_batched_workspace_bytes(items, len(xs)))
+    ws = _lib.workspace(dev, lib.vx_calib_batched_workspace_bytes(items, len(xs)))
     out = torch.empty((len(xs), 63), dtype=torch.float64, device=dev)
     _lib.check(lib.vx_calib_bins_batched(items, len(xs), ab, edges, ign, _lib.ptr(out), _lib.ptr(ws), ws.numel(), st),
                "vx_calib_bins_batched")
@@ -149,6 +136,12 @@ def test_platt_sums_and_bins_batched_equal_the_per_image_calls(ignore):
     assert np.array_equal(got, want)
     assert np.array_equal(want[:, 42:].sum(1), np.array(vm._platt_sums_batch(xs, params))[:, 0])    # every valid voxel in a bin
     assert (np.count_nonzero(want[4:, 42:], axis=1) >= 3).all()
+    # the two counts are exact: numpy's number of valid rater-voxels and of correct ones; every correct one is in a bin
+    sums = np.array(vm._platt_sums_batch(xs, params))
+    valid = [np.ones_like(ref, dtype=bool) if ignore is None else ref != ignore for ref, _, _ in cases]
+    assert np.array_equal(sums[:, 0], np.array([float(v.sum()) for v in valid]))
+    assert np.array_equal(sums[:, 1], np.array([float((v & (ref == pred[None])).sum()) for v, (ref, pred, _) in zip(valid, cases)]))
+    assert np.array_equal(got[:, 21:42].sum(1), sums[:, 1])
 
 
 @pytest.fixture(scope="module")

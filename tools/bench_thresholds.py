@@ -3,11 +3,10 @@ writers -- "3d": .nii.gz maps and masks (results.ResultsWriter), "2d": TIFF maps
 (results2d.save_images_device) -- in three legs, in one process:
 
   host      ExperimentDataloader + get_foreground_quantile, find_threshold(loader=experiment._load_file)
-  parent    the device path before the batched calls: DeviceExperimentDataloader + get_foreground_quantile (one
-            vx_count_nonzero_u8 call and one .item() per mask), and for the thresholds the maps read on the device, cast to
-            float32, joined with torch.cat and handed to thresholds.quantile (isnan pass, two vx_select_kth calls).  The
-            parent's find_threshold(device_io=True) read NIfTI only; for the 2D tree this leg is that form restated over
-            experiment._read_batches_device.
+  single    the single-array forms: DeviceExperimentDataloader + get_foreground_quantile (thresholds.count_nonzero per mask:
+            one vx_count_nonzero_batched call of one item and one host copy each), and for the thresholds the maps read on
+            the device, cast to float32, joined with torch.cat and handed to thresholds.quantile (one vx_select_segments
+            call over the one joined array), restated over experiment._read_batches_device for every kind of file.
   new       get_foreground_quantile_device (one count_nonzero_batch call per reader batch) and
             find_threshold(device_io=True) (one quantile_segments call per uncertainty type over the tensors as read)
 
@@ -17,14 +16,14 @@ reported).  One JSON line per (case, leg):
   quantile_wall_s, threshold_wall_s   host clock around the two drivers, files read from disk, final synchronise included
                                       (min and max of --wall-reps runs; the host leg runs once)
 and one JSON line per case with the device calls alone, on masks / maps already resident on the device:
-  count_ms, select_ms                 {"parent": [min, max], "new": [min, max]} of --reps repetitions, device events around
+  count_ms, select_ms                 {"single": [min, max], "new": [min, max]} of --reps repetitions, device events around
                                       all count calls of the split's masks / the quantile of ONE uncertainty type
-  count_ratio, select_ratio           parent min / new min (above 1: the new path is faster)
+  count_ratio, select_ratio           single min / new min (above 1: the batched path is faster)
   launches_per_type                   kernel launches and other stream operations of one uncertainty type's quantile,
-                                      counted from the launchers: parent = per-map cast / gather copies + cat + isnan +
-                                      any + 2 x (init + 4 x (histogram + pick)); new = memset + table upload + 8 kernels
-  count_launches                      parent: one launch, one memset and one .item() per mask (+ a cast pass unless uint8
-                                      and contiguous); new: one launch, one memset, one table upload, one copy per batch
+                                      counted from the launchers: single = per-map cast / gather copies + cat + what new
+                                      takes; new = memset + table upload + 8 kernels
+  count_launches                      single: one launch, one memset, one table upload and one host copy per mask; new: the
+                                      same per batch
   extra_bytes                         peak device bytes allocated during one uncertainty type's quantile beyond the maps
                                       themselves (torch's allocator statistics; the workspace is allocated inside)
 
@@ -125,8 +124,8 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return [round(min(ms), 4), round(max(ms), 4)]
 
-    def parent_find_threshold(paths, qdir, out_dir):
-        """the parent's find_threshold(device_io=True), over every kind of file: cast, torch.cat, thresholds.quantile"""
+    def single_find_threshold(paths, qdir, out_dir):
+        """find_threshold over the single-array form, for every kind of file: cast, torch.cat, thresholds.quantile"""
         flat = {(pm, unc): p for pm, vs in paths.items() for v in vs.values() for unc, p in v.items()}
         with open(os.path.join(qdir, "quantile_analysis.json")) as f:
             qs = json.load(f)
@@ -153,7 +152,7 @@ def main():
             host, dev = ExperimentDataloader(ev, "val"), DeviceExperimentDataloader(ev, "val")
             paths = th.threshold_images_paths(host)
             legs = {"host": (lambda: th.get_foreground_quantile(host), lambda d: th.find_threshold(paths, d, d, loader=_load_file)),
-                    "parent": (lambda: th.get_foreground_quantile(dev), lambda d: parent_find_threshold(paths, d, d)),
+                    "single": (lambda: th.get_foreground_quantile(dev), lambda d: single_find_threshold(paths, d, d)),
                     "new": (lambda: th.get_foreground_quantile_device(dev, batch=a.batch),
                             lambda d: th.find_threshold(paths, d, d, device_io=True, batch=a.batch))}
             if a.skip_host:
@@ -169,7 +168,7 @@ def main():
                 files[leg] = [open(os.path.join(d, f), "rb").read() for f in ("quantile_analysis.json", "threshold_analysis.json")]
                 lines.append({"case": case, "leg": leg, "images": images, "shape": shape, "masks_per_image": a.masks + 1,
                               "quantile_wall_s": tq, "threshold_wall_s": tt})
-            # the legs' own "Mean" entry: the parent restatement has one pred model, as find_threshold has here
+            # the legs' own "Mean" entry: the single-array restatement has one pred model, as find_threshold has here
             assert all(f == files["new"] for f in files.values()), f"{case}: the legs wrote different files"
             for line in lines:
                 print(json.dumps(line), flush=True)
@@ -179,14 +178,14 @@ def main():
             masks = [t for _, t in _read_batches_device(mask_paths, a.batch)]
             maps = [t for _, t in _read_batches_device(paths["Dropout"][ev.version_name][TYPES[0]], a.batch)]
             q = json.loads(files["new"][0])["Dropout"]
-            parent_count = lambda: [th.count_nonzero(m) for m in masks]
+            single_count = lambda: [th.count_nonzero(m) for m in masks]
             new_count = lambda: [c for i in range(0, len(masks), a.batch) for c in th.count_nonzero_batch(masks[i:i + a.batch])]
-            parent_select = lambda: th.quantile(torch.cat([t.reshape(-1).to(torch.float32) for t in maps]), q)
+            single_select = lambda: th.quantile(torch.cat([t.reshape(-1).to(torch.float32) for t in maps]), q)
             new_select = lambda: th.quantile_segments(maps, q)
-            assert parent_count() == new_count() and parent_select() == new_select(), f"{case}: the device calls differ"
+            assert single_count() == new_count() and single_select() == new_select(), f"{case}: the device calls differ"
             extra = {}
-            for name, fn in (("parent", parent_select), ("new", new_select)):
-                th._ws.clear()
+            for name, fn in (("single", single_select), ("new", new_select)):
+                _lib._ws.clear()
                 torch.cuda.synchronize()
                 torch.cuda.empty_cache()
                 torch.cuda.reset_peak_memory_stats()
@@ -194,18 +193,17 @@ def main():
                 fn()
                 torch.cuda.synchronize()
                 extra[name] = int(torch.cuda.max_memory_allocated() - base)
-            cm = {"parent": events(parent_count, a.reps), "new": events(new_count, a.reps)}
-            sm = {"parent": events(parent_select, a.reps), "new": events(new_select, a.reps)}
+            cm = {"single": events(single_count, a.reps), "new": events(new_count, a.reps)}
+            sm = {"single": events(single_select, a.reps), "new": events(new_select, a.reps)}
             copies = sum(1 for t in maps if not (t.is_contiguous() and t.dtype == torch.float32))
-            casts = sum(1 for m in masks if not (m.is_contiguous() and m.dtype == torch.uint8))
             batches = -(-len(masks) // a.batch)
             print(json.dumps({
                 "case": case, "leg": "device calls", "masks": len(masks), "maps_per_type": len(maps), "map_dtype": str(maps[0].dtype),
                 "map_bytes_per_type": sum(t.numel() * t.element_size() for t in maps),
-                "count_ms": cm, "count_ratio": round(cm["parent"][0] / cm["new"][0], 2),
-                "select_ms": sm, "select_ratio": round(sm["parent"][0] / sm["new"][0], 2),
-                "launches_per_type": {"parent": copies + 1 + 2 + 2 * 9, "new": 10},
-                "count_launches": {"parent": {"launches": len(masks) + casts, "memsets": len(masks), "host_copies": len(masks)},
+                "count_ms": cm, "count_ratio": round(cm["single"][0] / cm["new"][0], 2),
+                "select_ms": sm, "select_ratio": round(sm["single"][0] / sm["new"][0], 2),
+                "launches_per_type": {"single": copies + 1 + 10, "new": 10},
+                "count_launches": {"single": {"launches": len(masks), "memsets": len(masks), "table_uploads": len(masks), "host_copies": len(masks)},
                                    "new": {"launches": batches, "memsets": batches, "table_uploads": batches, "host_copies": batches}},
                 "extra_bytes": extra}), flush=True)
 

@@ -279,9 +279,6 @@ SIGNATURES = {
     "vx_fuse_sum": (_i, [C.POINTER(FuseArgs), _p]),
     "vx_tta_views_2d": (_i, [_p, _i, _p, _p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i, _i,
                              C.POINTER(C.c_int32), _p, _p]),
-    "vx_select_workspace_bytes": (_i64, []),
-    "vx_select_kth": (_i, [_p, _i64, _i64, _p, _p, _p]),
-    "vx_count_nonzero_u8": (_i, [_p, _i64, _p, _p]),
     "vx_count_nonzero_batched_workspace_bytes": (_i64, [_i]),
     "vx_count_nonzero_batched": (_i, [C.POINTER(CountItem), _i, _p, _p, _i64, _p]),
     "vx_select_segments_workspace_bytes": (_i64, [_i]),
@@ -305,10 +302,6 @@ SIGNATURES = {
     "vx_affine_gather": (_i, [C.POINTER(AffineArgs), _p]),
     "vx_bilinear_nchw": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "vx_bilinear_softmax_nchw": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
-    "vx_evalmetrics_workspace_bytes": (_i64, []),
-    "vx_ncc_sums": (_i, [_p, _i, _p, _i, _i64, _i, C.c_double, C.c_double, _p, _p, _p]),
-    "vx_platt_sums": (_i, [_p, _i, _p, _p, _i, _i64, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p]),
-    "vx_calib_bins": (_i, [_p, _i, _p, _p, _i, _i64, _i, C.c_double, C.c_double, C.POINTER(C.c_double), _p, _p, _p]),
     "vx_ncc_batched_workspace_bytes": (C.c_size_t, [C.POINTER(NccItem), _i]),
     "vx_ncc_batched": (_i, [C.POINTER(NccItem), _i, _p, _p, C.c_size_t, _p]),
     "vx_rater_variance": (_i, [_p, _i, _i64, _p, _p]),
@@ -424,6 +417,22 @@ def zeros(shape, dtype=None, device=None):
     t = torch.empty(shape, dtype=dtype or torch.float32, device=device)
     check(load().vx_zero(ptr(t), t.numel() * t.element_size(), stream_ptr()), "vx_zero")
     return t
+
+
+_ws = {}
+
+
+def workspace(dev, need):
+    """the device's shared workspace for the batched entry points: a uint8 tensor of at least `need` bytes (64 KiB at the
+    least) that only ever grows.  One buffer serves aggregation, evalmetrics and thresholds alike, which assumes what the
+    per-module caches it replaces assumed: the callers of a device issue their calls from one thread onto one stream, so
+    a call's kernels are ordered before the next call's on that stream.  Work on several streams or threads needs a
+    workspace of its own per stream (the C entry points take any caller-owned buffer)."""
+    import torch
+    key = str(dev)
+    if key not in _ws or _ws[key].numel() < need:
+        _ws[key] = torch.empty(max(int(need), 1 << 16), dtype=torch.uint8, device=dev)
+    return _ws[key]
 
 
 def stream_ptr():

@@ -88,7 +88,6 @@ def threshold_aggregation(image, threshold=None, threshold_path=None, pred_model
 
 _REF_MODULES = ("evaluation.uncertainty_aggregation.aggregate_uncertainties", "uncertainty_aggregation.aggregate_uncertainties")
 _KINDS = {"image_level_aggregation": "image", "threshold_aggregation": "threshold", "patch_level_aggregation": "patch"}
-_ws = {}
 
 
 def register_targets():
@@ -276,12 +275,10 @@ def aggregate_batch(images, aggregations, pred_model=None, unc_type=None, budget
                 items = (_lib.AggItem * len(maps))(*[_item(t.data_ptr(), t.dtype == torch.float64, tuple(t.shape)) for t in maps])
                 sp = _spec_array(specs)
                 need = int(lib.vx_aggregate_workspace_bytes(items, len(maps), sp, len(specs)))
-                key = str(dev)
-                if key not in _ws or _ws[key].numel() < need:
-                    _ws[key] = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=dev)
+                ws = _lib.workspace(dev, need)
                 out = torch.empty((len(maps), len(specs), 4), dtype=torch.float64, device=dev)
-                rc = lib.vx_aggregate_batched(items, len(maps), sp, len(specs), _lib.ptr(out), _lib.ptr(_ws[key]),
-                                              _ws[key].numel(), _lib.stream_ptr())
+                rc = lib.vx_aggregate_batched(items, len(maps), sp, len(specs), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                              _lib.stream_ptr())
                 _lib.check(rc, "vx_aggregate_batched")
                 rows = out.cpu().tolist()
                 for i, r in zip(members, rows):

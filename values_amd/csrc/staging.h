@@ -1,5 +1,6 @@
 // Descriptor upload without a wait on the stream, for the batched entry points that build a small table on the host
-// (vx_aggregate_batched, vx_ncc_batched, vx_platt_sums_batched, vx_calib_bins_batched): the table goes through one pinned
+// (vx_aggregate_batched, vx_ncc_batched, vx_platt_sums_batched, vx_calib_bins_batched, vx_count_nonzero_batched,
+// vx_select_segments): the table goes through one pinned
 // staging buffer, and a call waits only for the event behind the PREVIOUS call's upload (long complete unless calls are
 // issued back to back).  Not capturable into a hipGraph.
 #pragma once

@@ -1,15 +1,17 @@
 """Downstream scalars of the evaluation stage: same function names, arguments and result files as
 evaluation/metrics/{aurc,ncc,ace,auroc}.py, so the task functions of evaluation/configs/tasks/*.yaml can be re-pointed.
 
-Where the work is per voxel it runs on the GPU in float64 (values_amd/csrc/evalmetrics.hip, deterministic reductions):
-  compute_ncc              ncc.py:9-25      two-pass mean / std(ddof=1) / cross product of two maps
-  sigmoid_calibration      ace.py:13-41     Platt scaling of -uncertainty against "reference == prediction": loss,
-                                            gradient and Hessian sums on the device, Newton steps on the host
-  calc_ace                 ace.py:44-90     platt_scale_confid + the 20-bin statistics of calib_stats in one pass
-The same three scores for a whole batch of images per device call (values_amd/csrc/evalmetrics_batched.hip, the per-image
-results bit for bit): ncc_batch, sigmoid_calibration_batch (the Newton iterations of all images in lock step), calc_ace_batch,
-and the drivers ambiguity_modeling_device / platt_scale_params_device / calibration_error_device / calibration_device, which
-take a DeviceExperimentDataloader and write the same JSON files byte for byte.
+Where the work is per voxel it runs on the GPU in float64 (values_amd/csrc/evalmetrics.hip, deterministic reductions), a
+whole batch of images per device call:
+  ncc_batch                  ncc.py:9-25    two-pass mean / std(ddof=1) / cross product of two maps
+  sigmoid_calibration_batch  ace.py:13-41   Platt scaling of -uncertainty against "reference == prediction": loss,
+                                            gradient and Hessian sums on the device, Newton steps on the host (the
+                                            iterations of all images in lock step)
+  calc_ace_batch             ace.py:44-90   platt_scale_confid + the 20-bin statistics of calib_stats in one pass
+compute_ncc, sigmoid_calibration and calc_ace, the reference's per-image functions, are a batch of one: an image's numbers
+do not depend on its batch mates, so both forms give the same bits.  The drivers ambiguity_modeling_device /
+platt_scale_params_device / calibration_error_device / calibration_device take a DeviceExperimentDataloader and write the
+same JSON files as the reference's per-image loops (ambiguity_modeling, platt_scale_params, ...), byte for byte.
 Where it is one scalar per IMAGE (AURC / E-AURC over (risk, confidence) pairs, AUROC over (OoD label, score) pairs:
 a few hundred numbers) it stays on the host, restated in numpy float64: aurc.py:14-67, and sklearn's roc_curve + auc
 as auroc.py:126-127 calls them.  scikit-learn itself is not needed.
@@ -24,22 +26,6 @@ import numpy as np
 import torch
 
 from . import _lib
-
-_ws = {}
-
-
-def _workspace(dev):
-    key = str(dev)
-    if key not in _ws:
-        _ws[key] = torch.empty(_lib.load().vx_evalmetrics_workspace_bytes(), dtype=torch.uint8, device=dev)
-    return _ws[key]
-
-
-def _workspace_batched(dev, need):
-    key = ("batched", str(dev))
-    if key not in _ws or _ws[key].numel() < need:
-        _ws[key] = torch.empty(max(int(need), 1 << 16), dtype=torch.uint8, device=dev)
-    return _ws[key]
 
 
 def _on_device(a):
@@ -155,20 +141,12 @@ def failure_detection(exp_dataloader):
 def compute_ncc(gt_unc_map, pred_unc_map):
     """ncc.py:9-25 on the device: numpy's two-pass moments, in float64 whatever the maps' dtype (numpy works in the
     dtype of the map: a float32 map read back from NIfTI gives the reference a float32-rounded value, ~1e-7 away)."""
-    lib, dev = _lib.load(), _dev()
-    g, gd = _float_map(gt_unc_map, dev)
-    p, pd = _float_map(pred_unc_map, dev)
-    n = g.numel()
-    if p.numel() != n:
+    dev = _dev()
+    g, p = _float_map(gt_unc_map, dev)[0], _float_map(pred_unc_map, dev)[0]     # (an integer ground truth is a MAP here)
+    if p.numel() != g.numel():
         raise ValueError("compute_ncc: maps of different size")
-    sums = torch.empty(3, dtype=torch.float64, device=dev)
-    ws = _workspace(dev)
-    st = _lib.stream_ptr()
-    _lib.check(lib.vx_ncc_sums(_lib.ptr(g), gd, _lib.ptr(p), pd, n, 0, 0.0, 0.0, _lib.ptr(sums), _lib.ptr(ws), st), "vx_ncc_sums")
-    s0 = sums.tolist()
-    mg, mp = s0[0] / n, s0[1] / n
-    _lib.check(lib.vx_ncc_sums(_lib.ptr(g), gd, _lib.ptr(p), pd, n, 1, mg, mp, _lib.ptr(sums), _lib.ptr(ws), st), "vx_ncc_sums")
-    return _ncc_value(n, *sums.tolist())
+    (n, row), = _ncc_sums_batch([g], [p])
+    return _ncc_value(n, row[2], row[3], row[4])
 
 
 def _ncc_value(n, vg, vp, prod):
@@ -228,7 +206,7 @@ def _ncc_sums_batch(gts, preds):
             keep.append((gt, pt))
             items.append(_lib.NccItem(gt.data_ptr(), pt.data_ptr(), n_gt, pt.numel(), gdt, pdt, R, 0))
         arr = (_lib.NccItem * len(items))(*items)
-        ws = _workspace_batched(dev, int(lib.vx_ncc_batched_workspace_bytes(arr, len(items))))
+        ws = _lib.workspace(dev, int(lib.vx_ncc_batched_workspace_bytes(arr, len(items))))
         sums = torch.empty((len(items), 5), dtype=torch.float64, device=dev)
         _lib.check(lib.vx_ncc_batched(arr, len(items), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
                    "vx_ncc_batched")
@@ -301,11 +279,7 @@ class _RaterInputs:
 
 
 def _platt_sums(x: _RaterInputs, A, B, t_pos, t_neg):
-    sums = torch.empty(8, dtype=torch.float64, device=x.dev)
-    _lib.check(_lib.load().vx_platt_sums(_lib.ptr(x.unc), x.dtype, _lib.ptr(x.ref), _lib.ptr(x.pred), x.R, x.nvox, x.ignore,
-                                         float(A), float(B), float(t_pos), float(t_neg), _lib.ptr(sums),
-                                         _lib.ptr(_workspace(x.dev)), _lib.stream_ptr()), "vx_platt_sums")
-    return sums.tolist()
+    return _platt_sums_batch([x], [(A, B, t_pos, t_neg)])[0]
 
 
 def _em_items(xs):
@@ -314,7 +288,8 @@ def _em_items(xs):
 
 
 def _platt_sums_batch(xs, params):
-    """the eight sums of _platt_sums for every x of xs at its own (A, B, t_pos, t_neg): one vx_platt_sums_batched call
+    """the eight sums (valid and correct voxels, loss, gradient, Hessian: em_platt_body of evalmetrics.hip) for every x of
+    xs at its own (A, B, t_pos, t_neg): one vx_platt_sums_batched call
     and one device -> host copy per VX_EM_MAX_ITEMS inputs"""
     lib, rows = _lib.load(), []
     for lo in range(0, len(xs), _lib.VX_EM_MAX_ITEMS):
@@ -322,7 +297,7 @@ def _platt_sums_batch(xs, params):
         dev, n = part[0].dev, len(part)
         items = _em_items(part)
         flat = (C.c_double * (4 * n))(*[float(v) for p in par for v in p])
-        ws = _workspace_batched(dev, int(lib.vx_platt_batched_workspace_bytes(items, n)))
+        ws = _lib.workspace(dev, int(lib.vx_platt_batched_workspace_bytes(items, n)))
         sums = torch.empty((n, 8), dtype=torch.float64, device=dev)
         _lib.check(lib.vx_platt_sums_batched(items, n, flat, part[0].ignore, _lib.ptr(sums), _lib.ptr(ws), ws.numel(),
                                              _lib.stream_ptr()), "vx_platt_sums_batched")
@@ -441,14 +416,7 @@ def platt_scale_confid(uncalib_confid, platt_scale_file, uncertainty):
 def calib_stats(reference_segs, pred_seg, unc_map, a, b, ignore_value=None):
     """calib_stats (ace.py:51-82) of platt_scale_confid(-unc, a, b) against "reference == prediction": bin discrepancies,
     bin weights and the number of non-empty bins; the 20 bins of np.linspace(0, 1 + 1e-8, 21)."""
-    x = _RaterInputs(reference_segs, pred_seg, unc_map, ignore_value)
-    edges = np.linspace(0.0, 1.0 + 1e-8, 21)
-    e = (C.c_double * 21)(*edges.tolist())
-    out = torch.empty(63, dtype=torch.float64, device=x.dev)
-    _lib.check(_lib.load().vx_calib_bins(_lib.ptr(x.unc), x.dtype, _lib.ptr(x.ref), _lib.ptr(x.pred), x.R, x.nvox, x.ignore,
-                                         float(a), float(b), e, _lib.ptr(out), _lib.ptr(_workspace(x.dev)),
-                                         _lib.stream_ptr()), "vx_calib_bins")
-    return _calib_from_bins(out.cpu().numpy())
+    return calib_stats_batch([reference_segs], [pred_seg], [unc_map], a, b, ignore_value)[0]
 
 
 def _calib_from_bins(h):
@@ -478,7 +446,7 @@ def calib_stats_batch(ref_list, pred_list, unc_list, a, b, ignore_value=None):
         dev, n = part[0].dev, len(part)
         items = _em_items(part)
         ab = (C.c_double * (2 * n))(*([float(a), float(b)] * n))
-        ws = _workspace_batched(dev, int(lib.vx_calib_batched_workspace_bytes(items, n)))
+        ws = _lib.workspace(dev, int(lib.vx_calib_batched_workspace_bytes(items, n)))
         out = torch.empty((n, 63), dtype=torch.float64, device=dev)
         _lib.check(lib.vx_calib_bins_batched(items, n, ab, e, part[0].ignore, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                                              _lib.stream_ptr()), "vx_calib_bins_batched")

@@ -6,17 +6,16 @@ Same function names and JSON files as the reference script:
 (`threshold_aggregation` reads "Mean {predictive|aleatoric|epistemic} threshold", aggregate_uncertainties.py:59-60).
 
 np.quantile over every voxel of every validation map is a selection problem on tens of millions of floats; here the
-two order statistics around q * (n - 1) come from `vx_select_kth` (radix select on the device) and numpy's linear
-interpolation (`_lerp`, method="linear") is applied to them in float64 with a float64 virtual index -- what
-numpy 1.24.3 (the reference's pin, requirements.txt:48) computes for a python-float q, and bit-identical to
-np.quantile(maps.astype(float64), q) on any numpy.  (numpy >= 2 rounds q, the index and the interpolation to float32
-when the data are float32; the two differ in the 8th digit.)
+two order statistics around q * (n - 1) come from ONE `vx_select_segments` call (radix select on the device, over the maps
+where they lie) and numpy's linear interpolation (`_lerp`, method="linear") is applied to them in float64 with a float64
+virtual index -- what numpy 1.24.3 (the reference's pin, requirements.txt:48) computes for a python-float q, and
+bit-identical to np.quantile(maps.astype(float64), q) on any numpy.  (numpy >= 2 rounds q, the index and the interpolation
+to float32 when the data are float32; the two differ in the 8th digit.)
 
 The device drivers work on whole reader batches: `get_foreground_quantile_device` counts a batch of predicted masks with
-one `vx_count_nonzero_batched` call (`count_nonzero_batch`), and `find_threshold(device_io=True)` takes both order
-statistics from ONE `vx_select_segments` call over the maps where the readers left them (`quantile_segments`: no
-concatenation, no float32 copy; NIfTI volumes and the 2D tree's TIFF maps alike).  `quantile` / `count_nonzero` are the
-single-array forms.
+one `vx_count_nonzero_batched` call (`count_nonzero_batch`), and `find_threshold(device_io=True)` selects from the maps
+where the readers left them (`quantile_segments`: no concatenation, no float32 copy; NIfTI volumes and the 2D tree's TIFF
+maps alike).  `quantile` / `count_nonzero` are the single-array forms: a batch of one.
 
 Note on the reference: `find_threshold` calls `calculate_threshold_image(np.array(unc_images), pred_model)` although
 the function is defined as `(quantile_path, image, method)` (find_threshold.py:61-66 vs :93) -- as shipped it raises
@@ -39,15 +38,7 @@ from .experiment import _read_batches_device
 
 
 def count_nonzero(mask: torch.Tensor) -> int:
-    _lib.require_gpu()
-    lib = _lib.load()
-    m = mask.reshape(-1)
-    if m.dtype != torch.uint8:
-        m = (m != 0).to(torch.uint8)
-    m = m.contiguous()
-    out = torch.empty(1, dtype=torch.int64, device=m.device)
-    _lib.check(lib.vx_count_nonzero_u8(m.data_ptr(), m.numel(), out.data_ptr(), _lib.stream_ptr()), "vx_count_nonzero_u8")
-    return int(out.item())
+    return count_nonzero_batch([mask])[0]
 
 
 def _dense_block(t: torch.Tensor) -> torch.Tensor:
@@ -67,14 +58,6 @@ def _dense_block(t: torch.Tensor) -> torch.Tensor:
 _COUNT_KINDS = {torch.bool: _lib.VX_COUNT_B1, torch.uint8: _lib.VX_COUNT_B1, torch.int8: _lib.VX_COUNT_B1,
                 torch.int16: _lib.VX_COUNT_B2, torch.int32: _lib.VX_COUNT_B4, torch.int64: _lib.VX_COUNT_B8,
                 torch.float32: _lib.VX_COUNT_F32, torch.float64: _lib.VX_COUNT_F64}
-_ws = {}
-
-
-def _workspace(dev, need: int) -> torch.Tensor:
-    key = str(dev)
-    if key not in _ws or _ws[key].numel() < need:
-        _ws[key] = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=dev)
-    return _ws[key]
 
 
 def count_nonzero_batch(masks) -> list:
@@ -99,7 +82,7 @@ def count_nonzero_batch(masks) -> list:
             part = blocks[i:i + _lib.VX_SELECT_MAX_ITEMS]
             items = (_lib.CountItem * len(part))(*[_lib.CountItem(t.data_ptr() if t.numel() else None, t.numel(),
                                                                   _COUNT_KINDS[t.dtype], 0) for t in part])
-            ws = _workspace(dev, int(lib.vx_count_nonzero_batched_workspace_bytes(len(part))))
+            ws = _lib.workspace(dev, int(lib.vx_count_nonzero_batched_workspace_bytes(len(part))))
             counts = torch.empty(len(part), dtype=torch.int64, device=dev)
             _lib.check(lib.vx_count_nonzero_batched(items, len(part), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
                                                     _lib.stream_ptr()), "vx_count_nonzero_batched")
@@ -117,30 +100,10 @@ def calculate_foreground_quantile_image(image) -> float:
 
 
 def quantile(values: torch.Tensor, q: float) -> float:
-    """np.quantile(values, q) (method='linear') of a float32 device tensor, any shape."""
+    """np.quantile(values, q) (method='linear') of a tensor of any shape: quantile_segments over the one tensor.  A host
+    tensor goes up to the device; a dtype other than float32 / float64 is cast to float32, float64 is narrowed on load."""
     _lib.require_gpu()
-    lib = _lib.load()
-    if not 0.0 <= q <= 1.0:
-        raise ValueError("Quantiles must be in the range [0, 1]")
-    x = values.reshape(-1)
-    if not x.is_cuda:
-        x = x.cuda()
-    x = x.to(torch.float32).contiguous()
-    n = x.numel()
-    if n == 0:
-        raise ValueError("quantile of an empty array")
-    if bool(torch.isnan(x).any()):
-        return float("nan")
-    virt = q * (n - 1)                      # numpy: _compute_virtual_index(n, q, alpha=1, beta=1)
-    lo = int(np.floor(virt))
-    hi = min(lo + 1, n - 1)
-    gamma = virt - lo
-    ws = torch.empty(int(lib.vx_select_workspace_bytes()), dtype=torch.uint8, device=x.device)
-    out = torch.empty(2, dtype=torch.float32, device=x.device)
-    _lib.check(lib.vx_select_kth(x.data_ptr(), n, lo, out.data_ptr(), ws.data_ptr(), _lib.stream_ptr()), "vx_select_kth")
-    _lib.check(lib.vx_select_kth(x.data_ptr(), n, hi, out.data_ptr() + 4, ws.data_ptr(), _lib.stream_ptr()), "vx_select_kth")
-    a, b = out.cpu().numpy()
-    return _lerp(a, b, gamma)
+    return quantile_segments([values], q)
 
 
 def _lerp(a, b, gamma: float) -> float:
@@ -181,7 +144,7 @@ def quantile_segments(tensors, q: float) -> float:
     with torch.cuda.device(dev):
         items = (_lib.SelectItem * len(blocks))(*[_lib.SelectItem(t.data_ptr(), t.numel(), _lib.VX_F64 if t.dtype == torch.float64
                                                                   else _lib.VX_F32, 0) for t in blocks])
-        ws = _workspace(dev, int(lib.vx_select_segments_workspace_bytes(len(blocks))))
+        ws = _lib.workspace(dev, int(lib.vx_select_segments_workspace_bytes(len(blocks))))
         res = torch.empty(3, dtype=torch.int32, device=dev)       # two float32 order statistics, then the status
         _lib.check(lib.vx_select_segments(items, len(blocks), lo, _lib.ptr(res), res.data_ptr() + 8, _lib.ptr(ws), ws.numel(),
                                           _lib.stream_ptr()), "vx_select_segments")
