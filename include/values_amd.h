@@ -758,32 +758,33 @@ int vx_calib_bins_batched(const vx_em_item* items /* host */, int n_items, const
                           size_t workspace_bytes, vx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
- * K19/K20: map -> scalar aggregations (evaluation/uncertainty_aggregation/aggregate_uncertainties.py).
- *   vx_box_max : patch_level_aggregation (:13-31): box-sum 'valid' (pd,ph,pw) in float64, max and
- *                first (C-order) index with isclose(value, max); result[0]=max, idx[0..2]
- *   vx_sum_thr : image_level_aggregation (:34-37) + threshold_aggregation (:61-67):
- *                sums[0]=sum(map), sums[1]=sum(map[map>=thr]), sums[2]=count(map>=thr); map VX_F32 or VX_F64 (a map
- *                read back from NIfTI is float64), the comparison (double)map >= thr runs in float64 like the reference's
- * vx_box_max: map is f32 [D][H][W] (2D maps: D = 1, pd = 1). workspace: 2 * D*H*W doubles.
- */
-int vx_box_max(const float* map, int D, int H, int W, int pd, int ph, int pw, double* result, int32_t* idx,
-               void* workspace, size_t workspace_bytes, vx_stream_t stream);
-int vx_sum_thr(const void* map, int dtype, int64_t n, double thr, double* sums, vx_stream_t stream);
-
-/* vx_aggregate_batched (K38): the three aggregations above for a batch of maps in one call, with the per-image kernels'
- * float64 results bit for bit (every sum keeps their association; a map's results do not depend on its batch mates).
+ * K38: map -> scalar aggregations (evaluation/uncertainty_aggregation/aggregate_uncertainties.py:13-67) for a batch of
+ * maps in one call; one map is a batch of one.
  *   items  host array: a device map [D][H][W] (a 2D map: D = 1) of VX_F32 or VX_F64 each; shapes and dtypes may differ.
- *   specs  host array, shared by all items.  kind IMAGE: sum of the map.  THRESHOLD: sum and count of the elements with
- *          (double)x >= thr.  PATCH: maximum of the 'valid' (pd, ph, pw) box sums and its first C-order index with
- *          |v - max| <= 1e-8 + 1e-5 |max| (np.isclose); a float64 map is narrowed to float32 first, as vx_box_max takes it.
+ *   specs  host array, shared by all items.  kind IMAGE: image_level_aggregation (:34-37), the sum of the map.
+ *          THRESHOLD: threshold_aggregation (:61-67), sum and count of the elements with x >= thr.  PATCH:
+ *          patch_level_aggregation (:13-31), maximum of the 'valid' (pd, ph, pw) box sums and the first C-order index
+ *          close to it.
  *   out    device [n_items][n_specs][4] float64:  IMAGE {sum, 0, 0, 0};  THRESHOLD {sum, count, 0, 0};
  *          PATCH {maximum, d, h, w} (the index as exact integers).
- * 1 <= n_items <= 4096, 1 <= n_specs <= 8, a patch must fit every item's map (the message names the item), and a patch so
- * large that no LDS tile holds its halo is refused: VX_E_SHAPE, before any device call.  All IMAGE / THRESHOLD specs of
- * an item come from one read of its map (one workgroup per item); the box sums run on LDS tiles and keep two 8-byte
- * words per tile in the workspace, never the box sums themselves.  At most four launches, whatever n_items and n_specs
- * are.  The descriptor tables go up through a pinned staging buffer: the call does not wait for the stream (only, if
- * it is still in flight, for the previous call's upload), and it is not capturable into a hipGraph.
+ * The order of every float64 operation is part of the contract (tests/agg_restated.py restates it on the host, and the
+ * results are compared with ==); a map's results do not depend on its batch mates, the tiling or the workspace:
+ *   sums   element i of the flattened map belongs to lane i % 1024; a lane adds its elements, widened to float64, in
+ *          ascending i from 0.0.  It keeps three accumulators: the sum, the sum of the elements with x >= thr and their
+ *          count, the comparison in float64 on both sides (a map read back from NIfTI is float64, and so is the
+ *          reference's threshold).  In every wave of 64 lanes the xor butterfly v = v + v[lane ^ off] runs for off = 1, 2,
+ *          4, 8, 16, 32; the 16 wave results are added in wave order from 0.0.
+ *   box    a float64 map is narrowed to float32 first; every element is then widened to float64.  Box sums along W, then
+ *          along H, then along D: each starts from 0.0 and adds its p terms in ascending k (an axis with p = 1 keeps its
+ *          0.0 + x).  The maximum over all box sums, then the first C-order index with |v - max| <= 1e-8 + 1e-5 |max|
+ *          (np.isclose with b = max), unravelled over (D - pd + 1, H - ph + 1, W - pw + 1).
+ * 1 <= n_items <= 4096, 1 <= n_specs <= 8, every map has at least one element, a patch must fit every item's map (the
+ * message names the item), and a patch so large that no LDS tile holds its halo is refused: VX_E_SHAPE, before any
+ * device call.  All IMAGE / THRESHOLD specs of an item come from one read of its map (one workgroup per item); the box
+ * sums run on LDS tiles and keep two 8-byte words per tile in the workspace, never the box sums themselves.  At most
+ * four launches, whatever n_items and n_specs are.  The descriptor tables go up through a pinned staging buffer: the
+ * call does not wait for the stream (only, if it is still in flight, for the previous call's upload), and it is not
+ * capturable into a hipGraph.
  * workspace of vx_aggregate_workspace_bytes(the same arguments), 0 for arguments the call refuses. */
 #define VX_AGG_IMAGE 0
 #define VX_AGG_THRESHOLD 1

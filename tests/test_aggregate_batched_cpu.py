@@ -1,11 +1,13 @@
-"""CPU: the host half of aggregation.aggregate_batch: the ABI structs against the C header, spec building from aggregation
-configs, result-dict assembly from a hand-written device array.  No device call."""
+"""CPU: the host half of values_amd.aggregation: the ABI structs against the C header, spec building from aggregation
+configs, result-dict assembly from a hand-written device array; the host restatement of the device's summation order
+(tests/agg_restated.py) against the oracle, and the inputs that can tell one order from another.  No device call."""
 import builtins
 import ctypes
 import json
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,6 +111,7 @@ def test_result_dicts_from_a_hand_written_out_array():
 def test_workspace_query_and_refusals_need_no_device():
     from values_amd import _lib
     lib = _lib.load()
+    assert lib.vx_version() >= 810
     item = lambda d, h, w: _lib.AggItem(0x1000, _lib.VX_F32, d, h, w)
     items = (_lib.AggItem * 2)(item(64, 64, 64), item(1, 1024, 512))
     sums = (_lib.AggSpec * 2)(_lib.AggSpec(_lib.VX_AGG_IMAGE, 1, 1, 1, 0.0), _lib.AggSpec(_lib.VX_AGG_THRESHOLD, 1, 1, 1, 0.5))
@@ -129,3 +132,73 @@ def test_workspace_query_and_refusals_need_no_device():
     assert lib.vx_aggregate_batched(items, 2, patch, 1, out, out, 16, None) == -4     # VX_E_WORKSPACE
     huge = (_lib.AggSpec * 1)(_lib.AggSpec(_lib.VX_AGG_PATCH, 1, 512, 512, 0.0))     # no LDS tile holds this halo
     assert lib.vx_aggregate_batched((_lib.AggItem * 1)(item(1, 1024, 512)), 1, huge, 1, out, out, 1 << 20, None) == -2
+
+
+def test_restatement_matches_the_oracle_on_exact_inputs():
+    """float32 values in [0, 1) widened to float64: every box sum is exact in any order, so the bounding boxes must be the
+    oracle's exactly.  max_score and the sums within rel 1e-12: all summands are positive and no path has more than
+    ceil(n / 1024) + 22 sequential adds, so either side's error is below 1e-14 relative for n <= 49210 (the largest map
+    here); the float64 maps of the sums (m + 1e-9) are not exact, the bound covers them."""
+    from oracle import aggregation_oracle as ao
+    from tests import agg_restated as ar
+    rng = np.random.default_rng(0)
+    cases = [((7, 9, 11), 3), ((7, 9, 11), 5), ((5, 5, 5), 5), ((12, 10, 33), [5, 4, 10]), ((12, 10, 33), 10), ((19, 37, 70), 3),
+             ((19, 37, 70), [5, 4, 10]), ((19, 37, 70), 10), ((13, 70), 10), ((13, 70), [3, 7]), ((13, 70), 1), ((6, 5), 1),
+             ((150, 301), 10), ((150, 301), [3, 7])]
+    for shape, patch in cases:
+        m = rng.random(shape, dtype=np.float32)
+        for mean in (False, True):
+            got = ar.patch_level_aggregation(m, patch, mean)
+            want = ao.patch_level_aggregation(m.astype(np.float64), patch, mean)
+            assert got["bounding_box"] == [tuple(int(v) for v in bb) for bb in want["bounding_box"]], (shape, patch)
+            assert got["max_score"] == pytest.approx(want["max_score"], rel=1e-12)
+            assert all(type(v) is int for bb in got["bounding_box"] for v in bb) and type(got["max_score"]) is float
+    for shape in ((1, 1), (8, 125), (32, 32), (25, 41), (11, 467), (19, 37, 70)):
+        m32 = rng.random(shape, dtype=np.float32)
+        for m in (m32, m32.astype(np.float64) + 1e-9):
+            ref = m.astype(np.float64)
+            assert ar.image_level_aggregation(m)["max_score"] == pytest.approx(ao.image_level_aggregation(ref)["max_score"], rel=1e-12)
+            mean = ar.image_level_aggregation(m, mean=True)
+            assert type(mean) is float and mean == pytest.approx(ao.image_level_aggregation(ref, mean=True), rel=1e-12)
+            for thr, mn in ((0.5, True), (0.5, False), (2.0, True)):
+                got, want = ar.threshold_aggregation(m, thr, mn), ao.threshold_aggregation(ref, threshold=thr, mean=mn)
+                assert got["threshold"] == thr and got["max_score"] == pytest.approx(float(want["max_score"]), rel=1e-12)
+
+
+def test_wide_range_inputs_see_the_order_of_the_adds():
+    """the conditions the GPU tests rely on: with these maps a kernel that added in another order would not pass `==`"""
+    from tests import agg_restated as ar
+    ranks = set()
+    for shape, patch, seed in ar.WIDE_BOX:
+        m = ar.wide_range(shape, seed)
+        patch = len(shape) * [patch] if type(patch) == int else patch
+        up, down = ar.box_sums(m, patch), ar.box_sums(m, patch, descending=True)
+        assert np.mean(up != down) > 0.25, (shape, float(np.mean(up != down)))
+        assert ar.box_max(m, patch)[0] != ar.box_max(m, patch, descending=True)[0], shape
+        ranks.add(len(shape))
+    assert ranks == {2, 3}
+    dtypes = set()
+    for shape, dtype, seed, thr in ar.WIDE_SUMS:
+        m = ar.wide_range(shape, seed, dtype)
+        x = m.astype(np.float64)
+        s, st, ct = ar.sums(m, thr)
+        assert s != float(np.sum(x)) and st != float(np.sum(x[x >= thr])), shape
+        assert ct == float(np.count_nonzero(x >= thr)) and 0 < ct < x.size
+        dtypes.add(m.dtype)
+    assert dtypes == {np.dtype(np.float32), np.dtype(np.float64)}
+
+
+def test_threshold_is_resolved_before_any_device_call(tmp_path):
+    """threshold_aggregation's two exceptions, in its order of checks (the file is opened before the names are asked for)"""
+    from values_amd.aggregation import threshold_aggregation
+    m = np.zeros((2, 2), np.float32)
+    with pytest.raises(Exception, match="^A threshold needs to be provided for threshold aggregation!$") as e:
+        threshold_aggregation(m)
+    assert type(e.value) is Exception
+    (tmp_path / "thr.json").write_text(json.dumps({"Dropout": {}}))
+    with pytest.raises(Exception, match="^If you want to load the threshold from a json file, you have to provide the prediction "
+                                        "model and the uncertainty type$") as e:
+        threshold_aggregation(m, threshold_path=str(tmp_path / "thr.json"), pred_model="Dropout")
+    assert type(e.value) is Exception
+    with pytest.raises(FileNotFoundError):
+        threshold_aggregation(m, threshold_path=str(tmp_path / "none.json"))

@@ -1,7 +1,8 @@
-"""GPU: aggregation.aggregate_batch / vx_aggregate_batched against the per-image functions of values_amd.aggregation on the
-same maps.  Equality is exact (`==` on the result dicts): the batched kernels form every float64 with the per-image
-kernels' association.  Shapes are the smallest that reach every path of the box kernel: maps below one tile, tiles cut in
-every axis, chunks along D, a single output element, 2D maps (no ring), float32 and float64 maps in one call."""
+"""GPU: aggregation.aggregate_batch and the three per-image functions of values_amd.aggregation (a batch of one through the
+same vx_aggregate_batched) against the host restatement of the documented summation order (tests/agg_restated.py).
+Equality is exact (`==` on the result dicts).  Shapes are the smallest that reach every path of the box kernel: maps below
+one tile, tiles cut in every axis, chunks along D, a single output element, 2D maps (no ring), float32 and float64 maps in
+one call; the wide-range maps are the ones whose float64 sums depend on the order of the adds."""
 import json
 import math
 import os
@@ -9,6 +10,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+from tests import agg_restated as ar
 
 pytestmark = pytest.mark.gpu
 
@@ -57,8 +60,9 @@ def test_box_shapes_match_per_image():
     for k, (shapes, aggs) in enumerate(groups):
         maps = [m.cuda() for m in _maps(shapes, seed=k)]
         got = aggregate_batch(maps, aggs)
-        want = _per_image(maps, aggs)
+        want = ar.restated(maps, aggs)
         assert got == want, (k, got, want)
+        assert _per_image(maps, aggs) == want, k
         for g, m in zip(got, maps):
             for name, r in g.items():
                 assert len(r["bounding_box"]) == m.dim() and all(type(v) is int for bb in r["bounding_box"] for v in bb)
@@ -82,7 +86,8 @@ def test_ties_and_the_isclose_quirk(shape):
     maps = [const.cuda(), tie.cuda(), quirk.cuda(), quirk.double().cuda()]
     aggs = {"p3": _patch(3), "p3m": _patch(3, True)}
     got = aggregate_batch(maps, aggs)
-    assert got == _per_image(maps, aggs)
+    assert got == ar.restated(maps, aggs)
+    assert _per_image(maps, aggs) == ar.restated(maps, aggs)
     assert got[0]["p3"]["bounding_box"] == [(0, 3)] * nd
     first = [(max(i - 2, 0), max(i - 2, 0) + 3) for i in early]
     assert got[1]["p3"]["bounding_box"] == first and got[1]["p3"]["max_score"] == 1.0
@@ -101,7 +106,8 @@ def test_sums_and_thresholds_match_per_image():
     aggs = {"sum": _image(), "mean": _image(True), "none": _thr(2.0), "none_sum": _thr(2.0, False), "eq": _thr(equal),
             "eq_sum": _thr(equal, False), "t3": _thr(0.3, False), "t3m": _thr(0.3)}
     got = aggregate_batch(maps, aggs)
-    assert got == _per_image(maps, aggs)
+    assert got == ar.restated(maps, aggs)
+    assert _per_image(maps, aggs) == ar.restated(maps, aggs)
     assert all(g["none"] == {"max_score": 0.0, "threshold": 2.0} for g in got)
     assert type(got[0]["mean"]) is float and got[0]["sum"] == {"max_score": float(maps[0].sum())}
     assert got[5]["t3"]["max_score"] == (0.3 + 1e-9) + 0.3 and got[5]["t3m"]["max_score"] == ((0.3 + 1e-9) + 0.3) / 2
@@ -117,7 +123,8 @@ def test_results_do_not_depend_on_the_batch(monkeypatch):
     others = [m.numpy() for m in _maps(shapes, seed=12)]
     aggs = {"p3": _patch(3), "p4m": _patch([4, 2, 5], True), "sum": _image(), "thr": _thr(0.5), "thr2": _thr(0.25, False)}
     alone = aggregate_batch([probe], aggs)
-    assert alone == _per_image([probe], aggs)
+    assert alone == ar.restated([probe], aggs)
+    assert _per_image([probe], aggs) == ar.restated([probe], aggs)
     batch = [probe] + others + [probe]
     assert len(batch) == 37
     full = aggregate_batch(batch, aggs)
@@ -129,6 +136,84 @@ def test_results_do_not_depend_on_the_batch(monkeypatch):
     chunked = aggregate_batch(batch, aggs, budget_bytes=200_000)
     assert len(calls) > 3 and sum(calls) == 37
     assert chunked == full
+
+
+def test_wide_range_maps_pin_the_order_of_the_adds():
+    """float32 values in [0, 1) have exact float64 sums in any order; these maps span 60 binades, and each one's own
+    sensitivity is asserted on the host first (tests/test_aggregate_batched_cpu.py asserts the same without a device)"""
+    from values_amd.aggregation import aggregate_batch
+    for shape, patch, seed in ar.WIDE_BOX:
+        m32, m64 = ar.wide_range(shape, seed), ar.wide_range(shape, seed, np.float64)
+        full = len(shape) * [patch] if type(patch) == int else patch
+        assert ar.box_max(m32, full)[0] != ar.box_max(m32, full, descending=True)[0]
+        maps = [torch.from_numpy(m32).cuda(), torch.from_numpy(m64).cuda()]
+        aggs = {"p": _patch(patch), "pm": _patch(patch, True)}
+        want = ar.restated(maps, aggs)
+        assert aggregate_batch(maps, aggs) == want, shape
+        assert _per_image(maps, aggs) == want, shape
+    for shape, dtype, seed, thr in ar.WIDE_SUMS:
+        m = ar.wide_range(shape, seed, dtype)
+        x = m.astype(np.float64)
+        s, st, _ = ar.sums(m, thr)
+        assert s != float(np.sum(x)) and st != float(np.sum(x[x >= thr]))
+        maps = [torch.from_numpy(m).cuda()]
+        aggs = {"sum": _image(), "mean": _image(True), "t": _thr(thr), "t_sum": _thr(thr, False)}
+        want = ar.restated(maps, aggs)
+        assert want[0]["sum"]["max_score"] == s and want[0]["t_sum"]["max_score"] == st
+        assert aggregate_batch(maps, aggs) == want, shape
+        assert _per_image(maps, aggs) == want, shape
+
+
+def test_per_image_surface(tmp_path):
+    """the three functions called directly: input kinds, patch_size spellings, ranks, what they raise"""
+    from values_amd import _lib
+    from values_amd.aggregation import image_level_aggregation, patch_level_aggregation, threshold_aggregation
+    base = np.random.default_rng(9).random((9, 12, 14))
+    inputs = [base, torch.from_numpy(base).half(), torch.from_numpy(base).float().cuda()]
+    assert inputs[0].dtype == np.float64 and not inputs[1].is_cuda
+    thr = np.float32(0.5)
+    for im in inputs:
+        for ps in (3, [3, 2, 4], (3, 2, 4), [np.int64(3), np.int64(2), np.int64(4)]):
+            for mean in (False, True):
+                got = patch_level_aggregation(im, ps, mean)
+                assert got == ar.patch_level_aggregation(im, ps, mean), (type(im), ps, mean)
+                assert type(got["max_score"]) is float and all(type(v) is int for bb in got["bounding_box"] for v in bb)
+        assert patch_level_aggregation(im, patch_size=3, mean=True, pred_model="x", unc_type="y") == ar.patch_level_aggregation(im, 3, True)
+        assert image_level_aggregation(im) == ar.image_level_aggregation(im)
+        mean = image_level_aggregation(im, mean=True, unc_type="y")
+        assert type(mean) is float and mean == ar.image_level_aggregation(im, mean=True)
+        for mn in (True, False):
+            got = threshold_aggregation(im, threshold=thr, mean=mn)
+            assert got == ar.threshold_aggregation(im, thr, mn) and got["threshold"] is thr
+    with pytest.raises(TypeError):
+        patch_level_aggregation(base, np.int64(3))       # (not an `int` to the reference either: no expansion to the rank)
+    for im in (np.random.default_rng(10).random(5000), torch.rand(2, 3, 5, 7).cuda()):      # _dhw: rank 1, rank 4
+        assert image_level_aggregation(im) == ar.image_level_aggregation(im)
+        assert image_level_aggregation(im, mean=True) == ar.image_level_aggregation(im, mean=True)
+        assert threshold_aggregation(im, threshold=0.25) == ar.threshold_aggregation(im, 0.25)
+    # what stays: the rank of a patch map, the two threshold exceptions
+    with pytest.raises(ValueError, match="^patch_level_aggregation: 2D or 3D maps only$"):
+        patch_level_aggregation(torch.rand(2, 3, 5, 7).cuda(), 2)
+    with pytest.raises(Exception, match="^A threshold needs to be provided for threshold aggregation!$"):
+        threshold_aggregation(base)
+    (tmp_path / "thr.json").write_text(json.dumps({"Dropout": {"Mean predictive threshold": 0.5}}))
+    with pytest.raises(Exception, match="^If you want to load the threshold from a json file, you have to provide the prediction "
+                                        "model and the uncertainty type$"):
+        threshold_aggregation(base, threshold_path=str(tmp_path / "thr.json"), pred_model="Dropout")
+    got = threshold_aggregation(base, threshold_path=str(tmp_path / "thr.json"), pred_model="Dropout", unc_type="predictive_uncertainty")
+    assert got == ar.threshold_aggregation(base, 0.5)
+    # what changed with vx_version 810 (INTEGRATION.md): all four are refusals of the one device path
+    with pytest.raises(_lib.VxError, match=r"vx_aggregate_batched failed \(rc=-2\).*item 0: patch \(1,13,3\) of spec 0 must fit map \(1,12,14\)"):
+        patch_level_aggregation(base[0], [13, 3])
+    with pytest.raises(ValueError, match=r"patch_size \[3, 3\] for a map of rank 3"):
+        patch_level_aggregation(base, [3, 3])
+    with pytest.raises(_lib.VxError, match=r"rc=-2.*leaves no LDS tile"):
+        patch_level_aggregation(torch.rand(210, 205).cuda(), 200)     # 200 * 200 floats of halo: more than 156 KB at a 1 x 1 tile
+    for empty in (np.zeros((0, 5), np.float32), torch.zeros(3, 0, 2).cuda()):
+        with pytest.raises(_lib.VxError, match=r"rc=-2.*item 0: map"):
+            image_level_aggregation(empty)
+        with pytest.raises(_lib.VxError, match=r"rc=-2.*item 0: map"):
+            threshold_aggregation(empty, threshold=0.5)
 
 
 def _lidc_tree(root, n=3):

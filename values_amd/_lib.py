@@ -310,8 +310,6 @@ SIGNATURES = {
     "vx_calib_batched_workspace_bytes": (C.c_size_t, [C.POINTER(EmItem), _i]),
     "vx_calib_bins_batched": (_i, [C.POINTER(EmItem), _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _p, _p,
                                    C.c_size_t, _p]),
-    "vx_box_max": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
-    "vx_sum_thr": (_i, [_p, _i, _i64, C.c_double, _p, _p]),
     "vx_aggregate_workspace_bytes": (C.c_size_t, [C.POINTER(AggItem), _i, C.POINTER(AggSpec), _i]),
     "vx_aggregate_batched": (_i, [C.POINTER(AggItem), _i, C.POINTER(AggSpec), _i, _p, _p, C.c_size_t, _p]),
     "vx_nifti_workspace_bytes": (C.c_size_t, [_i]),

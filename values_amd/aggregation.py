@@ -12,79 +12,39 @@ import torch
 from . import _lib
 
 
-def _dev_map(image):
-    _lib.require_gpu()
-    if isinstance(image, np.ndarray):
-        image = torch.from_numpy(np.ascontiguousarray(image))
-    dev = image.device if image.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    return image.to(dev, torch.float32).contiguous(), dev
-
-
 def patch_level_aggregation(image, patch_size, mean=False, **kwargs):
-    if type(patch_size) == int:
-        patch_size = len(image.shape) * [patch_size]
-    img, dev = _dev_map(image)
-    nd = img.dim()
-    if nd not in (2, 3):
-        raise ValueError("patch_level_aggregation: 2D or 3D maps only")
-    shape = (1,) * (3 - nd) + tuple(img.shape)
-    patch = (1,) * (3 - nd) + tuple(int(p) for p in patch_size)
-    n = img.numel()
-    ws = torch.empty(2 * n + 2, dtype=torch.float64, device=dev)
-    res = torch.empty(1, dtype=torch.float64, device=dev)
-    idx = torch.empty(3, dtype=torch.int32, device=dev)
-    rc = _lib.load().vx_box_max(_lib.ptr(img), *shape, *patch, _lib.ptr(res), _lib.ptr(idx), _lib.ptr(ws),
-                                ws.numel() * 8, _lib.stream_ptr())
-    _lib.check(rc, "vx_box_max")
-    mx = float(res.item())
-    first = idx.tolist()[3 - nd:]
-    if mean:
-        mx = mx / float(np.prod(patch_size))
-    return {"max_score": mx, "bounding_box": [(int(i), int(i + patch_size[d])) for d, i in enumerate(first)]}
-
-
-def _sums(image, thr):
-    """(sum, sum of values >= thr, count of values >= thr) in float64; a float64 map (what medpy hands the reference
-    after a NIfTI round trip) stays float64, so `map >= threshold` is the reference's comparison bit for bit."""
-    _lib.require_gpu()
-    if isinstance(image, np.ndarray):
-        image = torch.from_numpy(np.ascontiguousarray(image))
-    dev = image.device if image.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    f64 = image.dtype == torch.float64
-    img = image.to(dev, torch.float64 if f64 else torch.float32).contiguous()
-    sums = torch.empty(3, dtype=torch.float64, device=dev)
-    rc = _lib.load().vx_sum_thr(_lib.ptr(img), _lib.VX_F64 if f64 else _lib.VX_F32, img.numel(), float(thr),
-                                _lib.ptr(sums), _lib.stream_ptr())
-    _lib.check(rc, "vx_sum_thr")
-    return sums.tolist(), img.numel()
+    return _one(image, "patch", {"patch_size": patch_size, "mean": mean})
 
 
 def image_level_aggregation(image, mean=False, **kwargs):
-    (s, _, _), n = _sums(image, float("inf"))
-    if mean:
-        return float(s / n)  # the reference returns a bare float here (:35-36)
-    return {"max_score": float(s)}
+    return _one(image, "image", {"mean": mean})  # the reference returns a bare float for mean=True (:35-36)
 
 
 def threshold_aggregation(image, threshold=None, threshold_path=None, pred_model=None, unc_type=None, mean=True):
+    threshold = _threshold(threshold, threshold_path, pred_model, unc_type, {})
+    return _one(image, "threshold", {"threshold": threshold, "mean": mean})
+
+
+def _threshold(threshold, threshold_path, pred_model, unc_type, files):
+    """the threshold of a threshold_aggregation call: as given, or from the json file (read once per `files` dict); the
+    reference's order of checks and messages (:40-59)"""
     if threshold is None:
         if threshold_path is None:
             raise Exception("A threshold needs to be provided for threshold aggregation!")
-        with open(threshold_path) as f:
-            threshold_json = json.load(f)
+        if threshold_path not in files:
+            with open(threshold_path) as f:
+                files[threshold_path] = json.load(f)
         if pred_model is None or unc_type is None:
             raise Exception("If you want to load the threshold from a json file, you have to provide the prediction "
                             "model and the uncertainty type")
         unc_type_split = unc_type.split("_")[0]
-        threshold = threshold_json[pred_model][f"Mean {unc_type_split} threshold"]
-    (_, st, ct), _ = _sums(image, threshold)
-    if mean and ct > 0:
-        return {"max_score": st / ct, "threshold": threshold}
-    return {"max_score": st, "threshold": threshold}
+        threshold = files[threshold_path][pred_model][f"Mean {unc_type_split} threshold"]
+    return threshold
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The same three aggregations for a batch of maps: one vx_aggregate_batched call and one device -> host copy per chunk.
+# One device path: a list of maps and a plan [(name, kind, params)] -> one vx_aggregate_batched call and one device ->
+# host copy per chunk.  The three functions above are a plan of one entry for a batch of one map.
 
 _REF_MODULES = ("evaluation.uncertainty_aggregation.aggregate_uncertainties", "uncertainty_aggregation.aggregate_uncertainties")
 _KINDS = {"image_level_aggregation": "image", "threshold_aggregation": "threshold", "patch_level_aggregation": "patch"}
@@ -126,18 +86,7 @@ def _plan(aggregations, pred_model=None, unc_type=None):
             extra = set(params) - {"threshold", "threshold_path", "pred_model", "unc_type", "mean"}
             if extra:
                 raise TypeError(f"threshold_aggregation() got an unexpected keyword argument {sorted(extra)[0]!r}")
-            threshold = params.get("threshold")
-            if threshold is None:      # threshold_aggregation's own order of checks and messages
-                path = params.get("threshold_path")
-                if path is None:
-                    raise Exception("A threshold needs to be provided for threshold aggregation!")
-                if path not in files:
-                    with open(path) as f:
-                        files[path] = json.load(f)
-                if pred_model is None or unc_type is None:
-                    raise Exception("If you want to load the threshold from a json file, you have to provide the prediction "
-                                    "model and the uncertainty type")
-                threshold = files[path][pred_model][f"Mean {unc_type.split('_')[0]} threshold"]
+            threshold = _threshold(params.get("threshold"), params.get("threshold_path"), pred_model, unc_type, files)
             plan.append((name, kind, {"threshold": threshold, "mean": params.get("mean", True)}))
     return plan
 
@@ -231,6 +180,65 @@ def _spec_array(specs):
     return (_lib.AggSpec * max(len(specs), 1))(*[_lib.AggSpec(*s) for s in specs])
 
 
+def _chunks(images, plan, lib, budget_bytes):
+    """([(rank, [image numbers])], {rank: _specs_for(plan, rank)}): consecutive maps of one rank, at most VX_AGG_MAX_ITEMS; a
+    chunk ends where the device copies of its maps plus their calls' workspaces would pass budget_bytes.  One map is one
+    chunk and asks the library nothing."""
+    rank = len(images[0].shape)
+    if len(images) == 1:
+        return [(rank, [0])], {rank: _specs_for(plan, rank)}
+    by_rank, chunks, used = {}, [], 0
+    for i, im in enumerate(images):
+        shape = tuple(im.shape)
+        if len(shape) not in by_rank:
+            by_rank[len(shape)] = _specs_for(plan, len(shape))
+        specs, _ = by_rank[len(shape)]
+        dhw = _dhw(shape)
+        for s in specs:
+            if s[0] == _lib.VX_AGG_PATCH and any(p > n for p, n in zip(s[1:4], dhw)):
+                raise _lib.VxError(f"aggregate_batch: image {i}: patch {s[1:4]} must fit map {dhw}")
+        one = _item(0x100, False, shape)      # (the size query reads no map)
+        need = _copy_bytes(im) + int(lib.vx_aggregate_workspace_bytes(one, 1, _spec_array(specs), len(specs)))
+        if not chunks or len(chunks[-1][1]) == _lib.VX_AGG_MAX_ITEMS or chunks[-1][0] != len(shape) or used + need > budget_bytes:
+            chunks.append((len(shape), []))
+            used = 0
+        chunks[-1][1].append(i)
+        used += need
+    return chunks, by_rank
+
+
+def _run(images, plan, budget_bytes=1 << 30):
+    """[{name: result}] of a plan's device entries for a list of maps (a foreign entry: None)"""
+    if all(kind == "foreign" for _, kind, _ in plan):
+        return [{name: None for name, _, _ in plan} for _ in images]
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = next((im.device for im in images if not isinstance(im, np.ndarray) and im.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+    chunks, by_rank = _chunks(images, plan, lib, budget_bytes)
+    results = [None] * len(images)
+    with torch.cuda.device(dev):
+        for rank, members in chunks:
+            specs, index = by_rank[rank]
+            maps = [_to_device(images[i], dev) for i in members]
+            # (an empty map has no storage: the pointer stands in, so that the library refuses the shape and not a null map)
+            items = (_lib.AggItem * len(maps))(*[_item(t.data_ptr() or 0x100, t.dtype == torch.float64, tuple(t.shape)) for t in maps])
+            sp = _spec_array(specs)
+            need = int(lib.vx_aggregate_workspace_bytes(items, len(maps), sp, len(specs)))
+            ws = _lib.workspace(dev, need)
+            out = torch.empty((len(maps), len(specs), 4), dtype=torch.float64, device=dev)
+            rc = lib.vx_aggregate_batched(items, len(maps), sp, len(specs), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                          _lib.stream_ptr())
+            _lib.check(rc, "vx_aggregate_batched")
+            for i, r in zip(members, out.cpu().tolist()):
+                results[i] = _assemble(plan, index, r, tuple(images[i].shape))
+    return results
+
+
+def _one(image, kind, params):
+    return _run([image], [("r", kind, params)])[0]["r"]
+
+
 def aggregate_batch(images, aggregations, pred_model=None, unc_type=None, budget_bytes=1 << 30):
     """[{name: result}] for a list of maps (numpy arrays or tensors, host or device; shapes and dtypes may differ) and an
     aggregations dict {name: {"_target_": ..., **params}}: entry i equals what the three functions above return for
@@ -242,49 +250,7 @@ def aggregate_batch(images, aggregations, pred_model=None, unc_type=None, budget
     if not images:
         return []
     plan = _plan(aggregations, pred_model, unc_type)
-    results = [None] * len(images)
-    if any(kind != "foreign" for _, kind, _ in plan):
-        _lib.require_gpu()
-        lib = _lib.load()
-        dev = next((im.device for im in images if not isinstance(im, np.ndarray) and im.is_cuda),
-                   torch.device("cuda", torch.cuda.current_device()))
-        by_rank, chunks, used = {}, [], 0
-        for i, im in enumerate(images):
-            shape = tuple(im.shape)
-            if len(shape) not in by_rank:
-                by_rank[len(shape)] = _specs_for(plan, len(shape))
-            specs, _ = by_rank[len(shape)]
-            dhw = _dhw(shape)
-            for s in specs:
-                if s[0] == _lib.VX_AGG_PATCH and any(p > n for p, n in zip(s[1:4], dhw)):
-                    raise _lib.VxError(f"aggregate_batch: image {i}: patch {s[1:4]} must fit map {dhw}")
-            one = _item(0x100, False, shape)      # (the size query reads no map)
-            need = _copy_bytes(im) + int(lib.vx_aggregate_workspace_bytes(one, 1, _spec_array(specs), len(specs)))
-            if chunks and (len(chunks[-1][1]) == _lib.VX_AGG_MAX_ITEMS or chunks[-1][0] != len(shape)
-                           or used + need > budget_bytes):
-                chunks.append((len(shape), []))
-                used = 0
-            elif not chunks:
-                chunks.append((len(shape), []))
-            chunks[-1][1].append(i)
-            used += need
-        with torch.cuda.device(dev):
-            for rank, members in chunks:
-                specs, index = by_rank[rank]
-                maps = [_to_device(images[i], dev) for i in members]
-                items = (_lib.AggItem * len(maps))(*[_item(t.data_ptr(), t.dtype == torch.float64, tuple(t.shape)) for t in maps])
-                sp = _spec_array(specs)
-                need = int(lib.vx_aggregate_workspace_bytes(items, len(maps), sp, len(specs)))
-                ws = _lib.workspace(dev, need)
-                out = torch.empty((len(maps), len(specs), 4), dtype=torch.float64, device=dev)
-                rc = lib.vx_aggregate_batched(items, len(maps), sp, len(specs), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                              _lib.stream_ptr())
-                _lib.check(rc, "vx_aggregate_batched")
-                rows = out.cpu().tolist()
-                for i, r in zip(members, rows):
-                    results[i] = _assemble(plan, index, r, tuple(images[i].shape))
-    else:
-        results = [{name: None for name, _, _ in plan} for _ in images]
+    results = _run(images, plan, budget_bytes)
     for name, kind, cfg in plan:
         if kind == "foreign":
             for i, im in enumerate(images):

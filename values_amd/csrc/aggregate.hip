@@ -1,165 +1,313 @@
-// K19/K20: map -> scalar aggregations of evaluation/uncertainty_aggregation/aggregate_uncertainties.py.
-//   vx_box_max: patch_level_aggregation (:13-31).  The reference box-sums with scipy.signal.convolve
-//     (float64 result); here three separable sliding sums in float64, then a deterministic single-block
-//     max + "first index with np.isclose(value, max)" (rtol 1e-5, atol 1e-8, C order) search.
-//   vx_sum_thr: image_level_aggregation (:34-37) and threshold_aggregation (:61-67) in one pass.
-// Maps are small (64^3 .. 256x478), so these are latency-, not bandwidth-bound: few launches, no atomics.
+// K38: the map -> scalar aggregations of evaluation/uncertainty_aggregation/aggregate_uncertainties.py:13-67
+// (patch_level_aggregation, image_level_aggregation, threshold_aggregation) for a batch of maps in one call;
+// one map is a batch of one.
+//   vx_aggregate_batched: every IMAGE / THRESHOLD spec of an item from ONE read of its map (agg_sums_kernel, one
+//     workgroup of 1024 threads per item), every PATCH spec from separable box sums on LDS tiles (agg_box_kernel: tile
+//     maxima, then the first index close to the item's maximum in the tiles that can hold one) and a per-pair finish
+//     (agg_box_finish_kernel: minimum index, unravel, store).
+// Every value is a float64 formed in the order include/values_amd.h documents for K38 (stated again at the kernels below),
+// so the results do not depend on the batch, the tiling or the chunking.  At most four launches per call, whatever n_items
+// and n_specs are; no atomics; nothing but the descriptor upload touches the host.
+#include "aggregate_plan.h"
 #include "common.h"
+#include "staging.h"
 
-// out[o][j'][i] = sum_{k<p} in[o][j'+k][i]; axis length n -> n-p+1, inner stride `inner`
-template <typename TIn>
-__global__ __launch_bounds__(256) void box_axis_kernel(const TIn* __restrict__ in, double* __restrict__ out, int64_t outer,
-                                                       int n, int64_t inner, int p) {
-  const int no = n - p + 1;
-  const int64_t total = outer * no * inner;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t in_i = i % inner;
-    const int64_t j = (i / inner) % no;
-    const int64_t o = i / (inner * no);
-    const TIn* src = in + (o * n + j) * inner + in_i;
-    double s = 0.0;
-    for (int k = 0; k < p; ++k) s += (double)src[(int64_t)k * inner];
-    out[i] = s;
-  }
-}
+// the IMAGE / THRESHOLD specs of a call, by value: thr[j] is the j-th distinct THRESHOLD spec, slot[s] its j for spec s
+struct agg_sum_specs {
+  int32_t n_specs, n_thr;
+  int32_t kind[VX_AGG_MAX_SPECS];
+  int32_t slot[VX_AGG_MAX_SPECS];
+  double thr[VX_AGG_MAX_SPECS];
+};
 
-__global__ __launch_bounds__(1024) void max_first_close_kernel(const double* __restrict__ v, int64_t n, double* result,
-                                                               int64_t* first) {
-  __shared__ double s_max[16];
-  __shared__ long long s_idx[16];
-  __shared__ double s_gmax;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double m = -INFINITY;
-  for (int64_t i = tid; i < n; i += 1024) m = fmax(m, v[i]);
+struct agg_acc {
+  double s;
+  double st[VX_AGG_MAX_SPECS], ct[VX_AGG_MAX_SPECS];
+};
+
+// (every loop over the thresholds is unrolled with constant bounds: st / ct stay in registers)
+__device__ __forceinline__ void agg_add(agg_acc& a, double x, const double (&thr)[VX_AGG_MAX_SPECS], int n_thr) {
+  a.s += x;
 #pragma unroll
-  for (int off = 1; off < 64; off <<= 1) m = fmax(m, __shfl_xor(m, off, 64));
-  if (lane == 0) s_max[wave] = m;
-  __syncthreads();
-  if (tid == 0) {
-    double g = s_max[0];
-    for (int w = 1; w < 16; ++w) g = fmax(g, s_max[w]);
-    s_gmax = g;
-  }
-  __syncthreads();
-  const double g = s_gmax;
-  const double tol = 1e-8 + 1e-5 * fabs(g);  // np.isclose(a, b): |a-b| <= atol + rtol*|b|, b = max
-  long long fi = 0x7fffffffffffffffLL;
-  for (int64_t i = tid; i < n; i += 1024)
-    if (fabs(v[i] - g) <= tol) { fi = (long long)i; break; }  // ascending i per thread: first hit is its minimum
+  for (int t = 0; t < VX_AGG_MAX_SPECS; ++t)
+    if (t < n_thr && x >= thr[t]) { a.st[t] += x; a.ct[t] += 1.0; }
+}
+
+// element i to thread i % 1024, each thread adding its elements in ascending i from 0.0; eight loads in flight per thread
+template <typename T>
+__device__ __forceinline__ void agg_accumulate(agg_acc& a, const T* __restrict__ v, int64_t n, int tid,
+                                               const double (&thr)[VX_AGG_MAX_SPECS], int n_thr) {
+  int64_t i = tid;
+  for (; i + 7 * 1024 < n; i += 8 * 1024) {
+    T x[8];
 #pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long o = __shfl_xor(fi, off, 64);
-    fi = o < fi ? o : fi;
+    for (int k = 0; k < 8; ++k) x[k] = v[i + k * 1024];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) agg_add(a, (double)x[k], thr, n_thr);
   }
-  if (lane == 0) s_idx[wave] = fi;
-  __syncthreads();
-  if (tid == 0) {
-    long long b = s_idx[0];
-    for (int w = 1; w < 16; ++w) b = s_idx[w] < b ? s_idx[w] : b;
-    result[0] = g;
-    first[0] = b;
-  }
-}
-
-__global__ void unravel_kernel(const int64_t* first, int od, int oh, int ow, int32_t* idx) {
-  const int64_t f = first[0];
-  idx[0] = (int32_t)(f / ((int64_t)oh * ow));
-  idx[1] = (int32_t)((f / ow) % oh);
-  idx[2] = (int32_t)(f % ow);
-}
-
-extern "C" int vx_box_max(const float* map, int D, int H, int W, int pd, int ph, int pw, double* result, int32_t* idx,
-                          void* workspace, size_t workspace_bytes, vx_stream_t stream) {
-  if (!map || !result || !idx || !workspace) VX_FAIL(VX_E_NULL, "vx_box_max: null pointer");
-  if (D <= 0 || H <= 0 || W <= 0 || pd <= 0 || ph <= 0 || pw <= 0 || pd > D || ph > H || pw > W)
-    VX_FAIL(VX_E_SHAPE, "vx_box_max: patch (%d,%d,%d) must fit map (%d,%d,%d)", pd, ph, pw, D, H, W);
-  const int64_t n = (int64_t)D * H * W;
-  if (workspace_bytes < (size_t)(2 * n + 2) * sizeof(double)) VX_FAIL(VX_E_WORKSPACE, "vx_box_max: workspace needs %lld bytes", (long long)((2 * n + 2) * 8));
-  double* a = (double*)workspace;
-  double* b = a + n;
-  int64_t* first = (int64_t*)(b + n);
-  hipStream_t s = (hipStream_t)stream;
-  const int ow = W - pw + 1, oh = H - ph + 1, od = D - pd + 1;
-  auto nb = [](int64_t t) { int x = (int)((t + 255) / 256); return x > 4096 ? 4096 : (x < 1 ? 1 : x); };
-  // along W (inner = 1)
-  hipLaunchKernelGGL(box_axis_kernel<float>, dim3(nb((int64_t)D * H * ow)), dim3(256), 0, s, map, a, (int64_t)D * H, W, (int64_t)1, pw);
-  // along H (inner = ow)
-  hipLaunchKernelGGL(box_axis_kernel<double>, dim3(nb((int64_t)D * oh * ow)), dim3(256), 0, s, a, b, (int64_t)D, H, (int64_t)ow, ph);
-  // along D (inner = oh*ow)
-  hipLaunchKernelGGL(box_axis_kernel<double>, dim3(nb((int64_t)od * oh * ow)), dim3(256), 0, s, b, a, (int64_t)1, D, (int64_t)oh * ow, pd);
-  hipLaunchKernelGGL(max_first_close_kernel, dim3(1), dim3(1024), 0, s, a, (int64_t)od * oh * ow, result, first);
-  hipLaunchKernelGGL(unravel_kernel, dim3(1), dim3(1), 0, s, first, od, oh, ow, idx);
-  VX_CHECK_LAUNCH("vx_box_max");
-  return VX_OK;
+  for (; i < n; i += 1024) agg_add(a, (double)v[i], thr, n_thr);
 }
 
 // The comparison runs in float64 on both sides: the reference compares the stored map (float64 when it was read back
 // from NIfTI) with a float64 threshold (aggregate_uncertainties.py:61-66); a float32 threshold could move voxels within
-// one float32 ulp of it across the >= boundary.
-template <typename T>
-__global__ __launch_bounds__(1024) void sum_thr_kernel(const T* __restrict__ v, int64_t n, double thr, double* sums) {
-  __shared__ double s_red[3][16];
+// one float32 ulp of it across the >= boundary.  After the per-thread sums: in every wave the xor butterfly
+// v += v[lane ^ off] for off = 1, 2, ..., 32, then the 16 wave partials added in wave order from 0.0.
+__global__ __launch_bounds__(1024) void agg_sums_kernel(const agg_sum_item* __restrict__ items, agg_sum_specs sp, double* __restrict__ out) {
+  __shared__ double s_red[1 + 2 * VX_AGG_MAX_SPECS][16];
+  __shared__ int s_kind[VX_AGG_MAX_SPECS], s_slot[VX_AGG_MAX_SPECS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double s = 0.0, st = 0.0, ct = 0.0;
-  for (int64_t i = tid; i < n; i += 1024) {
-    const double x = (double)v[i];
-    s += x;
-    if (x >= thr) { st += x; ct += 1.0; }
+  const agg_sum_item it = items[blockIdx.x];
+  double thr[VX_AGG_MAX_SPECS];
+#pragma unroll
+  for (int t = 0; t < VX_AGG_MAX_SPECS; ++t) thr[t] = sp.thr[t];
+  if (tid == 0) {
+#pragma unroll
+    for (int t = 0; t < VX_AGG_MAX_SPECS; ++t) { s_kind[t] = sp.kind[t]; s_slot[t] = sp.slot[t]; }
   }
+  const int n_thr = sp.n_thr;
+  agg_acc a;
+  a.s = 0.0;
+#pragma unroll
+  for (int t = 0; t < VX_AGG_MAX_SPECS; ++t) { a.st[t] = 0.0; a.ct[t] = 0.0; }
+  if (it.dtype == VX_F64) agg_accumulate(a, (const double*)it.map, it.n, tid, thr, n_thr);
+  else agg_accumulate(a, (const float*)it.map, it.n, tid, thr, n_thr);
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {
-    s += __shfl_xor(s, off, 64);
-    st += __shfl_xor(st, off, 64);
-    ct += __shfl_xor(ct, off, 64);
+    a.s += __shfl_xor(a.s, off, 64);
+#pragma unroll
+    for (int t = 0; t < VX_AGG_MAX_SPECS; ++t)
+      if (t < n_thr) { a.st[t] += __shfl_xor(a.st[t], off, 64); a.ct[t] += __shfl_xor(a.ct[t], off, 64); }
   }
-  if (lane == 0) { s_red[0][wave] = s; s_red[1][wave] = st; s_red[2][wave] = ct; }
+  if (lane == 0) {
+    s_red[0][wave] = a.s;
+#pragma unroll
+    for (int t = 0; t < VX_AGG_MAX_SPECS; ++t)
+      if (t < n_thr) { s_red[1 + 2 * t][wave] = a.st[t]; s_red[2 + 2 * t][wave] = a.ct[t]; }
+  }
   __syncthreads();
-  if (tid < 3) {
-    double t = 0.0;
-    for (int w = 0; w < 16; ++w) t += s_red[tid][w];
-    sums[tid] = t;
+  if (tid < sp.n_specs && s_kind[tid] != VX_AGG_PATCH) {
+    const int row = s_kind[tid] == VX_AGG_IMAGE ? 0 : 1 + 2 * s_slot[tid];
+    double t0 = 0.0, t1 = 0.0;
+    for (int w = 0; w < 16; ++w) t0 += s_red[row][w];
+    if (row > 0)
+      for (int w = 0; w < 16; ++w) t1 += s_red[row + 1][w];
+    double* o = out + ((int64_t)blockIdx.x * sp.n_specs + tid) * 4;
+    o[0] = t0; o[1] = t1; o[2] = 0.0; o[3] = 0.0;
   }
-}
-
-extern "C" int vx_sum_thr(const void* map, int dtype, int64_t n, double thr, double* sums, vx_stream_t stream) {
-  if (!map || !sums) VX_FAIL(VX_E_NULL, "vx_sum_thr: null pointer");
-  if (n < 0) VX_FAIL(VX_E_SHAPE, "vx_sum_thr: negative size");
-  if (dtype == VX_F32)
-    hipLaunchKernelGGL(sum_thr_kernel<float>, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)map, n, thr, sums);
-  else if (dtype == VX_F64)
-    hipLaunchKernelGGL(sum_thr_kernel<double>, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double*)map, n, thr, sums);
-  else
-    VX_FAIL(VX_E_DTYPE, "vx_sum_thr: dtype %d", dtype);
-  VX_CHECK_LAUNCH("vx_sum_thr");
-  return VX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Colour rendering of an arg-max mask (Tester.save_prediction, test_2D.py:124-134): label -> RGB through a 256-entry
-// table, pixels of the ignore map first set to `unlabeled`.  Byte gather, HBM-bound.
-__global__ __launch_bounds__(256) void colorize_u8_kernel(const uint8_t* __restrict__ labels, const uint8_t* __restrict__ ignore,
-                                                          int64_t n, const uint8_t* __restrict__ lut, int unlabeled,
-                                                          uint8_t* __restrict__ rgb) {
-  __shared__ uint8_t s_lut[768];
-  for (int i = threadIdx.x; i < 768; i += 256) s_lut[i] = lut[i];
+// Box sums of one tile: TD output slices x TH rows x TW columns of one (item, PATCH spec) pair.  The workgroup walks the
+// TD + pd - 1 input slices of the tile; per slice it loads the (TH + ph - 1) x (TW + pw - 1) input rows as floats, sums
+// along W into doubles, along H into the ring slot of the slice, and (from slice pd - 1 on) along D over the ring in
+// ascending slice order.  Every sum starts from 0.0 and adds its p terms in ascending k (an axis with p = 1 keeps its
+// 0.0 + x), so a box sum has the same bits whatever tile it falls in.
+__device__ __forceinline__ double agg_block_max(double m, double* s_d) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) m = fmax(m, __shfl_xor(m, off, 64));
   __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    int l = labels[i];
-    if (ignore && ignore[i]) l = unlabeled;
-    rgb[3 * i + 0] = s_lut[3 * l + 0];
-    rgb[3 * i + 1] = s_lut[3 * l + 1];
-    rgb[3 * i + 2] = s_lut[3 * l + 2];
+  if ((threadIdx.x & 63) == 0) s_d[threadIdx.x >> 6] = m;
+  __syncthreads();
+  return fmax(fmax(s_d[0], s_d[1]), fmax(s_d[2], s_d[3]));
+}
+
+__device__ __forceinline__ long long agg_block_min(long long f, long long* s_i) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const long long o = __shfl_xor(f, off, 64);
+    f = o < f ? o : f;
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_i[threadIdx.x >> 6] = f;
+  __syncthreads();
+  const long long a = s_i[0] < s_i[1] ? s_i[0] : s_i[1], b = s_i[2] < s_i[3] ? s_i[2] : s_i[3];
+  return a < b ? a : b;
+}
+
+#define AGG_NO_INDEX 0x7fffffffffffffffLL
+
+template <bool SECOND>
+__global__ __launch_bounds__(VX_AGG_THREADS) void agg_box_kernel(const agg_pair* __restrict__ pairs, int n_pairs,
+                                                                 double* __restrict__ tmax, long long* __restrict__ first) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char agg_smem[];
+  __shared__ double s_d[4];
+  __shared__ long long s_i[4];
+  const int tid = threadIdx.x;
+  const int64_t tile = blockIdx.x;
+  int lo = 0, hi = n_pairs - 1;          // the last pair whose first tile is not after this one
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pairs[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+  }
+  const agg_pair q = pairs[lo];
+  const int n_tiles = q.ntd * q.nth * q.ntw;
+  double g = 0.0, tol = 0.0;
+  if (SECOND) {
+    double m = -INFINITY;
+    for (int t = tid; t < n_tiles; t += VX_AGG_THREADS) m = fmax(m, tmax[q.tile0 + t]);
+    g = agg_block_max(m, s_d);
+    tol = 1e-8 + 1e-5 * fabs(g);
+    // every box sum of a tile is <= its maximum <= g, so a tile whose maximum is not close holds no close element
+    if (!(fabs(tmax[tile] - g) <= tol)) {
+      if (tid == 0) first[tile] = AGG_NO_INDEX;
+      return;
+    }
+  }
+  const int t = (int)(tile - q.tile0);
+  const int tw = t % q.ntw, th = (t / q.ntw) % q.nth, td = t / (q.ntw * q.nth);
+  const int TW = 1 << q.tw_log2;
+  const int d0 = td * q.TD, h0 = th * q.TH, w0 = tw * TW;
+  const int nd = min(q.TD, q.od - d0), nh = min(q.TH, q.oh - h0), nw = min(TW, q.ow - w0);
+  const int IH = nh + q.ph - 1, IW = nw + q.pw - 1;
+  const int in_stride = TW + q.pw - 1;
+  float* s_in = (float*)agg_smem;
+  double* s_ws = (double*)(agg_smem + (((size_t)(q.TH + q.ph - 1) * in_stride * sizeof(float) + 255) & ~(size_t)255));
+  double* s_ring = s_ws + (size_t)(q.TH + q.ph - 1) * TW;
+  const int slice = q.TH * TW;
+  const bool f64 = q.dtype == VX_F64;
+
+  double m = -INFINITY;
+  long long fi = AGG_NO_INDEX;
+  int slot = 0;                                            // ring slot of input slice s: s % pd
+  for (int s = 0; s < nd + q.pd - 1; ++s) {
+    const int64_t base = ((int64_t)(d0 + s) * q.H + h0) * q.W + w0;
+    for (int i = tid; i < IH * IW; i += VX_AGG_THREADS) {
+      const int r = i / IW, c = i - r * IW;
+      const int64_t a = base + (int64_t)r * q.W + c;
+      s_in[r * in_stride + c] = f64 ? (float)((const double*)q.map)[a] : ((const float*)q.map)[a];   // a float64 map is narrowed first
+    }
+    __syncthreads();
+    for (int i = tid; i < (IH << q.tw_log2); i += VX_AGG_THREADS) {
+      const int r = i >> q.tw_log2, c = i & (TW - 1);
+      if (c < nw) {
+        const float* src = s_in + r * in_stride + c;
+        double v = 0.0;
+        for (int k = 0; k < q.pw; ++k) v += (double)src[k];
+        s_ws[i] = v;
+      }
+    }
+    __syncthreads();
+    // a thread sums along H and along D for the same (row, column) cells in every slice: it reads only its own ring entries
+    const int oldest = slot + 1 == q.pd ? 0 : slot + 1;    // ring slot of input slice s - (pd - 1)
+    for (int i = tid; i < (nh << q.tw_log2); i += VX_AGG_THREADS) {
+      const int r = i >> q.tw_log2, c = i & (TW - 1);
+      if (c < nw) {
+        double hs = 0.0;
+        for (int k = 0; k < q.ph; ++k) hs += s_ws[i + (k << q.tw_log2)];
+        double v = 0.0;
+        if (q.pd == 1) {
+          v += hs;
+        } else {
+          s_ring[slot * slice + i] = hs;
+          if (s >= q.pd - 1) {
+            int j = oldest;
+            for (int k = 0; k < q.pd; ++k) {
+              v += s_ring[j * slice + i];
+              j = j + 1 == q.pd ? 0 : j + 1;
+            }
+          }
+        }
+        if (s >= q.pd - 1) {
+          if (!SECOND) m = fmax(m, v);
+          else if (fabs(v - g) <= tol) {
+            const long long gi = ((long long)(d0 + s - (q.pd - 1)) * q.oh + (h0 + r)) * q.ow + (w0 + c);
+            fi = gi < fi ? gi : fi;
+          }
+        }
+      }
+    }
+    slot = oldest;
+    // (the next slice's loads wait at its first barrier for every thread to leave this loop; s_ws is rewritten after it)
+  }
+  if (!SECOND) {
+    m = agg_block_max(m, s_d);
+    if (tid == 0) tmax[tile] = m;
+  } else {
+    fi = agg_block_min(fi, s_i);
+    if (tid == 0) first[tile] = fi;
   }
 }
 
-extern "C" int vx_colorize_u8(const uint8_t* labels, const uint8_t* ignore, int64_t n, const uint8_t* lut, int unlabeled,
-                              uint8_t* rgb, vx_stream_t stream) {
-  if (n < 0 || unlabeled < 0 || unlabeled > 255) VX_FAIL(VX_E_SHAPE, "vx_colorize_u8: n=%lld unlabeled=%d", (long long)n, unlabeled);
-  if (n == 0) return VX_OK;
-  if (!labels || !lut || !rgb) VX_FAIL(VX_E_NULL, "vx_colorize_u8: null pointer");
-  int bx = (int)((n + 255) / 256);
-  if (bx > 4096) bx = 4096;
-  hipLaunchKernelGGL(colorize_u8_kernel, dim3(bx), dim3(256), 0, (hipStream_t)stream, labels, ignore, n, lut, unlabeled, rgb);
-  VX_CHECK_LAUNCH("vx_colorize_u8");
+// one wave per pair: the item's maximum, the lowest close index, its (d, h, w), stored as exact integers in doubles
+__global__ __launch_bounds__(64) void agg_box_finish_kernel(const agg_pair* __restrict__ pairs, const double* __restrict__ tmax,
+                                                            const long long* __restrict__ first, double* __restrict__ out) {
+  const agg_pair q = pairs[blockIdx.x];
+  const int n_tiles = q.ntd * q.nth * q.ntw;
+  double m = -INFINITY;
+  long long f = AGG_NO_INDEX;
+  for (int t = threadIdx.x; t < n_tiles; t += 64) {
+    m = fmax(m, tmax[q.tile0 + t]);
+    const long long o = first[q.tile0 + t];
+    f = o < f ? o : f;
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    m = fmax(m, __shfl_xor(m, off, 64));
+    const long long o = __shfl_xor(f, off, 64);
+    f = o < f ? o : f;
+  }
+  if (threadIdx.x == 0) {
+    double* o = out + (int64_t)q.out_index * 4;
+    o[0] = m;
+    o[1] = (double)(f / ((long long)q.oh * q.ow));
+    o[2] = (double)((f / q.ow) % q.oh);
+    o[3] = (double)(f % q.ow);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The two tables go up through the pinned staging buffer of staging.h: no wait on the stream.
+static vx_staging g_stage;
+
+static int agg_upload(const agg_plan& p, void* workspace, hipStream_t s) {
+  const vx_stage_part parts[2] = {{p.sums.data(), p.sums.size() * sizeof(agg_sum_item), 0},
+                                  {p.pairs.data(), p.pairs.size() * sizeof(agg_pair), p.off_pairs}};
+  return vx_staged_upload(g_stage, "vx_aggregate_batched", parts, 2, p.off_tmax, workspace, s);
+}
+
+extern "C" size_t vx_aggregate_workspace_bytes(const vx_agg_item* items, int n_items, const vx_agg_spec* specs, int n_specs) {
+  agg_plan p;
+  return agg_make_plan(items, n_items, specs, n_specs, &p) == VX_OK ? p.bytes : 0;
+}
+
+extern "C" int vx_aggregate_batched(const vx_agg_item* items, int n_items, const vx_agg_spec* specs, int n_specs, double* out,
+                                    void* workspace, size_t workspace_bytes, vx_stream_t stream) {
+  agg_plan p;
+  const int rc = agg_make_plan(items, n_items, specs, n_specs, &p);
+  if (rc != VX_OK) VX_FAIL(rc, "%s", p.err);
+  if (!out || !workspace) VX_FAIL(VX_E_NULL, "vx_aggregate_batched: null out or workspace");
+  if (workspace_bytes < p.bytes) VX_FAIL(VX_E_WORKSPACE, "vx_aggregate_batched: workspace needs %zu bytes", p.bytes);
+  if (!vx_aligned16(workspace)) VX_FAIL(VX_E_ALIGN, "vx_aggregate_batched: workspace not 16-byte aligned");
+  if (p.tiles > 0x7fffffffLL) VX_FAIL(VX_E_SHAPE, "vx_aggregate_batched: %lld tiles in one call", (long long)p.tiles);
+  hipStream_t s = (hipStream_t)stream;
+  const int up = agg_upload(p, workspace, s);
+  if (up != VX_OK) return up;
+  char* ws = (char*)workspace;
+  if (p.any_sum) {
+    agg_sum_specs sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.n_specs = n_specs;
+    for (int i = 0; i < n_specs; ++i) {
+      sp.kind[i] = specs[i].kind;
+      if (specs[i].kind == VX_AGG_THRESHOLD) { sp.slot[i] = sp.n_thr; sp.thr[sp.n_thr++] = specs[i].thr; }
+    }
+    hipLaunchKernelGGL(agg_sums_kernel, dim3(n_items), dim3(1024), 0, s, (const agg_sum_item*)ws, sp, out);
+  }
+  if (!p.pairs.empty()) {
+    const agg_pair* pairs = (const agg_pair*)(ws + p.off_pairs);
+    double* tmax = (double*)(ws + p.off_tmax);
+    long long* first = (long long*)(ws + p.off_first);
+    if (p.lds > (size_t)VX_AGG_LDS_SHARED) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(agg_box_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(agg_box_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+      if (e != hipSuccess) VX_FAIL((int)e, "vx_aggregate_batched: hipFuncSetAttribute(%zu B LDS): %s", p.lds, hipGetErrorString(e));
+    }
+    const int n_pairs = (int)p.pairs.size();
+    hipLaunchKernelGGL(agg_box_kernel<false>, dim3((unsigned)p.tiles), dim3(VX_AGG_THREADS), p.lds, s, pairs, n_pairs, tmax, first);
+    hipLaunchKernelGGL(agg_box_kernel<true>, dim3((unsigned)p.tiles), dim3(VX_AGG_THREADS), p.lds, s, pairs, n_pairs, tmax, first);
+    hipLaunchKernelGGL(agg_box_finish_kernel, dim3(n_pairs), dim3(64), 0, s, pairs, tmax, first, out);
+  }
+  VX_CHECK_LAUNCH("vx_aggregate_batched");
   return VX_OK;
 }

@@ -1,4 +1,4 @@
-// Host-side plan of vx_aggregate_batched (aggregate_batched.hip): argument checks, the LDS tile of every (item, PATCH spec)
+// Host-side plan of vx_aggregate_batched (aggregate.hip): argument checks, the LDS tile of every (item, PATCH spec)
 // pair, the workspace layout.  Plain C++ with no HIP in it, so a stand-alone program can run it under a host sanitizer.
 #pragma once
 #include <stdint.h>

@@ -2,7 +2,7 @@
 // (DESIGN 4.40).
 //   vx_count_nonzero_batched: np.count_nonzero of every item of a batch -- masks of any integer / bool / float type and any
 //     size -- in ONE launch.  An item is cut into 16-byte aligned chunks, 1024 chunks make a work block, and the work
-//     blocks of all items are dealt to the workgroups through the items' block0 prefix (the way aggregate_batched.hip
+//     blocks of all items are dealt to the workgroups through the items' block0 prefix (the way aggregate.hip
 //     deals its tiles): thousands of small 2D masks and a few large volumes share one grid.
 //   vx_select_segments: the k-th and (k+1)-th smallest of the UNION of the items' elements (float32, or float64 narrowed
 //     on load), where the reader left them: no concatenation, no cast copy.  MSB-first radix select over the

@@ -227,44 +227,35 @@ class ExperimentDataloader:
         return _load_file(self.unc_path_dict[unc_type] / f"{image_id}{self.exp_version.unc_ending}")
 
 
-def _aggregate(exp_dataloader, aggregations, images_of, batch=None):
+def _aggregate(exp_dataloader, aggregations, images_of, batch):
     """aggregated_<unc>.json for every uncertainty type; images_of(unc_path, keys) yields the (key, image) pairs of a type's
     files, each image loaded once (the reference reloads per aggregation).  `_target_`s naming the reference's functions
-    are re-pointed to values_amd.aggregation (GPU).  batch=None: every image and aggregation on its own (instantiate);
-    batch=n: n consecutive images per aggregation.aggregate_batch call, the same results in one device call each."""
+    are re-pointed to values_amd.aggregation (GPU).  `batch` consecutive images go to one aggregation.aggregate_batch
+    call (one device call each; any other `_target_` is instantiated per image there)."""
     from . import aggregation
-    aggregation.register_targets()
     ending = exp_dataloader.exp_version.unc_ending
     pred_model = exp_dataloader.exp_version.pred_model
     for unc, unc_path in exp_dataloader.unc_path_dict.items():
-        all_uncs = {}
-        pairs = images_of(unc_path, [f"{image_id}{ending}" for image_id in exp_dataloader.image_ids])
-        if batch is None:
-            for key, unc_image in pairs:
-                all_uncs[key] = {}
-                for name, cfg in aggregations.items():
-                    all_uncs[key][name] = instantiate(dict(cfg), image=unc_image, pred_model=pred_model, unc_type=unc)
-        else:
-            pending = []
+        all_uncs, pending = {}, []
 
-            def flush():
-                got = aggregation.aggregate_batch([im for _, im in pending], aggregations, pred_model=pred_model, unc_type=unc)
-                all_uncs.update(zip((k for k, _ in pending), got))
-                pending.clear()
-            for pair in pairs:
-                pending.append(pair)
-                if len(pending) >= max(int(batch), 1):
-                    flush()
-            if pending:
+        def flush():
+            got = aggregation.aggregate_batch([im for _, im in pending], aggregations, pred_model=pred_model, unc_type=unc)
+            all_uncs.update(zip((k for k, _ in pending), got))
+            pending.clear()
+        for pair in images_of(unc_path, [f"{image_id}{ending}" for image_id in exp_dataloader.image_ids]):
+            pending.append(pair)
+            if len(pending) >= max(int(batch), 1):
                 flush()
+        if pending:
+            flush()
         with open(exp_dataloader.dataset_path / f"aggregated_{unc}.json", "w") as f:
             json.dump(all_uncs, f, indent=4)
 
 
 def aggregate_uncertainties(exp_dataloader: ExperimentDataloader, aggregations):
     """aggregate_uncertainties.py:70-95: for every uncertainty type, image and aggregation config
-    ({"_target_": ..., **params}) -> aggregated_<unc>.json."""
-    _aggregate(exp_dataloader, aggregations, lambda unc_path, keys: ((k, _load_file(unc_path / k)) for k in keys))
+    ({"_target_": ..., **params}) -> aggregated_<unc>.json.  The files are read on the host, one image per device call."""
+    _aggregate(exp_dataloader, aggregations, lambda unc_path, keys: ((k, _load_file(unc_path / k)) for k in keys), batch=1)
 
 
 class DeviceExperimentDataloader(ExperimentDataloader):
