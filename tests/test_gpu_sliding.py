@@ -71,6 +71,25 @@ def test_sliding_window_vs_oracle(overlap):
     srt = np.sort(mean, axis=0)
     clear = (srt[-1] - srt[-2]) > 1e-5
     assert (out["pred_seg_mean"].cpu().numpy() == mean.argmax(0))[clear].all()
+    # the softmax variance is the float64 variance of the NORMALISED sums: compat mode divides the variance of the
+    # un-normalised sums by count^2.  (A sum is within 5e-5 of the oracle's and |d var / d p| <= 1.)
+    norm = acc.softmax_pred / np.clip(acc.num_predictions, 1, None)
+    var = norm.var(axis=0).mean(axis=0)
+    np.testing.assert_allclose(out["softmax_variance"].cpu().numpy(), var, atol=5e-5)
+    if overlap == 1:
+        return
+    # normalised mode where it differs from compat (counts up to 8): maps of the normalised sums
+    nrm = predict_image_sliding(models, torch.from_numpy(img), patch_size=patch, patch_overlap=overlap, n_pred=1,
+                                patch_batch=5, compat=False)
+    assert acc.num_predictions.max() == 8
+    np.testing.assert_array_equal(nrm["num_predictions"].cpu().numpy(), acc.num_predictions[0])
+    refn = uo.calculate_uncertainty(norm)
+    for k in KEYS:
+        np.testing.assert_allclose(nrm[k].cpu().numpy(), refn[k], atol=1e-4)
+    # (the two modes really differ here: the entropies of the un-normalised sums are off by log(count))
+    assert np.abs(refn["pred_entropy"] - ref["pred_entropy"] / cl).max() > 0.1
+    np.testing.assert_allclose(nrm["mean_softmax"].cpu().numpy(), mean, atol=5e-5)
+    np.testing.assert_allclose(nrm["softmax_variance"].cpu().numpy(), var, atol=5e-5)
 
 
 def test_image_not_covered_by_patches_keeps_zero_count():

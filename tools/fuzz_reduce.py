@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised shapes through the reductions: uncertainty maps (T, C, odd voxel counts, f32 / f64, logits / probs) against
-a float64 torch restatement of test_3D.py:486-518, the radix-select quantile against np.quantile on float64 data, and
+a float64 torch restatement of test_3D.py:486-518, the extras of vx_unc_reduce_ex (variance, in_count / out_count with
+counts 0..8) against tests/reduce_ref.py, the radix-select quantile against np.quantile on float64 data, and
 the mask-agreement counts / GED against a direct evaluation.     python tools/fuzz_reduce.py [cases] [seed]"""
 import os, random, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,6 +11,7 @@ import torch
 from values_amd.uncertainty import uncertainty_maps, softmax_variance
 from values_amd.thresholds import quantile, count_nonzero
 from values_amd.metrics import mask_agreement
+from tests import reduce_ref
 
 dev = torch.device("cuda", 0)
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
@@ -17,7 +19,7 @@ rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 bad = 0
 for case in range(cases):
     g = torch.Generator().manual_seed(case)
-    kind = rng.choice(["unc", "unc", "quantile", "agree", "var"])
+    kind = rng.choice(["unc", "unc", "quantile", "agree", "var", "ex"])
     tag = ""
     try:
         if kind in ("unc", "var"):
@@ -56,6 +58,36 @@ for case in range(cases):
                 ok = err < (2e-5 if not f64 else 1e-5) and am and sam
             if not ok:
                 raise AssertionError(f"err {err:.2e}")
+        elif kind == "ex":
+            B, T = rng.randint(1, 3), rng.randint(1, 8)
+            from_logits = rng.random() < 0.5
+            C = rng.randint(2, 8) if from_logits else rng.randint(2, 12)
+            spatial = tuple(rng.randint(1, 13) for _ in range(rng.choice([1, 2, 3])))
+            nvox = int(np.prod(spatial))
+            f64 = rng.random() < 0.3
+            mode = rng.choice(["out_count", "var"] if from_logits else ["in_count", "out_count", "var"])
+            cnt = torch.randint(0, 9, (B, nvox), generator=g).float()
+            x = torch.randn((B, T, C, nvox), generator=g, dtype=torch.float64) * rng.choice([0.5, 3.0])
+            if not from_logits:      # un-normalised sums: count x softmax, zeros where the count is 0
+                x = torch.softmax(x, 2) * cnt[:, None, None, :].double()
+            xin = x if f64 else x.float()
+            kw = {} if mode == "var" else {mode: cnt}
+            tag = f"ex B={B} T={T} C={C} {spatial} f64={f64} logits={from_logits} {mode}"
+            m = uncertainty_maps(xin.reshape((B, T, C) + spatial).to(dev), from_logits=from_logits, want_sample_argmax=True,
+                                 want_variance=True, **{k: v.reshape((B,) + spatial).to(dev) for k, v in kw.items()})
+            ref = reduce_ref.maps(xin.numpy(), from_logits, **{k: v.numpy() for k, v in kw.items()})
+            err = max(np.abs(m[a].cpu().numpy().reshape(ref[b].shape) - ref[b]).max()
+                      for a, b in (("pred_entropy",) * 2, ("expected_entropy",) * 2, ("mutual_information",) * 2,
+                                   ("mean_softmax",) * 2, ("softmax_variance", "variance")))
+            zero = (cnt == 0).numpy() & (not from_logits)
+            clear = reduce_ref.clear_mean(ref["mean_softmax"]) | zero
+            am = (m["argmax"].cpu().numpy().reshape(B, nvox) == ref["argmax"])[clear].all()
+            xe = xin.numpy() / np.clip(cnt.numpy(), 1, None)[:, None, None, :] if mode == "in_count" else xin.numpy()
+            sclear = reduce_ref.clear_sample(xe, from_logits) | zero[:, None, :]
+            sam = (m["sample_argmax"].cpu().numpy().reshape(B, T, nvox) == ref["sample_argmax"])[sclear].all()
+            nan = any(torch.isnan(t.float()).any().item() for t in m.values())
+            if not (err < 2e-5 and am and sam and not nan):
+                raise AssertionError(f"err {err:.2e} argmax {am} sample_argmax {sam} nan {nan}")
         elif kind == "quantile":
             n = rng.choice([1, 2, 3, 17, 1000, 65537, 300001])
             q = rng.choice([0.0, 1.0, 0.5, 0.95, 0.98, rng.random()])

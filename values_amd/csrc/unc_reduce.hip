@@ -220,7 +220,10 @@ __global__ __launch_bounds__(256) void unc_reduce_logit_kernel(const TIn* __rest
         for (int c = 0; c < C; ++c) {
           const TIn p = e[c] * inv;
           sum[c][k] += p;
-          ee[k] += p * ((z[c][k] - m) - lden);  // p*log(p) via log-softmax
+          // p*log(p) via log-softmax.  A class at -inf (a masked class) has p == 0 exactly and 0 * -inf = NaN: the
+          // reference softmaxes first and skips that NaN product (test_3D.py:503-504), so the term is selected away.
+          // Every finite product is what it was (0 * finite added +-0).
+          ee[k] += p > (TIn)0 ? p * ((z[c][k] - m) - lden) : (TIn)0;
           if (EX) {
             if (t == 0) p0[c][k] = p;
             const TIn d = p - p0[c][k];
@@ -331,7 +334,7 @@ __global__ __launch_bounds__(256) void unc_stats_accumulate_kernel(const float* 
         for (int c = 0; c < C; ++c) {
           const float p = e[c] * inv;
           sum[c][k] += p;
-          ee[k] += p * ((z[c][k] - m) - lden);
+          ee[k] += p > 0.f ? p * ((z[c][k] - m) - lden) : 0.f;   // (a class at -inf: see unc_reduce_logit_kernel)
         }
       }
     }
