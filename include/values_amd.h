@@ -556,7 +556,14 @@ int vx_bilinear_nchw(const float* x, int x_pitch, int N, int H, int W, int C, in
                      const int32_t* dst, const int32_t* flip, vx_stream_t stream);
 /* The same upsample followed by F.softmax(dim=1) (test_2D.py:300-303: `output_softmax = F.softmax(output, dim=1)` of every
  * forward), in one pass: out holds PROBABILITIES, the full-resolution logits are never written.  Bit-identical to
- * vx_bilinear_nchw + vx_softmax_planar. */
+ * vx_bilinear_nchw + vx_softmax_planar.
+ * Any x_pitch >= C is accepted and no float at or beyond x_pitch of a pixel is read.  The register-resident instances
+ * (1, 2, 5 or 8 channel quads per pixel, loaded whole) need x 16-byte aligned, x_pitch a multiple of 4 and x_pitch >=
+ * 4 Q for the smallest of those Q >= ceil(C / 4): 19 classes at pitch 20 (Q = 5), up to 8 at pitch 8, 29 .. 32 at pitch
+ * 32.  Everything else -- among it 9 .. 16 classes at pitch 12 / 16 and 21 .. 28 at pitch 24 / 28, unless the caller pads
+ * the pitch to 20 / 32, as HighResolutionNet does for its logits -- takes the scalar kernel: the same bits at 2.3 - 2.4 x
+ * the time (8 x 128x256 -> 512x1024 on an MI355X: 12 classes 235 us against 100 us, 24 classes 437 against 182).
+ * Channels [C, x_pitch) may hold anything. */
 int vx_bilinear_softmax_nchw(const float* x, int x_pitch, int N, int H, int W, int C, int OH, int OW, float* out,
                              const int32_t* dst, const int32_t* flip, vx_stream_t stream);
 

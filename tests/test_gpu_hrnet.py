@@ -467,3 +467,31 @@ def test_graphed_predictor_2d_replays_the_eager_bits():
     m3, gg, _ = make(dropout_final=True)
     with pytest.raises(ValueError):
         GraphedPredictor2D([m3], torch.from_numpy(gg["input"]).cuda(), n_pred=2)
+
+
+@pytest.mark.parametrize("ncls,pitch,inst", [(12, 20, 5), (21, 32, 8)])
+def test_logits_of_12_and_21_classes_travel_at_the_pitch_of_a_vector_softmax_instance(ncls, pitch, inst):
+    """Class counts whose round4(C) pitch holds fewer channel quads than the softmax-upsample instance that covers them: the
+    head writes its logits at pitch 20 / 32 (hrnet._softmax_pitch), vx_bilinear_softmax_nchw stays on vec<5> / vec<8>, the
+    probabilities are the class softmax of the logits path (which reads the same padded tensor) and the logits match the
+    float64 oracle as for every other class count."""
+    from oracle.hrnet_oracle import hrnet_forward
+    from values_amd import _lib
+    from values_amd.hrnet import HighResolutionNet, _softmax_pitch
+    from values_amd.predict2d import predict_logits_2d
+    assert _softmax_pitch(ncls) == pitch
+    m = HighResolutionNet(small_cfg(dropout_final=False, ncls=ncls))
+    sd = formula_state_dict_from_shapes({k: tuple(v.shape) for k, v in m.state_dict().items()})
+    m.load_state_dict({k: torch.from_numpy(v).float() for k, v in sd.items()}, strict=False)
+    m = m.cuda()
+    x = torch.from_numpy(formula_tensor((2, 3, 64, 96), tag=97)).float().cuda()
+    lg = predict_logits_2d([m], x)
+    pr = predict_logits_2d([m], x, softmax=True)
+    torch.cuda.synchronize()
+    assert _lib.load().vx_last_kernel_name().decode() == f"bilinear_softmax_nchw_vec_kernel<{inst}>"
+    assert lg.shape == pr.shape and lg.shape[2] == ncls
+    assert (pr - torch.softmax(lg.double(), 2)).abs().max().item() < 1e-6
+    with torch.no_grad():
+        y64 = hrnet_forward(dict(HRNET_SMALL_EXTRA, DROPOUT_FINAL=False), {k: torch.from_numpy(v).double() for k, v in sd.items()},
+                            x.double().cpu())
+    assert (lg[:, 0].double().cpu() - y64).abs().max().item() < LOGIT_TOL

@@ -364,13 +364,19 @@ extern "C" int vx_bilinear_softmax_nchw(const float* x, int x_pitch, int N, int 
   int blocks = (int)((total + 255) / 256);
   if (blocks > 16384) blocks = 16384;
   const int c4 = (C + 3) / 4;
-  const bool vec = x_pitch % 4 == 0 && x_pitch >= 4 * c4 && vx_aligned16(x) && c4 <= 8;
-#define VX_BS_LAUNCH(K) hipLaunchKernelGGL(K, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, x_pitch, N, H, W, C, OH, OW, out, dst, flip)
-  if (vec && c4 <= 1) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<1>);
-  else if (vec && c4 <= 2) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<2>);
-  else if (vec && c4 <= 5) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<5>);
-  else if (vec) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<8>);
-  else VX_BS_LAUNCH(bilinear_softmax_nchw_kernel);
+  const bool vec = x_pitch % 4 == 0 && vx_aligned16(x);
+  // a vec<Q> instance loads Q quads of every corner pixel whatever C is (only the uses are guarded by c < C): it runs only
+  // where the pixel HAS Q quads (x_pitch >= 4 Q), or the last pixel's loads would pass the end of the tensor.  Class counts
+  // whose pitch holds fewer quads than the smallest instance that covers them (C = 9 .. 16, 21 .. 28 at pitch round4(C))
+  // take the scalar kernel: the same bits.
+  auto fits = [&](int Q) { return vec && c4 <= Q && x_pitch >= 4 * Q; };
+#define VX_BS_LAUNCH(K, NAME) do { vx_note_kernel(NAME); \
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, x_pitch, N, H, W, C, OH, OW, out, dst, flip); } while (0)
+  if (fits(1)) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<1>, "bilinear_softmax_nchw_vec_kernel<1>");
+  else if (fits(2)) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<2>, "bilinear_softmax_nchw_vec_kernel<2>");
+  else if (fits(5)) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<5>, "bilinear_softmax_nchw_vec_kernel<5>");
+  else if (fits(8)) VX_BS_LAUNCH(bilinear_softmax_nchw_vec_kernel<8>, "bilinear_softmax_nchw_vec_kernel<8>");
+  else VX_BS_LAUNCH(bilinear_softmax_nchw_kernel, "bilinear_softmax_nchw_kernel");
 #undef VX_BS_LAUNCH
   VX_CHECK_LAUNCH("vx_bilinear_softmax_nchw");
   return VX_OK;

@@ -143,6 +143,18 @@ def _rp(c: int) -> int:
     return (c + 3) // 4 * 4
 
 
+def _softmax_pitch(c: int) -> int:
+    """pitch of the class logits: vx_bilinear_softmax_nchw keeps the C interpolated logits in registers only where a pixel
+    holds ALL the channel quads of the instance that covers them (1, 2, 5 or 8).  9 .. 16 classes therefore travel at 20
+    floats per pixel and 21 .. 28 at 32 (round4(C) would send them to the three-sweep scalar kernel); every other count at
+    round4(C) as before (19 classes: 20).  The lanes beyond round4(C) are never written and never used."""
+    q = (c + 3) // 4
+    for inst in (1, 2, 5, 8):
+        if q <= inst:
+            return 4 * inst
+    return 4 * q
+
+
 def _pad_mask(m: torch.Tensor, dev) -> torch.Tensor:
     """(B, C, H, W) bool keep-mask -> channels-last uint8 with the channel padding of the activations"""
     t = m.to(dev).permute(0, 2, 3, 1).to(torch.uint8)
@@ -335,7 +347,7 @@ class HighResolutionNet(nn.Module):
         return packed
 
     # ------------------------------------------------------------------ kernel wrappers
-    def _conv(self, x: _Act, name, stats=True, pre=None):
+    def _conv(self, x: _Act, name, stats=True, pre=None, out_pitch=None):
         """pre = (scale, shift): `x` is the RAW output of the previous conv and relu(x * scale + shift) -- its training-mode
         BatchNorm + ReLU -- is applied while this conv stages its tiles (vx_conv2d_args.in_scale): the affine pass that
         would write the activated tensor (and the read of it) disappear."""
@@ -362,6 +374,9 @@ class HighResolutionNet(nn.Module):
             self._zreal[name] = cout
             out = hit[1]
         else:
+            if out_pitch is not None:       # (the class logits: _softmax_pitch)
+                assert out_pitch % 4 == 0 and out_pitch >= pitch
+                pitch = out_pitch
             out = torch.empty((n, oh, ow, pitch), dtype=torch.float32, device=x.t.device)
         part = None
         a = _lib.Conv2dArgs()
@@ -662,9 +677,10 @@ class HighResolutionNet(nn.Module):
             off += f.C
         r = self._conv_bn(cat, "last_layer.0", "last_layer.1")
         if self._fold():
-            raw, _, _ = self._conv(r[0], "last_layer.3", stats=False, pre=(r[1], r[2]))
+            raw, _, _ = self._conv(r[0], "last_layer.3", stats=False, pre=(r[1], r[2]), out_pitch=_softmax_pitch(self.num_classes))
         else:
-            raw, _, _ = self._conv(self._aff(r[0], r[1], r[2], relu=True), "last_layer.3", stats=False)
+            raw, _, _ = self._conv(self._aff(r[0], r[1], r[2], relu=True), "last_layer.3", stats=False,
+                                   out_pitch=_softmax_pitch(self.num_classes))
         # softmax: `out` receives F.softmax(dim=1) of the upsampled logits (what test_2D.py:300-303 takes of every forward)
         # in the same pass; the full-resolution logits are not written
         fn = lib.vx_bilinear_softmax_nchw if softmax else lib.vx_bilinear_nchw
