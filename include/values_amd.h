@@ -153,6 +153,37 @@ int vx_softmax_planar(const float* logits, int64_t R, int C, int64_t nvox, float
  * (evaluation/experiment_dataloader.py:38-49): out[v] = 1 - max_c x[c][v]; x [C][nvox]. */
 int vx_one_minus_msr(const void* x, int dtype, int C, int64_t nvox, void* out, vx_stream_t stream);
 
+/* The same score for a whole batch in ONE launch (unc_reduce.hip; DeviceExperimentDataloader's Softmax tree setup, the
+ * T = 1 branch of process_output_2d): item i takes its C planes from planes[first_plane .. first_plane + C), separate
+ * device arrays of n elements each at any element-aligned address (the tensors the readers return for C files), and
+ * out[v] = 1 - max_c planes[c][v] with vx_one_minus_msr's comparison (from plane 0, q > best ? q : best in plane order):
+ * every input, NaN and -0.0 included, gives the bits vx_one_minus_msr gives on the same planes stacked contiguously, and
+ * an item's result does not depend on its batch mates.  Items may differ in n, C and dtype; an item with n = 0 writes
+ * nothing and its pointers are not looked at.  Where an item's planes and out share their 16-byte phase the kernel moves
+ * 16 bytes per lane with an element-wise first and last work block, otherwise the item goes element by element; no byte
+ * outside [ptr, ptr + n * esize) of a plane or of out is read or written.  Traffic: (C + 1) * n * esize bytes per item.
+ * 1 <= n_items <= VX_MSR_MAX_ITEMS, 1 <= n_planes <= VX_MSR_MAX_PLANES; planes may be shared between items.
+ * Refused before any device call: a null table, or a null out / plane of an item with n > 0 (VX_E_NULL); n_items or
+ * n_planes out of range, n < 0, C < 1, first_plane < 0 or first_plane + C > n_planes (VX_E_SHAPE); an unknown dtype
+ * (VX_E_DTYPE); a pointer off its element alignment or a workspace off 16 bytes (VX_E_ALIGN); a short workspace
+ * (VX_E_WORKSPACE).  workspace: vx_one_minus_msr_batched_workspace_bytes(n_items, n_planes) bytes, 0 for counts the call
+ * refuses.  Both tables go up through a pinned staging buffer inside the call: no wait on the stream (only, if it is
+ * still in flight, for the previous call's upload), and the call is not capturable into a hipGraph. */
+#define VX_MSR_MAX_ITEMS 65536
+#define VX_MSR_MAX_PLANES (1 << 22)
+typedef struct vx_msr_item {
+  void* out;           /* device, n elements of dtype */
+  int64_t n;           /* elements per plane; 0 allowed (then out / planes may be null) */
+  int32_t first_plane; /* index into planes[] */
+  int32_t C;           /* >= 1 planes: planes[first_plane .. first_plane + C) */
+  int32_t dtype;       /* VX_F32 | VX_F64: the planes and out */
+  int32_t reserved;
+} vx_msr_item;
+int64_t vx_one_minus_msr_batched_workspace_bytes(int n_items, int n_planes);
+int vx_one_minus_msr_batched(const vx_msr_item* items /* host */, int n_items,
+                             const void* const* planes /* host array of device pointers */, int n_planes, void* workspace,
+                             int64_t ws_bytes, vx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------
  * Weight packing (one-off, at checkpoint load: load_models_from_checkpoint, test_3D.py:222-247).
  *   conv3d  : torch (Cout, Cin, 3,3,3) f32 -> MFMA fragment order; returns floats needed via *_size

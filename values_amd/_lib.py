@@ -217,6 +217,15 @@ class SelectItem(C.Structure):
     _fields_ = [("ptr", _p), ("n", _i64), ("dtype", _i32), ("reserved", _i32)]
 
 
+VX_MSR_MAX_ITEMS, VX_MSR_MAX_PLANES = 65536, 1 << 22
+
+
+class MsrItem(C.Structure):
+    """vx_msr_item: one image of vx_one_minus_msr_batched: out and the C planes planes[first_plane .. first_plane + C) of n
+    VX_F32 / VX_F64 elements each."""
+    _fields_ = [("out", _p), ("n", _i64), ("first_plane", _i32), ("C", _i32), ("dtype", _i32), ("reserved", _i32)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "vx_version": (_i, []),
@@ -233,6 +242,8 @@ SIGNATURES = {
     "vx_unc_stats_finalize": (_i, [_p, _i, _i, _i, _i64, _p, _p, _p, _p, _p, _p]),
     "vx_softmax_planar": (_i, [_p, _i64, _i, _i64, _p, _p]),
     "vx_one_minus_msr": (_i, [_p, _i, _i, _i64, _p, _p]),
+    "vx_one_minus_msr_batched_workspace_bytes": (_i64, [_i, _i]),
+    "vx_one_minus_msr_batched": (_i, [C.POINTER(MsrItem), _i, C.POINTER(_p), _i, _p, _i64, _p]),
     "vx_conv3d_k3_packed_floats": (_i64, [_i, _i]),
     "vx_pack_conv3d_k3": (_i, [_p, _p, _i, _i, _p]),
     "vx_convT_k2s2_packed_floats": (_i64, [_i, _i]),
@@ -436,6 +447,20 @@ def workspace(dev, need):
 def stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def dense_block(t):
+    """`t` itself when its elements fill one block of memory without gaps or overlap -- a contiguous tensor or a permuted
+    view of one, such as the [x, y, z] views the readers return: data_ptr() is then the block's first element, and what an
+    element-wise or order-free kernel computes does not depend on the order.  Anything else: a contiguous copy."""
+    if t.is_contiguous():
+        return t
+    expect = 1
+    for size, stride in sorted(((n, s) for n, s in zip(t.shape, t.stride()) if n != 1), key=lambda d: d[1]):
+        if stride != expect:
+            return t.contiguous()
+        expect *= size
+    return t
 
 
 def ptr(t):

@@ -7,7 +7,13 @@
 //   are skipped, float32 maps.  With from_logits the class softmax (test_3D.py:472) is fused and the
 //   entropy of a sample is computed from log-softmax, which is the same value without the 0*log(0)
 //   singularity.
+// Also here: 1 - max softmax (calculate_one_minus_msr, test_3D.py:521-525) for one image (vx_one_minus_msr) and for a
+// batch of images whose class planes are separate device arrays (vx_one_minus_msr_batched: one launch, item table through
+// staging.h), and the softmax variance.
+#include <vector>
+
 #include "common.h"
+#include "staging.h"
 
 template <typename T> struct VecOf;
 template <> struct VecOf<float> { static constexpr int N = 4; };
@@ -607,6 +613,147 @@ extern "C" int vx_one_minus_msr(const void* x, int dtype, int C, int64_t nvox, v
   else
     VX_FAIL(VX_E_DTYPE, "vx_one_minus_msr: dtype %d", dtype);
   VX_CHECK_LAUNCH("vx_one_minus_msr");
+  return VX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// vx_one_minus_msr_batched: out[v] = 1 - max_c planes[c][v] for a whole batch of images in ONE launch.  The C
+// planes of an item are separate device arrays (what the readers return for C files), items differ in n, C and dtype.
+// An item is cut into 16-byte chunks counted from the 16-byte boundary at or below its pointers, 1024 chunks make a work
+// block, and the work blocks of all items are dealt to the workgroups through the items' block0 prefix (select.hip).
+//   * the planes and out of an item share their 16-byte phase (lead >= 0): a work block that lies inside the item moves
+//     16 bytes per lane and plane, four chunks per lane in flight; the item's first and last work block go element by
+//     element, so no byte outside [ptr, ptr + n * esize) is touched;
+//   * they do not (lead < 0): the whole item goes element by element (coalesced 4- / 8-byte accesses).
+// The comparison is one_minus_msr_kernel's -- start from plane 0, q > best ? q : best in plane order, (TIn)1 - best -- and
+// exact in the input precision, so the result has that kernel's bits whatever path an element takes.
+#define MSR_THREADS 256
+#define MSR_BLOCK_CHUNKS 1024   // 16-byte chunks per work block: four per thread
+#define MSR_MAX_GRID 2048
+
+struct msr_dev_item {
+  void* out;
+  int64_t n;
+  int64_t block0;
+  int32_t first_plane, C;
+  int32_t dtype, lead;   // lead: elements between the 16-byte boundary at or below the pointers and the pointers; -1: phases differ
+};
+
+template <typename TIn>
+__device__ __forceinline__ void msr_work_block(const msr_dev_item& it, const void* const* __restrict__ pl, int64_t wb, int tid) {
+  constexpr int PER = 16 / (int)sizeof(TIn), U = MSR_BLOCK_CHUNKS / MSR_THREADS;
+  typedef TIn vt __attribute__((ext_vector_type(PER)));
+  TIn* __restrict__ out = (TIn*)it.out;
+  const int64_t e_first = wb * (MSR_BLOCK_CHUNKS * PER) - (it.lead > 0 ? it.lead : 0);   // element of the block's first chunk
+  if (it.lead >= 0 && e_first >= 0 && e_first + MSR_BLOCK_CHUNKS * PER <= it.n) {          // (uniform over the workgroup)
+    const int64_t e0 = e_first + (int64_t)tid * PER;
+    vt best[U];
+    {
+      const TIn* __restrict__ p = (const TIn*)pl[0];
+#pragma unroll
+      for (int u = 0; u < U; ++u) best[u] = *reinterpret_cast<const vt*>(p + e0 + u * (MSR_THREADS * PER));
+    }
+    for (int c = 1; c < it.C; ++c) {
+      const TIn* __restrict__ p = (const TIn*)pl[c];
+      vt q[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) q[u] = *reinterpret_cast<const vt*>(p + e0 + u * (MSR_THREADS * PER));
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int k = 0; k < PER; ++k) best[u][k] = q[u][k] > best[u][k] ? q[u][k] : best[u][k];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      vt o;
+#pragma unroll
+      for (int k = 0; k < PER; ++k) o[k] = (TIn)1 - best[u][k];
+      *reinterpret_cast<vt*>(out + e0 + u * (MSR_THREADS * PER)) = o;
+    }
+    return;
+  }
+#pragma unroll 4
+  for (int j = 0; j < U * PER; ++j) {
+    const int64_t e = e_first + j * MSR_THREADS + tid;
+    if (e >= 0 && e < it.n) {
+      TIn best = ((const TIn*)pl[0])[e];
+      for (int c = 1; c < it.C; ++c) {
+        const TIn q = ((const TIn*)pl[c])[e];
+        best = q > best ? q : best;
+      }
+      out[e] = (TIn)1 - best;
+    }
+  }
+}
+
+__global__ __launch_bounds__(MSR_THREADS) void one_minus_msr_batched_kernel(const msr_dev_item* __restrict__ items, int n_items,
+                                                                            const void* const* __restrict__ planes, int64_t n_blocks) {
+  for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+    int lo = 0, hi = n_items - 1;   // the last item whose block0 is not after blk (the same for every thread)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (items[mid].block0 <= blk) lo = mid; else hi = mid - 1;
+    }
+    const msr_dev_item it = items[lo];
+    if (it.dtype == VX_F64) msr_work_block<double>(it, planes + it.first_plane, blk - it.block0, (int)threadIdx.x);
+    else msr_work_block<float>(it, planes + it.first_plane, blk - it.block0, (int)threadIdx.x);
+  }
+}
+
+static vx_staging g_msr_stage;
+
+extern "C" int64_t vx_one_minus_msr_batched_workspace_bytes(int n_items, int n_planes) {
+  if (n_items < 1 || n_items > VX_MSR_MAX_ITEMS || n_planes < 1 || n_planes > VX_MSR_MAX_PLANES) return 0;
+  return (int64_t)(vx_align256((size_t)n_items * sizeof(msr_dev_item)) + vx_align256((size_t)n_planes * sizeof(void*)));
+}
+
+extern "C" int vx_one_minus_msr_batched(const vx_msr_item* items, int n_items, const void* const* planes, int n_planes,
+                                        void* workspace, int64_t ws_bytes, vx_stream_t stream) {
+  if (!items || !planes) VX_FAIL(VX_E_NULL, "vx_one_minus_msr_batched: null item or plane table");
+  if (n_items < 1 || n_items > VX_MSR_MAX_ITEMS)
+    VX_FAIL(VX_E_SHAPE, "vx_one_minus_msr_batched: n_items %d outside 1..%d", n_items, VX_MSR_MAX_ITEMS);
+  if (n_planes < 1 || n_planes > VX_MSR_MAX_PLANES)
+    VX_FAIL(VX_E_SHAPE, "vx_one_minus_msr_batched: n_planes %d outside 1..%d", n_planes, VX_MSR_MAX_PLANES);
+  std::vector<msr_dev_item> table;
+  int64_t n_blocks = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const vx_msr_item& it = items[i];
+    if (it.dtype != VX_F32 && it.dtype != VX_F64) VX_FAIL(VX_E_DTYPE, "vx_one_minus_msr_batched: item %d: dtype %d", i, it.dtype);
+    if (it.n < 0 || it.n > (int64_t)1 << 59) VX_FAIL(VX_E_SHAPE, "vx_one_minus_msr_batched: item %d: n=%lld", i, (long long)it.n);
+    if (it.C < 1 || it.first_plane < 0 || (int64_t)it.first_plane + it.C > n_planes)
+      VX_FAIL(VX_E_SHAPE, "vx_one_minus_msr_batched: item %d: planes [%d, %d + %d) of %d", i, it.first_plane, it.first_plane, it.C, n_planes);
+    if (it.n == 0) continue;
+    const int es = it.dtype == VX_F64 ? 8 : 4, per = 16 / es;
+    if (!it.out) VX_FAIL(VX_E_NULL, "vx_one_minus_msr_batched: item %d: null out", i);
+    if ((uintptr_t)it.out % es) VX_FAIL(VX_E_ALIGN, "vx_one_minus_msr_batched: item %d: out not aligned to its %d-byte elements", i, es);
+    bool same = true;
+    for (int c = 0; c < it.C; ++c) {
+      const void* p = planes[it.first_plane + c];
+      if (!p) VX_FAIL(VX_E_NULL, "vx_one_minus_msr_batched: item %d: plane %d is null", i, c);
+      if ((uintptr_t)p % es) VX_FAIL(VX_E_ALIGN, "vx_one_minus_msr_batched: item %d: plane %d not aligned to its %d-byte elements", i, c, es);
+      same = same && (((uintptr_t)p ^ (uintptr_t)it.out) & 15) == 0;
+    }
+    const int lead = same ? (int)(((uintptr_t)it.out & 15) / es) : -1;
+    const int64_t chunks = ((same ? lead : 0) + it.n + per - 1) / per;
+    table.push_back(msr_dev_item{it.out, it.n, n_blocks, it.first_plane, it.C, it.dtype, lead});
+    n_blocks += (chunks + MSR_BLOCK_CHUNKS - 1) / MSR_BLOCK_CHUNKS;
+  }
+  if (!workspace) VX_FAIL(VX_E_NULL, "vx_one_minus_msr_batched: null workspace");
+  if (ws_bytes < vx_one_minus_msr_batched_workspace_bytes(n_items, n_planes))
+    VX_FAIL(VX_E_WORKSPACE, "vx_one_minus_msr_batched: workspace needs %lld bytes",
+            (long long)vx_one_minus_msr_batched_workspace_bytes(n_items, n_planes));
+  if (!vx_aligned16(workspace)) VX_FAIL(VX_E_ALIGN, "vx_one_minus_msr_batched: workspace not 16-byte aligned");
+  if (table.empty()) return VX_OK;
+  const size_t planes_off = vx_align256((size_t)n_items * sizeof(msr_dev_item));
+  const vx_stage_part parts[2] = {{table.data(), table.size() * sizeof(msr_dev_item), 0},
+                                  {planes, (size_t)n_planes * sizeof(void*), planes_off}};
+  hipStream_t s = (hipStream_t)stream;
+  const int up = vx_staged_upload(g_msr_stage, "vx_one_minus_msr_batched", parts, 2, planes_off + parts[1].bytes, workspace, s);
+  if (up != VX_OK) return up;
+  const int grid = (int)(n_blocks < MSR_MAX_GRID ? n_blocks : MSR_MAX_GRID);
+  hipLaunchKernelGGL(one_minus_msr_batched_kernel, dim3(grid), dim3(MSR_THREADS), 0, s, (const msr_dev_item*)workspace, (int)table.size(),
+                     (const void* const*)((const char*)workspace + planes_off), n_blocks);
+  VX_CHECK_LAUNCH("vx_one_minus_msr_batched");
   return VX_OK;
 }
 

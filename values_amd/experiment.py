@@ -101,6 +101,31 @@ def _read_batches_device(paths, batch, batch_2d=None):
                     yield p, t.transpose(0, 1)
 
 
+def _decoded_shape_dtype(path):
+    """(shape, numpy dtype) of what the readers return for one results file, from the file's header alone"""
+    path = str(path)
+    if _kind(path) == "nifti":
+        import gzip
+        with (gzip.open if path.lower().endswith(".gz") else open)(path, "rb") as f:
+            h = nifti.parse_header(f.read(352), path)
+        return h.shape, np.dtype(h.out_dtype)
+    from .image_io import tiff_parse
+    with open(path, "rb") as f:
+        buf = f.read()
+    lay = tiff_parse(buf, path)
+    return (lay.w, lay.h), np.dtype("float32")
+
+
+def softmax_chunk_size(shapes, dtypes, n_classes: int, chunk: int, budget_bytes: int) -> int:
+    """Images per chunk of the Softmax tree setup: `chunk`, shrunk until the decoded class planes of a chunk of the
+    largest images -- n_classes planes of `shape` and `dtype` each -- stay under budget_bytes; never below one image.
+    Host logic on shapes and dtypes only."""
+    largest = max((int(np.prod(s, dtype=np.int64)) * np.dtype(d).itemsize * int(n_classes) for s, d in zip(shapes, dtypes)),
+                  default=0)
+    fit = int(budget_bytes) // largest if largest > 0 else int(chunk)
+    return max(1, min(int(chunk), fit))
+
+
 class ExperimentVersion:
     def __init__(self, base_path, naming_scheme_version, pred_model, image_ending, unc_ending, unc_types, aggregations,
                  n_reference_segs, second_cycle_path=None, n_classes=2, naming_scheme_pred_model="{pred_model}",
@@ -263,11 +288,48 @@ class DeviceExperimentDataloader(ExperimentDataloader):
     images.load_png_device / load_tiff_device (same constructor, same paths, same axis order as the host getters).  get_reference_segs returns the stacked reference segmentations as one device tensor in the
     file branch; the GTA hooks (values_amd.gta) run in their device forms, any other hook, get_gt_unc_map without a hook
     and the datamodule branch are inherited unchanged.  prefetch() reads a split's files in
-    batches ahead of the getters, under a byte budget."""
+    batches ahead of the getters, under a byte budget.  For a Softmax model the constructor builds pred_entropy/ on the
+    device as well (_setup_pred_entropy_softmax), and get_max_softmax_pred returns a device tensor."""
 
     def __init__(self, exp_version: ExperimentVersion, dataset_split):
         self._cache = {}
         super().__init__(exp_version, dataset_split)
+
+    softmax_chunk = 32              # images per one_minus_msr_batch call of the Softmax tree setup ...
+    softmax_budget_bytes = 1 << 30  # ... shrunk so that a chunk's decoded class planes stay under this (softmax_chunk_size)
+
+    def _prob_paths(self, image_id):
+        return [os.path.join(self.pred_prob_dir, f"{image_id}_01_{str(c + 1).zfill(2)}{self.exp_version.unc_ending}")
+                for c in range(self.exp_version.n_classes)]
+
+    def get_max_softmax_pred(self, image_id: str):
+        """1 - max softmax of one image as a device tensor: the class files read on the device, a batch of one"""
+        from . import uncertainty
+        return uncertainty.one_minus_msr_batch([self._load_many(self._prob_paths(image_id))])[0]
+
+    def _setup_pred_entropy_softmax(self):
+        """pred_entropy/ of a Softmax tree without the host codecs: per chunk of images the C class files of each go
+        through the pipelined readers, one one_minus_msr_batch call reduces the chunk, and results.MapsWriter encodes the
+        maps on the device and writes chunk i while chunk i + 1 is read and reduced.  Same file names and decoded bytes as
+        the host dataloader's; an existing directory is left alone."""
+        from . import results, uncertainty
+        target = self.dataset_path / "pred_entropy"
+        if os.path.isdir(target):
+            return
+        os.makedirs(target)
+        if not self.image_ids:
+            return
+        C, end = self.exp_version.n_classes, self.exp_version.unc_ending
+        first = [_decoded_shape_dtype(self._prob_paths(i)[0]) for i in self.image_ids]
+        B = softmax_chunk_size([s for s, _ in first], [d for _, d in first], C, self.softmax_chunk, self.softmax_budget_bytes)
+        stream = _read_batches_device([p for i in self.image_ids for p in self._prob_paths(i)], C * B)
+        try:
+            with results.MapsWriter() as writer:
+                for part in _chunks(self.image_ids, B):
+                    planes = [[next(stream)[1] for _ in range(C)] for _ in part]
+                    writer.submit([target / f"{i}{end}" for i in part], uncertainty.one_minus_msr_batch(planes))
+        finally:
+            stream.close()
 
     def _load(self, path):
         p = str(path)

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, uncertainty
 from .uncertainty import uncertainty_maps
 
 
@@ -197,9 +197,7 @@ def process_output_2d(logits: Optional[torch.Tensor], ssn: bool = False, probs: 
         a, e = ("aleatoric_uncertainty", "epistemic_uncertainty") if not ssn else ("epistemic_uncertainty", "aleatoric_uncertainty")
         out[a], out[e] = m["expected_entropy"], m["mutual_information"]
     else:  # calculate_one_minus_msr: 1 - max softmax under the key "pred_entropy" (test_3D.py:521-525)
-        msr = torch.empty((B, H, W), dtype=torch.float32, device=probs.device)
-        for b in range(B):
-            _lib.check(lib.vx_one_minus_msr(_lib.ptr(probs[b, 0]), _lib.VX_F32, Cc, H * W, _lib.ptr(msr[b]), _lib.stream_ptr()),
-                       "vx_one_minus_msr")
+        msr = torch.empty((B, H, W), dtype=torch.float32, device=probs.device)   # one launch for the B images of the step
+        uncertainty.one_minus_msr_batch([probs[b, 0] for b in range(B)], out=list(msr.unbind(0)))
         out["pred_entropy"] = msr
     return out

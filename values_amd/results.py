@@ -276,6 +276,147 @@ class ResultsWriter(_devio.PipelinedWriter):
         self._submit(save_dir, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# maps a dataloader writes itself (pred_entropy of a Softmax tree), from the device
+
+class PlannedMap(NamedTuple):
+    """One map file of save_maps_device: its path, "gz" (a gzipped NIfTI), "nii" (a plain one) or "tif", voxel shape and
+    the numpy dtype the file stores."""
+    path: str
+    kind: str
+    shape: tuple
+    dtype: np.dtype
+
+
+def plan_maps(paths, tensors) -> List[PlannedMap]:
+    """What experiment._save_file writes for each (path, map): host logic on endings, shapes and dtypes only."""
+    if len(paths) != len(tensors):
+        raise ValueError(f"save_maps_device: {len(paths)} paths for {len(tensors)} maps")
+    out = []
+    for p, t in zip(paths, tensors):
+        p = os.path.abspath(str(p))
+        low = p.lower()
+        shp, dt = _shape_dtype(t)
+        if low.endswith((".tif", ".tiff")):
+            if len(shp) != 2:
+                raise ValueError(f"save_maps_device: {p}: a TIFF map is 2D, got {tuple(shp)}")
+            out.append(PlannedMap(p, "tif", (shp[1], shp[0]), np.dtype("float32")))   # the file is (H, W): axes swapped back
+        elif low.endswith((".nii.gz", ".nii")):
+            out.append(PlannedMap(p, "gz" if low.endswith(".gz") else "nii", tuple(shp), _file_dtype(dt)))
+        else:
+            raise ValueError(f"save_maps_device: {p}: .nii, .nii.gz, .tif or .tiff expected")
+    return out
+
+
+def _encode_maps(bufs, paths, tensors, header=False, timing=None):
+    """COPY payloads of the NIfTI maps in one vx_nifti_payload launch, one gz.encode_into over the .gz ones, and one copy
+    per kind of file into pinned memory: -> (plan, host uint8 array, spans)"""
+    import torch
+    from . import _lib, gz
+    from .image_io import tiff_f32_parts
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    plan = plan_maps(paths, tensors)
+    vols = [i for i, f in enumerate(plan) if f.kind != "tif"]
+    keep, parts = [], {}        # parts: file -> (region, offset, size[, head, tail]) before the regions are placed
+    members = payload = None
+    gz_used = pay_bytes = 0
+    if vols:
+        items = (_lib.NiftiItem * len(vols))()
+        sizes_in, off = [], 0
+        for it, i in zip(items, vols):
+            f, t = plan[i], _to_device(tensors[i], dev)
+            rev = t.permute(*reversed(range(t.dim())))
+            if 1 < t.dim() <= 3 and rev.is_contiguous() and str(t.dtype).replace("torch.", "") == f.dtype.name:
+                src, X, Y, Z = rev, 1, 1, int(t.numel())   # a reader's [x, y, z] view, x fastest in memory: copied in order
+            else:
+                src, X, Y, Z = _copy_source(t, f.dtype)
+            keep.append(src)
+            it.kind, it.src, it.esize = _lib.VX_NIFTI_COPY, (src.data_ptr() if src.numel() else None), f.dtype.itemsize
+            it.X, it.Y, it.Z, it.dst_off = X, Y, Z, off
+            C.memmove(it.header, nifti.header_bytes(f.shape, f.dtype, header), 352)
+            n = int(lib.vx_nifti_payload_bytes(C.byref(it)))
+            sizes_in.append((off, n))
+            off += (n + 15) // 16 * 16
+        pay_bytes = off
+        payload = bufs.get("payload", off, dev)
+        nws = bufs.get("nifti_ws", int(lib.vx_nifti_workspace_bytes(len(vols))), dev)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
+        if ev:
+            ev[0].record()
+        _lib.check(lib.vx_nifti_payload(items, len(vols), _lib.ptr(payload), payload.numel(), _lib.ptr(nws), nws.numel(),
+                                        _lib.stream_ptr()), "vx_nifti_payload")
+        if ev:
+            ev[1].record()
+        zipped = [k for k, i in enumerate(vols) if plan[i].kind == "gz"]
+        if zipped:
+            slots, goff = [], 0
+            for k in zipped:
+                slots.append(goff)
+                goff += gz.bound(sizes_in[k][1])
+            members = bufs.get("members", goff, dev)
+            sizes = bufs.get("sizes", 8 * len(zipped), dev)[:8 * len(zipped)].view(torch.int64)
+            gws = bufs.get("gzip_ws", gz.workspace_bytes([sizes_in[k][1] for k in zipped]), dev)
+            base = payload.data_ptr()
+            gz.encode_into([(base + sizes_in[k][0], sizes_in[k][1], s,
+                             gz.hints_for(plan[vols[k]].dtype.itemsize, plan[vols[k]].shape)) for k, s in zip(zipped, slots)],
+                           members, sizes, gws)
+            if ev:
+                ev[2].record()
+            host_sizes = sizes.cpu().tolist()      # synchronises the stream
+            if ev:
+                timing["payload_ms"] = timing.get("payload_ms", 0.0) + ev[0].elapsed_time(ev[1])
+                timing["encode_ms"] = timing.get("encode_ms", 0.0) + ev[1].elapsed_time(ev[2])
+                timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(sizes_in[k][1] for k in zipped)
+            gz_used = max(s + n for s, n in zip(slots, host_sizes))
+            for k, s, n in zip(zipped, slots, host_sizes):
+                parts[vols[k]] = ("gz", s, n)
+        for k, i in enumerate(vols):
+            if plan[i].kind == "nii":
+                parts[i] = ("nii", sizes_in[k][0], sizes_in[k][1])
+    flat, toff = [], 0
+    for i, f in enumerate(plan):
+        if f.kind == "tif":
+            m = _to_device(tensors[i], dev).to(torch.float32).transpose(0, 1).contiguous()
+            flat.append(m.reshape(-1))
+            parts[i] = ("tif", toff, 4 * m.numel()) + tiff_f32_parts(int(m.shape[0]), int(m.shape[1]))
+            toff += 4 * m.numel()
+    need_nii = any(f.kind == "nii" for f in plan)
+    base = {"gz": 0, "nii": (gz_used + 15) // 16 * 16}
+    base["tif"] = base["nii"] + (pay_bytes if need_nii else 0)
+    total = base["tif"] + toff
+    host = bufs.get("host", total, dev, pinned=True)
+    if gz_used:
+        host[:gz_used].copy_(members[:gz_used])
+    if need_nii:
+        host[base["nii"]:base["nii"] + pay_bytes].copy_(payload[:pay_bytes])
+    if flat:
+        host[base["tif"]:total].copy_(torch.cat(flat).view(torch.uint8))
+    del keep
+    return plan, host.numpy(), [(base[parts[i][0]] + parts[i][1],) + tuple(parts[i][2:]) for i in range(len(plan))]
+
+
+def save_maps_device(paths, tensors, header=False, _timing=None) -> None:
+    """experiment._save_file for a batch of device maps: path i gets tensors[i], a map indexed [x, y(, z)] as the readers
+    return it.  A .nii.gz / .nii file holds the 352 header bytes and voxel bytes nifti.save writes for the same array (a
+    float64 map stays float64), a .tif file is byte-identical to the host writer's (float32, axes swapped back).  One
+    vx_nifti_payload launch (COPY items), one gz.encode_into and one device -> host copy into reused pinned memory; the
+    host writes the files before the call returns.  MapsWriter is the pipelined form."""
+    _devio.save_once("", (), _encode_maps, list(paths), list(tensors), header, _timing)
+
+
+class MapsWriter(_devio.PipelinedWriter):
+    """Pipelined save_maps_device: submit() encodes a batch of maps on the GPU and hands its files to a small thread pool,
+    so the files of batch i are written while batch i + 1 is read and reduced.  close() (or leaving the `with` block)
+    waits and re-raises the first write error."""
+
+    _encode = staticmethod(_encode_maps)
+
+    def submit(self, paths, tensors, header=False) -> None:
+        self._submit("", list(paths), list(tensors), header)
+
+
 def results_dir(root_dir: str, exp_name: str, version, test_split: str = "id") -> str:
     return os.path.join(root_dir, exp_name, "test_results", str(version), test_split)  # data_carrier_3D.py:40-42
 

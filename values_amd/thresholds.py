@@ -41,18 +41,7 @@ def count_nonzero(mask: torch.Tensor) -> int:
     return count_nonzero_batch([mask])[0]
 
 
-def _dense_block(t: torch.Tensor) -> torch.Tensor:
-    """`t` itself when its elements fill one block of memory without gaps or overlap -- a contiguous tensor or a permuted
-    view of one, such as the transposed views the 2D readers return: data_ptr() is then the block's first element, and
-    neither a count nor an order statistic depends on the order.  Anything else: a contiguous copy."""
-    if t.is_contiguous():
-        return t
-    expect = 1
-    for size, stride in sorted(((n, s) for n, s in zip(t.shape, t.stride()) if n != 1), key=lambda d: d[1]):
-        if stride != expect:
-            return t.contiguous()
-        expect *= size
-    return t
+_dense_block = _lib.dense_block
 
 
 _COUNT_KINDS = {torch.bool: _lib.VX_COUNT_B1, torch.uint8: _lib.VX_COUNT_B1, torch.int8: _lib.VX_COUNT_B1,

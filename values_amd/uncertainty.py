@@ -7,7 +7,7 @@ test_2D.py:16-22): same names, arguments, returned keys, dtypes and NaN-skip beh
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 
@@ -138,3 +138,89 @@ def calculate_one_minus_msr(softmax_pred: torch.Tensor) -> Dict[str, torch.Tenso
                               _lib.ptr(out), _lib.stream_ptr())
     _lib.check(rc, "vx_one_minus_msr")
     return {"pred_entropy": out.to(softmax_pred.device)}
+
+
+def msr_tables(entries):
+    """The two host tables of one vx_one_minus_msr_batched call.  entries: per image (out pointer, n, dtype code, [plane
+    pointers]) -> (MsrItem array, plane pointer array, number of planes): the images' planes follow each other in the plane
+    table, `first_plane` is where an image's begin.  Host logic only."""
+    import ctypes as C
+    items = (_lib.MsrItem * len(entries))()
+    flat = []
+    for it, (out, n, dtype, planes) in zip(items, entries):
+        it.out, it.n, it.first_plane, it.C, it.dtype, it.reserved = out, int(n), len(flat), len(planes), int(dtype), 0
+        flat += list(planes)
+    return items, (C.c_void_p * max(len(flat), 1))(*flat), len(flat)
+
+
+def _same_order(a, b) -> bool:
+    """equal shapes and the same memory order: equal strides along every axis that has more than one element"""
+    return a.shape == b.shape and (a.numel() == 0 or all(sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()) if n > 1))
+
+
+def _planes_of(image, i):
+    """One element of one_minus_msr_batch's list -> (plane 0, the C plane pointers, what keeps them alive): planes of equal
+    shape, dtype and memory order, each a dense block."""
+    if isinstance(image, torch.Tensor):
+        if image.dim() < 1 or image.shape[0] < 1:
+            raise ValueError(f"one_minus_msr_batch: image {i}: (C, *spatial) with C >= 1 expected, got {tuple(image.shape)}")
+        if not image.is_cuda:
+            raise ValueError(f"one_minus_msr_batch: image {i}: device tensors only")
+        if image.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"one_minus_msr_batch: image {i}: float32 or float64 expected, got {image.dtype}")
+        image = image.detach()
+        if _lib.dense_block(image[0]) is not image[0]:
+            image = image.contiguous()
+        p0 = image[0]            # the planes of one tensor share their strides: plane c lies stride(0) elements after c - 1
+        step = image.stride(0) * image.element_size()
+        base = image.data_ptr()
+        return p0, [base + c * step if p0.numel() else None for c in range(image.shape[0])], image
+    planes = list(image)
+    if not planes:
+        raise ValueError(f"one_minus_msr_batch: image {i}: no planes")
+    p0 = planes[0]
+    for p in planes:
+        if not isinstance(p, torch.Tensor) or not p.is_cuda:
+            raise ValueError(f"one_minus_msr_batch: image {i}: device tensors only")
+        if p.dtype != p0.dtype or p.shape != p0.shape or p.device != p0.device:
+            raise ValueError(f"one_minus_msr_batch: image {i}: its planes differ in shape, dtype or device")
+    if p0.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"one_minus_msr_batch: image {i}: float32 or float64 planes expected, got {p0.dtype}")
+    planes = [p.detach() for p in planes]
+    if any(not _same_order(p, planes[0]) or _lib.dense_block(p) is not p for p in planes):
+        planes = [p.contiguous() for p in planes]
+    return planes[0], [p.data_ptr() if p.numel() else None for p in planes], planes
+
+
+def one_minus_msr_batch(images, out=None) -> List[torch.Tensor]:
+    """calculate_one_minus_msr for a batch of images in ONE vx_one_minus_msr_batched call: [1 - max over the C planes].
+    Each element of `images` is a (C, *spatial) device tensor or a sequence of C device tensors of equal shape, dtype
+    (float32 or float64) and strides -- what the readers return for an image's C probability files; planes that are not
+    dense blocks are made contiguous.  Each result is a new tensor in its planes' dtype, shape and memory order (`out`: a
+    list of such tensors to write into instead).  Images may differ in shape, C and dtype.  An empty list: [] without a
+    call."""
+    images = list(images)
+    if not images:
+        return []
+    _lib.require_gpu()
+    lib = _lib.load()
+    parts = [_planes_of(im, i) for i, im in enumerate(images)]
+    dev = parts[0][0].device
+    if out is None:
+        outs = [torch.empty_strided(p0.shape, p0.stride(), dtype=p0.dtype, device=p0.device) for p0, _, _ in parts]
+    else:
+        outs = list(out)
+        if len(outs) != len(images):
+            raise ValueError(f"one_minus_msr_batch: {len(outs)} outputs for {len(images)} images")
+        for i, (o, (p0, _, _)) in enumerate(zip(outs, parts)):
+            if not _same_order(o, p0) or o.dtype != p0.dtype or o.device != p0.device:
+                raise ValueError(f"one_minus_msr_batch: out[{i}] must have its planes' shape, dtype, strides and device")
+    with torch.cuda.device(dev):
+        for i0 in range(0, len(images), _lib.VX_MSR_MAX_ITEMS):
+            entries = [(o.data_ptr() if o.numel() else None, o.numel(), _lib.VX_F64 if o.dtype == torch.float64 else _lib.VX_F32, ptrs)
+                       for o, (_, ptrs, _) in zip(outs[i0:i0 + _lib.VX_MSR_MAX_ITEMS], parts[i0:i0 + _lib.VX_MSR_MAX_ITEMS])]
+            items, table, n_planes = msr_tables(entries)
+            ws = _lib.workspace(dev, int(lib.vx_one_minus_msr_batched_workspace_bytes(len(entries), n_planes)))
+            _lib.check(lib.vx_one_minus_msr_batched(items, len(entries), table, n_planes, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                       "vx_one_minus_msr_batched")
+    return outs
