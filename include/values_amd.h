@@ -1020,6 +1020,56 @@ int vx_png_unfilter(const vx_png_unfilter_item* items /* host array */, int n_it
 int vx_rgb_to_trainid(const uint8_t* rgb, int64_t n, const uint32_t* table /* device */, int n_table, int default_id,
                       uint8_t* out, vx_stream_t stream);
 
+/* LZW-compressed float32 TIFF maps (Compression 5; values_amd/images.py: load_tiff_device) -- what libtiff writes for a
+ * float32 image: cv2.imwrite, PIL, GDAL, ImageJ.
+ *
+ * vx_tiff_lzw: decodes each item's LZW strip (src, src_n: device; TIFF 6.0 section 13: codes MSB first, 9 to 12 bits,
+ *   ClearCode 256, EndOfInformation 257, early change; with a full table and no ClearCode the decode goes on at 12 bits
+ *   without new entries) into dst[dst_off, dst_off + dst_cap).  A strip's first code must be ClearCode.  An item ends
+ *   with VX_LZW_OK when its window is full, whatever follows (a string reaching beyond the window is cut there), and at
+ *   EndOfInformation, where a window not yet full shows in out_sizes[i].  Statuses are per item: out_status[i] (device)
+ *   is VX_LZW_OK or one of the codes below, out_sizes[i] (device) the bytes written into the item's window, also on
+ *   error.  The return value is reserved for argument errors (refused before any launch) and hipError_t.  No input reads
+ *   outside [src, src + src_n) or writes outside the item's window, and every loop of the decoder makes progress on input
+ *   or output.  The windows must not overlap each other or any source.  workspace: vx_tiff_lzw_workspace_bytes(n_items)
+ *   bytes, 16-byte aligned.  Like vx_inflate it uploads its table and synchronises the stream before it launches: not
+ *   capturable into a hipGraph.
+ * vx_tiff_unpredict: undoes the predictor of tag 317 on float32 rows of a little-endian file.  Per item, `rows` rows of W
+ *   samples at src (device, 4 * rows * W bytes) go to dst (the same size); rows are independent.
+ *   predictor 2  horizontal differencing on 32-bit words: within a row word[i] += word[i - 1] mod 2^32;
+ *   predictor 3  floating point (libtiff's fpAcc): within a row byte[i] += byte[i - 1] mod 256 over all 4 W bytes, then
+ *                sample x is put together from the row's four byte planes, the most significant bytes first (plane 0
+ *                holds W most significant bytes, plane 3 the least significant).
+ *   Any W >= 1 and any alignment of src and dst.  src == dst is allowed for predictor 2 only; src and dst may not overlap
+ *   otherwise.  out_status[i] (device) is set to VX_LZW_OK: no input makes an item fail.  Argument errors (a null table or
+ *   pointer, rows or W < 1, a predictor other than 2 / 3, a workspace below vx_tiff_unpredict_workspace_bytes(n_items)) are
+ *   refused before any launch.  Uploads its table and synchronises the stream, as vx_tiff_lzw. */
+enum {
+  VX_LZW_OK = 0,
+  VX_LZW_TRUNCATED = 1,   /* the input ends before EndOfInformation or a full window */
+  VX_LZW_BAD_CODE = 2     /* a code above the next free entry, or a first code that is not ClearCode (the LSB-first variant) */
+};
+typedef struct vx_tiff_lzw_item {
+  const uint8_t* src;
+  int64_t src_n;
+  int64_t dst_off;
+  int64_t dst_cap;
+} vx_tiff_lzw_item;
+int64_t vx_tiff_lzw_workspace_bytes(int n_items);
+int vx_tiff_lzw(const vx_tiff_lzw_item* items /* host array */, int n_items, uint8_t* dst, int64_t dst_n,
+                int64_t* out_sizes /* device */, int32_t* out_status /* device */, void* workspace,
+                int64_t workspace_bytes, vx_stream_t stream);
+typedef struct vx_tiff_unpredict_item {
+  const uint8_t* src;
+  uint8_t* dst;
+  int32_t rows, W;
+  int32_t predictor;
+  int32_t pad;
+} vx_tiff_unpredict_item;
+int64_t vx_tiff_unpredict_workspace_bytes(int n_items);
+int vx_tiff_unpredict(const vx_tiff_unpredict_item* items /* host array */, int n_items, int32_t* out_status /* device */,
+                      void* workspace, int64_t workspace_bytes, vx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,20 @@ VX_PNG_OK, VX_PNG_BAD_FILTER, VX_PNG_BAD_SIZE = 0, 1, 2
 PNG_STATUS = ("ok", "filter byte above 4", "stream size is not H (1 + W bpp)")
 
 
+class TiffLzwItem(C.Structure):
+    """vx_tiff_lzw_item: one LZW strip (device src, src_n bytes) and its output window dst[dst_off, +dst_cap)."""
+    _fields_ = [("src", _p), ("src_n", _i64), ("dst_off", _i64), ("dst_cap", _i64)]
+
+
+class TiffUnpredictItem(C.Structure):
+    """vx_tiff_unpredict_item: `rows` float32 rows of W samples (device src -> dst) whose predictor (2 / 3) is undone."""
+    _fields_ = [("src", _p), ("dst", _p), ("rows", _i32), ("W", _i32), ("predictor", _i32), ("pad", _i32)]
+
+
+VX_LZW_OK, VX_LZW_TRUNCATED, VX_LZW_BAD_CODE = 0, 1, 2
+LZW_STATUS = ("ok", "truncated", "bad code")
+
+
 VX_AGG_IMAGE, VX_AGG_THRESHOLD, VX_AGG_PATCH = 0, 1, 2
 VX_AGG_MAX_SPECS, VX_AGG_MAX_ITEMS = 8, 4096
 
@@ -340,6 +354,10 @@ SIGNATURES = {
     "vx_png_unfilter_workspace_bytes": (_i64, [_i]),
     "vx_png_unfilter": (_i, [C.POINTER(PngUnfilterItem), _i, _p, _p, _i64, _p]),
     "vx_rgb_to_trainid": (_i, [_p, _i64, _p, _i, _i, _p, _p]),
+    "vx_tiff_lzw_workspace_bytes": (_i64, [_i]),
+    "vx_tiff_lzw": (_i, [C.POINTER(TiffLzwItem), _i, _p, _i64, _p, _p, _p, _i64, _p]),
+    "vx_tiff_unpredict_workspace_bytes": (_i64, [_i]),
+    "vx_tiff_unpredict": (_i, [C.POINTER(TiffUnpredictItem), _i, _p, _p, _i64, _p]),
 }
 
 _lib = None

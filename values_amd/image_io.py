@@ -134,9 +134,10 @@ def write_tiff_f32(path, img: np.ndarray) -> None:
 
 class TiffLayout:
     """What tiff_parse reads from a single-channel float32 strip TIFF: w, h, endian ("<" / ">"), deflate (the strips are
-    zlib streams) and strips: [(first row, rows, offset, size)] in row order."""
+    zlib streams), lzw (the strips are LZW streams), predictor (tag 317: 1, or 2 / 3 with lzw) and strips: [(first row,
+    rows, offset, size)] in row order."""
 
-    __slots__ = ("w", "h", "endian", "deflate", "strips")
+    __slots__ = ("w", "h", "endian", "deflate", "lzw", "predictor", "strips")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -145,9 +146,10 @@ class TiffLayout:
 
 def tiff_parse(buf, name: str = "") -> TiffLayout:
     """The layout of a single-channel 32-bit float strip TIFF held in `buf` (either byte order; any RowsPerStrip;
-    Compression 1 = none or 8 / 32946 = Deflate, Predictor 1).  Shared by read_tiff_f32 and the device reader
-    (values_amd.images.load_tiff_device).  LZW (Compression 5, OpenCV's default) and the floating-point predictor
-    (Predictor 3) are not decoded: ValueError naming the tag and its value."""
+    Compression 1 = none or 8 / 32946 = Deflate with Predictor 1; Compression 5 = LZW -- what libtiff writes: cv2.imwrite,
+    PIL, GDAL -- with Predictor 1, 2 = horizontal differencing or 3 = floating point).  Shared by read_tiff_f32 and the
+    device reader (values_amd.images.load_tiff_device).  A predictor with Deflate or uncompressed strips is not decoded:
+    ValueError naming the tag and its value."""
     pre = f"{name}: " if name else ""
     bo = {b"II": "<", b"MM": ">"}.get(bytes(buf[:2]))
     if bo is None or len(buf) < 8 or struct.unpack(bo + "H", buf[2:4])[0] != 42:
@@ -170,10 +172,11 @@ def tiff_parse(buf, name: str = "") -> TiffLayout:
         tags[tag] = vals
     w, h = tags[256][0], tags[257][0]
     comp, pred = tags.get(259, (1,))[0], tags.get(317, (1,))[0]
-    if comp not in (1, 8, 32946):
-        what = " (LZW)" if comp == 5 else ""
-        raise ValueError(f"{pre}read_tiff_f32: Compression (tag 259) = {comp}{what}: only 1 (none) and 8 / 32946 (Deflate)")
-    if pred != 1:
+    if comp not in (1, 5, 8, 32946):
+        raise ValueError(f"{pre}read_tiff_f32: Compression (tag 259) = {comp}: only 1 (none), 5 (LZW) and 8 / 32946 (Deflate)")
+    if comp == 5 and pred not in (1, 2, 3):
+        raise ValueError(f"{pre}read_tiff_f32: Predictor (tag 317) = {pred}: only 1 (none), 2 and 3 with LZW")
+    if comp != 5 and pred != 1:
         what = " (floating point)" if pred == 3 else ""
         raise ValueError(f"{pre}read_tiff_f32: Predictor (tag 317) = {pred}{what}: only 1 (none)")
     if tags.get(258, (0,))[0] != 32 or tags.get(339, (1,))[0] != 3 or tags.get(277, (1,))[0] != 1:
@@ -187,23 +190,94 @@ def tiff_parse(buf, name: str = "") -> TiffLayout:
         if o + c > len(buf):
             raise ValueError(f"{pre}read_tiff_f32: strip {k} [{o}, +{c}) beyond the file's {len(buf)} bytes")
         strips.append((k * rps, min(rps, h - k * rps), o, c))
-    return TiffLayout(w=w, h=h, endian=bo, deflate=comp != 1, strips=strips)
+    return TiffLayout(w=w, h=h, endian=bo, deflate=comp in (8, 32946), lzw=comp == 5, predictor=pred, strips=strips)
+
+
+def lzw_decode(data, want: int):
+    """The first `want` bytes a TIFF LZW strip (TIFF 6.0 section 13: codes MSB first, 9 to 12 bits, ClearCode 256,
+    EndOfInformation 257, early change) decodes to -> (bytes, None) or (bytes so far, what went wrong).  As libtiff's
+    decoder: the strip ends when `want` bytes are there, whatever follows, or at EndOfInformation; with a full table and
+    no ClearCode it goes on at 12 bits without new entries.  The first code must be ClearCode (the old LSB-first
+    variant is not decoded)."""
+    out = bytearray()
+    table = None           # strings of the entries from 258 on
+    prev = None
+    acc = nacc = 0
+    width, i, n, k = 9, 0, len(data), 0
+    while len(out) < want:
+        while nacc < width:
+            if i >= n:
+                return bytes(out), "the strip ends before EndOfInformation or its last row"
+            acc = ((acc << 8) | data[i]) & 0xFFFFFFFF
+            i += 1
+            nacc += 8
+        nacc -= width
+        code = (acc >> nacc) & ((1 << width) - 1)
+        if code == 256:
+            table, prev, width, k = [], None, 9, 0
+            continue
+        if table is None:
+            return bytes(out), f"the first code is {code}, not ClearCode (256)"
+        if code == 257:
+            break
+        if code < 256:
+            cur = bytes((code,))
+        elif prev is not None and code - 258 < len(table):
+            cur = table[code - 258]
+        elif prev is not None and code - 258 == len(table):
+            cur = prev + prev[:1]          # KwKwK
+        else:
+            return bytes(out), f"code {code} above the next free entry ({258 + len(table)})"
+        out += cur
+        if prev is not None and len(table) < 4096 - 258:
+            table.append(prev + cur[:1])
+        prev = cur
+        # the next free entry after this code: one entry per code after the first since the ClearCode
+        k += 1
+        nfree = 258 + k - 1
+        width = 9 + (nfree >= 511) + (nfree >= 1023) + (nfree >= 2047)
+    return bytes(out[:want]), None
+
+
+def _unpredict(rows: np.ndarray, predictor: int, endian: str) -> np.ndarray:
+    """rows: (n, 4 w) uint8, the decoded bytes of n rows -> (n, w) float32 with the predictor of tag 317 undone"""
+    n, w = rows.shape[0], rows.shape[1] // 4
+    if predictor == 2:       # horizontal differencing on the file's 32-bit words
+        words = rows.view(endian + "u4").astype(np.uint32)
+        return np.cumsum(words, axis=1, dtype=np.uint32).view(np.float32)
+    # 3, libtiff's fpAcc: a running byte sum over the row, then sample x from the four byte planes, plane 0 the most
+    # significant bytes -- in either byte order of the file
+    acc = np.cumsum(rows, axis=1, dtype=np.uint8).reshape(n, 4, w)
+    return np.ascontiguousarray(acc.transpose(0, 2, 1)).view(">f4").reshape(n, w).astype(np.float32)
 
 
 def tiff_decode(buf, t: TiffLayout, name: str = "") -> np.ndarray:
-    """The (h, w) float32 map of a file held in `buf` whose layout tiff_parse read."""
+    """The (h, w) float32 map of a file held in `buf` whose layout tiff_parse read.  LZW strips are decoded code by code
+    in Python and the predictor undone with numpy: a reference reader like read_png's loop, correct and not fast (the
+    fast path is values_amd.images.load_tiff_device)."""
     out = np.empty((t.h, t.w), dtype=np.float32)
     for r0, rows, o, c in t.strips:
-        data = zlib.decompress(buf[o:o + c]) if t.deflate else buf[o:o + c]
-        if len(data) < 4 * rows * t.w:
-            raise ValueError(f"{name}: read_tiff_f32: strip at row {r0} holds {len(data)} bytes, {4 * rows * t.w} expected")
+        need = 4 * rows * t.w
+        if t.lzw:
+            data, err = lzw_decode(bytes(buf[o:o + c]), need)
+            if err is None and len(data) < need:
+                err = f"the strip holds {len(data)} bytes, {need} expected"
+            if err is not None:
+                raise ValueError(f"{name}: read_tiff_f32: Compression (tag 259) = 5 (LZW): strip at row {r0}: {err}")
+            if t.predictor != 1:
+                out[r0:r0 + rows] = _unpredict(np.frombuffer(data, np.uint8).reshape(rows, 4 * t.w), t.predictor, t.endian)
+                continue
+        else:
+            data = zlib.decompress(buf[o:o + c]) if t.deflate else buf[o:o + c]
+        if len(data) < need:
+            raise ValueError(f"{name}: read_tiff_f32: strip at row {r0} holds {len(data)} bytes, {need} expected")
         out[r0:r0 + rows] = np.frombuffer(data, dtype=t.endian + "f4", count=rows * t.w).reshape(rows, t.w)
     return out
 
 
 def read_tiff_f32(path) -> np.ndarray:
     """Reads what write_tiff_f32 writes and any single-channel float32 strip TIFF tiff_parse accepts: either byte order,
-    several strips of any RowsPerStrip, uncompressed or Deflate without predictor."""
+    several strips of any RowsPerStrip, uncompressed or Deflate without predictor, LZW with predictor 1, 2 or 3."""
     with open(path, "rb") as f:
         buf = f.read()
     return tiff_decode(buf, tiff_parse(buf, str(path)), str(path))

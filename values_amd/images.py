@@ -5,8 +5,11 @@ image_io.read_png / read_tiff_f32 read) as device tensors -- the 2D counterpart 
            buffer and uploaded in one copy; one vx_inflate call (zlib) for the batch, then one vx_png_unfilter call
            reconstructs every image's scanlines into its own tensor.
     TIFF   tiff_parse on the host; every Deflate strip is one vx_inflate item that decodes straight into its rows of
-           the map, an uncompressed strip is copied into place.  The maps of a batch are views of one device buffer.
-           A big-endian file is decoded on the host and uploaded.
+           the map, an uncompressed strip is copied into place.  Every LZW strip (what libtiff writes: cv2.imwrite, PIL,
+           GDAL) is one vx_tiff_lzw item: with predictor 1 it decodes straight into its rows of the map, with predictor
+           2 or 3 into a scratch area of the same layout, and one vx_tiff_unpredict call undoes the predictor of every
+           such file into its map.  The maps of a batch are views of one device buffer.  A big-endian file is decoded
+           on the host and uploaded.
 
 The arrays are the ones the host readers return: (H, W) or (H, W, 3 | 4) uint8, (H, W) float32.
 """
@@ -89,6 +92,47 @@ def png_unfilter(entries, device):
     return status.cpu().tolist()
 
 
+def lzw_into(items, device, dst):
+    """items: (device pointer, src_n, dst_off, capacity) -> (sizes, statuses), host lists: one vx_tiff_lzw call, item i
+    decoded into dst[dst_off:dst_off + capacity] (dst: a device uint8 tensor; the windows do not overlap)."""
+    import torch
+    if not items:
+        return [], []
+    lib = _lib.load()
+    arr = (_lib.TiffLzwItem * len(items))()
+    for it, (ptr, n, off, cap) in zip(arr, items):
+        it.src, it.src_n, it.dst_off, it.dst_cap = ptr, int(n), int(off), int(cap)
+    res = torch.empty(len(items) * 3, dtype=torch.int32, device=device)   # [sizes (int64) | statuses]
+    sizes = res[:2 * len(items)].view(torch.int64)
+    status = res[2 * len(items):]
+    ws = torch.empty(int(lib.vx_tiff_lzw_workspace_bytes(len(items))), dtype=torch.uint8, device=device)
+    _lib.check(lib.vx_tiff_lzw(arr, len(items), _lib.ptr(dst), dst.numel(), _lib.ptr(sizes), _lib.ptr(status),
+                               _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw")
+    host = res.cpu()
+    return host[:2 * len(items)].view(torch.int64).tolist(), host[2 * len(items):].tolist()
+
+
+def tiff_unpredict(entries, device):
+    """entries: (src pointer, dst pointer, rows, W, predictor) -> the items' statuses (host list): one vx_tiff_unpredict
+    call over float32 rows of little-endian files."""
+    import torch
+    if not entries:
+        return []
+    lib = _lib.load()
+    arr = (_lib.TiffUnpredictItem * len(entries))()
+    for it, (src, dst, rows, w, pred) in zip(arr, entries):
+        it.src, it.dst, it.rows, it.W, it.predictor = src, dst, int(rows), int(w), int(pred)
+    status = torch.empty(len(entries), dtype=torch.int32, device=device)
+    ws = torch.empty(int(lib.vx_tiff_unpredict_workspace_bytes(len(entries))), dtype=torch.uint8, device=device)
+    _lib.check(lib.vx_tiff_unpredict(arr, len(entries), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "vx_tiff_unpredict")
+    return status.cpu().tolist()
+
+
+def lzw_status_name(st: int) -> str:
+    return _lib.LZW_STATUS[st] if 0 <= st < len(_lib.LZW_STATUS) else f"status {st}"
+
+
 def _decode_png(names, raws, device, staging, timing=None):
     import torch
     from .gz import inflate_into, status_name
@@ -134,18 +178,21 @@ def _decode_tiff(names, raws, device, staging, timing=None):
     from .gz import _align, inflate_into, status_name
     lay = [tiff_parse(r, str(nm)) for nm, r in zip(names, raws)]
     on_dev = [i for i, t in enumerate(lay) if t.endian == "<"]
-    # the maps of the batch: one buffer, every map at a 256-byte boundary
+    # the maps of the batch: one buffer, every map at a 256-byte boundary; behind them, where a file has a predictor,
+    # a scratch area of the same layout for the strips as they decode
     moffs, off = {}, 0
     for i in on_dev:
         moffs[i] = off
         off += _align(max(4 * lay[i].h * lay[i].w, 1))
-    maps = torch.empty(max(off, 1), dtype=torch.uint8, device=device)
+    predicted = [i for i in on_dev if lay[i].lzw and lay[i].predictor != 1]
+    maps = torch.empty(max(off * (2 if predicted else 1), 1), dtype=torch.uint8, device=device)
     strips = [(i, s) for i in on_dev for s in lay[i].strips]
     src, soffs, sizes = staging.upload([(raws[i], [(s[2], s[3])]) for i, s in strips], device)
-    ev = _events(timing)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing is not None else None
     if ev:
         ev[0].record()
     items, at, who = [], [], []
+    litems, lwho = [], []
     for (i, (r0, rows, _, _)), so, n in zip(strips, soffs, sizes):
         w = lay[i].w
         d0, nb = moffs[i] + 4 * r0 * w, 4 * rows * w
@@ -153,6 +200,9 @@ def _decode_tiff(names, raws, device, staging, timing=None):
             items.append((C.c_void_p(src.data_ptr() + so) if n else None, n, _lib.VX_INFLATE_ZLIB, nb))
             at.append(d0)
             who.append((i, r0, nb))
+        elif lay[i].lzw:
+            litems.append((C.c_void_p(src.data_ptr() + so) if n else None, n, d0 + (off if lay[i].predictor != 1 else 0), nb))
+            lwho.append((i, r0, nb))
         else:
             if n < nb:
                 raise ValueError(f"{names[i]}: strip at row {r0} holds {n} bytes, {nb} expected")
@@ -164,8 +214,23 @@ def _decode_tiff(names, raws, device, staging, timing=None):
                 raise _lib.VxError(f"{names[i]}: strip at row {r0}: {status_name(s)} (status {s}, {n} of {nb} bytes decoded)")
     if ev:
         ev[1].record()
-        ev[1].synchronize()
+    if litems:
+        dn, st = lzw_into(litems, device, maps)
+        for (i, r0, nb), s, n in zip(lwho, st, dn):
+            if s != 0 or n != nb:
+                raise _lib.VxError(f"{names[i]}: strip at row {r0}: LZW: {lzw_status_name(s)} (status {s}, {n} of {nb} bytes decoded)")
+    if ev:
+        ev[2].record()
+    if predicted:
+        base = maps.data_ptr()
+        tiff_unpredict([(C.c_void_p(base + off + moffs[i]), C.c_void_p(base + moffs[i]), lay[i].h, lay[i].w, lay[i].predictor)
+                        for i in predicted if lay[i].h * lay[i].w], device)
+    if ev:
+        ev[3].record()
+        ev[3].synchronize()
         timing["inflate_ms"] = timing.get("inflate_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timing["lzw_ms"] = timing.get("lzw_ms", 0.0) + ev[1].elapsed_time(ev[2])
+        timing["unpredict_ms"] = timing.get("unpredict_ms", 0.0) + ev[2].elapsed_time(ev[3])
         timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(4 * t.h * t.w for t in lay)
     outs = []
     for i, t in enumerate(lay):
@@ -224,7 +289,9 @@ def load_png_device(paths, device=None, _timing=None):
 
 def load_tiff_device(paths, device=None, _timing=None):
     """-> [float32 device tensor (H, W)] for a batch of single-channel float32 strip TIFF files: the arrays
-    image_io.read_tiff_f32 returns.  The tensors of a batch are views of one device buffer."""
+    image_io.read_tiff_f32 returns (uncompressed, Deflate or LZW strips; LZW with predictor 1, 2 or 3).  The tensors of a
+    batch are views of one device buffer.  A strip that does not decode raises VxError naming the file, the strip's
+    first row, the status and the bytes decoded of the bytes expected."""
     return _load(paths, device, _timing, "tiff")
 
 
