@@ -12,21 +12,13 @@
 #include <vector>
 
 #include "../values_amd/csrc/inflate_core.h"
+#include "../values_amd/csrc/stream_items.h"
 
 using namespace vxinf;
 
 namespace {
 
-struct HostSrc {
-  const uint8_t* p;
-  int64_t n;
-  uint32_t u32(int64_t pos) const {
-    uint32_t v = 0;
-    for (int k = 0; k < 4; ++k)
-      if (pos + k < n) v |= (uint32_t)p[pos + k] << (8 * k);
-    return v;
-  }
-};
+using HostSrc = vxsi::Bytes;   // the clamped loads the device decoder falls back to outside its window
 
 uint32_t crc32_of(const uint8_t* p, int64_t n) {
   uint32_t c = 0xFFFFFFFFu;

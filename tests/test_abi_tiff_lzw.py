@@ -72,6 +72,7 @@ def test_argument_errors_are_refused_without_a_gpu(lib):
     for rc in refused:
         assert rc < 0, (rc, lib.vx_last_error_string())
     assert b"overlaps" in lib.vx_last_error_string()
+    assert lzw([(dummy, 10, 2**63 - 51, 100)]) == -2                         # dst_off + dst_cap overflows int64
 
     def unp(items, n=None, status=dummy, ws=dummy, ws_n=big, table=True):
         arr = (_lib.TiffUnpredictItem * max(len(items), 1))()

@@ -68,7 +68,9 @@ def test_inflate_refusals(lib):
     assert call() == -2                              # overlapping windows
     it[1].dst_off = -5
     assert call() == -2
-    it[1].dst_off = 1000
+    it[1].dst_off, it[1].dst_cap = 2**63 - 51, 100
+    assert call() == -2                              # dst_off + dst_cap overflows int64: still a window beyond dst
+    it[1].dst_off, it[1].dst_cap = 1000, 1000
     it[0].src_n = -1
     assert call() == -2
     it[0].src_n = 100

@@ -12,20 +12,17 @@
 //       dst: the staging buffer is flushed to dst (the item's window) with lane-parallel stores followed by
 //       __syncthreads(), whose workgroup release / acquire waits for the stores before any later read of them.
 //     Input: a 2 KiB window of the compressed bytes in LDS, refilled by the wave (clamped loads) when the reader is
-//       less than 1 KiB from its end; a read outside the window falls back to clamped global loads.
+//       less than 1 KiB from its end; a read outside the window falls back to clamped global loads (stream_items.h,
+//       which also has the item loop and the launcher's window checks, shared with tiff_lzw.hip).
 //     Stored blocks: a lane-parallel copy from the source to dst.
 //     Checks: after each member, a second pass over its decoded bytes: the CRC-32 (lane slices joined with
 //       crc_join_block) or the Adler-32 (lane slices joined with adler_combine), checksum.h.
 // LDS per wave: tables 3.6 KiB + window 2 KiB + staging 4 KiB + checksum joins 0.5 KiB (about 10 KiB): 16 waves per CU.
 //
 // Every store in this file is a plain C++ store of a vector register.
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-
 #include "checksum.h"
 #include "inflate_core.h"
+#include "stream_items.h"
 
 namespace {
 
@@ -37,15 +34,6 @@ constexpr int IF_WIN = 2048;     // input window bytes
 constexpr int IF_AHEAD = 1024;   // refill when fewer bytes than this lie ahead of the reader in the window
 constexpr int IF_WAVES_PER_CU = 16;
 
-struct InfItemDev {
-  const uint8_t* src;
-  int64_t src_n;
-  int64_t dst_off;
-  int64_t dst_cap;
-  int32_t format;
-  int32_t index;   // the item's place in the caller's table (out_sizes / out_status)
-};
-
 struct InfShared {
   uint32_t win[IF_WIN / 4];
   Tables t;
@@ -54,41 +42,11 @@ struct InfShared {
   uint32_t cklen[IF_LANES];
 };
 
-// the reader's byte source: the LDS window, else clamped global loads (never outside [g, g + n))
-struct DevSrc {
-  const uint32_t* win;
-  int64_t wbase;
-  const uint8_t* g;
-  int64_t n;
-  __device__ uint32_t u32(int64_t pos) const {
-    if (pos >= wbase && pos + 4 <= wbase + IF_WIN) return win[(pos - wbase) >> 2];
-    uint32_t v = 0;
-    for (int k = 0; k < 4; ++k)
-      if (pos + k < n) v |= (uint32_t)g[pos + k] << (8 * k);
-    return v;
-  }
-};
+using DevSrc = vxsi::WinSrc<IF_WIN>;   // the reader's byte source (stream_items.h)
+using vxsi::WinItem;                   // spare: the format
 
-// load the window at base (a multiple of 4), zeros beyond n
-__device__ void win_load(InfShared& S, DevSrc& s, int64_t base) {
-  __syncthreads();   // every lane is done with the old window
-  s.wbase = base;
-  const bool al = ((uintptr_t)(s.g + base) & 3) == 0;
-  for (int w = threadIdx.x; w < IF_WIN / 4; w += IF_LANES) {
-    const int64_t p = base + 4 * w;
-    uint32_t v = 0;
-    if (al && p + 4 <= s.n) {
-      v = *reinterpret_cast<const uint32_t*>(s.g + p);
-    } else {
-      for (int k = 0; k < 4; ++k)
-        if (p + k < s.n) v |= (uint32_t)s.g[p + k] << (8 * k);
-    }
-    S.win[w] = v;
-  }
-  __syncthreads();
-}
 __device__ __forceinline__ void win_ensure(InfShared& S, DevSrc& s, const Bits& b) {
-  if (b.pos < s.wbase || b.pos + IF_AHEAD > s.wbase + IF_WIN) win_load(S, s, b.pos);
+  if (s.stale(b.pos, IF_AHEAD)) vxsi::win_load<IF_WIN, IF_LANES>(S.win, s, b.pos);
 }
 
 struct Out {
@@ -214,17 +172,18 @@ __device__ uint32_t wave_adler32(InfShared& S, const uint8_t* p, int64_t n) {
 }
 
 // one item; *written: bytes in its window
-__device__ int inflate_item(InfShared& S, const InfItemDev& it, uint8_t* dst, int64_t* written) {
+__device__ int inflate_item(InfShared& S, const WinItem& it, uint8_t* dst, int64_t* written) {
+  const int format = it.spare;
   const int lane = threadIdx.x;
-  DevSrc s{S.win, 0, it.src, it.src_n};
-  win_load(S, s, 0);
+  DevSrc s{S.win, 0, {it.src, it.src_n}};
+  vxsi::win_load<IF_WIN, IF_LANES>(S.win, s, 0);
   Bits b = bits_init(it.src_n);
   Out o{dst, it.dst_cap, 0, 0};
   int st = 0;
   for (;;) {   // members: each one consumes its header, so the loop ends with the input
     const int64_t mstart = o.sbase + o.fill;
-    if (it.format == VX_INFLATE_GZIP) st = gzip_header(b, s);
-    else if (it.format == VX_INFLATE_ZLIB) st = zlib_header(b, s);
+    if (format == VX_INFLATE_GZIP) st = gzip_header(b, s);
+    else if (format == VX_INFLATE_ZLIB) st = zlib_header(b, s);
     if (st) break;
     int final = 0;
     do {
@@ -264,12 +223,12 @@ __device__ int inflate_item(InfShared& S, const InfItemDev& it, uint8_t* dst, in
     flush(S, o);
     if (st) break;
     bits_align(b);
-    if (it.format == VX_INFLATE_RAW) {
+    if (format == VX_INFLATE_RAW) {
       if (bits_bytepos(b) < it.src_n) st = VX_INFLATE_TRAILING;
       break;
     }
     win_ensure(S, s, b);
-    if (it.format == VX_INFLATE_ZLIB) {
+    if (format == VX_INFLATE_ZLIB) {
       const uint32_t ad = trailer_u32(b, s, true);
       if (bits_truncated(b)) st = VX_INFLATE_TRUNCATED;
       else if (ad != wave_adler32(S, o.dst + mstart, o.sbase - mstart)) st = VX_INFLATE_BAD_CHECK;
@@ -290,32 +249,23 @@ __device__ int inflate_item(InfShared& S, const InfItemDev& it, uint8_t* dst, in
   return st;
 }
 
-__global__ __launch_bounds__(IF_LANES) void inflate_kernel(const InfItemDev* __restrict__ items, int n_items, int* counter,
+__global__ __launch_bounds__(IF_LANES) void inflate_kernel(const WinItem* __restrict__ items, int n_items, int* counter,
                                                            uint8_t* dst, int64_t* __restrict__ out_sizes,
                                                            int32_t* __restrict__ out_status) {
   __shared__ InfShared S;
-  for (;;) {
-    int idx = 0;
-    if (threadIdx.x == 0) idx = atomicAdd(counter, 1);
-    idx = __shfl(idx, 0);
-    if (idx >= n_items) return;
-    const InfItemDev it = items[idx];
+  vxsi::for_each_item(items, n_items, counter, [&](const WinItem& it) {
     int64_t written = 0;
     const int st = inflate_item(S, it, dst + it.dst_off, &written);
     if (threadIdx.x == 0) {
       out_sizes[it.index] = written;
       out_status[it.index] = st;
     }
-    __syncthreads();
-  }
+  });
 }
 
 }  // namespace
 
-extern "C" int64_t vx_inflate_workspace_bytes(int n_items) {
-  if (n_items < 0) return -1;
-  return 256 + (int64_t)vx_align256(sizeof(InfItemDev) * (size_t)(n_items > 0 ? n_items : 1));
-}
+extern "C" int64_t vx_inflate_workspace_bytes(int n_items) { return vxsi::item_table_bytes(sizeof(WinItem), n_items); }
 
 extern "C" int vx_inflate(const vx_inflate_item* items, int n_items, uint8_t* dst, int64_t dst_n, int64_t* out_sizes,
                           int32_t* out_status, void* workspace, int64_t ws_bytes, vx_stream_t stream) {
@@ -324,39 +274,18 @@ extern "C" int vx_inflate(const vx_inflate_item* items, int n_items, uint8_t* ds
   if (!items || !dst || !out_sizes || !out_status || !workspace) VX_FAIL(VX_E_NULL, "vx_inflate: null pointer");
   const int64_t need = vx_inflate_workspace_bytes(n_items);
   if (ws_bytes < need) VX_FAIL(VX_E_WORKSPACE, "vx_inflate: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
-  std::vector<InfItemDev> di(n_items);
-  for (int i = 0; i < n_items; ++i) {
-    const vx_inflate_item& g = items[i];
-    if (g.format < VX_INFLATE_GZIP || g.format > VX_INFLATE_RAW) VX_FAIL(VX_E_DTYPE, "vx_inflate: item %d: format %d", i, g.format);
-    if (g.src_n < 0 || g.dst_off < 0 || g.dst_cap < 0 || g.dst_cap > (int64_t)0xFFFFFFFF)
-      VX_FAIL(VX_E_SHAPE, "vx_inflate: item %d: src_n=%lld dst_off=%lld dst_cap=%lld", i, (long long)g.src_n,
-              (long long)g.dst_off, (long long)g.dst_cap);
-    if (g.src_n > 0 && !g.src) VX_FAIL(VX_E_NULL, "vx_inflate: item %d: null source", i);
-    if (g.dst_off + g.dst_cap > dst_n)
-      VX_FAIL(VX_E_SHAPE, "vx_inflate: item %d: window [%lld, +%lld) beyond dst_n=%lld", i, (long long)g.dst_off,
-              (long long)g.dst_cap, (long long)dst_n);
-    di[i] = InfItemDev{g.src, g.src_n, g.dst_off, g.dst_cap, g.format, i};
-  }
-  // the windows may not overlap
-  std::vector<int> byoff(n_items);
-  for (int i = 0; i < n_items; ++i) byoff[i] = i;
-  std::sort(byoff.begin(), byoff.end(), [&](int a, int b) { return di[a].dst_off < di[b].dst_off; });
-  int64_t end = 0;
-  for (int k = 0; k < n_items; ++k) {
-    const InfItemDev& d = di[byoff[k]];
-    if (d.dst_cap == 0) continue;
-    if (d.dst_off < end) VX_FAIL(VX_E_SHAPE, "vx_inflate: item %d: window overlaps another", d.index);
-    end = d.dst_off + d.dst_cap;
-  }
-  // largest streams first: a batch with one large file does not end with one wave working
-  std::stable_sort(di.begin(), di.end(), [](const InfItemDev& a, const InfItemDev& b) { return a.src_n > b.src_n; });
-  std::vector<uint8_t> table(256 + sizeof(InfItemDev) * n_items, 0);   // [counter | items]
-  memcpy(table.data() + 256, di.data(), sizeof(InfItemDev) * n_items);
+  std::vector<WinItem> di;
+  if (int rc = vxsi::win_items("vx_inflate", items, n_items, dst_n, di, [](int i, const vx_inflate_item& g, int32_t* spare) -> int {
+        if (g.format < VX_INFLATE_GZIP || g.format > VX_INFLATE_RAW) VX_FAIL(VX_E_DTYPE, "vx_inflate: item %d: format %d", i, g.format);
+        *spare = g.format;
+        return VX_OK;
+      }))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = vx_upload_table("vx_inflate", "table upload", workspace, table.data(), table.size(), s)) return rc;
-  const int grid = std::min(n_items, vx_cu_count() * IF_WAVES_PER_CU);
-  hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)grid), dim3(IF_LANES), 0, s,
-                     (const InfItemDev*)((uint8_t*)workspace + 256), n_items, (int*)workspace, dst, out_sizes, out_status);
+  int grid = 0;
+  if (int rc = vxsi::item_table_upload("vx_inflate", workspace, di, s, n_items, IF_WAVES_PER_CU, &grid)) return rc;
+  hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)grid), dim3(IF_LANES), 0, s, vxsi::item_table<WinItem>(workspace), n_items,
+                     vxsi::item_counter(workspace), dst, out_sizes, out_status);
   VX_CHECK_LAUNCH("vx_inflate");
   return VX_OK;
 }

@@ -28,12 +28,7 @@
 //                          Four pixels per lane, three dword loads and one dword store, where rgb and out are aligned.
 //
 // Every store in this file is a plain C++ store of a vector register.
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-
-#include "common.h"
+#include "stream_items.h"   // the [counter | items] table of the launcher
 
 namespace {
 
@@ -186,12 +181,7 @@ __global__ __launch_bounds__(PU_LANES) void png_unfilter_kernel(const PuItemDev*
                                                                 int32_t* __restrict__ out_status) {
   extern __shared__ uint8_t pu_row[];
   const int lane = threadIdx.x;
-  for (;;) {
-    int idx = 0;
-    if (lane == 0) idx = atomicAdd(counter, 1);
-    idx = __shfl(idx, 0);
-    if (idx >= n_items) return;
-    const PuItemDev it = items[idx];
+  vxsi::for_each_item(items, n_items, counter, [&](const PuItemDev& it) {
     const int wb = it.W * it.bpp;
     int st = VX_PNG_OK;
     if ((int64_t)it.src_n != (int64_t)it.H * (wb + 1)) {
@@ -217,8 +207,7 @@ __global__ __launch_bounds__(PU_LANES) void png_unfilter_kernel(const PuItemDev*
       }
     }
     if (lane == 0) out_status[it.index] = st;
-    __syncthreads();
-  }
+  });
 }
 
 constexpr int RT_MAX = 256;
@@ -273,10 +262,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rgb_to_trainid_kernel(const uint8_t*
 
 }  // namespace
 
-extern "C" int64_t vx_png_unfilter_workspace_bytes(int n_items) {
-  if (n_items < 0) return -1;
-  return 256 + (int64_t)vx_align256(sizeof(PuItemDev) * (size_t)(n_items > 0 ? n_items : 1));
-}
+extern "C" int64_t vx_png_unfilter_workspace_bytes(int n_items) { return vxsi::item_table_bytes(sizeof(PuItemDev), n_items); }
 
 extern "C" int vx_png_unfilter(const vx_png_unfilter_item* items, int n_items, int32_t* out_status, void* workspace,
                                int64_t ws_bytes, vx_stream_t stream) {
@@ -305,15 +291,13 @@ extern "C" int vx_png_unfilter(const vx_png_unfilter_item* items, int n_items, i
   std::stable_sort(di.begin(), di.end(), [](const PuItemDev& a, const PuItemDev& b) {
     return (int64_t)a.H * a.W * a.bpp > (int64_t)b.H * b.W * b.bpp;
   });
-  std::vector<uint8_t> table(256 + sizeof(PuItemDev) * n_items, 0);   // [counter | items]
-  memcpy(table.data() + 256, di.data(), sizeof(PuItemDev) * n_items);
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = vx_upload_table("vx_png_unfilter", "table upload", workspace, table.data(), table.size(), s)) return rc;
   const int lds = (int)vx_align256((size_t)row_max);   // <= 64 KiB: the default limit of a launch
   const int per_cu = std::max(1, std::min(PU_WAVES_PER_CU, PU_LDS_PER_CU / lds));
-  const int grid = std::min(n_items, vx_cu_count() * per_cu);
-  hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)grid), dim3(PU_LANES), (size_t)lds, s,
-                     (const PuItemDev*)((uint8_t*)workspace + 256), n_items, (int*)workspace, out_status);
+  int grid = 0;
+  if (int rc = vxsi::item_table_upload("vx_png_unfilter", workspace, di, s, n_items, per_cu, &grid)) return rc;
+  hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)grid), dim3(PU_LANES), (size_t)lds, s, vxsi::item_table<PuItemDev>(workspace),
+                     n_items, vxsi::item_counter(workspace), out_status);
   VX_CHECK_LAUNCH("vx_png_unfilter");
   return VX_OK;
 }

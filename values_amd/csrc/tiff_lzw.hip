@@ -16,7 +16,8 @@
 //       string that does not fit behind the batch ends the batch undecoded and is decoded again after the flush.
 //     Input: a 2 KiB window of the compressed bytes in LDS, refilled by the wave (clamped loads) when the reader is
 //       less than 1 KiB from its end (a batch consumes at most 64 codes of 12 bits); a read outside the window falls
-//       back to clamped global loads.
+//       back to clamped global loads (stream_items.h, which also has the item loop and the launcher's window checks,
+//       shared with inflate.hip).
 //     A strip ends at its window's last byte (whatever follows: many writers omit EndOfInformation, and a string that
 //       reaches beyond the window is cut there, as libtiff cuts it), at EndOfInformation (a window not yet full shows in
 //       the size), or with a status.
@@ -37,12 +38,8 @@
 //       of 4 and byte by byte elsewhere.  Predictor 2 may run in place: a lane reads its words before it writes them.
 //
 // Every store in this file is a plain C++ store of a vector register.
-#include <string.h>
+#include "stream_items.h"
 
-#include <algorithm>
-#include <vector>
-
-#include "common.h"
 #include "lzw_core.h"
 
 namespace {
@@ -57,61 +54,21 @@ constexpr int LZ_WAVES_PER_CU = 7;
 
 static_assert(LZ_STAGE >= LZW_MAX_STRING, "an empty staging buffer holds any one string");
 
-struct LzItemDev {
-  const uint8_t* src;
-  int64_t src_n;
-  int64_t dst_off;
-  int64_t dst_cap;
-  int32_t index;   // the item's place in the caller's table (out_sizes / out_status)
-  int32_t pad;
-};
-
 struct LzShared {
   uint32_t win[LZ_WIN / 4];
   uint32_t pos[LZW_POS + 1];
   uint8_t stage[LZ_STAGE];
 };
 
-// the reader's byte source: the LDS window, else clamped global loads (never outside [g, g + n))
-struct LzSrc {
-  const uint32_t* win;
-  int64_t wbase;
-  const uint8_t* g;
-  int64_t n;
-  __device__ uint32_t u32(int64_t pos) const {
-    if (pos >= wbase && pos + 4 <= wbase + LZ_WIN) return win[(pos - wbase) >> 2];
-    uint32_t v = 0;
-    for (int k = 0; k < 4; ++k)
-      if (pos + k < n) v |= (uint32_t)g[pos + k] << (8 * k);
-    return v;
-  }
-};
-
-// load the window at base (a multiple of 4), zeros beyond n
-__device__ void lz_win_load(LzShared& S, LzSrc& s, int64_t base) {
-  __syncthreads();   // every lane is done with the old window
-  s.wbase = base;
-  const bool al = ((uintptr_t)(s.g + base) & 3) == 0;
-  for (int w = threadIdx.x; w < LZ_WIN / 4; w += LZ_LANES) {
-    const int64_t p = base + 4 * w;
-    uint32_t v = 0;
-    if (al && p + 4 <= s.n) {
-      v = *reinterpret_cast<const uint32_t*>(s.g + p);
-    } else {
-      for (int k = 0; k < 4; ++k)
-        if (p + k < s.n) v |= (uint32_t)s.g[p + k] << (8 * k);
-    }
-    S.win[w] = v;
-  }
-  __syncthreads();
-}
+using LzSrc = vxsi::WinSrc<LZ_WIN>;   // the reader's byte source (stream_items.h)
+using vxsi::WinItem;
 
 // one item; *written: bytes in its window
-__device__ int lzw_item(LzShared& S, const LzItemDev& it, uint8_t* dst, int64_t* written) {
+__device__ int lzw_item(LzShared& S, const WinItem& it, uint8_t* dst, int64_t* written) {
   const int lane = threadIdx.x;
   const uint32_t cap = (uint32_t)it.dst_cap;
-  LzSrc s{S.win, 0, it.src, it.src_n};
-  lz_win_load(S, s, 0);
+  LzSrc s{S.win, 0, {it.src, it.src_n}};
+  vxsi::win_load<LZ_WIN, LZ_LANES>(S.win, s, 0);
   MBits b = mbits_init(it.src_n);
   Lzw z = lzw_init(S.pos);
   uint32_t sbase = 0;   // output offset of stage[0]
@@ -119,7 +76,7 @@ __device__ int lzw_item(LzShared& S, const LzItemDev& it, uint8_t* dst, int64_t*
   int st = VX_LZW_OK;
   bool done = cap == 0;
   while (!done) {
-    if (b.pos < s.wbase || b.pos + LZ_AHEAD > s.wbase + LZ_WIN) lz_win_load(S, s, b.pos);
+    if (s.stale(b.pos, LZ_AHEAD)) vxsi::win_load<LZ_WIN, LZ_LANES>(S.win, s, b.pos);
     // decode up to 64 strings (every lane the same); lane j keeps string j
     int tlit = -1, tlen = 0, tp = 0;
     uint32_t tfrom = 0;
@@ -185,24 +142,18 @@ __device__ int lzw_item(LzShared& S, const LzItemDev& it, uint8_t* dst, int64_t*
   return st;
 }
 
-__global__ __launch_bounds__(LZ_LANES) void tiff_lzw_kernel(const LzItemDev* __restrict__ items, int n_items, int* counter,
+__global__ __launch_bounds__(LZ_LANES) void tiff_lzw_kernel(const WinItem* __restrict__ items, int n_items, int* counter,
                                                             uint8_t* dst, int64_t* __restrict__ out_sizes,
                                                             int32_t* __restrict__ out_status) {
   __shared__ LzShared S;
-  for (;;) {
-    int idx = 0;
-    if (threadIdx.x == 0) idx = atomicAdd(counter, 1);
-    idx = __shfl(idx, 0);
-    if (idx >= n_items) return;
-    const LzItemDev it = items[idx];
+  vxsi::for_each_item(items, n_items, counter, [&](const WinItem& it) {
     int64_t written = 0;
     const int st = lzw_item(S, it, dst + it.dst_off, &written);
     if (threadIdx.x == 0) {
       out_sizes[it.index] = written;
       out_status[it.index] = st;
     }
-    __syncthreads();
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -342,10 +293,7 @@ __global__ __launch_bounds__(UP_BLOCK) void tiff_unpredict_kernel(const UpItemDe
 
 }  // namespace
 
-extern "C" int64_t vx_tiff_lzw_workspace_bytes(int n_items) {
-  if (n_items < 0) return -1;
-  return 256 + (int64_t)vx_align256(sizeof(LzItemDev) * (size_t)(n_items > 0 ? n_items : 1));
-}
+extern "C" int64_t vx_tiff_lzw_workspace_bytes(int n_items) { return vxsi::item_table_bytes(sizeof(WinItem), n_items); }
 
 extern "C" int vx_tiff_lzw(const vx_tiff_lzw_item* items, int n_items, uint8_t* dst, int64_t dst_n, int64_t* out_sizes,
                            int32_t* out_status, void* workspace, int64_t ws_bytes, vx_stream_t stream) {
@@ -354,47 +302,19 @@ extern "C" int vx_tiff_lzw(const vx_tiff_lzw_item* items, int n_items, uint8_t* 
   if (!items || !dst || !out_sizes || !out_status || !workspace) VX_FAIL(VX_E_NULL, "vx_tiff_lzw: null pointer");
   const int64_t need = vx_tiff_lzw_workspace_bytes(n_items);
   if (ws_bytes < need) VX_FAIL(VX_E_WORKSPACE, "vx_tiff_lzw: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
-  std::vector<LzItemDev> di(n_items);
-  for (int i = 0; i < n_items; ++i) {
-    const vx_tiff_lzw_item& g = items[i];
-    if (g.src_n < 0 || g.dst_off < 0 || g.dst_cap < 0 || g.dst_cap > (int64_t)0xFFFFFFFF)
-      VX_FAIL(VX_E_SHAPE, "vx_tiff_lzw: item %d: src_n=%lld dst_off=%lld dst_cap=%lld", i, (long long)g.src_n,
-              (long long)g.dst_off, (long long)g.dst_cap);
-    if (g.src_n > 0 && !g.src) VX_FAIL(VX_E_NULL, "vx_tiff_lzw: item %d: null source", i);
-    if (g.dst_off > dst_n || g.dst_cap > dst_n - g.dst_off)
-      VX_FAIL(VX_E_SHAPE, "vx_tiff_lzw: item %d: window [%lld, +%lld) beyond dst_n=%lld", i, (long long)g.dst_off,
-              (long long)g.dst_cap, (long long)dst_n);
-    di[i] = LzItemDev{g.src, g.src_n, g.dst_off, g.dst_cap, i, 0};
-  }
-  // the windows may not overlap
-  std::vector<int> byoff(n_items);
-  for (int i = 0; i < n_items; ++i) byoff[i] = i;
-  std::sort(byoff.begin(), byoff.end(), [&](int a, int b) { return di[a].dst_off < di[b].dst_off; });
-  int64_t end = 0;
-  for (int k = 0; k < n_items; ++k) {
-    const LzItemDev& d = di[byoff[k]];
-    if (d.dst_cap == 0) continue;
-    if (d.dst_off < end) VX_FAIL(VX_E_SHAPE, "vx_tiff_lzw: item %d: window overlaps another", d.index);
-    end = d.dst_off + d.dst_cap;
-  }
-  // largest strips first: a batch with one large strip does not end with one wave working
-  std::stable_sort(di.begin(), di.end(), [](const LzItemDev& a, const LzItemDev& b) { return a.src_n > b.src_n; });
-  std::vector<uint8_t> table(256 + sizeof(LzItemDev) * n_items, 0);   // [counter | items]
-  memcpy(table.data() + 256, di.data(), sizeof(LzItemDev) * n_items);
+  std::vector<WinItem> di;
+  if (int rc = vxsi::win_items("vx_tiff_lzw", items, n_items, dst_n, di, [](int, const vx_tiff_lzw_item&, int32_t*) -> int { return VX_OK; }))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = vx_upload_table("vx_tiff_lzw", "table upload", workspace, table.data(), table.size(), s)) return rc;
-  const int grid = std::min(n_items, vx_cu_count() * LZ_WAVES_PER_CU);
-  hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)grid), dim3(LZ_LANES), 0, s,
-                     (const LzItemDev*)((uint8_t*)workspace + 256), n_items, (int*)workspace, dst, out_sizes, out_status);
+  int grid = 0;
+  if (int rc = vxsi::item_table_upload("vx_tiff_lzw", workspace, di, s, n_items, LZ_WAVES_PER_CU, &grid)) return rc;
+  hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)grid), dim3(LZ_LANES), 0, s, vxsi::item_table<WinItem>(workspace), n_items,
+                     vxsi::item_counter(workspace), dst, out_sizes, out_status);
   VX_CHECK_LAUNCH("vx_tiff_lzw");
   return VX_OK;
 }
 
-extern "C" int64_t vx_tiff_unpredict_workspace_bytes(int n_items) {
-  if (n_items < 0) return -1;
-  return 256 + (int64_t)vx_align256(sizeof(UpItemDev) * (size_t)(n_items > 0 ? n_items : 1));
-}
-
+extern "C" int64_t vx_tiff_unpredict_workspace_bytes(int n_items) { return vxsi::item_table_bytes(sizeof(UpItemDev), n_items); }
 extern "C" int vx_tiff_unpredict(const vx_tiff_unpredict_item* items, int n_items, int32_t* out_status, void* workspace,
                                  int64_t ws_bytes, vx_stream_t stream) {
   if (n_items < 0) VX_FAIL(VX_E_SHAPE, "vx_tiff_unpredict: n_items=%d", n_items);
@@ -419,13 +339,11 @@ extern "C" int vx_tiff_unpredict(const vx_tiff_unpredict_item* items, int n_item
     n_rows += g.rows;
   }
   if (n_rows > 0x7FFFFFFF - 65536) VX_FAIL(VX_E_SHAPE, "vx_tiff_unpredict: %lld rows in one call", (long long)n_rows);
-  std::vector<uint8_t> table(256 + sizeof(UpItemDev) * n_items, 0);   // [counter | items]
-  memcpy(table.data() + 256, di.data(), sizeof(UpItemDev) * n_items);
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = vx_upload_table("vx_tiff_unpredict", "table upload", workspace, table.data(), table.size(), s)) return rc;
-  const int grid = (int)std::min<int64_t>(n_rows, (int64_t)vx_cu_count() * UP_BLOCKS_PER_CU);
-  hipLaunchKernelGGL(tiff_unpredict_kernel, dim3((unsigned)grid), dim3(UP_BLOCK), 0, s,
-                     (const UpItemDev*)((uint8_t*)workspace + 256), n_items, n_rows, (int*)workspace, out_status);
+  int grid = 0;
+  if (int rc = vxsi::item_table_upload("vx_tiff_unpredict", workspace, di, s, n_rows, UP_BLOCKS_PER_CU, &grid)) return rc;
+  hipLaunchKernelGGL(tiff_unpredict_kernel, dim3((unsigned)grid), dim3(UP_BLOCK), 0, s, vxsi::item_table<UpItemDev>(workspace),
+                     n_items, n_rows, vxsi::item_counter(workspace), out_status);
   VX_CHECK_LAUNCH("vx_tiff_unpredict");
   return VX_OK;
 }

@@ -10,6 +10,7 @@ import ctypes as C
 from typing import List, Optional, Sequence
 
 from . import _lib
+from ._devio import current_device, decode_windows, plan
 
 MAX_HINT = 32768   # a DEFLATE distance reaches 32 KiB back
 
@@ -93,11 +94,6 @@ def gzip_encode(tensors, stride_hints: Optional[Sequence] = None) -> List[bytes]
 
 FORMATS = {"gzip": _lib.VX_INFLATE_GZIP, "zlib": _lib.VX_INFLATE_ZLIB, "raw": _lib.VX_INFLATE_RAW}
 MAX_RATIO = 1032   # DEFLATE expands at most 1032:1 (258-byte matches of 2 bits); a capacity that always suffices
-ALIGN = 256
-
-
-def _align(n: int) -> int:
-    return (int(n) + ALIGN - 1) // ALIGN * ALIGN
 
 
 def inflate_into(items: List[tuple], device, dst=None, offsets: Optional[Sequence[int]] = None):
@@ -107,10 +103,7 @@ def inflate_into(items: List[tuple], device, dst=None, offsets: Optional[Sequenc
     do not overlap); otherwise dst is allocated here, the windows back to back at 256-byte boundaries."""
     import torch
     if dst is None:
-        offs, off = [], 0
-        for _, _, _, cap in items:
-            offs.append(off)
-            off += _align(max(int(cap), 1))
+        offs, _, off = plan([(None, [(0, int(cap))]) for _, _, _, cap in items])
         dst = torch.empty(max(off, 1), dtype=torch.uint8, device=device)
     else:
         offs = [int(o) for o in offsets]
@@ -119,14 +112,8 @@ def inflate_into(items: List[tuple], device, dst=None, offsets: Optional[Sequenc
     arr = (_lib.InflateItem * len(items))()
     for i, (ptr, n, fmt, cap) in enumerate(items):
         arr[i].src, arr[i].src_n, arr[i].dst_off, arr[i].dst_cap, arr[i].format = ptr, int(n), offs[i], int(cap), int(fmt)
-    res = torch.empty(len(items) * 3, dtype=torch.int32, device=device)   # [sizes (int64) | statuses]
-    sizes = res[:2 * len(items)].view(torch.int64)
-    status = res[2 * len(items):]
-    ws = torch.empty(int(_lib.load().vx_inflate_workspace_bytes(len(items))), dtype=torch.uint8, device=device)
-    _lib.check(_lib.load().vx_inflate(arr, len(items), _lib.ptr(dst), dst.numel(), _lib.ptr(sizes), _lib.ptr(status),
-                                      _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "vx_inflate")
-    host = res.cpu()
-    return dst, offs, host[:2 * len(items)].view(torch.int64).tolist(), host[2 * len(items):].tolist()
+    sizes, statuses = decode_windows("vx_inflate", arr, dst, device)
+    return dst, offs, sizes, statuses
 
 
 def status_name(st: int) -> str:
@@ -144,7 +131,7 @@ def gunzip(blobs, fmt: str = "gzip", sizes: Optional[Sequence[int]] = None, devi
     if fmt not in FORMATS:
         raise ValueError(f"gunzip: format {fmt!r} (gzip, zlib or raw)")
     f = FORMATS[fmt]
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = current_device(device)
     srcs, keep = [], []
     for b in blobs:
         if isinstance(b, torch.Tensor):

@@ -16,13 +16,13 @@ The arrays are the ones the host readers return: (H, W) or (H, W, 3 | 4) uint8, 
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 import numpy as np
 
 from . import _lib
+from ._devio import PipelinedReader, Stages, decode_windows, item_statuses, load_once, plan
 from .image_io import png_parse, tiff_decode, tiff_parse
-from .nifti import MAX_FILE, _read
+from .nifti import MAX_FILE
 
 PNG_ENDINGS, TIFF_ENDINGS = (".png",), (".tif", ".tiff")
 
@@ -37,96 +37,36 @@ def kind_of(path) -> str:
     raise ValueError(f"{path}: neither a .png nor a .tif / .tiff file")
 
 
-class _Staging:
-    """a pinned host buffer reused across batches (grown when a batch needs more): spans of the files' bytes are joined
-    in it and uploaded in one copy; that copy is waited for before the buffer is written again"""
-
-    def __init__(self):
-        self.buf = None
-        self.event = None
-
-    def upload(self, pieces, device):
-        """pieces: per item (bytes, [(offset, size)]) -> (device uint8 tensor, item offsets, item sizes)"""
-        import torch
-        from .gz import _align
-        offs, sizes, off = [], [], 0
-        for _, spans in pieces:
-            n = sum(s for _, s in spans)
-            offs.append(off)
-            sizes.append(n)
-            off += _align(max(n, 1))
-        if self.event is not None:
-            self.event.synchronize()
-        if self.buf is None or self.buf.numel() < off:
-            self.buf = torch.empty(max(off, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        host = self.buf.numpy()
-        for (raw, spans), o in zip(pieces, offs):
-            view = np.frombuffer(raw, np.uint8)
-            for so, sn in spans:
-                host[o:o + sn] = view[so:so + sn]
-                o += sn
-        dev = self.buf[:max(off, 1)].to(device, non_blocking=True)
-        self.event = torch.cuda.Event()
-        self.event.record()
-        return dev, offs, sizes
-
-
-def _events(timing):
-    import torch
-    return [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
-
-
 def png_unfilter(entries, device):
     """entries: (src pointer, src_n, H, W, bpp, dst pointer) -> the items' statuses (host list): one vx_png_unfilter call."""
-    import torch
     if not entries:
         return []
-    lib = _lib.load()
     arr = (_lib.PngUnfilterItem * len(entries))()
     for it, (src, n, h, w, bpp, dst) in zip(arr, entries):
         it.src, it.src_n, it.dst, it.H, it.W, it.bpp = src, int(n), dst, int(h), int(w), int(bpp)
-    status = torch.empty(len(entries), dtype=torch.int32, device=device)
-    ws = torch.empty(int(lib.vx_png_unfilter_workspace_bytes(len(entries))), dtype=torch.uint8, device=device)
-    _lib.check(lib.vx_png_unfilter(arr, len(entries), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-               "vx_png_unfilter")
-    return status.cpu().tolist()
+    return item_statuses("vx_png_unfilter", arr, device)
 
 
 def lzw_into(items, device, dst):
     """items: (device pointer, src_n, dst_off, capacity) -> (sizes, statuses), host lists: one vx_tiff_lzw call, item i
     decoded into dst[dst_off:dst_off + capacity] (dst: a device uint8 tensor; the windows do not overlap)."""
-    import torch
     if not items:
         return [], []
-    lib = _lib.load()
     arr = (_lib.TiffLzwItem * len(items))()
     for it, (ptr, n, off, cap) in zip(arr, items):
         it.src, it.src_n, it.dst_off, it.dst_cap = ptr, int(n), int(off), int(cap)
-    res = torch.empty(len(items) * 3, dtype=torch.int32, device=device)   # [sizes (int64) | statuses]
-    sizes = res[:2 * len(items)].view(torch.int64)
-    status = res[2 * len(items):]
-    ws = torch.empty(int(lib.vx_tiff_lzw_workspace_bytes(len(items))), dtype=torch.uint8, device=device)
-    _lib.check(lib.vx_tiff_lzw(arr, len(items), _lib.ptr(dst), dst.numel(), _lib.ptr(sizes), _lib.ptr(status),
-                               _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw")
-    host = res.cpu()
-    return host[:2 * len(items)].view(torch.int64).tolist(), host[2 * len(items):].tolist()
+    return decode_windows("vx_tiff_lzw", arr, dst, device)
 
 
 def tiff_unpredict(entries, device):
     """entries: (src pointer, dst pointer, rows, W, predictor) -> the items' statuses (host list): one vx_tiff_unpredict
     call over float32 rows of little-endian files."""
-    import torch
     if not entries:
         return []
-    lib = _lib.load()
     arr = (_lib.TiffUnpredictItem * len(entries))()
     for it, (src, dst, rows, w, pred) in zip(arr, entries):
         it.src, it.dst, it.rows, it.W, it.predictor = src, dst, int(rows), int(w), int(pred)
-    status = torch.empty(len(entries), dtype=torch.int32, device=device)
-    ws = torch.empty(int(lib.vx_tiff_unpredict_workspace_bytes(len(entries))), dtype=torch.uint8, device=device)
-    _lib.check(lib.vx_tiff_unpredict(arr, len(entries), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-               "vx_tiff_unpredict")
-    return status.cpu().tolist()
+    return item_statuses("vx_tiff_unpredict", arr, device)
 
 
 def lzw_status_name(st: int) -> str:
@@ -145,9 +85,8 @@ def _decode_png(names, raws, device, staging, timing=None):
         except ValueError as e:
             raise ValueError(f"{nm}: {e}") from None
     src, soffs, sizes = staging.upload([(r, h[4]) for r, h in zip(raws, heads)], device)
-    ev = _events(timing)
-    if ev:
-        ev[0].record()
+    stages = Stages(timing)
+    stages.mark()
     need = [h * (1 + w * bpp) for w, h, _, bpp, _ in heads]
     items = [(C.c_void_p(src.data_ptr() + o) if n else None, n, _lib.VX_INFLATE_ZLIB, cap)
              for o, n, cap in zip(soffs, sizes, need)]
@@ -155,8 +94,7 @@ def _decode_png(names, raws, device, staging, timing=None):
     for nm, s, n in zip(names, st, ln):
         if s != 0:
             raise _lib.VxError(f"{nm}: IDAT: {status_name(s)} (status {s}, {n} bytes decoded)")
-    if ev:
-        ev[1].record()
+    stages.mark()
     outs = [torch.empty((h, w) if bpp == 1 else (h, w, bpp), dtype=torch.uint8, device=device) for w, h, _, bpp, _ in heads]
     st = png_unfilter([(C.c_void_p(lines.data_ptr() + lo), n, h, w, bpp, C.c_void_p(out.data_ptr()))
                        for lo, n, (w, h, _, bpp, _), out in zip(loffs, ln, heads, outs)], device)
@@ -164,33 +102,26 @@ def _decode_png(names, raws, device, staging, timing=None):
         if s != 0:
             what = _lib.PNG_STATUS[s] if 0 <= s < len(_lib.PNG_STATUS) else "?"
             raise _lib.VxError(f"{nm}: scanlines: {what} (status {s})")
-    if ev:
-        ev[2].record()
-        ev[2].synchronize()
-        timing["inflate_ms"] = timing.get("inflate_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["unfilter_ms"] = timing.get("unfilter_ms", 0.0) + ev[1].elapsed_time(ev[2])
-        timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(need)
+    stages.mark()
+    stages.add(("inflate_ms", "unfilter_ms"), sum(need))
     return outs
 
 
 def _decode_tiff(names, raws, device, staging, timing=None):
     import torch
-    from .gz import _align, inflate_into, status_name
+    from .gz import inflate_into, status_name
     lay = [tiff_parse(r, str(nm)) for nm, r in zip(names, raws)]
     on_dev = [i for i, t in enumerate(lay) if t.endian == "<"]
     # the maps of the batch: one buffer, every map at a 256-byte boundary; behind them, where a file has a predictor,
     # a scratch area of the same layout for the strips as they decode
-    moffs, off = {}, 0
-    for i in on_dev:
-        moffs[i] = off
-        off += _align(max(4 * lay[i].h * lay[i].w, 1))
+    offs, _, off = plan([(None, [(0, 4 * lay[i].h * lay[i].w)]) for i in on_dev])
+    moffs = dict(zip(on_dev, offs))
     predicted = [i for i in on_dev if lay[i].lzw and lay[i].predictor != 1]
     maps = torch.empty(max(off * (2 if predicted else 1), 1), dtype=torch.uint8, device=device)
     strips = [(i, s) for i in on_dev for s in lay[i].strips]
     src, soffs, sizes = staging.upload([(raws[i], [(s[2], s[3])]) for i, s in strips], device)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing is not None else None
-    if ev:
-        ev[0].record()
+    stages = Stages(timing)
+    stages.mark()
     items, at, who = [], [], []
     litems, lwho = [], []
     for (i, (r0, rows, _, _)), so, n in zip(strips, soffs, sizes):
@@ -212,26 +143,19 @@ def _decode_tiff(names, raws, device, staging, timing=None):
         for (i, r0, nb), s, n in zip(who, st, dn):
             if s != 0 or n != nb:
                 raise _lib.VxError(f"{names[i]}: strip at row {r0}: {status_name(s)} (status {s}, {n} of {nb} bytes decoded)")
-    if ev:
-        ev[1].record()
+    stages.mark()
     if litems:
         dn, st = lzw_into(litems, device, maps)
         for (i, r0, nb), s, n in zip(lwho, st, dn):
             if s != 0 or n != nb:
                 raise _lib.VxError(f"{names[i]}: strip at row {r0}: LZW: {lzw_status_name(s)} (status {s}, {n} of {nb} bytes decoded)")
-    if ev:
-        ev[2].record()
+    stages.mark()
     if predicted:
         base = maps.data_ptr()
         tiff_unpredict([(C.c_void_p(base + off + moffs[i]), C.c_void_p(base + moffs[i]), lay[i].h, lay[i].w, lay[i].predictor)
                         for i in predicted if lay[i].h * lay[i].w], device)
-    if ev:
-        ev[3].record()
-        ev[3].synchronize()
-        timing["inflate_ms"] = timing.get("inflate_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["lzw_ms"] = timing.get("lzw_ms", 0.0) + ev[1].elapsed_time(ev[2])
-        timing["unpredict_ms"] = timing.get("unpredict_ms", 0.0) + ev[2].elapsed_time(ev[3])
-        timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(4 * t.h * t.w for t in lay)
+    stages.mark()
+    stages.add(("inflate_ms", "lzw_ms", "unpredict_ms"), sum(4 * t.h * t.w for t in lay))
     outs = []
     for i, t in enumerate(lay):
         if i in moffs:
@@ -254,30 +178,22 @@ def _decode(names, raws, device, staging, timing=None):
     return outs
 
 
-def _device(device):
-    import torch
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-_shared = None   # the one-shot loaders' reader: its thread pool and pinned staging buffer, used by one call at a time
-_shared_lock = threading.Lock()
-
-
 def _load(paths, device, timing, kind):
-    global _shared
     _lib.require_gpu()
     paths = [str(p) for p in paths]
     for p in paths:
         if kind_of(p) != kind:
             raise ValueError(f"{p}: not a {kind} file")
-    if not paths:
-        return []
-    dev = _device(device)
-    with _shared_lock:
-        if _shared is None:
-            _shared = ImageReader()
-        raws = list(_shared._pool.map(_read, paths))
-        return _decode(paths, raws, dev, _shared._staging, timing)
+    return load_once(ImageReader, paths, device, timing)
+
+
+class ImageReader(PipelinedReader):
+    """Pipelined load_png_device / load_tiff_device over batches of files (PNG and TIFF may be mixed): the files of batch
+    i + 1 are read from disk on a thread pool while batch i is decoded on the device.  read(batches) yields one list of
+    tensors per batch, in order -- nifti.NiftiReader for the 2D tree."""
+
+    def _decode(self, names, raws, device):
+        return _decode(names, raws, device, self._staging, self._timing)
 
 
 def load_png_device(paths, device=None, _timing=None):
@@ -293,44 +209,3 @@ def load_tiff_device(paths, device=None, _timing=None):
     batch are views of one device buffer.  A strip that does not decode raises VxError naming the file, the strip's
     first row, the status and the bytes decoded of the bytes expected."""
     return _load(paths, device, _timing, "tiff")
-
-
-class ImageReader:
-    """Pipelined load_png_device / load_tiff_device over batches of files (PNG and TIFF may be mixed): the files of batch
-    i + 1 are read from disk on a thread pool while batch i is decoded on the device.  read(batches) yields one list of
-    tensors per batch, in order -- nifti.NiftiReader for the 2D tree."""
-
-    def __init__(self, device=None, workers: int = 8, _timing=None):
-        if workers < 1:
-            raise ValueError("ImageReader: workers >= 1")
-        from concurrent.futures import ThreadPoolExecutor
-        self.device = device
-        self._pool = ThreadPoolExecutor(max_workers=int(workers))
-        self._staging = _Staging()
-        self._timing = _timing
-
-    def _submit(self, batch):
-        return [str(p) for p in batch], [self._pool.submit(_read, str(p)) for p in batch]
-
-    def read(self, batches):
-        _lib.require_gpu()
-        dev = _device(self.device)
-        it = iter(batches)
-        nxt = next(it, None)
-        pending = self._submit(nxt) if nxt is not None else None
-        while pending is not None:
-            names, futs = pending
-            nxt = next(it, None)
-            raws = [f.result() for f in futs]
-            pending = self._submit(nxt) if nxt is not None else None
-            yield _decode(names, raws, dev, self._staging, self._timing) if names else []
-
-    def close(self):
-        self._pool.shutdown(wait=True)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False

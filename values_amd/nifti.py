@@ -12,9 +12,10 @@ from __future__ import annotations
 import ctypes as C
 import gzip
 import struct
-import threading
 
 import numpy as np
+
+from ._devio import PipelinedReader, Stages, load_once
 
 _DT = {np.dtype("uint8"): (2, 8), np.dtype("int16"): (4, 16), np.dtype("int32"): (8, 32), np.dtype("float32"): (16, 32),
        np.dtype("float64"): (64, 64), np.dtype("int8"): (256, 8), np.dtype("uint16"): (512, 16),
@@ -150,39 +151,6 @@ _TORCH = {"uint8": "uint8", "int8": "int8", "int16": "int16", "int32": "int32", 
           "float64": "float64", "uint16": "uint16", "uint32": "uint32", "uint64": "uint64"}
 
 
-def _read(path):
-    with open(path, "rb") as f:
-        return f.read()
-
-
-class _Staging:
-    """a pinned host buffer reused across batches (grown when a batch needs more); the H2D copy out of it is waited
-    for before the buffer is written again"""
-
-    def __init__(self):
-        self.buf = None
-        self.event = None
-
-    def upload(self, raws, device):
-        import torch
-        from .gz import _align
-        offs, off = [], 0
-        for r in raws:
-            offs.append(off)
-            off += _align(max(len(r), 1))
-        if self.event is not None:
-            self.event.synchronize()
-        if self.buf is None or self.buf.numel() < off:
-            self.buf = torch.empty(max(off, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        host = self.buf.numpy()
-        for r, o in zip(raws, offs):
-            host[o:o + len(r)] = np.frombuffer(r, np.uint8)
-        dev = self.buf[:max(off, 1)].to(device, non_blocking=True)
-        self.event = torch.cuda.Event()
-        self.event.record()
-        return dev, offs
-
-
 def _torch_dtype(dt):
     import torch
     return getattr(torch, _TORCH[np.dtype(dt).name])
@@ -196,11 +164,10 @@ def _decode(names, raws, device, staging, timing=None):
     for nm, r in zip(names, raws):
         if len(r) >= MAX_FILE:
             raise ValueError(f"{nm}: {len(r)} bytes: files of 4 GiB or more are not read on the device")
-    src, soffs = staging.upload(raws, device)
+    src, soffs, _ = staging.upload([(r, [(0, len(r))]) for r in raws], device)
     gz = [str(nm).endswith(".gz") for nm in names]
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
-    if ev:
-        ev[0].record()
+    stages = Stages(timing)
+    stages.mark()
     items = []
     for i, r in enumerate(raws):
         if gz[i]:
@@ -247,8 +214,7 @@ def _decode(names, raws, device, staging, timing=None):
             if st2[k] != 0:
                 raise _lib.VxError(f"{names[i]}: {status_name(st2[k])} (status {st2[k]}, {n2[k]} bytes decoded)")
             where[i] = [dst2, offs2[k], n2[k], 0]
-    if ev:
-        ev[1].record()
+    stages.mark()
     outs = []
     arr = (_lib.NiftiDecItem * len(raws))()
     for i, h in enumerate(heads):
@@ -268,17 +234,17 @@ def _decode(names, raws, device, staging, timing=None):
         it.slope, it.inter = float(h.slope), float(h.inter)
     ws = torch.empty(int(_lib.load().vx_nifti_decode_workspace_bytes(len(raws))), dtype=torch.uint8, device=device)
     _lib.check(_lib.load().vx_nifti_decode(arr, len(raws), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "vx_nifti_decode")
-    if ev:
-        ev[2].record()
-        ev[2].synchronize()
-        timing["inflate_ms"] = timing.get("inflate_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["decode_ms"] = timing.get("decode_ms", 0.0) + ev[1].elapsed_time(ev[2])
-        timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(h.nbytes for h in heads)
+    stages.mark()
+    stages.add(("inflate_ms", "decode_ms"), sum(h.nbytes for h in heads))
     return [(o, h.header) for o, h in zip(outs, heads)]
 
 
-_shared = None   # load_device's reader: its thread pool and pinned staging buffer, used by one call at a time
-_shared_lock = threading.Lock()
+class NiftiReader(PipelinedReader):
+    """Pipelined load_device over batches of files: the files of batch i + 1 are read from disk on a thread pool while
+    batch i is decoded on the device.  read(batches) yields one load_device result per batch, in order."""
+
+    def _decode(self, names, raws, device):
+        return _decode(names, raws, device, self._staging, self._timing)
 
 
 def load_device(paths, device=None, _timing=None):
@@ -286,58 +252,6 @@ def load_device(paths, device=None, _timing=None):
     returns, as tensors on `device` (default: the current device).  The files are read on a thread pool into a reused
     pinned buffer and uploaded in one copy; the .gz files are inflated in one vx_inflate call (capacities from their
     ISIZE trailers), the voxels decoded in one vx_nifti_decode call."""
-    import torch
     from . import _lib
-    global _shared
     _lib.require_gpu()
-    paths = [str(p) for p in paths]
-    if not paths:
-        return []
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    with _shared_lock:
-        if _shared is None:
-            _shared = NiftiReader()
-        raws = list(_shared._pool.map(_read, paths))
-        return _decode(paths, raws, dev, _shared._staging, _timing)
-
-
-class NiftiReader:
-    """Pipelined load_device over batches of files: the files of batch i + 1 are read from disk on a thread pool while
-    batch i is decoded on the device.  read(batches) yields one load_device result per batch, in order."""
-
-    def __init__(self, device=None, workers: int = 8, _timing=None):
-        if workers < 1:
-            raise ValueError("NiftiReader: workers >= 1")
-        from concurrent.futures import ThreadPoolExecutor
-        self.device = device
-        self._pool = ThreadPoolExecutor(max_workers=int(workers))
-        self._staging = _Staging()
-        self._timing = _timing
-
-    def _submit(self, batch):
-        return [str(p) for p in batch], [self._pool.submit(_read, str(p)) for p in batch]
-
-    def read(self, batches):
-        import torch
-        from . import _lib
-        _lib.require_gpu()
-        dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
-        it = iter(batches)
-        nxt = next(it, None)
-        pending = self._submit(nxt) if nxt is not None else None
-        while pending is not None:
-            names, futs = pending
-            nxt = next(it, None)
-            raws = [f.result() for f in futs]
-            pending = self._submit(nxt) if nxt is not None else None
-            yield _decode(names, raws, dev, self._staging, self._timing) if names else []
-
-    def close(self):
-        self._pool.shutdown(wait=True)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
+    return load_once(NiftiReader, paths, device, _timing)
