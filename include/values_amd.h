@@ -728,7 +728,10 @@ int vx_soft_metric_sums_batched(const float* prob, const uint8_t* gt, int B, int
  * vx_ssn2d_lowres: channels-last head outputs at the head's resolution -- mean [B*pix][mean_pitch] (C used),
  *   factor [B*pix][factor_pitch] (channel r*C + c) -- and eps_w [S][B][R] (nullable: generated) ->
  *   comb [S][B*pix][C] = mean + sum_r factor_r * eps_w,  expm [B*pix][C] = exp(mean) (nullable).
- * vx_ssn2d_add_diag: out [B][S][per] += sqrt(diag [B][per] + epsilon) * eps_d [S][B][per] (nullable: generated). */
+ *   mean_pitch >= C, factor_pitch >= R*C, B * pix < 2^32, B * S < 2^31; anything else is VX_E_SHAPE, a null mean or comb
+ *   (or factor with R > 0) VX_E_NULL, both before any launch.
+ * vx_ssn2d_add_diag: out [B][S][per] += sqrt(diag [B][per] + epsilon) * eps_d [S][B][per] (nullable: generated).
+ *   0 < per < 2^32. */
 int vx_ssn2d_lowres(const float* mean, int mean_pitch, const float* factor, int factor_pitch, const float* eps_w,
                     uint32_t seed, int B, int64_t pix_per_image, int S, int C, int R, float* comb, float* expm,
                     vx_stream_t stream);

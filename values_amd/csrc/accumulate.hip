@@ -200,8 +200,12 @@ __global__ __launch_bounds__(256) void ssn2d_lowres_kernel(const float* __restri
 extern "C" int vx_ssn2d_lowres(const float* mean, int mean_pitch, const float* factor, int factor_pitch, const float* eps_w,
                                uint32_t seed, int B, int64_t pix_per_image, int S, int C, int R, float* comb, float* expm,
                                vx_stream_t stream) {
-  if (B <= 0 || pix_per_image <= 0 || S <= 0 || C <= 0 || R < 0 || mean_pitch < C || (R > 0 && factor_pitch < R * C))
+  if (B <= 0 || pix_per_image <= 0 || S <= 0 || C <= 0 || R < 0 || mean_pitch < C ||
+      (R > 0 && (int64_t)factor_pitch < (int64_t)R * C))
     VX_FAIL(VX_E_SHAPE, "vx_ssn2d_lowres: bad shape");
+  // the sibling calls' size guard: B * pix pixels index in 32 bits, and the generator's slot b * S + s is an int
+  if ((int64_t)B * pix_per_image >= (1ll << 32) || (int64_t)B * S >= (1ll << 31))
+    VX_FAIL(VX_E_SHAPE, "vx_ssn2d_lowres: batch too large");
   if (!mean || !comb || (R > 0 && !factor)) VX_FAIL(VX_E_NULL, "vx_ssn2d_lowres: null pointer");
   const int64_t total = (int64_t)B * pix_per_image * C;
   int bx = (int)((total + 255) / 256);

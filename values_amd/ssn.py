@@ -97,5 +97,7 @@ class SsnUNet3D(UNet3D):
         if not enable_concat:
             raise NotImplementedError("values_amd.SsnUNet3D: enable_concat=False is training-only")
         head = self._run(x, **kw).float()
+        if mean_only:   # rank 0: vx_ssn_sample strides an image's head by (2 + R) * C planes, so the factor planes must go
+            head = head[:, :2 * self.num_classes].contiguous()
         dist = LowRankNormal(head, self.num_classes, 0 if mean_only else self.rank, self.epsilon, self.seed + self._calls)
         return dist
