@@ -1050,7 +1050,8 @@ int vx_rgb_to_trainid(const uint8_t* rgb, int64_t n, const uint32_t* table /* de
 enum {
   VX_LZW_OK = 0,
   VX_LZW_TRUNCATED = 1,   /* the input ends before EndOfInformation or a full window */
-  VX_LZW_BAD_CODE = 2     /* a code above the next free entry, or a first code that is not ClearCode (the LSB-first variant) */
+  VX_LZW_BAD_CODE = 2,    /* a code above the next free entry, or a first code that is not ClearCode (the LSB-first variant) */
+  VX_LZW_NO_ROOM = 3      /* vx_tiff_lzw_encode: the item's window is smaller than its strip */
 };
 typedef struct vx_tiff_lzw_item {
   const uint8_t* src;
@@ -1072,6 +1073,51 @@ typedef struct vx_tiff_unpredict_item {
 int64_t vx_tiff_unpredict_workspace_bytes(int n_items);
 int vx_tiff_unpredict(const vx_tiff_unpredict_item* items /* host array */, int n_items, int32_t* out_status /* device */,
                       void* workspace, int64_t workspace_bytes, vx_stream_t stream);
+
+/* Writing LZW-compressed float32 TIFF maps (values_amd/results2d.py: save_images_device(tiff="lzw")) -- the strips of
+ * a Compression 5 file with Predictor 1, 2 or 3, byte for byte what image_io.write_tiff_f32(compression="lzw") writes.
+ * All three calls upload a table and synchronise the stream before they launch, as vx_tiff_lzw: not capturable into a
+ * hipGraph.  The return value is reserved for argument errors (refused before any launch) and hipError_t.
+ *
+ * vx_tiff_predict: the forward of vx_tiff_unpredict, with its item.  Per item, `rows` rows of W float32 samples at src
+ *   (device, 4 * rows * W bytes) go to dst (the same size) as the bytes the strips hold; rows are independent.
+ *   predictor 2  within a row word[i] -= word[i - 1] mod 2^32 on the little-endian 32-bit words;
+ *   predictor 3  libtiff's fpDiff: the row's four byte planes, the most significant bytes first, then
+ *                byte[i] -= byte[i - 1] mod 256 over all 4 W bytes.
+ *   Any W >= 1 and any alignment of src and dst; src and dst may not overlap (not in place either).  out_status[i]
+ *   (device) is set to VX_LZW_OK: no input makes an item fail.  Refused: a null table or pointer, rows or W < 1, a
+ *   predictor other than 2 / 3, overlapping src and dst, a workspace below vx_tiff_predict_workspace_bytes(n_items).
+ * vx_tiff_lzw_bound: the largest strip n >= 0 input bytes can produce: at most n data codes, one ClearCode at the start
+ *   and one more per 3836 table insertions (of which there are fewer than n), one EndOfInformation, each at most 12 bits:
+ *   (12 * (n + n / 3836 + 2) + 7) / 8.  -1 for n < 0.
+ * vx_tiff_lzw_encode: encodes each item's bytes src[0, src_n) (device) as one LZW strip (TIFF 6.0 section 13 with
+ *   libtiff's policy: ClearCode first, greedy longest match, codes MSB first, 9 to 12 bits, early change, a ClearCode
+ *   when the next free entry would be 4094, EndOfInformation, the last byte zero-padded; an empty input is ClearCode +
+ *   EndOfInformation, 3 bytes) into dst[dst_off, dst_off + dst_cap); the item table is vx_tiff_lzw's, read the other
+ *   way round.  out_sizes[i] (device) is the strip's length and out_status[i] (device) VX_LZW_OK; a window smaller than
+ *   the strip (dst_cap < vx_tiff_lzw_bound(src_n) may be one) ends the item with VX_LZW_NO_ROOM, out_sizes[i] = dst_cap
+ *   and the strip's first dst_cap bytes in the window.  No read outside [src, src + src_n); no write
+ *   outside the item's window and none at or beyond its out_sizes[i] bytes: the packer's last partial word is stored
+ *   byte by byte.  Items are independent: an item's bytes do not depend on what else the call holds.  The windows must
+ *   not overlap each other or any source.  workspace: vx_tiff_lzw_encode_workspace_bytes(n_items) bytes, 16-byte aligned.
+ * vx_tiff_lzw_pack: makes the strips contiguous.  The items name the strips' windows src[dst_off, dst_off + dst_cap)
+ *   in the order the blob holds them (a file's strips in row order, file after file), sizes[i] (device: the encoder's
+ *   out_sizes) their lengths, read as clamped to [0, dst_cap].  out_offsets (device, n_items + 1) receives the exclusive
+ *   scan of the sizes, out_offsets[n_items] the blob's size; strip i is copied to out[out_offsets[i], + sizes[i]) unless
+ *   it would end beyond out_n (out_n >= the sum of the dst_cap always suffices).  src and out may not overlap.
+ *   workspace: vx_tiff_lzw_pack_workspace_bytes(n_items) bytes, 16-byte aligned. */
+int64_t vx_tiff_predict_workspace_bytes(int n_items);
+int vx_tiff_predict(const vx_tiff_unpredict_item* items /* host array */, int n_items, int32_t* out_status /* device */,
+                    void* workspace, int64_t workspace_bytes, vx_stream_t stream);
+int64_t vx_tiff_lzw_bound(int64_t n);
+int64_t vx_tiff_lzw_encode_workspace_bytes(int n_items);
+int vx_tiff_lzw_encode(const vx_tiff_lzw_item* items /* host array */, int n_items, uint8_t* dst, int64_t dst_n,
+                       int64_t* out_sizes /* device */, int32_t* out_status /* device */, void* workspace,
+                       int64_t workspace_bytes, vx_stream_t stream);
+int64_t vx_tiff_lzw_pack_workspace_bytes(int n_items);
+int vx_tiff_lzw_pack(const vx_tiff_lzw_item* items /* host array */, int n_items, const uint8_t* src, int64_t src_n,
+                     const int64_t* sizes /* device */, uint8_t* out, int64_t out_n, int64_t* out_offsets /* device */,
+                     void* workspace, int64_t workspace_bytes, vx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -185,6 +185,7 @@ class TiffUnpredictItem(C.Structure):
 
 VX_LZW_OK, VX_LZW_TRUNCATED, VX_LZW_BAD_CODE = 0, 1, 2
 LZW_STATUS = ("ok", "truncated", "bad code")
+VX_LZW_NO_ROOM = 3   # vx_tiff_lzw_encode alone: the item's window is smaller than its strip
 
 
 VX_AGG_IMAGE, VX_AGG_THRESHOLD, VX_AGG_PATCH = 0, 1, 2
@@ -358,6 +359,13 @@ SIGNATURES = {
     "vx_tiff_lzw": (_i, [C.POINTER(TiffLzwItem), _i, _p, _i64, _p, _p, _p, _i64, _p]),
     "vx_tiff_unpredict_workspace_bytes": (_i64, [_i]),
     "vx_tiff_unpredict": (_i, [C.POINTER(TiffUnpredictItem), _i, _p, _p, _i64, _p]),
+    "vx_tiff_predict_workspace_bytes": (_i64, [_i]),
+    "vx_tiff_predict": (_i, [C.POINTER(TiffUnpredictItem), _i, _p, _p, _i64, _p]),
+    "vx_tiff_lzw_bound": (_i64, [_i64]),
+    "vx_tiff_lzw_encode_workspace_bytes": (_i64, [_i]),
+    "vx_tiff_lzw_encode": (_i, [C.POINTER(TiffLzwItem), _i, _p, _i64, _p, _p, _p, _i64, _p]),
+    "vx_tiff_lzw_pack_workspace_bytes": (_i64, [_i]),
+    "vx_tiff_lzw_pack": (_i, [C.POINTER(TiffLzwItem), _i, _p, _i64, _p, _p, _i64, _p, _p, _i64, _p]),
 }
 
 _lib = None

@@ -3,8 +3,8 @@
 The reference writes the 2D outputs with OpenCV (test_2D.py:116-159): `cv2.imwrite(<id>_NN.png, BGR colour image)` for
 the arg-max masks and `cv2.imwrite(<id>.tif, float32 map)` for the uncertainty maps, and the evaluation side reads them
 back with cv2.imread.  OpenCV is not a dependency here; these writers produce standard files any reader (OpenCV,
-PIL, tifffile) decodes to the same arrays.  Byte streams are not the same as OpenCV's (different deflate / no LZW):
-parity is on decoded content.  CPU I/O code -- not on the GPU path.
+PIL, tifffile) decodes to the same arrays.  Byte streams are not the same as OpenCV's (different deflate; the TIFFs are
+uncompressed unless compression="lzw" is asked for): parity is on decoded content.  CPU I/O code -- not on the GPU path.
 """
 from __future__ import annotations
 
@@ -120,15 +120,149 @@ def tiff_f32_parts(h: int, w: int):
     return b"II*\x00" + struct.pack("<I", ifd_off), pad + ifd
 
 
-def write_tiff_f32(path, img: np.ndarray) -> None:
-    """img (H, W) float32 -> baseline little-endian TIFF: one strip, uncompressed, SampleFormat = IEEE float."""
+def lzw_bound(n: int) -> int:
+    """The largest strip lzw_encode makes of n bytes (vx_tiff_lzw_bound): at most n data codes, one ClearCode at the start
+    and one more per 3836 table insertions, one EndOfInformation, each at most 12 bits."""
+    return (12 * (n + n // 3836 + 2) + 7) // 8
+
+
+def lzw_encode(data) -> bytes:
+    """data -> a TIFF LZW strip (TIFF 6.0 section 13 with libtiff's policy: ClearCode 256 first, greedy longest match,
+    codes MSB first, 9 to 12 bits, early change, a ClearCode when the next free entry would be 4094, EndOfInformation 257,
+    the last byte zero-padded).  Greedy matching with a fixed reset rule has one output per input: the device encoder
+    (vx_tiff_lzw_encode) writes the same bytes.  Plain Python like lzw_decode: a reference writer, correct and not fast."""
+    out = bytearray()
+    acc = nacc = 0
+    table = {}
+    nxt, k = 258, 0       # the next free entry; codes since the last ClearCode
+    width = 9             # of the next code: the decoder's next free entry is 258 + k - 1 when it reads it
+
+    def put(code):
+        nonlocal acc, nacc
+        acc = (acc << width) | code
+        nacc += width
+        while nacc >= 8:
+            nacc -= 8
+            out.append((acc >> nacc) & 0xFF)
+        acc &= (1 << nacc) - 1
+
+    put(256)
+    w = -1
+    for c in bytes(data):
+        if w < 0:
+            w = c
+            continue
+        key = (w << 8) | c
+        hit = table.get(key)
+        if hit is not None:
+            w = hit
+            continue
+        put(w)
+        k += 1
+        nfree = 258 + k - 1
+        width = 9 + (nfree >= 511) + (nfree >= 1023) + (nfree >= 2047)
+        table[key] = nxt
+        nxt += 1
+        w = c
+        if nxt >= 4094:
+            put(256)
+            table, nxt, k, width = {}, 258, 0, 9
+    if w >= 0:
+        put(w)
+        k += 1
+        nfree = 258 + k - 1
+        width = 9 + (nfree >= 511) + (nfree >= 1023) + (nfree >= 2047)
+    put(257)
+    if nacc:
+        out.append((acc << (8 - nacc)) & 0xFF)
+    return bytes(out)
+
+
+def _predict(m: np.ndarray, predictor: int) -> np.ndarray:
+    """the forward predictor of tag 317 on the (h, w) float32 map m -> (h, 4 w) uint8, the bytes the strips of a
+    little-endian file hold (the inverse of _unpredict)"""
+    h, w = m.shape
+    if predictor == 1:
+        return np.ascontiguousarray(m, dtype="<f4").view(np.uint8).reshape(h, 4 * w)
+    if predictor == 2:       # horizontal differencing on the 32-bit words
+        words = np.ascontiguousarray(m, dtype=np.float32).view(np.uint32)
+        d = words.copy()
+        d[:, 1:] -= words[:, :-1]
+        return np.ascontiguousarray(d.astype("<u4")).view(np.uint8).reshape(h, 4 * w)
+    # 3, libtiff's fpDiff: the row's four byte planes, the most significant bytes first, then a byte difference over the row
+    planes = np.ascontiguousarray(np.ascontiguousarray(m, dtype=">f4").view(np.uint8).reshape(h, w, 4).transpose(0, 2, 1)).reshape(h, 4 * w)
+    d = planes.copy()
+    d[:, 1:] -= planes[:, :-1]
+    return d
+
+
+def tiff_rows_per_strip(h: int, w: int, rows_per_strip=None) -> int:
+    """RowsPerStrip of an LZW file: the argument capped at h, by default libtiff's 8 KiB rule max(1, 8192 // (4 w))"""
+    rps = max(1, 8192 // (4 * w)) if rows_per_strip is None else int(rows_per_strip)
+    if rps < 1:
+        raise ValueError(f"write_tiff_f32: rows_per_strip={rows_per_strip}")
+    return min(rps, h)
+
+
+def tiff_lzw_parts(h: int, w: int, strip_sizes, rows_per_strip: int, predictor: int):
+    """(head, tail) of write_tiff_f32(compression="lzw")'s file for an (h, w) float32 map whose LZW strips have the given
+    sizes: the file is head + the strips back to back from offset 8 in row order + tail (a pad byte where the IFD would
+    start at an odd offset, the IFD, then the StripOffsets and StripByteCounts arrays; with one strip both are inline).
+    The 2D device writer (results2d.save_images_device(tiff="lzw")) wraps the strips it copies back in these."""
+    sizes = [int(v) for v in strip_sizes]
+    n = len(sizes)
+    if predictor not in (1, 2, 3):
+        raise ValueError(f"write_tiff_f32: predictor={predictor}: 1, 2 or 3")
+    if rows_per_strip < 1 or n != -(-h // rows_per_strip):
+        raise ValueError(f"write_tiff_f32: {n} strips for {h} rows of {rows_per_strip} per strip")
+    offs, o = [], 8
+    for v in sizes:
+        offs.append(o)
+        o += v
+    pad = b"\x00" * (o % 2)
+    ifd_off = o + len(pad)
+    ntags = 12
+    extra_off = ifd_off + 2 + 12 * ntags + 4
+    tags = [  # (tag, type, count, value)   type 3 = SHORT, 4 = LONG
+        (256, 4, 1, w), (257, 4, 1, h), (258, 3, 1, 32), (259, 3, 1, 5), (262, 3, 1, 1),
+        (273, 4, n, offs[0] if n == 1 else extra_off), (277, 3, 1, 1), (278, 4, 1, rows_per_strip),
+        (279, 4, n, sizes[0] if n == 1 else extra_off + 4 * n), (284, 3, 1, 1), (317, 3, 1, predictor), (339, 3, 1, 3),
+    ]
+    ifd = struct.pack("<H", ntags)
+    for tag, typ, cnt, val in tags:
+        ifd += struct.pack("<HHI", tag, typ, cnt) + (struct.pack("<HH", val, 0) if typ == 3 else struct.pack("<I", val))
+    ifd += struct.pack("<I", 0)
+    if n > 1:
+        ifd += struct.pack(f"<{n}I", *offs) + struct.pack(f"<{n}I", *sizes)
+    return b"II*\x00" + struct.pack("<I", ifd_off), pad + ifd
+
+
+def write_tiff_f32(path, img: np.ndarray, compression=None, predictor: int = 3, rows_per_strip=None) -> None:
+    """img (H, W) float32 -> a little-endian TIFF, SampleFormat = IEEE float.  compression=None: baseline, one
+    uncompressed strip (predictor and rows_per_strip are not looked at).  compression="lzw": Compression 5 with Predictor
+    1, 2 (horizontal differencing) or 3 (floating point), what libtiff writes; strips of rows_per_strip rows (default:
+    libtiff's 8 KiB rule, max(1, 8192 // (4 W)), capped at H; the last strip may be shorter), laid out as tiff_lzw_parts
+    says."""
     a = np.ascontiguousarray(img, dtype="<f4")
     if a.ndim != 2:
         raise ValueError("write_tiff_f32: (H, W) expected")
-    head, tail = tiff_f32_parts(*a.shape)
+    if compression is None:
+        head, tail = tiff_f32_parts(*a.shape)
+        body = [a.tobytes()]
+    elif compression == "lzw":
+        h, w = a.shape
+        if predictor not in (1, 2, 3):
+            raise ValueError(f"write_tiff_f32: predictor={predictor}: 1, 2 or 3")
+        rps = tiff_rows_per_strip(h, w, rows_per_strip)
+        rows = _predict(a, predictor)
+        body = [lzw_encode(rows[r:r + rps].tobytes()) for r in range(0, h, rps)]
+        head, tail = tiff_lzw_parts(h, w, [len(b) for b in body], rps, predictor)
+    else:
+        raise ValueError(f"write_tiff_f32: compression={compression!r}: None or \"lzw\"")
     with open(path, "wb") as f:
         f.write(head)
-        f.write(a.tobytes())
+        for b in body:
+            f.write(b)
         f.write(tail)
 
 

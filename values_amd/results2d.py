@@ -10,9 +10,16 @@ with values_amd.image_io.
 
 save_images_device / ResultsWriter2D write the same tree from the device: one vx_png_encode call builds every PNG file of a
 batch (colour lookup, scanlines, DEFLATE, zlib and PNG framing) and the host only copies the finished bytes back.
+
+The uncertainty maps are uncompressed single-strip TIFFs by default.  With compression="lzw" (save_uncertainty) /
+tiff="lzw" (save_images_device, ResultsWriter2D) they are LZW strip TIFFs with Predictor 1, 2 or 3 -- the file libtiff
+writes for cv2.imwrite, read by image_io.read_tiff_f32, images.load_tiff_device, PIL and OpenCV alike -- and the device
+writers compress them on the GPU (vx_tiff_predict, vx_tiff_lzw_encode, vx_tiff_lzw_pack): only the compressed bytes
+come back.  Host and device writers produce the same bytes.
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import os
 from typing import Dict, List, NamedTuple, Optional, Sequence
@@ -21,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _devio, _lib
-from .image_io import tiff_f32_parts, write_png, write_tiff_f32
+from .image_io import lzw_bound, tiff_f32_parts, tiff_lzw_parts, tiff_rows_per_strip, write_png, write_tiff_f32
 
 UNLABELED = 255  # cs_labels.name2trainId["unlabeled"]
 TRAINID2COLOR = {
@@ -79,13 +86,15 @@ def save_prediction(save_pred_dir: str, image_id: str, pred_masks: torch.Tensor,
         write_png(os.path.join(save_pred_dir, f"{name}.png"), img)
 
 
-def save_uncertainty(save_dir: str, image_id: str, uncertainty_dict: Dict[str, torch.Tensor]) -> None:
-    """test_2D.py:151-158: one float32 TIFF per uncertainty type."""
+def save_uncertainty(save_dir: str, image_id: str, uncertainty_dict: Dict[str, torch.Tensor], compression=None, predictor: int = 3,
+                     rows_per_strip=None) -> None:
+    """test_2D.py:151-158: one float32 TIFF per uncertainty type.  compression, predictor, rows_per_strip: as
+    image_io.write_tiff_f32 takes them (None: uncompressed; "lzw": what the reference's cv2.imwrite writes)."""
     for unc_type, unc_map in uncertainty_dict.items():
         d = os.path.join(save_dir, unc_type)
         os.makedirs(d, exist_ok=True)
         m = unc_map.detach().cpu().numpy() if isinstance(unc_map, torch.Tensor) else np.asarray(unc_map)
-        write_tiff_f32(os.path.join(d, f"{image_id}.tif"), m.astype(np.float32))
+        write_tiff_f32(os.path.join(d, f"{image_id}.tif"), m.astype(np.float32), compression, predictor, rows_per_strip)
 
 
 def save_results_dict(save_dir: str, results_dict: Dict[str, Dict]) -> Dict[str, Dict]:
@@ -191,10 +200,79 @@ def png_encode(masks: Sequence[torch.Tensor], ignores: Optional[Sequence] = None
     return [host[o:o + k].tobytes() for o, k in zip(pl[:n], pl[n:])]
 
 
-def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, timing=None):
+_LZW_ITEM = np.dtype([("src", "<u8"), ("src_n", "<i8"), ("dst_off", "<i8"), ("dst_cap", "<i8")])   # vx_tiff_lzw_item
+_UNPREDICT_ITEM = np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("W", "<i4"), ("predictor", "<i4"), ("pad", "<i4")])
+
+
+def _tiff_strips(shapes, rows_per_strip):
+    """The LZW strips of a batch of (h, w) maps lying back to back: -> (per map (rows per strip, number of strips), table
+    of vx_tiff_lzw_item whose src is the strip's byte offset in the maps, bytes of the windows)"""
+    layout, parts, base, off = [], [], 0, 0
+    for h, w in shapes:
+        rps = tiff_rows_per_strip(h, w, rows_per_strip)
+        r0 = np.arange(0, h, rps, dtype=np.int64)
+        it = np.zeros(len(r0), dtype=_LZW_ITEM)
+        it["src"] = base + 4 * w * r0
+        it["src_n"] = 4 * w * np.minimum(rps, h - r0)
+        it["dst_cap"] = lzw_bound(it["src_n"])
+        win = (it["dst_cap"] + 15) // 16 * 16   # every window starts at a multiple of 16: whole-word stores
+        it["dst_off"] = off + np.cumsum(win) - win
+        off += int(win.sum())
+        base += 4 * h * w
+        layout.append((rps, len(r0)))
+        parts.append(it)
+    return layout, np.concatenate(parts), off
+
+
+def _tiff_lzw_launch(bufs, flat, shapes, items, win_bytes, predictor, sizes, status, offsets, dev, ev):
+    """The maps `flat` (float32, back to back, of the given shapes) to LZW strips: vx_tiff_predict over all maps (predictor
+    2 / 3), vx_tiff_lzw_encode over all strips, vx_tiff_lzw_pack -> the device buffer that holds the strips back to back.
+    sizes, status, offsets: device views that receive the strips' sizes, statuses and places in the blob."""
+    lib = _lib.load()
+    n = len(items)
+    src = flat
+    if ev:
+        ev[0].record()
+    if predictor != 1:
+        src = bufs.get("tif_pred", 4 * flat.numel(), dev)
+        pi = np.zeros(len(shapes), dtype=_UNPREDICT_ITEM)
+        o = 0
+        for k, (h, w) in enumerate(shapes):
+            pi[k] = (flat.data_ptr() + o, src.data_ptr() + o, h, w, predictor, 0)
+            o += 4 * h * w
+        pst = bufs.get("tif_pst", 4 * len(shapes), dev)
+        ws = bufs.get("tif_pws", int(lib.vx_tiff_predict_workspace_bytes(len(shapes))), dev)
+        _lib.check(lib.vx_tiff_predict(pi.ctypes.data_as(ctypes.POINTER(_lib.TiffUnpredictItem)), len(shapes), pst.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "vx_tiff_predict")
+    if ev:
+        ev[1].record()
+    items = items.copy()
+    items["src"] += src.data_ptr()
+    table = items.ctypes.data_as(ctypes.POINTER(_lib.TiffLzwItem))
+    enc = bufs.get("tif_enc", win_bytes, dev)
+    ws = bufs.get("tif_ws", max(int(lib.vx_tiff_lzw_encode_workspace_bytes(n)), int(lib.vx_tiff_lzw_pack_workspace_bytes(n))), dev)
+    _lib.check(lib.vx_tiff_lzw_encode(table, n, enc.data_ptr(), win_bytes, sizes.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw_encode")
+    if ev:
+        ev[2].record()
+    packed = bufs.get("tif_pack", win_bytes, dev)
+    _lib.check(lib.vx_tiff_lzw_pack(table, n, enc.data_ptr(), win_bytes, sizes.data_ptr(), packed.data_ptr(), win_bytes,
+                                    offsets.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw_pack")
+    if ev:
+        ev[3].record()
+    return packed
+
+
+def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, timing=None, tiff=None,
+                   tiff_predictor=3, tiff_rows_per_strip=None):
     """vx_png_encode over every mask of the batch + one small read of the file sizes + one copy of the PNG bytes and one
     of the uncertainty maps into pinned memory: -> (plan, host uint8 array, [(offset, size)] per planned PNG file,
-    [(offset, size, head, tail)] per TIFF)"""
+    [(offset, size, head, tail)] per TIFF).  tiff="lzw": the maps are compressed on the device (_tiff_lzw_launch), the
+    strips' sizes come back in the same small read and the compressed bytes take the maps' place in the copy."""
+    if tiff not in (None, "lzw"):
+        raise ValueError(f"save_images_device: tiff={tiff!r}: None or \"lzw\"")
+    if tiff == "lzw" and tiff_predictor not in (1, 2, 3):
+        raise ValueError(f"save_images_device: tiff_predictor={tiff_predictor}: 1, 2 or 3")
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     pm = _as_device(pred_masks, dev, torch.uint8)
@@ -225,8 +303,17 @@ def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_
         entries.append((lab.data_ptr(), ign[b].data_ptr() if ign is not None else None, H, W))
     items, bound, ws_bytes = _png_table(entries)
     n = len(pngs)
+    lzw = tiff == "lzw" and bool(unc)
+    shapes = [tuple(int(v) for v in unc[k].shape[1:]) for _ in range(B) for k in unc]   # the maps in plan order
+    ns = 0
+    if lzw:
+        layout, strips, win_bytes = _tiff_strips(shapes, tiff_rows_per_strip)
+        ns = len(strips)
     dst = bufs.get("png", bound, dev)
-    place = bufs.get("place", 16 * n, dev)[:16 * n].view(torch.int64)
+    # [PNG offsets | PNG sizes | strip sizes | strip places, the blob's size] int64, then the strips' statuses int32
+    place_bytes = 16 * n + (8 * (2 * ns + 1) + 4 * ns if lzw else 0)
+    place_all = bufs.get("place", place_bytes, dev)[:place_bytes]
+    place = place_all[:16 * n].view(torch.int64)
     ws = bufs.get("png_ws", ws_bytes, dev)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing is not None else None
     if ev:
@@ -235,35 +322,64 @@ def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_
     if ev:
         ev[1].record()
     flat = torch.cat([unc[k][b].reshape(-1) for b in range(B) for k in unc]) if unc else None
-    pl = place.cpu().tolist()              # the one small read: synchronises the stream
+    tev = None
+    if lzw:
+        tev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing is not None else None
+        tail = place_all[16 * n:]
+        packed = _tiff_lzw_launch(bufs, flat, shapes, strips, win_bytes, tiff_predictor, tail[:8 * ns].view(torch.int64),
+                                  tail[8 * (2 * ns + 1):].view(torch.int32), tail[8 * ns:8 * (2 * ns + 1)].view(torch.int64), dev, tev)
+    pl_host = place_all.cpu()              # the one small read: synchronises the stream
+    pl = pl_host[:16 * n].view(torch.int64).tolist()
     offs, sizes = pl[:n], pl[n:]
     png_bytes = offs[-1] + sizes[-1]
     unc0 = (png_bytes + 15) // 16 * 16
-    total = unc0 + (4 * flat.numel() if flat is not None else 0)
+    if lzw:
+        ssz = pl_host[16 * n:16 * n + 8 * ns].view(torch.int64).tolist()
+        bad = [i for i, v in enumerate(pl_host[16 * n + 8 * (2 * ns + 1):].view(torch.int32).tolist()) if v != _lib.VX_LZW_OK]
+        if bad:
+            raise RuntimeError(f"save_images_device: vx_tiff_lzw_encode: strip {bad[0]} of the batch did not fit its window")
+        unc_bytes = sum(ssz)
+    else:
+        unc_bytes = 4 * flat.numel() if flat is not None else 0
+    total = unc0 + unc_bytes
     host = bufs.get("host", total, dev, pinned=True)
     host[:png_bytes].copy_(dst[:png_bytes])
-    if flat is not None:
+    if lzw:
+        host[unc0:total].copy_(packed[:unc_bytes])
+    elif flat is not None:
         host[unc0:total].copy_(flat.view(torch.uint8))
     if ev:
         timing["encode_ms"] = timing.get("encode_ms", 0.0) + ev[0].elapsed_time(ev[1])
         timing["raw_bytes"] = timing.get("raw_bytes", 0) + n * H * (3 * W + 1)
         timing["png_bytes"] = timing.get("png_bytes", 0) + png_bytes
-    spans, k, u = [], 0, unc0
+        timing["tiff_raw_bytes"] = timing.get("tiff_raw_bytes", 0) + (4 * flat.numel() if flat is not None else 0)
+        timing["tiff_bytes"] = timing.get("tiff_bytes", 0) + unc_bytes
+    if tev:
+        for key, a, b in zip(("tiff_predict_ms", "tiff_encode_ms", "tiff_pack_ms"), tev, tev[1:]):
+            timing[key] = timing.get(key, 0.0) + a.elapsed_time(b)
+    spans, k, u, t, s0 = [], 0, unc0, 0, 0
     for f in plan:
         if f.kind == "png":
             spans.append((offs[k], sizes[k]))
             k += 1
-        else:
-            m = unc[f.source[1]]
-            nb = 4 * int(m[f.source[2]].numel())
-            h, w = (int(v) for v in m.shape[1:])
-            spans.append((u, nb) + tiff_f32_parts(h, w))   # TIFF: host-built header + the map's bytes + IFD
-            u += nb
+            continue
+        h, w = shapes[t]
+        if lzw:    # TIFF: host-built header + the map's strips + IFD and strip table
+            rps, cnt = layout[t]
+            mine = ssz[s0:s0 + cnt]
+            nb = sum(mine)
+            spans.append((u, nb) + tiff_lzw_parts(h, w, mine, rps, tiff_predictor))
+            s0 += cnt
+        else:      # TIFF: host-built header + the map's bytes + IFD
+            nb = 4 * h * w
+            spans.append((u, nb) + tiff_f32_parts(h, w))
+        u += nb
+        t += 1
     return plan, host.numpy(), spans
 
 
 def save_images_device(save_dir: str, image_ids: Sequence[str], pred_masks, mean_masks, uncertainty: Optional[Dict] = None,
-                       ignore_index_map=None, _timing=None) -> None:
+                       ignore_index_map=None, _timing=None, tiff=None, tiff_predictor: int = 3, tiff_rows_per_strip=None) -> None:
     """Writes the tree save_prediction(<save_dir>/pred_seg, id, pred_masks[b], mean_masks[b], ignore) and
     save_uncertainty(<save_dir>, id, {name: map[b]}) write for every image b of a batch, with the same names, the same
     decoded PNG pixels and byte-identical TIFFs.
@@ -278,19 +394,32 @@ def save_images_device(save_dir: str, image_ids: Sequence[str], pred_masks, mean
                            {k: out[k] for k in ("pred_entropy", "aleatoric_uncertainty", "epistemic_uncertainty") if k in out})
 
     One vx_png_encode call encodes all B (N + 1) masks (B N with one prediction); one small read brings back the file
-    sizes, then the PNG bytes and the uncertainty maps come back in one copy each into reused pinned memory."""
+    sizes, then the PNG bytes and the uncertainty maps come back in one copy each into reused pinned memory.
+
+    tiff=None: uncompressed TIFFs, the bytes of write_tiff_f32(path, map).  tiff="lzw": the bytes of write_tiff_f32(path, map,
+    "lzw", tiff_predictor, tiff_rows_per_strip) -- LZW strips with Predictor 1, 2 or 3 -- compressed on the device: one
+    vx_tiff_predict call over all maps (not for predictor 1), one vx_tiff_lzw_encode call over all strips of all maps, one
+    vx_tiff_lzw_pack; the strips' sizes join the small read and only the compressed bytes are copied back.  The PNG files
+    are the same bytes either way."""
     _devio.save_once(save_dir, ("pred_seg",), _encode_images, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map,
-                     _timing)
+                     _timing, tiff, tiff_predictor, tiff_rows_per_strip)
 
 
 class ResultsWriter2D(_devio.PipelinedWriter):
     """Pipelined save_images_device: submit() encodes a batch on the GPU and hands its files to a small thread pool, so
     the files of batch i are written while batch i + 1 is encoded.  Two buffer sets alternate; a set is reused only once
-    its files are written.  close() (or leaving the `with` block) waits and re-raises the first write error."""
+    its files are written.  close() (or leaving the `with` block) waits and re-raises the first write error.
+    tiff, tiff_predictor, tiff_rows_per_strip: as save_images_device takes them, for every batch of this writer."""
 
     _encode = staticmethod(_encode_images)
     _dirs = ("pred_seg",)
 
+    def __init__(self, workers: int = 4, tiff=None, tiff_predictor: int = 3, tiff_rows_per_strip=None):
+        if tiff not in (None, "lzw"):
+            raise ValueError(f"ResultsWriter2D: tiff={tiff!r}: None or \"lzw\"")
+        super().__init__(workers)
+        self._tiff = (tiff, tiff_predictor, tiff_rows_per_strip)
+
     def submit(self, save_dir: str, image_ids: Sequence[str], pred_masks, mean_masks, uncertainty: Optional[Dict] = None,
                ignore_index_map=None, _timing=None) -> None:
-        self._submit(save_dir, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, _timing)
+        self._submit(save_dir, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, _timing, *self._tiff)
