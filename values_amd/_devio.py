@@ -1,7 +1,9 @@
-"""What the device results writers (results.py: 3D, results2d.py: 2D) share: the grow-only buffer set of one case or
-batch in flight, the step that puts an encoded plan on disk, and the pipelined writer built on the two.  Below them, what
-the device readers (nifti.py: 3D, images.py: 2D) share: the pinned staging buffer of a batch, the pipelined reader, the
-one-shot loaders' shared reader, stage timing, and the batched decoder calls (gz.py, images.py).
+"""What the device results writers (results.py: 3D and maps, results2d.py: 2D) share: the grow-only buffer set of one case
+or batch in flight, `gather` (the encoded regions into the pinned host buffer), the TIFF stage (raw or LZW float32
+maps), the step that puts an encoded plan on disk, and the pipelined writer built on them.  Below them, what the device
+readers (nifti.py: 3D, images.py: 2D) share: the pinned staging buffer of a batch, the pipelined reader, the one-shot
+loaders' shared reader, and the batched decoder calls (gz.py, images.py).  Writers and readers time their stages with
+`Stages`.
 
 An encoder is a function (bufs, *arguments) -> (plan, host, spans): the planned files (each with a `path` relative to the
 save directory), the pinned host array their bytes were copied into, and per file the arguments of write_span after the
@@ -9,11 +11,15 @@ array: (offset, size) or (offset, size, head, tail).
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
+
 from . import _lib
+from .image_io import lzw_bound, tiff_f32_parts, tiff_lzw_parts, tiff_rows_per_strip
 
 
 class Buffers:
@@ -30,6 +36,158 @@ class Buffers:
             b = torch.empty(n, dtype=torch.uint8, pin_memory=True) if pinned else torch.empty(n, dtype=torch.uint8, device=dev)
             self.t[name] = b
         return b
+
+
+class Stages:
+    """GPU time of the stages of an encode or a decode, added into a `timing` dict (None: nothing is recorded): mark()
+    before the first stage and after every stage, then add(keys, counters) adds the milliseconds between consecutive
+    marks to timing[key] (a key of None: that interval is no stage) and every counter (bytes) to timing[its name]."""
+
+    def __init__(self, timing):
+        self.timing = timing
+        self.marks = []
+
+    def mark(self):
+        if self.timing is not None:
+            import torch
+            self.marks.append(torch.cuda.Event(enable_timing=True))
+            self.marks[-1].record()
+
+    def add(self, keys, counters):
+        if self.timing is not None:
+            self.marks[-1].synchronize()
+            for k, a, b in zip(keys, self.marks, self.marks[1:]):
+                if k is not None:
+                    self.timing[k] = self.timing.get(k, 0.0) + a.elapsed_time(b)
+            for k, v in counters.items():
+                self.timing[k] = self.timing.get(k, 0) + v
+
+
+def gather(bufs, regions, dev):
+    """regions: (device uint8 tensor, nbytes) each -> (the buffer set's pinned host buffer as a numpy array, each region's base in it): the
+    regions at 16-byte multiples, one copy per region that holds bytes."""
+    bases, total = [], 0
+    for _, n in regions:
+        bases.append(total)
+        total += (n + 15) // 16 * 16
+    host = bufs.get("host", total, dev, pinned=True)
+    for (t, n), b in zip(regions, bases):
+        if n:
+            host[b:b + n].copy_(t[:n])
+    return host.numpy(), bases
+
+
+_LZW_ITEM = np.dtype([("src", "<u8"), ("src_n", "<i8"), ("dst_off", "<i8"), ("dst_cap", "<i8")])   # vx_tiff_lzw_item
+_UNPREDICT_ITEM = np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("W", "<i4"), ("predictor", "<i4"), ("pad", "<i4")])
+
+
+def _tiff_strips(shapes, rows_per_strip):
+    """The LZW strips of a batch of (h, w) maps lying back to back: -> (per map (rows per strip, number of strips), table
+    of vx_tiff_lzw_item whose src is the strip's byte offset in the maps, bytes of the windows)"""
+    layout, parts, base, off = [], [], 0, 0
+    for h, w in shapes:
+        rps = tiff_rows_per_strip(h, w, rows_per_strip)
+        r0 = np.arange(0, h, rps, dtype=np.int64)
+        it = np.zeros(len(r0), dtype=_LZW_ITEM)
+        it["src"] = base + 4 * w * r0
+        it["src_n"] = 4 * w * np.minimum(rps, h - r0)
+        it["dst_cap"] = lzw_bound(it["src_n"])
+        win = (it["dst_cap"] + 15) // 16 * 16   # every window starts at a multiple of 16: whole-word stores
+        it["dst_off"] = off + np.cumsum(win) - win
+        off += int(win.sum())
+        base += 4 * h * w
+        layout.append((rps, len(r0)))
+        parts.append(it)
+    return layout, np.concatenate(parts), off
+
+
+class TiffStage:
+    """The float32 TIFF maps of a batch, uncompressed (tiff=None) or as LZW strips with Predictor 1, 2 or 3 (tiff="lzw"),
+    planned from the maps' (h, w) shapes.  launch() puts the maps' file bytes -- all but the host-built ends -- into one
+    device region; with LZW the strips' sizes, their places in the region and their statuses go to `place`, place_bytes
+    of a device buffer the caller reads back in its one small read; finish() then gives the region's bytes and each
+    map's (offset, size, head, tail).  `who` names the entry point in the messages."""
+
+    def __init__(self, who, shapes, tiff=None, predictor=3, rows_per_strip=None):
+        if tiff not in (None, "lzw"):
+            raise ValueError(f"{who}: tiff={tiff!r}: None or \"lzw\"")
+        if tiff == "lzw" and predictor not in (1, 2, 3):
+            raise ValueError(f"{who}: tiff_predictor={predictor}: 1, 2 or 3")
+        self.who, self.shapes, self.predictor = who, list(shapes), predictor
+        self.lzw = tiff == "lzw" and bool(self.shapes)
+        self.raw_bytes = sum(4 * h * w for h, w in self.shapes)
+        self.ns = 0
+        if self.lzw:
+            self.layout, self.strips, self.win_bytes = _tiff_strips(self.shapes, rows_per_strip)
+            self.ns = len(self.strips)
+        self.place_bytes = 8 * (2 * self.ns + 1) + 4 * self.ns if self.lzw else 0
+
+    def _place(self, buf):
+        """[strip sizes | strip places, the region's bytes] int64, then the strips' statuses int32: views of buf"""
+        import torch
+        a, b = 8 * self.ns, 8 * (2 * self.ns + 1)
+        return buf[:a].view(torch.int64), buf[a:b].view(torch.int64), buf[b:b + 4 * self.ns].view(torch.int32)
+
+    def launch(self, bufs, maps, place, dev, stages):
+        """maps: the (h, w) float32 device tensors -> the device region (uint8; None without maps).  LZW: vx_tiff_predict
+        over all maps (predictor 2 / 3), vx_tiff_lzw_encode over all strips, vx_tiff_lzw_pack, a mark of `stages`
+        before the first and after each."""
+        import torch
+        if not maps:
+            return None
+        flat = torch.cat([m.reshape(-1) for m in maps])
+        if not self.lzw:
+            return flat.view(torch.uint8)
+        lib, n, shapes = _lib.load(), self.ns, self.shapes
+        sizes, offsets, status = self._place(place)
+        src = flat
+        stages.mark()
+        if self.predictor != 1:
+            src = bufs.get("tif_pred", self.raw_bytes, dev)
+            pi = np.zeros(len(shapes), dtype=_UNPREDICT_ITEM)
+            o = 0
+            for k, (h, w) in enumerate(shapes):
+                pi[k] = (flat.data_ptr() + o, src.data_ptr() + o, h, w, self.predictor, 0)
+                o += 4 * h * w
+            pst = bufs.get("tif_pst", 4 * len(shapes), dev)
+            ws = bufs.get("tif_pws", int(lib.vx_tiff_predict_workspace_bytes(len(shapes))), dev)
+            _lib.check(lib.vx_tiff_predict(pi.ctypes.data_as(ctypes.POINTER(_lib.TiffUnpredictItem)), len(shapes), pst.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "vx_tiff_predict")
+        stages.mark()
+        items = self.strips.copy()
+        items["src"] += src.data_ptr()
+        table = items.ctypes.data_as(ctypes.POINTER(_lib.TiffLzwItem))
+        win_bytes = self.win_bytes
+        enc = bufs.get("tif_enc", win_bytes, dev)
+        ws = bufs.get("tif_ws", max(int(lib.vx_tiff_lzw_encode_workspace_bytes(n)), int(lib.vx_tiff_lzw_pack_workspace_bytes(n))), dev)
+        _lib.check(lib.vx_tiff_lzw_encode(table, n, enc.data_ptr(), win_bytes, sizes.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw_encode")
+        stages.mark()
+        packed = bufs.get("tif_pack", win_bytes, dev)
+        _lib.check(lib.vx_tiff_lzw_pack(table, n, enc.data_ptr(), win_bytes, sizes.data_ptr(), packed.data_ptr(), win_bytes,
+                                        offsets.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw_pack")
+        stages.mark()
+        return packed
+
+    def finish(self, place_host):
+        """place_host: the host copy of `place` -> (bytes of the region, per map (offset, size, head, tail))"""
+        if not self.lzw:
+            parts, u = [], 0
+            for h, w in self.shapes:   # TIFF: host-built header + the map's bytes + IFD
+                parts.append((u, 4 * h * w) + tiff_f32_parts(h, w))
+                u += 4 * h * w
+            return u, parts
+        sizes, _, status = (v.tolist() for v in self._place(place_host))
+        bad = [i for i, v in enumerate(status) if v != _lib.VX_LZW_OK]
+        if bad:
+            raise RuntimeError(f"{self.who}: vx_tiff_lzw_encode: strip {bad[0]} of the batch did not fit its window")
+        parts, u, s0 = [], 0, 0
+        for (h, w), (rps, cnt) in zip(self.shapes, self.layout):   # host-built header + the map's strips + IFD and strip table
+            mine = sizes[s0:s0 + cnt]
+            parts.append((u, sum(mine)) + tiff_lzw_parts(h, w, mine, rps, self.predictor))
+            u += sum(mine)
+            s0 += cnt
+        return u, parts
 
 
 def write_span(path, buf, off, n, head=b"", tail=b""):
@@ -142,7 +300,6 @@ class Staging:
 
     def upload(self, pieces, device):
         """pieces: as plan() takes them -> (device uint8 tensor, item offsets, item sizes)"""
-        import numpy as np
         import torch
         offs, sizes, off = plan(pieces)
         if self.event is not None:
@@ -164,28 +321,6 @@ class Staging:
 def current_device(device=None):
     import torch
     return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-class Stages:
-    """GPU time of the stages of a decode, added into a `timing` dict (None: nothing is recorded): mark() before the
-    first stage and after every stage, then add(keys) adds the milliseconds between consecutive marks to timing[key]."""
-
-    def __init__(self, timing):
-        self.timing = timing
-        self.marks = []
-
-    def mark(self):
-        if self.timing is not None:
-            import torch
-            self.marks.append(torch.cuda.Event(enable_timing=True))
-            self.marks[-1].record()
-
-    def add(self, keys, payload_bytes):
-        if self.timing is not None:
-            self.marks[-1].synchronize()
-            for k, a, b in zip(keys, self.marks, self.marks[1:]):
-                self.timing[k] = self.timing.get(k, 0.0) + a.elapsed_time(b)
-            self.timing["payload_bytes"] = self.timing.get("payload_bytes", 0) + payload_bytes
 
 
 def _read(path):

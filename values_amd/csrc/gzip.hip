@@ -17,7 +17,7 @@
 //     6. a non-final chunk ends byte aligned (an empty stored block after a Huffman block, as pigz does), so chunks
 //        concatenate without shifting; the chunk's CRC-32 is the slice CRCs joined with the GF(2) shift operator.
 //   gz_pack_kernel    (one workgroup per chunk): the chunk's offset in its member is the sum of the sizes of the chunks
-//     before it; it copies its bytes behind the 10-byte header, the first chunk writes the header and the last the
+//     before it; it copies its bytes behind the 10-byte header (pack_copy.h), the first chunk writes the header and the last the
 //     CRC-32 / ISIZE trailer and the member's size.
 //
 // The chunk kernel is compiled in deflate_chunk.hip and launched through deflate_chunk.h (shared with png.hip), the CRC-32
@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "deflate_chunk.h"
+#include "pack_copy.h"
 
 namespace {
 
@@ -50,16 +51,7 @@ __global__ __launch_bounds__(256) void gz_pack_kernel(const GzItemDev* __restric
   const uint64_t off = part[0];
   uint8_t* m = dst + it.dst_off;
   const uint32_t nb = meta[blockIdx.x].bytes;
-  const uint8_t* src = slots + (size_t)blockIdx.x * GZ_SLOT;
-  const uint32_t* src4 = reinterpret_cast<const uint32_t*>(src);
-  uint8_t* d = m + 10 + off;
-  for (uint32_t w = tid; w < (nb + 3) / 4; w += 256) {
-    const uint32_t v = src4[w];
-    const uint32_t b = w * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (b + j < nb) d[b + j] = (uint8_t)(v >> (8 * j));
-  }
+  vxpc::copy_bytes<256>(m + 10 + off, slots + (size_t)blockIdx.x * GZ_SLOT, nb);
   if (ch.index == 0 && tid < 10) {
     // ID1 ID2 CM=deflate FLG=0 MTIME=0 XFL=0 OS=255
     m[tid] = tid == 0 ? 0x1f : tid == 1 ? 0x8b : tid == 2 ? 8 : tid == 9 ? 255 : 0;

@@ -10,9 +10,9 @@
 //     then a tree join with adler_combine.
 //   gz_chunk_kernel     (deflate_chunk.hip, shared with gzip.hip): one byte-aligned raw DEFLATE fragment per
 //     chunk, stride hints (3, 3W + 1, 0): the previous pixel and the previous scanline.
-//   png_scan_kernel     (one workgroup): exclusive scan of the fragments' sizes over the whole batch.  File i starts at
+//   png_scan_kernel     (one workgroup): exclusive scan (pack_copy.h) of the fragments' sizes over the whole batch.  File i starts at
 //     the sum of the streams before it plus 63 bytes of framing per earlier file; out_offsets / out_sizes are written.
-//   png_pack_kernel     (one workgroup per chunk): copies its fragment behind the file's zlib header.
+//   png_pack_kernel     (one workgroup per chunk): copies its fragment behind the file's zlib header (pack_copy.h).
 //   png_frame_kernel    (one workgroup per file): signature, IHDR, the IDAT length, the zlib header 78 01, the
 //     big-endian Adler-32 (chunk Adlers joined in order), IEND; then the IDAT CRC-32 over "IDAT" + the zlib stream,
 //     which covers the packed bytes: lane slices, crc_join_block.
@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "deflate_chunk.h"
+#include "pack_copy.h"
 
 namespace {
 
@@ -124,28 +125,11 @@ __global__ __launch_bounds__(PNG_SCAN_LANES) void png_scan_kernel(const PngItemD
                                                                   int64_t* __restrict__ chunk_off,
                                                                   int64_t* __restrict__ out_offsets,
                                                                   int64_t* __restrict__ out_sizes) {
-  __shared__ uint64_t part[PNG_SCAN_LANES];
-  const int tid = threadIdx.x;
-  const int64_t per = (nch + PNG_SCAN_LANES - 1) / PNG_SCAN_LANES;
-  const int64_t a = min64(nch, per * tid), b = min64(nch, a + per);
-  uint64_t s = 0;
-  for (int64_t c = a; c < b; ++c) s += meta[c].bytes;
-  part[tid] = s;
-  __syncthreads();
-  // Hillis-Steele inclusive scan
-  for (int stride = 1; stride < PNG_SCAN_LANES; stride <<= 1) {
-    const uint64_t v = tid >= stride ? part[tid - stride] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  uint64_t run = part[tid] - s;
-  for (int64_t c = a; c < b; ++c) {
-    chunk_off[c] = (int64_t)run + (int64_t)PNG_FRAME * chunks[c].item + PNG_STREAM0;
-    run += meta[c].bytes;
-  }
+  vxpc::exclusive_scan<PNG_SCAN_LANES>(
+      nch, [&](int64_t c) { return (int64_t)meta[c].bytes; },
+      [&](int64_t c, int64_t run) { chunk_off[c] = run + (int64_t)PNG_FRAME * chunks[c].item + PNG_STREAM0; });
   __syncthreads();   // workgroup-scope fence: the chunk offsets written above are visible to every lane below
-  for (int i = tid; i < n_items; i += PNG_SCAN_LANES) {
+  for (int i = threadIdx.x; i < n_items; i += PNG_SCAN_LANES) {
     const PngItemDev it = items[i];
     const int last = it.first_chunk + it.nchunks - 1;
     const int64_t start = chunk_off[it.first_chunk] - PNG_STREAM0;
@@ -156,17 +140,7 @@ __global__ __launch_bounds__(PNG_SCAN_LANES) void png_scan_kernel(const PngItemD
 
 __global__ __launch_bounds__(256) void png_pack_kernel(const GzChunkMeta* __restrict__ meta, const int64_t* __restrict__ chunk_off,
                                                        const uint8_t* __restrict__ slots, uint8_t* __restrict__ dst) {
-  const int tid = threadIdx.x;
-  const uint32_t nb = meta[blockIdx.x].bytes;
-  const uint32_t* src4 = reinterpret_cast<const uint32_t*>(slots + (size_t)blockIdx.x * GZ_SLOT);
-  uint8_t* d = dst + chunk_off[blockIdx.x];
-  for (uint32_t w = tid; w < (nb + 3) / 4; w += 256) {
-    const uint32_t v = src4[w];
-    const uint32_t b = w * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (b + j < nb) d[b + j] = (uint8_t)(v >> (8 * j));
-  }
+  vxpc::copy_bytes<256>(dst + chunk_off[blockIdx.x], slots + (size_t)blockIdx.x * GZ_SLOT, meta[blockIdx.x].bytes);
 }
 
 __device__ __forceinline__ uint32_t crc_bytes(uint32_t c, const uint8_t* p, int n) {

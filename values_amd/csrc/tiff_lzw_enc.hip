@@ -27,9 +27,11 @@
 //   LDS per wave: table 32 KiB + window 2 KiB + staging 4 KiB (38 KiB): 4 waves per CU.
 //
 //   lzw_pack_scan_kernel  (one workgroup) exclusive scan of the strips' sizes in table order;
-//   lzw_pack_kernel       (workgroups over strips) copies each strip from its window to its place in the packed blob.
+//   lzw_pack_kernel       (workgroups over strips) copies each strip from its window to its place in the packed blob;
+//                         scan and copy are pack_copy.h's, shared with gzip.hip and png.hip.
 //
 // Every store in this file is a plain C++ store of a vector register.
+#include "pack_copy.h"
 #include "stream_items.h"
 
 #include "lzw_enc_core.h"
@@ -245,48 +247,18 @@ __device__ __forceinline__ int64_t pk_size(const int64_t* sizes, const PkItemDev
 // out_offsets[i]: the sum of the sizes before strip i; out_offsets[n]: the blob's size
 __global__ __launch_bounds__(PK_BLOCK) void lzw_pack_scan_kernel(const PkItemDev* __restrict__ items, int n, const int64_t* __restrict__ sizes,
                                                                  int64_t* __restrict__ out_offsets) {
-  __shared__ int64_t part[PK_BLOCK];
-  const int t = threadIdx.x;
-  const int per = (n + PK_BLOCK - 1) / PK_BLOCK;
-  const int lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-  int64_t sum = 0;
-  for (int i = lo; i < hi; ++i) sum += pk_size(sizes, items, i);
-  part[t] = sum;
-  __syncthreads();
-  // Hillis-Steele inclusive scan
-  for (int d = 1; d < PK_BLOCK; d <<= 1) {
-    const int64_t o = t >= d ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += o;
-    __syncthreads();
-  }
-  int64_t run = part[t] - sum;
-  for (int i = lo; i < hi; ++i) {
-    out_offsets[i] = run;
-    run += pk_size(sizes, items, i);
-  }
-  if (t == PK_BLOCK - 1) out_offsets[n] = part[t];
+  const int64_t total = vxpc::exclusive_scan<PK_BLOCK>(
+      n, [&](int64_t i) { return pk_size(sizes, items, (int)i); }, [&](int64_t i, int64_t run) { out_offsets[i] = run; });
+  if (threadIdx.x == PK_BLOCK - 1) out_offsets[n] = total;
 }
 
 __global__ __launch_bounds__(PK_BLOCK) void lzw_pack_kernel(const PkItemDev* __restrict__ items, int n, const int64_t* __restrict__ sizes,
                                                             const int64_t* __restrict__ offsets, const uint8_t* __restrict__ src,
                                                             uint8_t* __restrict__ out, int64_t out_n) {
-  const int t = threadIdx.x;
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     const int64_t sz = pk_size(sizes, items, i), o = offsets[i];
     if (o + sz > out_n) continue;   // a blob larger than out: out_offsets[n] tells the caller
-    const uint8_t* s = src + items[i].off;
-    uint8_t* d = out + o;
-    // bytes up to the first whole word of out, words, the bytes after the last
-    int64_t head = (4 - (int64_t)((uintptr_t)d & 3)) & 3;
-    if (head > sz) head = sz;
-    if (t < head) d[t] = s[t];
-    const int64_t nw = (sz - head) >> 2;
-    const bool sal = ((uintptr_t)(s + head) & 3) == 0;
-    for (int64_t k = t; k < nw; k += PK_BLOCK)
-      *reinterpret_cast<uint32_t*>(d + head + 4 * k) = fp_load_word(s + head + 4 * k, sal);
-    const int64_t k = head + 4 * nw + t;
-    if (k < sz) d[k] = s[k];
+    vxpc::copy_bytes<PK_BLOCK>(out + o, src + items[i].off, sz);
   }
 }
 

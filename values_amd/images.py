@@ -103,7 +103,7 @@ def _decode_png(names, raws, device, staging, timing=None):
             what = _lib.PNG_STATUS[s] if 0 <= s < len(_lib.PNG_STATUS) else "?"
             raise _lib.VxError(f"{nm}: scanlines: {what} (status {s})")
     stages.mark()
-    stages.add(("inflate_ms", "unfilter_ms"), sum(need))
+    stages.add(("inflate_ms", "unfilter_ms"), {"payload_bytes": sum(need)})
     return outs
 
 
@@ -155,7 +155,7 @@ def _decode_tiff(names, raws, device, staging, timing=None):
         tiff_unpredict([(C.c_void_p(base + off + moffs[i]), C.c_void_p(base + moffs[i]), lay[i].h, lay[i].w, lay[i].predictor)
                         for i in predicted if lay[i].h * lay[i].w], device)
     stages.mark()
-    stages.add(("inflate_ms", "lzw_ms", "unpredict_ms"), sum(4 * t.h * t.w for t in lay))
+    stages.add(("inflate_ms", "lzw_ms", "unpredict_ms"), {"payload_bytes": sum(4 * t.h * t.w for t in lay)})
     outs = []
     for i, t in enumerate(lay):
         if i in moffs:

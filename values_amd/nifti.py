@@ -235,7 +235,7 @@ def _decode(names, raws, device, staging, timing=None):
     ws = torch.empty(int(_lib.load().vx_nifti_decode_workspace_bytes(len(raws))), dtype=torch.uint8, device=device)
     _lib.check(_lib.load().vx_nifti_decode(arr, len(raws), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "vx_nifti_decode")
     stages.mark()
-    stages.add(("inflate_ms", "decode_ms"), sum(h.nbytes for h in heads))
+    stages.add(("inflate_ms", "decode_ms"), {"payload_bytes": sum(h.nbytes for h in heads)})
     return [(o, h.header) for o, h in zip(outs, heads)]
 
 

@@ -161,6 +161,46 @@ def _copy_source(t, dtype: np.dtype):
     return t.permute(*reversed(range(len(shp)))).contiguous(), 1, 1, int(np.prod(shp))
 
 
+def _nifti_gzip(bufs, items, hints, zipped, dev, timing):
+    """The NIfTI-and-gzip stage.  items: a NiftiItem table filled but for dst_off; hints: per item the stride hints of its
+    payload; zipped: the indices of the items that become gzip members.  Places the payloads at 16-byte multiples, one
+    vx_nifti_payload launch, places the members by gz.bound, one gz.encode_into over them and one read of their sizes ->
+    ((payload buffer, its bytes), (member buffer, its bytes), per item ("gz" or "nii", offset in that buffer, size))."""
+    import torch
+    from . import _lib, gz
+    lib = _lib.load()
+    parts, off = [], 0
+    for it in items:
+        it.dst_off = off
+        n = int(lib.vx_nifti_payload_bytes(C.byref(it)))
+        parts.append(("nii", off, n))
+        off += (n + 15) // 16 * 16
+    payload = bufs.get("payload", off, dev)
+    nws = bufs.get("nifti_ws", int(lib.vx_nifti_workspace_bytes(len(items))), dev)
+    stages = _devio.Stages(timing)
+    stages.mark()
+    _lib.check(lib.vx_nifti_payload(items, len(items), _lib.ptr(payload), payload.numel(), _lib.ptr(nws), nws.numel(),
+                                    _lib.stream_ptr()), "vx_nifti_payload")
+    stages.mark()
+    if not zipped:
+        return (payload, off), (None, 0), parts
+    slots, goff = [], 0
+    for k in zipped:
+        slots.append(goff)
+        goff += gz.bound(parts[k][2])
+    members = bufs.get("members", goff, dev)
+    sizes = bufs.get("sizes", 8 * len(zipped), dev)[:8 * len(zipped)].view(torch.int64)
+    gws = bufs.get("gzip_ws", gz.workspace_bytes([parts[k][2] for k in zipped]), dev)
+    base = payload.data_ptr()
+    gz.encode_into([(base + parts[k][1], parts[k][2], s, hints[k]) for k, s in zip(zipped, slots)], members, sizes, gws)
+    stages.mark()
+    host_sizes = sizes.cpu().tolist()      # synchronises the stream
+    stages.add(("payload_ms", "encode_ms"), {"payload_bytes": sum(parts[k][2] for k in zipped)})
+    for k, s, n in zip(zipped, slots, host_sizes):
+        parts[k] = ("gz", s, n)
+    return (payload, off), (members, max(s + n for s, n in zip(slots, host_sizes))), parts
+
+
 def _encode_case(bufs, image_id, softmax_pred, maps, data, gt_seg, num_predictions, header, timing=None):
     """payload launch + encode launch + one D2H copy: -> (plan, host uint8 array, [(offset, size)])"""
     import torch
@@ -188,13 +228,11 @@ def _encode_case(bufs, image_id, softmax_pred, maps, data, gt_seg, num_predictio
         cnt = cnt.contiguous()
     keep = [sm, cnt]
     items = (_lib.NiftiItem * len(plan))()
-    gz_items, off = [], 0
     kinds = {"COPY": _lib.VX_NIFTI_COPY, "PROB": _lib.VX_NIFTI_PROB, "MEAN_PROB": _lib.VX_NIFTI_MEAN_PROB,
              "ARGMAX": _lib.VX_NIFTI_ARGMAX, "ARGMAX_MEAN": _lib.VX_NIFTI_ARGMAX_MEAN}
     dsrc = _to_device(data, dev) if data is not None else None
     gsrc = _to_device(gt_seg, dev) if gt_seg is not None else None
-    for i, f in enumerate(plan):
-        it = items[i]
+    for it, f in zip(items, plan):
         it.kind = kinds[f.kind]
         if f.kind == "COPY":
             src = dsrc if f.source[0] == "input" else gsrc[f.source[1]] if f.source[0] == "gt_seg" else \
@@ -212,42 +250,12 @@ def _encode_case(bufs, image_id, softmax_pred, maps, data, gt_seg, num_predictio
             it.t = f.source[1] if f.kind in ("PROB", "ARGMAX") else 0
             it.c = f.source[-1] if f.kind in ("PROB", "MEAN_PROB") else 0
         it.X, it.Y, it.Z = X, Y, Z
-        it.dst_off = off
         C.memmove(it.header, nifti.header_bytes(f.shape, f.dtype, header), 352)
-        n = int(_lib.load().vx_nifti_payload_bytes(C.byref(it)))
-        gz_items.append((off, n, gz.hints_for(f.dtype.itemsize, f.shape)))
-        off += (n + 15) // 16 * 16
-    lib = _lib.load()
-    payload = bufs.get("payload", off, dev)
-    nws = bufs.get("nifti_ws", int(lib.vx_nifti_workspace_bytes(len(plan))), dev)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
-    if ev:
-        ev[0].record()
-    _lib.check(lib.vx_nifti_payload(items, len(plan), _lib.ptr(payload), payload.numel(), _lib.ptr(nws), nws.numel(),
-                                    _lib.stream_ptr()), "vx_nifti_payload")
-    if ev:
-        ev[1].record()
-    slots, goff = [], 0
-    for _, n, _h in gz_items:
-        slots.append(goff)
-        goff += gz.bound(n)
-    dst = bufs.get("members", goff, dev)
-    sizes = bufs.get("sizes", 8 * len(plan), dev)[:8 * len(plan)].view(torch.int64)
-    gws = bufs.get("gzip_ws", gz.workspace_bytes([n for _, n, _h in gz_items]), dev)
-    base = payload.data_ptr()
-    gz.encode_into([(base + o, n, s, h) for (o, n, h), s in zip(gz_items, slots)], dst, sizes, gws)
-    if ev:
-        ev[2].record()
-    host_sizes = sizes.cpu().tolist()      # synchronises the stream
-    used = max(s + n for s, n in zip(slots, host_sizes))
-    host = bufs.get("host", used, dev, pinned=True)
-    host[:used].copy_(dst[:used])
-    if ev:
-        timing["payload_ms"] = timing.get("payload_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["encode_ms"] = timing.get("encode_ms", 0.0) + ev[1].elapsed_time(ev[2])
-        timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(n for _, n, _h in gz_items)
+    _, members, parts = _nifti_gzip(bufs, items, [gz.hints_for(f.dtype.itemsize, f.shape) for f in plan], list(range(len(plan))),
+                                    dev, timing)
+    host, (base,) = _devio.gather(bufs, [members], dev)
     del keep
-    return plan, host.numpy(), list(zip(slots, host_sizes))
+    return plan, host, [(base + o, n) for _, o, n in parts]
 
 
 _DIRS = ("input", "gt_seg", "pred_seg", "pred_prob")   # save_case creates these four whatever it writes
@@ -309,22 +317,20 @@ def plan_maps(paths, tensors) -> List[PlannedMap]:
 
 
 def _encode_maps(bufs, paths, tensors, header=False, timing=None):
-    """COPY payloads of the NIfTI maps in one vx_nifti_payload launch, one gz.encode_into over the .gz ones, and one copy
-    per kind of file into pinned memory: -> (plan, host uint8 array, spans)"""
+    """COPY payloads of the NIfTI maps and one gz.encode_into over the .gz ones (_nifti_gzip), the .tif maps through the
+    TIFF stage (_devio.TiffStage, uncompressed), and one copy per kind of file into pinned memory: -> (plan, host uint8
+    array, spans)"""
     import torch
     from . import _lib, gz
-    from .image_io import tiff_f32_parts
     _lib.require_gpu()
-    lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device())
     plan = plan_maps(paths, tensors)
     vols = [i for i, f in enumerate(plan) if f.kind != "tif"]
-    keep, parts = [], {}        # parts: file -> (region, offset, size[, head, tail]) before the regions are placed
-    members = payload = None
-    gz_used = pay_bytes = 0
+    tifs = [i for i, f in enumerate(plan) if f.kind == "tif"]
+    keep, spans = [], {}
+    regions = {"gz": (None, 0), "nii": (None, 0)}
     if vols:
         items = (_lib.NiftiItem * len(vols))()
-        sizes_in, off = [], 0
         for it, i in zip(items, vols):
             f, t = plan[i], _to_device(tensors[i], dev)
             rev = t.permute(*reversed(range(t.dim())))
@@ -334,67 +340,21 @@ def _encode_maps(bufs, paths, tensors, header=False, timing=None):
                 src, X, Y, Z = _copy_source(t, f.dtype)
             keep.append(src)
             it.kind, it.src, it.esize = _lib.VX_NIFTI_COPY, (src.data_ptr() if src.numel() else None), f.dtype.itemsize
-            it.X, it.Y, it.Z, it.dst_off = X, Y, Z, off
+            it.X, it.Y, it.Z = X, Y, Z
             C.memmove(it.header, nifti.header_bytes(f.shape, f.dtype, header), 352)
-            n = int(lib.vx_nifti_payload_bytes(C.byref(it)))
-            sizes_in.append((off, n))
-            off += (n + 15) // 16 * 16
-        pay_bytes = off
-        payload = bufs.get("payload", off, dev)
-        nws = bufs.get("nifti_ws", int(lib.vx_nifti_workspace_bytes(len(vols))), dev)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
-        if ev:
-            ev[0].record()
-        _lib.check(lib.vx_nifti_payload(items, len(vols), _lib.ptr(payload), payload.numel(), _lib.ptr(nws), nws.numel(),
-                                        _lib.stream_ptr()), "vx_nifti_payload")
-        if ev:
-            ev[1].record()
-        zipped = [k for k, i in enumerate(vols) if plan[i].kind == "gz"]
-        if zipped:
-            slots, goff = [], 0
-            for k in zipped:
-                slots.append(goff)
-                goff += gz.bound(sizes_in[k][1])
-            members = bufs.get("members", goff, dev)
-            sizes = bufs.get("sizes", 8 * len(zipped), dev)[:8 * len(zipped)].view(torch.int64)
-            gws = bufs.get("gzip_ws", gz.workspace_bytes([sizes_in[k][1] for k in zipped]), dev)
-            base = payload.data_ptr()
-            gz.encode_into([(base + sizes_in[k][0], sizes_in[k][1], s,
-                             gz.hints_for(plan[vols[k]].dtype.itemsize, plan[vols[k]].shape)) for k, s in zip(zipped, slots)],
-                           members, sizes, gws)
-            if ev:
-                ev[2].record()
-            host_sizes = sizes.cpu().tolist()      # synchronises the stream
-            if ev:
-                timing["payload_ms"] = timing.get("payload_ms", 0.0) + ev[0].elapsed_time(ev[1])
-                timing["encode_ms"] = timing.get("encode_ms", 0.0) + ev[1].elapsed_time(ev[2])
-                timing["payload_bytes"] = timing.get("payload_bytes", 0) + sum(sizes_in[k][1] for k in zipped)
-            gz_used = max(s + n for s, n in zip(slots, host_sizes))
-            for k, s, n in zip(zipped, slots, host_sizes):
-                parts[vols[k]] = ("gz", s, n)
-        for k, i in enumerate(vols):
-            if plan[i].kind == "nii":
-                parts[i] = ("nii", sizes_in[k][0], sizes_in[k][1])
-    flat, toff = [], 0
-    for i, f in enumerate(plan):
-        if f.kind == "tif":
-            m = _to_device(tensors[i], dev).to(torch.float32).transpose(0, 1).contiguous()
-            flat.append(m.reshape(-1))
-            parts[i] = ("tif", toff, 4 * m.numel()) + tiff_f32_parts(int(m.shape[0]), int(m.shape[1]))
-            toff += 4 * m.numel()
-    need_nii = any(f.kind == "nii" for f in plan)
-    base = {"gz": 0, "nii": (gz_used + 15) // 16 * 16}
-    base["tif"] = base["nii"] + (pay_bytes if need_nii else 0)
-    total = base["tif"] + toff
-    host = bufs.get("host", total, dev, pinned=True)
-    if gz_used:
-        host[:gz_used].copy_(members[:gz_used])
-    if need_nii:
-        host[base["nii"]:base["nii"] + pay_bytes].copy_(payload[:pay_bytes])
-    if flat:
-        host[base["tif"]:total].copy_(torch.cat(flat).view(torch.uint8))
+        payload, regions["gz"], parts = _nifti_gzip(bufs, items, [gz.hints_for(plan[i].dtype.itemsize, plan[i].shape) for i in vols],
+                                                    [k for k, i in enumerate(vols) if plan[i].kind == "gz"], dev, timing)
+        if any(plan[i].kind == "nii" for i in vols):   # the plain files are spans of the payload buffer
+            regions["nii"] = payload
+        spans.update(zip(vols, parts))
+    maps = [_to_device(tensors[i], dev).to(torch.float32).transpose(0, 1).contiguous() for i in tifs]   # the file is (H, W)
+    tif = _devio.TiffStage("save_maps_device", [tuple(int(v) for v in m.shape) for m in maps])
+    regions["tif"] = (tif.launch(bufs, maps, None, dev, None), tif.raw_bytes)
+    spans.update(zip(tifs, (("tif",) + p for p in tif.finish(None)[1])))
+    host, bases = _devio.gather(bufs, list(regions.values()), dev)
+    base = dict(zip(regions, bases))
     del keep
-    return plan, host.numpy(), [(base[parts[i][0]] + parts[i][1],) + tuple(parts[i][2:]) for i in range(len(plan))]
+    return plan, host, [(base[spans[i][0]] + spans[i][1],) + tuple(spans[i][2:]) for i in range(len(plan))]
 
 
 def save_maps_device(paths, tensors, header=False, _timing=None) -> None:

@@ -19,7 +19,6 @@ come back.  Host and device writers produce the same bytes.
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import os
 from typing import Dict, List, NamedTuple, Optional, Sequence
@@ -28,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _devio, _lib
-from .image_io import lzw_bound, tiff_f32_parts, tiff_lzw_parts, tiff_rows_per_strip, write_png, write_tiff_f32
+from .image_io import write_png, write_tiff_f32
 
 UNLABELED = 255  # cs_labels.name2trainId["unlabeled"]
 TRAINID2COLOR = {
@@ -200,86 +199,21 @@ def png_encode(masks: Sequence[torch.Tensor], ignores: Optional[Sequence] = None
     return [host[o:o + k].tobytes() for o, k in zip(pl[:n], pl[n:])]
 
 
-_LZW_ITEM = np.dtype([("src", "<u8"), ("src_n", "<i8"), ("dst_off", "<i8"), ("dst_cap", "<i8")])   # vx_tiff_lzw_item
-_UNPREDICT_ITEM = np.dtype([("src", "<u8"), ("dst", "<u8"), ("rows", "<i4"), ("W", "<i4"), ("predictor", "<i4"), ("pad", "<i4")])
-
-
-def _tiff_strips(shapes, rows_per_strip):
-    """The LZW strips of a batch of (h, w) maps lying back to back: -> (per map (rows per strip, number of strips), table
-    of vx_tiff_lzw_item whose src is the strip's byte offset in the maps, bytes of the windows)"""
-    layout, parts, base, off = [], [], 0, 0
-    for h, w in shapes:
-        rps = tiff_rows_per_strip(h, w, rows_per_strip)
-        r0 = np.arange(0, h, rps, dtype=np.int64)
-        it = np.zeros(len(r0), dtype=_LZW_ITEM)
-        it["src"] = base + 4 * w * r0
-        it["src_n"] = 4 * w * np.minimum(rps, h - r0)
-        it["dst_cap"] = lzw_bound(it["src_n"])
-        win = (it["dst_cap"] + 15) // 16 * 16   # every window starts at a multiple of 16: whole-word stores
-        it["dst_off"] = off + np.cumsum(win) - win
-        off += int(win.sum())
-        base += 4 * h * w
-        layout.append((rps, len(r0)))
-        parts.append(it)
-    return layout, np.concatenate(parts), off
-
-
-def _tiff_lzw_launch(bufs, flat, shapes, items, win_bytes, predictor, sizes, status, offsets, dev, ev):
-    """The maps `flat` (float32, back to back, of the given shapes) to LZW strips: vx_tiff_predict over all maps (predictor
-    2 / 3), vx_tiff_lzw_encode over all strips, vx_tiff_lzw_pack -> the device buffer that holds the strips back to back.
-    sizes, status, offsets: device views that receive the strips' sizes, statuses and places in the blob."""
-    lib = _lib.load()
-    n = len(items)
-    src = flat
-    if ev:
-        ev[0].record()
-    if predictor != 1:
-        src = bufs.get("tif_pred", 4 * flat.numel(), dev)
-        pi = np.zeros(len(shapes), dtype=_UNPREDICT_ITEM)
-        o = 0
-        for k, (h, w) in enumerate(shapes):
-            pi[k] = (flat.data_ptr() + o, src.data_ptr() + o, h, w, predictor, 0)
-            o += 4 * h * w
-        pst = bufs.get("tif_pst", 4 * len(shapes), dev)
-        ws = bufs.get("tif_pws", int(lib.vx_tiff_predict_workspace_bytes(len(shapes))), dev)
-        _lib.check(lib.vx_tiff_predict(pi.ctypes.data_as(ctypes.POINTER(_lib.TiffUnpredictItem)), len(shapes), pst.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "vx_tiff_predict")
-    if ev:
-        ev[1].record()
-    items = items.copy()
-    items["src"] += src.data_ptr()
-    table = items.ctypes.data_as(ctypes.POINTER(_lib.TiffLzwItem))
-    enc = bufs.get("tif_enc", win_bytes, dev)
-    ws = bufs.get("tif_ws", max(int(lib.vx_tiff_lzw_encode_workspace_bytes(n)), int(lib.vx_tiff_lzw_pack_workspace_bytes(n))), dev)
-    _lib.check(lib.vx_tiff_lzw_encode(table, n, enc.data_ptr(), win_bytes, sizes.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw_encode")
-    if ev:
-        ev[2].record()
-    packed = bufs.get("tif_pack", win_bytes, dev)
-    _lib.check(lib.vx_tiff_lzw_pack(table, n, enc.data_ptr(), win_bytes, sizes.data_ptr(), packed.data_ptr(), win_bytes,
-                                    offsets.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "vx_tiff_lzw_pack")
-    if ev:
-        ev[3].record()
-    return packed
-
-
 def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, timing=None, tiff=None,
                    tiff_predictor=3, tiff_rows_per_strip=None):
-    """vx_png_encode over every mask of the batch + one small read of the file sizes + one copy of the PNG bytes and one
-    of the uncertainty maps into pinned memory: -> (plan, host uint8 array, [(offset, size)] per planned PNG file,
-    [(offset, size, head, tail)] per TIFF).  tiff="lzw": the maps are compressed on the device (_tiff_lzw_launch), the
-    strips' sizes come back in the same small read and the compressed bytes take the maps' place in the copy."""
-    if tiff not in (None, "lzw"):
-        raise ValueError(f"save_images_device: tiff={tiff!r}: None or \"lzw\"")
-    if tiff == "lzw" and tiff_predictor not in (1, 2, 3):
-        raise ValueError(f"save_images_device: tiff_predictor={tiff_predictor}: 1, 2 or 3")
+    """vx_png_encode over every mask of the batch, the TIFF stage over every map (_devio.TiffStage: raw, or LZW strips
+    compressed on the device), one small read of the PNG files' places and sizes (and the strips' sizes) + one copy of the
+    PNG bytes and one of the maps' bytes into pinned memory: -> (plan, host uint8 array, [(offset, size)] per planned PNG
+    file, [(offset, size, head, tail)] per TIFF)."""
+    ids = list(image_ids)
+    shapes = [tuple(int(v) for v in np.shape(m)[1:]) for m in (uncertainty or {}).values()] * len(ids)   # the maps in plan order
+    tif = _devio.TiffStage("save_images_device", shapes, tiff, tiff_predictor, tiff_rows_per_strip)   # refuses a bad option first
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     pm = _as_device(pred_masks, dev, torch.uint8)
     if pm.dim() != 4:
         raise ValueError(f"save_images_device: pred_masks (B, N, H, W) expected, got {tuple(pm.shape)}")
     B, N, H, W = (int(v) for v in pm.shape)
-    ids = list(image_ids)
     if len(ids) != B:
         raise ValueError(f"save_images_device: {len(ids)} image ids for {B} images")
     pm = pm.contiguous()
@@ -303,79 +237,26 @@ def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_
         entries.append((lab.data_ptr(), ign[b].data_ptr() if ign is not None else None, H, W))
     items, bound, ws_bytes = _png_table(entries)
     n = len(pngs)
-    lzw = tiff == "lzw" and bool(unc)
-    shapes = [tuple(int(v) for v in unc[k].shape[1:]) for _ in range(B) for k in unc]   # the maps in plan order
-    ns = 0
-    if lzw:
-        layout, strips, win_bytes = _tiff_strips(shapes, tiff_rows_per_strip)
-        ns = len(strips)
     dst = bufs.get("png", bound, dev)
-    # [PNG offsets | PNG sizes | strip sizes | strip places, the blob's size] int64, then the strips' statuses int32
-    place_bytes = 16 * n + (8 * (2 * ns + 1) + 4 * ns if lzw else 0)
-    place_all = bufs.get("place", place_bytes, dev)[:place_bytes]
-    place = place_all[:16 * n].view(torch.int64)
+    # [PNG offsets | PNG sizes] int64, then the TIFF stage's
+    place = bufs.get("place", 16 * n + tif.place_bytes, dev)[:16 * n + tif.place_bytes]
     ws = bufs.get("png_ws", ws_bytes, dev)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing is not None else None
-    if ev:
-        ev[0].record()
-    _png_launch(items, dst, place, ws)
-    if ev:
-        ev[1].record()
-    flat = torch.cat([unc[k][b].reshape(-1) for b in range(B) for k in unc]) if unc else None
-    tev = None
-    if lzw:
-        tev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing is not None else None
-        tail = place_all[16 * n:]
-        packed = _tiff_lzw_launch(bufs, flat, shapes, strips, win_bytes, tiff_predictor, tail[:8 * ns].view(torch.int64),
-                                  tail[8 * (2 * ns + 1):].view(torch.int32), tail[8 * ns:8 * (2 * ns + 1)].view(torch.int64), dev, tev)
-    pl_host = place_all.cpu()              # the one small read: synchronises the stream
-    pl = pl_host[:16 * n].view(torch.int64).tolist()
+    stages = _devio.Stages(timing)
+    stages.mark()
+    _png_launch(items, dst, place[:16 * n].view(torch.int64), ws)
+    stages.mark()
+    region = tif.launch(bufs, [unc[k][b] for b in range(B) for k in unc], place[16 * n:], dev, stages)
+    host_place = place.cpu()              # the one small read: synchronises the stream
+    pl = host_place[:16 * n].view(torch.int64).tolist()
     offs, sizes = pl[:n], pl[n:]
     png_bytes = offs[-1] + sizes[-1]
-    unc0 = (png_bytes + 15) // 16 * 16
-    if lzw:
-        ssz = pl_host[16 * n:16 * n + 8 * ns].view(torch.int64).tolist()
-        bad = [i for i, v in enumerate(pl_host[16 * n + 8 * (2 * ns + 1):].view(torch.int32).tolist()) if v != _lib.VX_LZW_OK]
-        if bad:
-            raise RuntimeError(f"save_images_device: vx_tiff_lzw_encode: strip {bad[0]} of the batch did not fit its window")
-        unc_bytes = sum(ssz)
-    else:
-        unc_bytes = 4 * flat.numel() if flat is not None else 0
-    total = unc0 + unc_bytes
-    host = bufs.get("host", total, dev, pinned=True)
-    host[:png_bytes].copy_(dst[:png_bytes])
-    if lzw:
-        host[unc0:total].copy_(packed[:unc_bytes])
-    elif flat is not None:
-        host[unc0:total].copy_(flat.view(torch.uint8))
-    if ev:
-        timing["encode_ms"] = timing.get("encode_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        timing["raw_bytes"] = timing.get("raw_bytes", 0) + n * H * (3 * W + 1)
-        timing["png_bytes"] = timing.get("png_bytes", 0) + png_bytes
-        timing["tiff_raw_bytes"] = timing.get("tiff_raw_bytes", 0) + (4 * flat.numel() if flat is not None else 0)
-        timing["tiff_bytes"] = timing.get("tiff_bytes", 0) + unc_bytes
-    if tev:
-        for key, a, b in zip(("tiff_predict_ms", "tiff_encode_ms", "tiff_pack_ms"), tev, tev[1:]):
-            timing[key] = timing.get(key, 0.0) + a.elapsed_time(b)
-    spans, k, u, t, s0 = [], 0, unc0, 0, 0
-    for f in plan:
-        if f.kind == "png":
-            spans.append((offs[k], sizes[k]))
-            k += 1
-            continue
-        h, w = shapes[t]
-        if lzw:    # TIFF: host-built header + the map's strips + IFD and strip table
-            rps, cnt = layout[t]
-            mine = ssz[s0:s0 + cnt]
-            nb = sum(mine)
-            spans.append((u, nb) + tiff_lzw_parts(h, w, mine, rps, tiff_predictor))
-            s0 += cnt
-        else:      # TIFF: host-built header + the map's bytes + IFD
-            nb = 4 * h * w
-            spans.append((u, nb) + tiff_f32_parts(h, w))
-        u += nb
-        t += 1
-    return plan, host.numpy(), spans
+    tif_bytes, parts = tif.finish(host_place[16 * n:])
+    host, (png0, tif0) = _devio.gather(bufs, [(dst, png_bytes), (region, tif_bytes)], dev)
+    stages.add(("encode_ms", None, "tiff_predict_ms", "tiff_encode_ms", "tiff_pack_ms"),
+               {"raw_bytes": n * H * (3 * W + 1), "png_bytes": png_bytes, "tiff_raw_bytes": tif.raw_bytes, "tiff_bytes": tif_bytes})
+    png_spans = iter([(png0 + o, k) for o, k in zip(offs, sizes)])
+    tif_spans = iter([(tif0 + p[0],) + p[1:] for p in parts])
+    return plan, host, [next(png_spans if f.kind == "png" else tif_spans) for f in plan]
 
 
 def save_images_device(save_dir: str, image_ids: Sequence[str], pred_masks, mean_masks, uncertainty: Optional[Dict] = None,
