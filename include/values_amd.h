@@ -512,7 +512,8 @@ int vx_unet3d_forward_profiled(const vx_unet3d_weights* w, const vx_unet3d_run* 
  * 2D path (HRNet, uncertainty_modeling/models/hrnet_module.py).  Activations: channels-last [N][H][W][pitch] fp32.
  * K15: 3x3 stride 1 / 3x3 stride 2 / 1x1 convolution, padding k/2 (hrnet_module.py:37-41, 85-93, 349-358, 411-428;
  * bias only on last_layer), raw output + per-tile (sum, sumsq) partials [ntiles_total][Cout][2] for the
- * TRAINING-mode BatchNorm that follows (batch statistics over N,H,W; the reference never calls .eval()).
+ * TRAINING-mode BatchNorm that follows (batch statistics over N,H,W; the reference never calls .eval()) -- or, for a
+ * model in eval mode, the running-statistics BatchNorm, residual and ReLU applied in the output epilogue (out_scale).
  * Cin must be a multiple of 16, weights packed by vx_pack_conv2d (real channel count: it pads).  The input of C real
  * channels needs NO padding to Cin: in_pitch may be any multiple of 4 in (Cin - 16, ...); channels at and beyond
  * min(Cin, in_pitch) read as zeros, channels [C, in_pitch) must hold zeros (an 18-channel tensor travels at 20 floats
@@ -531,6 +532,18 @@ typedef struct vx_conv2d_args {
    * floats apart.  Zero padding is that of the ACTIVATED tensor. */
   const float* in_scale; const float* in_shift;   /* nullable together */
   int32_t in_cpitch, in_group_images, in_relu;
+  /* Optional output EPILOGUE (split-fp16 kernels only; a zero-initialised struct has none):
+   *   out[.., out_coff + c] = act( out_add[.., c] + out_scale[c] * (acc + bias)[c] + out_shift[c] )
+   * -- a BatchNorm with FIXED statistics (vx_bn_running_affine), the residual of a block end and the ReLU applied as the
+   * conv stores, evaluated with the expressions of vx_affine_gather's identity instance in its order: bit-identical to
+   * vx_conv2d without the epilogue followed by vx_affine_gather(scale, shift, add, act).  out_scale / out_shift hold
+   * [Cout] floats; out_add is channels-last [N][OH][OW][out_add_pitch] at the OUTPUT geometry (channel c of it meets
+   * output channel c; out_coff does not apply to it; it may be `out` itself only at the same pitch and out_coff 0).
+   * Refused: out_scale with stats_partial (batch statistics of a tensor that is never written raw), out_add or out_act
+   * without out_scale, and any of them under vx_config.conv_fp32 = 1. */
+  const float* out_scale; const float* out_shift; /* nullable together */
+  const float* out_add; int32_t out_add_pitch;    /* nullable */
+  int32_t out_act;                                /* VX_ACT_NONE | VX_ACT_RELU */
 } vx_conv2d_args;
 int64_t vx_conv2d_packed_floats(int Cin, int Cout, int KS);
 int vx_pack_conv2d(const float* w_torch /* (Cout,Cin,KS,KS) */, float* w_packed, int Cin, int Cout, int KS, vx_stream_t stream);
@@ -546,6 +559,19 @@ int vx_bn_finalize(const float* stats_partial, int ntiles, int C, int64_t count,
  * [g * ntiles_per_group, ...) of the partials and row g of scale / shift [G][cpitch]. */
 int vx_bn_finalize_groups(const float* stats_partial, int ntiles_per_group, int G, int C, int cpitch, int64_t count_per_group,
                           float eps, const float* gamma, const float* beta, float* scale, float* shift, vx_stream_t stream);
+
+/* BatchNorm2d with RUNNING statistics (model.eval()) as a per-channel affine, for every BatchNorm layer of a model in one
+ * launch: scale[c] = gamma[c] / sqrt(running_var[c] + eps), shift[c] = beta[c] - running_mean[c] * scale[c], evaluated in
+ * float64 and rounded once to float32 exactly as vx_bn_finalize does from batch statistics; rows [C, cpitch) of scale and
+ * shift are written as zeros (the zero tail of a padded activation stays zero through the affine).  `items` is a DEVICE
+ * table of n_items entries (the item-table convention of the batched entry points); gamma / beta nullable (1 / 0).
+ * Refused before any launch: a null table (VX_E_NULL), n_items outside [1, 65536] or eps < 0 (VX_E_SHAPE). */
+typedef struct vx_bn_affine_item {
+  const float* gamma; const float* beta; const float* running_mean; const float* running_var;
+  float* scale; float* shift;
+  int32_t C, cpitch;
+} vx_bn_affine_item;
+int vx_bn_running_affine(const vx_bn_affine_item* items, int n_items, float eps, vx_stream_t stream);
 
 /* K16/K17/K18: out[.., out_coff + c] = act( add + scale[c] * G(drop(x))[c] + shift[c] ); G = identity (OH,OW == H,W) or
  * F.interpolate(mode="bilinear", align_corners=False) from (H,W) to (OH,OW); add / scale / drop optional; `add` may

@@ -66,7 +66,14 @@ class Conv2dArgs(C.Structure):
                 ("out", _p), ("out_pitch", _i32), ("out_coff", _i32),
                 ("N", _i32), ("H", _i32), ("W", _i32), ("Cin", _i32), ("Cout", _i32), ("KS", _i32), ("S", _i32),
                 ("stats_partial", _p), ("w_family", _i32),
-                ("in_scale", _p), ("in_shift", _p), ("in_cpitch", _i32), ("in_group_images", _i32), ("in_relu", _i32)]
+                ("in_scale", _p), ("in_shift", _p), ("in_cpitch", _i32), ("in_group_images", _i32), ("in_relu", _i32),
+                ("out_scale", _p), ("out_shift", _p), ("out_add", _p), ("out_add_pitch", _i32), ("out_act", _i32)]
+
+
+class BnAffineItem(C.Structure):
+    """vx_bn_affine_item: one BatchNorm layer of vx_bn_running_affine (running statistics -> scale / shift rows)."""
+    _fields_ = [("gamma", _p), ("beta", _p), ("running_mean", _p), ("running_var", _p), ("scale", _p), ("shift", _p),
+                ("C", _i32), ("cpitch", _i32)]
 
 
 class AffineArgs(C.Structure):
@@ -325,6 +332,7 @@ SIGNATURES = {
     "vx_conv2d": (_i, [C.POINTER(Conv2dArgs), _p]),
     "vx_bn_finalize": (_i, [_p, _i, _i, _i64, C.c_float, _p, _p, _p, _p, _p]),
     "vx_bn_finalize_groups": (_i, [_p, _i, _i, _i, _i, _i64, C.c_float, _p, _p, _p, _p, _p]),
+    "vx_bn_running_affine": (_i, [_p, _i, C.c_float, _p]),
     "vx_affine_gather": (_i, [C.POINTER(AffineArgs), _p]),
     "vx_bilinear_nchw": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "vx_bilinear_softmax_nchw": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),

@@ -69,6 +69,33 @@ extern "C" int vx_bn_finalize_groups(const float* stats_partial, int ntiles_per_
   return VX_OK;
 }
 
+// BatchNorm with RUNNING statistics as a per-channel affine, every layer of a model in one launch (one workgroup per item
+// of the device table): the float64 expressions of bn_finalize_kernel with the stored mean / variance in place of the
+// batch's, rounded once; rows [C, cpitch) are zeros.
+__global__ __launch_bounds__(256) void bn_running_affine_kernel(const vx_bn_affine_item* __restrict__ items, float eps) {
+  const vx_bn_affine_item it = items[blockIdx.x];
+  for (int c = threadIdx.x; c < it.cpitch; c += 256) {
+    float sc = 0.f, sh = 0.f;
+    if (c < it.C) {
+      const double mu = (double)it.running_mean[c];
+      const double rstd = 1.0 / sqrt((double)it.running_var[c] + (double)eps);
+      const double g = it.gamma ? (double)it.gamma[c] : 1.0, b = it.beta ? (double)it.beta[c] : 0.0;
+      sc = (float)(g * rstd);
+      sh = (float)(b - mu * g * rstd);
+    }
+    it.scale[c] = sc;
+    it.shift[c] = sh;
+  }
+}
+
+extern "C" int vx_bn_running_affine(const vx_bn_affine_item* items, int n_items, float eps, vx_stream_t stream) {
+  if (!items) VX_FAIL(VX_E_NULL, "vx_bn_running_affine: null item table");
+  if (n_items < 1 || n_items > 65536 || !(eps >= 0.f)) VX_FAIL(VX_E_SHAPE, "vx_bn_running_affine: n_items %d outside [1, 65536] or eps < 0", n_items);
+  hipLaunchKernelGGL(bn_running_affine_kernel, dim3((unsigned)n_items), dim3(256), 0, (hipStream_t)stream, items, eps);
+  VX_CHECK_LAUNCH("vx_bn_running_affine");
+  return VX_OK;
+}
+
 // bilinear source coordinates of F.interpolate(align_corners=False): src = (dst + 0.5) * in/out - 0.5, clamped at 0
 __device__ __forceinline__ void bil_coord(int d, int in, float ratio, int& i0, int& i1, float& l1) {
   float s = ((float)d + 0.5f) * ratio - 0.5f;

@@ -432,6 +432,24 @@ extern "C" int vx_conv2d(const vx_conv2d_args* ap, vx_stream_t stream) {
   if (a.in_scale && (a.in_cpitch < a.Cin - 15 || a.in_group_images < 0 || !c2_split16()))
     VX_FAIL(VX_E_SHAPE, "vx_conv2d: the input prologue needs rows of in_cpitch >= the real channel count and the split-fp16 "
             "kernels (vx_config.conv_fp32 = 0)");
+  // output epilogue (fixed affine + residual + ReLU as the conv stores): refused before any launch where it has no meaning
+  if ((a.out_scale == nullptr) != (a.out_shift == nullptr)) VX_FAIL(VX_E_NULL, "vx_conv2d: out_scale / out_shift must come together");
+  if (!a.out_scale && a.out_add) VX_FAIL(VX_E_NULL, "vx_conv2d: out_add needs out_scale / out_shift (the output epilogue)");
+  if (!a.out_scale && a.out_act != VX_ACT_NONE) VX_FAIL(VX_E_DTYPE, "vx_conv2d: out_act needs out_scale / out_shift (the output epilogue)");
+  if (a.out_scale) {
+    if (a.stats_partial)
+      VX_FAIL(VX_E_DTYPE, "vx_conv2d: out_scale together with stats_partial (batch statistics belong to the raw output, which the "
+              "epilogue does not write)");
+    if (!c2_split16())
+      VX_FAIL(VX_E_DTYPE, "vx_conv2d: the output epilogue (out_scale) needs the split-fp16 kernels (vx_config.conv_fp32 = 0): run "
+              "the raw conv and vx_affine_gather");
+    if (a.out_act != VX_ACT_NONE && a.out_act != VX_ACT_RELU) VX_FAIL(VX_E_DTYPE, "vx_conv2d: out_act must be none or relu");
+    if (a.out_add && (a.out_add_pitch % 4 || a.out_add_pitch < (a.Cout + 3) / 4 * 4))
+      VX_FAIL(VX_E_ALIGN, "vx_conv2d: out_add_pitch must be a multiple of 4 floats and cover the channels");
+    if (a.out_add && (int64_t)ka.OH * ka.OW * a.out_add_pitch * 4 >= (1ll << 31))
+      VX_FAIL(VX_E_SHAPE, "vx_conv2d: one image of out_add must stay below 2 GiB");
+    if (!vx_aligned16(a.out_add)) VX_FAIL(VX_E_ALIGN, "vx_conv2d: out_add must be 16-byte aligned");
+  }
   if (c2_split16()) return vx_conv2d_s16(a, (hipStream_t)stream);
   C2Cfg c = c2_config(a.KS, a.S, a.Cout);
   ka.tiles_x = (ka.OW + 15) / 16;

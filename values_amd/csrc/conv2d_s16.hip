@@ -66,7 +66,12 @@ __device__ __forceinline__ float row_ror(float x, int rot) {
 // (tap, octet) units of 8 channels, u = 4 step + k-group -> tap = u / OCT, octet = u % OCT: 18 channels (OCT = 3) take 7
 // steps, up to 8 channels (OCT = 1) 3.  One work item per tile, weights resident; the packed layout is its own
 // (pack_conv2d_s16_kernel, vx_conv2d_family = ... + 100 OCT).
-template <int KS, int S, int NT, int NSUB, int TY, int OCT = 0>
+//
+// EPI (vx_conv2d_args.out_scale): the output epilogue -- a fixed per-channel affine (BatchNorm with running statistics),
+// the residual of a block end and the ReLU applied to the finished accumulators as they are stored, in
+// affine_gather_kernel's expressions and order (bn2d.hip).  A template parameter: the instances without it are the code
+// they were (no statistics in an EPI instance, no affine in the others).
+template <int KS, int S, int NT, int NSUB, int TY, int OCT = 0, bool EPI = false>
 __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
   constexpr int NW = 8, NTH = 512, TX = 16;
   constexpr int R = TY / NW;
@@ -184,6 +189,16 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
   const bool pre = a.in_scale != nullptr;
   const int w_res_floats = (ka.w_all ? ka.nchunks : 1) * W_FLOATS;   // LDS floats the weights take
   float* s_ss = smem + IN_FLOATS + w_res_floats + NW * NT * 16 * 2;  // [scale | shift][TABC] of the item's chunk
+  // epilogue (vx_conv2d_args.out_scale): the row group's scale / shift rows, staged once for the kernel's life (read from
+  // global memory in the epilogue they are loop invariants, and hipcc keeps all of them in registers across the multiply
+  // phase).  [Cout] rows: channels beyond Cout take scale = shift = 0.  Visible behind the item loop's first barrier.
+  float* s_es = s_ss + 2 * TABC;                                     // [scale | shift][NT * 16]
+  if constexpr (EPI) {
+    if (tid < 2 * NT * 16) {
+      const int which = tid / (NT * 16), co = cg * NT * 16 + tid % (NT * 16);
+      s_es[tid] = co < a.Cout ? (which ? a.out_shift : a.out_scale)[co] : 0.f;
+    }
+  }
   unsigned p_bad = 0;
   const bool w_resident = ka.nchunks == 1 || ka.w_all;
   bool w_fresh = true;
@@ -397,6 +412,30 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
       const unsigned osoff = (unsigned)((ty * TY * ka.OW + tx * TX) * a.out_pitch) * 4u;
       const __amdgpu_buffer_rsrc_t osrd =
           __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)n * out_sample), 0, K_NUMREC, 0x00020000);
+      // EPI: a row tile's scale / shift quad and residual pieces are requested one row tile ahead of their use (two register
+      // sets, whatever NT is; the fragments of the multiply phase are dead here).  The residual goes through the store's
+      // addressing at its own pitch: lanes out of the tile and row tiles beyond Cout are steered out of range and touch no
+      // memory.
+      // (the five-row-tile 1x1 instance has no room for the second set: it requests each row tile's as it gets there)
+      constexpr bool AHEAD = NT < 5;
+      f32x4 esc[2], esh[2], eres[2][R];
+      auto eload = [&](int nt, int slot) {
+        esc[slot] = *reinterpret_cast<const f32x4*>(s_es + nt * 16 + g * 4);
+        esh[slot] = *reinterpret_cast<const f32x4*>(s_es + NT * 16 + nt * 16 + g * 4);
+        if (a.out_add) {
+          // (the row tile's channel offset is wave-uniform: it rides in the scalar offset, the lane part is one value per row)
+          const unsigned asoff = (unsigned)((ty * TY * ka.OW + tx * TX) * a.out_add_pitch + (cg * NT + nt) * 16) * 4u;
+          const __amdgpu_buffer_rsrc_t asrd = __builtin_amdgcn_make_buffer_rsrc(
+              (void*)(a.out_add + (size_t)n * ka.OH * ka.OW * a.out_add_pitch), 0, K_NUMREC, 0x00020000);
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            const bool bad = ((obad >> r) & 1u) || !cvalid[nt];
+            const unsigned avo = (unsigned)((((wave * R + r) * ka.OW + m) * a.out_add_pitch + g * 4) * 4);
+            eres[slot][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(asrd, (int)(bad ? K_OOB : avo), (int)asoff, 0));
+          }
+        }
+      };
+      if constexpr (EPI && AHEAD) eload(0, 0);
       float ssum[NT][4], ssq[NT][4];
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
@@ -405,13 +444,29 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const unsigned cshift = (unsigned)((cg * NT + nt) * 16);
+        if constexpr (EPI && AHEAD) {
+          if (nt + 1 < NT) eload(nt + 1, (nt + 1) & 1);
+        } else if constexpr (EPI) {
+          eload(nt, 0);
+        }
+        const int es = AHEAD ? (nt & 1) : 0;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const bool bad = ((obad >> r) & 1u) || !cvalid[nt];
           f32x4 v;     // main + cross * 2^-11: one fma per element (exact scaling: the bits of multiply-then-add)
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = fmaf(accx[r][nt][j], 1.0f / 2048.f, acc[r][nt][j]) + bias4[nt][j];
-          if (a.stats_partial && !bad) {
+          if constexpr (EPI) {
+            // affine_gather_kernel: v = v * sc + sh (two roundings: -ffp-contract=off); v = add + v; relu
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              float t = v[j] * esc[es][j];
+              t = t + esh[es][j];
+              if (a.out_add) t = eres[es][r][j] + t;
+              if (a.out_act == VX_ACT_RELU) t = fmaxf(t, 0.f);
+              v[j] = t;
+            }
+          } else if (a.stats_partial && !bad) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) { ssum[nt][j] += v[j]; ssq[nt][j] = fmaf(v[j], v[j], ssq[nt][j]); }
           }
@@ -423,7 +478,7 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      if (a.stats_partial) {
+      if (!EPI && a.stats_partial) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -540,7 +595,7 @@ int vx_pack_conv2d_s16(const float* w_torch, float* w_packed, int Cin, int Cout,
   return VX_OK;
 }
 
-template <int KS, int S, int NT, int NSUB, int TY, int OCT = 0>
+template <int KS, int S, int NT, int NSUB, int TY, int OCT = 0, bool EPI = false>
 static int launch_c2s(const Conv2dSArgs& ka_in, hipStream_t s) {
   constexpr int HX = 15 * S + KS, HY = (TY - 1) * S + KS;
   constexpr int NPP = ((HX + S - 1) / S) * ((HY + S - 1) / S);
@@ -549,13 +604,14 @@ static int launch_c2s(const Conv2dSArgs& ka_in, hipStream_t s) {
   constexpr int NSTEP = KS == 3 ? (OCT ? (9 * OCT + 3) / 4 : 5 * NSUB) : NSUB / 2;
   constexpr int TABC = OCT ? ((OCT * 8 + 15) / 16) * 16 : NSUB * 16;
   constexpr size_t wch = (size_t)NSTEP * NT * 2 * 64 * 8 * 2;
-  constexpr size_t rest = (size_t)IMG_H * 4 + (size_t)8 * NT * 16 * 2 * 4 + (size_t)2 * TABC * 4;   // image, statistics, prologue table
+  constexpr size_t rest = (size_t)IMG_H * 4 + (size_t)8 * NT * 16 * 2 * 4 + (size_t)2 * TABC * 4 +   // image, statistics, prologue table,
+                          (EPI ? (size_t)2 * NT * 16 * 4 : 0);                                       // epilogue table
   static_assert(rest + wch <= 160 * 1024, "LDS budget");
   Conv2dSArgs ka = ka_in;
   ka.w_all = (ka.nchunks > 1 && rest + ka.nchunks * wch <= 160 * 1024) ? 1 : 0;
   const size_t lds = rest + (ka.w_all ? ka.nchunks : 1) * wch;
   static size_t attr_lds = 0;
-  auto kern = conv2d_s16_kernel<KS, S, NT, NSUB, TY, OCT>;
+  auto kern = conv2d_s16_kernel<KS, S, NT, NSUB, TY, OCT, EPI>;
   if (lds > attr_lds) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) VX_FAIL((int)e, "vx_conv2d(s16): hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
@@ -570,21 +626,29 @@ static int launch_c2s(const Conv2dSArgs& ka_in, hipStream_t s) {
   int gx = (256 * per_cu + ygroups - 1) / ygroups;
   if (gx > total_tiles) gx = total_tiles;
   // every template argument, defaulted ones included: the list rocprofv3 prints for the instance
-  static const char* kname = vx_kname("conv2d_s16_kernel<%d,%d,%d,%d,%d,%d>", KS, S, NT, NSUB, TY, OCT);
+  // (the epilogue instances carry a seventh argument, 1; the others keep the six-argument name they always reported)
+  static const char* kname = EPI ? vx_kname("conv2d_s16_kernel<%d,%d,%d,%d,%d,%d,1>", KS, S, NT, NSUB, TY, OCT)
+                                 : vx_kname("conv2d_s16_kernel<%d,%d,%d,%d,%d,%d>", KS, S, NT, NSUB, TY, OCT);
   vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ygroups), dim3(512), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv2d(s16)");
   return VX_OK;
 }
 
+template <int KS, int S, int NSUB, int TY, int OCT, bool EPI>
+static int dispatch_c2s_e(const Conv2dSArgs& ka, int NT, hipStream_t s) {
+  if constexpr (KS == 1) {
+    if (NT == 5) return launch_c2s<KS, S, 5, NSUB, TY, OCT, EPI>(ka, s);
+  }
+  if (NT == 3) return launch_c2s<KS, S, 3, NSUB, TY, OCT, EPI>(ka, s);
+  if (NT == 2) return launch_c2s<KS, S, 2, NSUB, TY, OCT, EPI>(ka, s);
+  return launch_c2s<KS, S, 1, NSUB, TY, OCT, EPI>(ka, s);
+}
+// every instance family exists with and without the output epilogue (vx_conv2d_args.out_scale)
 template <int KS, int S, int NSUB, int TY, int OCT = 0>
 static int dispatch_c2s(const Conv2dSArgs& ka, int NT, hipStream_t s) {
-  if constexpr (KS == 1) {
-    if (NT == 5) return launch_c2s<KS, S, 5, NSUB, TY, OCT>(ka, s);
-  }
-  if (NT == 3) return launch_c2s<KS, S, 3, NSUB, TY, OCT>(ka, s);
-  if (NT == 2) return launch_c2s<KS, S, 2, NSUB, TY, OCT>(ka, s);
-  return launch_c2s<KS, S, 1, NSUB, TY, OCT>(ka, s);
+  if (ka.a.out_scale) return dispatch_c2s_e<KS, S, NSUB, TY, OCT, true>(ka, NT, s);
+  return dispatch_c2s_e<KS, S, NSUB, TY, OCT, false>(ka, NT, s);
 }
 
 // arguments validated by vx_conv2d (conv2d_mfma.hip)

@@ -6,12 +6,24 @@ and therefore the same state-dict key names (`conv1.weight`, `layer1.0.downsampl
 `stage3.2.fuse_layers.1.0.0.0.weight`, `last_layer.3.bias`, ...), so the reference's checkpoints load unchanged.
 The torch.nn layers are PARAMETER CONTAINERS; `forward` walks the tree and launches libvalues_amd.so kernels:
 vx_conv2d (+ batch statistics) -> vx_bn_finalize -> vx_affine_gather (BN affine, ReLU, residual add, bilinear
-fusion, dropout, concat) -> vx_bilinear_nchw.  ATen is never used for arithmetic.
+fusion, dropout, concat) -> vx_bilinear_nchw (eval mode: vx_conv2d with its output epilogue -> vx_fuse_sum / the
+concat -> vx_bilinear_nchw).  ATen is never used for arithmetic.
 
-Semantics kept from the reference: BatchNorm always normalises with the statistics of the CURRENT batch
-(the reference never calls .eval()); the running-statistics side effect is not reproduced (it cannot influence
-outputs).  DROPOUT_FINAL is F.dropout(0.5, training=True) on the four stage-4 outputs, so only the head differs
-between MC samples: `forward_samples` runs the backbone once and the head T times (exact).
+BatchNorm.  Default (train mode, the state of a fresh nn.Module): batch statistics as the reference runs --
+every BatchNorm normalises with the statistics of the CURRENT batch (the reference never calls .eval()); the running-
+statistics side effect is not reproduced, so a forward never changes the buffers.  `.eval()`: running statistics -- every
+BatchNorm is the per-channel affine of its stored running_mean / running_var (one table for the model, one
+vx_bn_running_affine launch per checkpoint), applied with the residual and the ReLU in the producing conv's epilogue
+(vx_conv2d_args.out_scale): no statistics partials, no vx_bn_finalize launches, no block-end affine pass, and an image's
+logits no longer depend on its batch mates; statistics groups (the batched TTA views) mean nothing there.  `.train()`
+afterwards gives the bits of a model that never left train mode.
+DROPOUT_FINAL is F.dropout(0.5, training=True) on the four stage-4 outputs -- live in BOTH modes, as in the reference --
+so only the head differs between MC samples: `forward_samples` runs the backbone once and the head T times (exact).
+
+fp16 range.  The split-fp16 convs stage every activation as hi + lo * 2^-11 in fp16: they assume |activation| < 65504.  In
+train mode the batch statistics renormalise every layer, whatever the weights; in eval mode the range is whatever the
+checkpoint's running statistics leave, and nothing guards it: a checkpoint whose activations pass 65504 needs the
+native-fp32 kernels (vx_config.conv_fp32 = 1, where eval mode takes the raw conv + vx_affine_gather route).
 
 HIP path limits: every branch width and the stem/bottleneck widths must be multiples of 16 (true for the shipped W48
 config: 48/96/192/384, 64/256, 720).  The SSN head (hrnet_config_ssn.yaml) returns a LowRankNormal2D.
@@ -276,6 +288,8 @@ class HighResolutionNet(nn.Module):
         # activation tensor has round16(C) channels whose tail is exactly 0 (zero weight rows, zero BN scale/shift)
         self._last_parts = list(pre)
         self._packed, self._packed_key = None, None
+        self._affine, self._affine_key, self._affine_hold = None, None, None   # eval mode: _ensure_affine
+        self._ev = False       # the forward in flight runs in eval mode (running statistics)
         self._zcache = {}      # persistent zero-padded buffers (see _conv): (layer, device, stream) -> (geometry, tensor)
         self._zreal = {}       # layer -> real channel count of its padded output (zero_tails_intact)
         self._groups = 1       # statistics groups of the forward in flight (forward_samples)
@@ -347,10 +361,15 @@ class HighResolutionNet(nn.Module):
         return packed
 
     # ------------------------------------------------------------------ kernel wrappers
-    def _conv(self, x: _Act, name, stats=True, pre=None, out_pitch=None):
+    def _conv(self, x: _Act, name, stats=True, pre=None, out_pitch=None, epi=None, tail=None):
         """pre = (scale, shift): `x` is the RAW output of the previous conv and relu(x * scale + shift) -- its training-mode
         BatchNorm + ReLU -- is applied while this conv stages its tiles (vx_conv2d_args.in_scale): the affine pass that
-        would write the activated tensor (and the read of it) disappear."""
+        would write the activated tensor (and the read of it) disappear.
+        epi = (scale, shift, add, relu): eval mode, the running-statistics BatchNorm, the residual `add` (an _Act or None)
+        and the ReLU applied as the conv stores (vx_conv2d_args.out_scale).  tail: the output feeds another conv, so a
+        width that is no multiple of 4 goes to the layer's zero-tailed buffer (default: as `stats`)."""
+        if tail is None:
+            tail = stats
         lib = _lib.load()
         wp, b, cin, cout, ks, stride, _w, fam = self._pk[name]
         cin_pad = (cin + 15) // 16 * 16
@@ -359,7 +378,7 @@ class HighResolutionNet(nn.Module):
         oh = (h + 2 * (ks // 2) - ks) // stride + 1
         ow = (w + 2 * (ks // 2) - ks) // stride + 1
         pitch = (cout + 3) // 4 * 4
-        if cout % 4 and stats:      # feeds another conv: the channels [cout, round4(cout)) stay zero (see __init__)
+        if cout % 4 and tail:       # feeds another conv: the channels [cout, round4(cout)) stay zero (see __init__)
             pitch = _rp(cout)
             # the conv writes channels [0, round4(cout)) only, so the zero tail survives from forward to forward: one
             # buffer per layer and geometry, zero-filled once (a fill kernel per conv launch was the top entry of the
@@ -394,6 +413,13 @@ class HighResolutionNet(nn.Module):
             a.in_scale, a.in_shift, a.in_relu = scale.data_ptr(), shift.data_ptr(), 1
             a.in_cpitch = x.C                                   # rows of scale / shift [G][C] (C = the padded channel count)
             a.in_group_images = (n // self._groups) if self._groups > 1 else 0
+        if epi is not None:
+            e_scale, e_shift, e_add, e_relu = epi
+            a.out_scale, a.out_shift = e_scale.data_ptr(), e_shift.data_ptr()
+            a.out_act = _lib.VX_ACT_RELU if e_relu else _lib.VX_ACT_NONE
+            if e_add is not None:
+                assert (e_add.N, e_add.H, e_add.W) == (n, oh, ow) and e_add.pitch >= _rp(cout), name
+                a.out_add, a.out_add_pitch = e_add.t.data_ptr(), e_add.pitch
         prof = getattr(self, "_prof", None)
         if prof is not None:       # diagnostic (profile_forward): a HIP event pair around the launch, on its stream
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -404,7 +430,7 @@ class HighResolutionNet(nn.Module):
             prof.append((lib.vx_last_kernel_name().decode(), 2.0 * ks * ks * cin * cout * n * oh * ow,
                          4.0 * (n * h * w * cin + n * oh * ow * cout + ks * ks * cin * cout), e0, e1))
         self._hold += [out, part]
-        act = _Act(out, pitch if (cout % 4 and stats) else cout)
+        act = _Act(out, pitch if (cout % 4 and tail) else cout)
         act.real_c = cout
         return act, part, ntiles
 
@@ -440,6 +466,56 @@ class HighResolutionNet(nn.Module):
         if self._fold():
             return self._conv_bn(r[0], conv_name, bn_name, pre=(r[1], r[2]))
         return self._conv_bn(self._aff(r[0], r[1], r[2], relu=True), conv_name, bn_name)
+
+    # ------------------------------------------------------------------ eval mode: running statistics
+    def _ensure_affine(self, dev):
+        """model.eval(): every BatchNorm is the per-channel affine of its RUNNING statistics, known before the forward
+        starts.  One table for the whole model -- per layer a scale row and a shift row of round4(C) floats, the tail
+        zero -- written by ONE vx_bn_running_affine launch, rebuilt when a parameter or a running buffer changes
+        (load_state_dict bumps their versions).  Built by the first eval forward, i.e. before any graph capture (graphed()
+        and GraphedPredictor2D warm up eagerly)."""
+        bns = [(n, m) for n, m in self.named_modules() if isinstance(m, nn.BatchNorm2d)]
+        for n, m in bns:
+            if m.running_mean is None or m.running_var is None:
+                raise ValueError(f"eval mode needs running statistics: {n} tracks none (track_running_stats=False)")
+        key = self._packed_key + tuple((b.data_ptr(), b._version, str(b.device)) for _, m in bns
+                                       for b in (m.running_mean, m.running_var)) + (str(dev),)
+        if self._affine is not None and self._affine_key == key:
+            return self._affine
+        eps = {float(m.eps) for _, m in bns}
+        if len(eps) != 1:
+            raise NotImplementedError("values_amd.HighResolutionNet: the BatchNorm layers must share one eps")
+        rows = torch.empty(sum(2 * _rp(m.num_features) for _, m in bns), dtype=torch.float32, device=dev)
+        items = (_lib.BnAffineItem * len(bns))()
+        tab, hold, off = {}, [], 0
+        for k, (n, m) in enumerate(bns):
+            c, cp = m.num_features, _rp(m.num_features)
+            gamma, beta = self._pk[n]
+            mean = m.running_mean.detach().to(dev, torch.float32).contiguous()
+            var = m.running_var.detach().to(dev, torch.float32).contiguous()
+            hold += [mean, var]
+            sc, sh = rows[off:off + cp], rows[off + cp:off + 2 * cp]
+            off += 2 * cp
+            it = items[k]
+            it.gamma, it.beta, it.running_mean, it.running_var = gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), var.data_ptr()
+            it.scale, it.shift, it.C, it.cpitch = sc.data_ptr(), sh.data_ptr(), c, cp
+            tab[n] = (sc, sh)
+        dtab = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(dev)
+        _lib.check(_lib.load().vx_bn_running_affine(_lib.ptr(dtab), len(bns), eps.pop(), _lib.stream_ptr()),
+                   "vx_bn_running_affine")
+        # the launch reads the statistics and the item table in stream order: keep them until the next rebuild
+        self._affine, self._affine_key, self._affine_hold = tab, key, (rows, dtab, hold)
+        return tab
+
+    def _cba(self, x: _Act, conv_name, bn_name, relu, add: Optional[_Act] = None) -> _Act:
+        """eval mode: act(add + bn(conv(x))) with the running statistics.  Split-fp16 path: in the conv's epilogue, nothing
+        else is launched.  VX_HRNET_NO_FOLD=1 / conv_fp32 = 1: the raw conv, then vx_affine_gather fed from the table
+        (the same bits: vx_conv2d_args.out_scale)."""
+        sc, sh = self._affine[bn_name]
+        if self._fold():
+            return self._conv(x, conv_name, stats=False, tail=True, epi=(sc, sh, add, relu))[0]
+        raw = self._conv(x, conv_name, stats=False, tail=True)[0]
+        return self._aff(raw, sc, sh, relu=relu, add=add)
 
     def _aff(self, x: _Act, scale=None, shift=None, relu=False, add: Optional[_Act] = None, out: Optional[_Act] = None,
                out_coff=0, size=None, drop=None):
@@ -490,6 +566,13 @@ class HighResolutionNet(nn.Module):
     def _block(self, x: _Act, p: str, blk: _Block) -> _Act:
         # relu(bn(conv)) feeding the next conv of the block is never written: that conv applies it on load (FOLD; the
         # separate affine pass remains behind VX_HRNET_NO_FOLD=1 for A/B and for the native-fp32 kernels)
+        if self._ev:     # running statistics: every conv finishes its BatchNorm (+ residual, ReLU) itself (_cba)
+            res = x if blk.downsample is None else self._cba(x, p + ".downsample.0", p + ".downsample.1", relu=False)
+            a = self._cba(x, p + ".conv1", p + ".bn1", relu=True)
+            if blk.kind == "BASIC":
+                return self._cba(a, p + ".conv2", p + ".bn2", relu=True, add=res)
+            a = self._cba(a, p + ".conv2", p + ".bn2", relu=True)
+            return self._cba(a, p + ".conv3", p + ".bn3", relu=True, add=res)
         if blk.kind == "BASIC":
             r1 = self._conv_bn(x, p + ".conv1", p + ".bn1")
             r2 = self._conv_bn_after(r1, p + ".conv2", p + ".bn2")
@@ -529,6 +612,29 @@ class HighResolutionNet(nn.Module):
         nb = mod.num_branches
         multifuse = nb <= 4 and not os.environ.get("VX_HRNET_NO_MULTIFUSE")
         for i in range(len(mod.fuse_layers)):
+            if self._ev:
+                # the reference's order: upsample(bn(conv(x))) -- the affine at the term's own resolution (in its conv), then
+                # the terms enter the sum with null scale / shift
+                terms = []
+                for j in range(nb):
+                    t = xs[j]
+                    if j > i:
+                        q = f"{p}.fuse_layers.{i}.{j}"
+                        t = self._cba(t, q + ".0", q + ".1", relu=False)
+                    elif j < i:
+                        for k in range(i - j):
+                            q = f"{p}.fuse_layers.{i}.{j}.{k}"
+                            t = self._cba(t, q + ".0", q + ".1", relu=k < i - j - 1)
+                    terms.append((t, None, None))
+                if multifuse:
+                    outs.append(self._fuse(terms, xs[i]))
+                    continue
+                size = (xs[i].H, xs[i].W)    # term by term (vx_fuse_sum states itself as this chain)
+                y = terms[0][0] if (terms[0][0].H, terms[0][0].W) == size else self._aff(terms[0][0], size=size)
+                for k in range(1, nb):
+                    y = self._aff(terms[k][0], relu=k == nb - 1, add=y, size=size)
+                outs.append(y)
+                continue
             if multifuse:
                 # Round 4: all terms of output i in ONE pass (vx_fuse_sum) -- the term-by-term chain below re-read and
                 # re-wrote the accumulator once per term (three passes over the full-resolution branch per stage-4 module)
@@ -605,9 +711,16 @@ class HighResolutionNet(nn.Module):
             if i < n_prev:
                 if tl is None:
                     out.append(ys[i])
+                elif self._ev:
+                    out.append(self._cba(ys[i], f"{tname}.{i}.0", f"{tname}.{i}.1", relu=True))
                 else:
                     r = self._conv_bn(ys[i], f"{tname}.{i}.0", f"{tname}.{i}.1")
                     out.append(self._aff(r[0], r[1], r[2], relu=True))
+            elif self._ev:
+                t = ys[-1]
+                for j in range(len(tl)):
+                    t = self._cba(t, f"{tname}.{i}.{j}.0", f"{tname}.{i}.{j}.1", relu=True)
+                out.append(t)
             else:
                 r = None
                 for j in range(len(tl)):
@@ -628,9 +741,12 @@ class HighResolutionNet(nn.Module):
             xin[..., :cin] = x.permute(0, 2, 3, 1)
         self._hold.append(xin)
         a = _Act(xin, _rp(cin))
-        r = self._conv_bn(a, "conv1", "bn1")
-        r = self._conv_bn_after(r, "conv2", "bn2")
-        a = self._aff(r[0], r[1], r[2], relu=True)
+        if self._ev:
+            a = self._cba(self._cba(a, "conv1", "bn1", relu=True), "conv2", "bn2", relu=True)
+        else:
+            r = self._conv_bn(a, "conv1", "bn1")
+            r = self._conv_bn_after(r, "conv2", "bn2")
+            a = self._aff(r[0], r[1], r[2], relu=True)
         for b, blk in enumerate(self.layer1):
             a = self._block(a, f"layer1.{b}", blk)
         ys = [a]
@@ -655,6 +771,9 @@ class HighResolutionNet(nn.Module):
             off += f.C
         outs = []
         for head in (("last_layer",) + (("cov_factor_conv",) if self.ssn else ())):
+            if self._ev:
+                outs.append(self._conv(self._cba(cat, head + ".0", head + ".1", relu=True), head + ".3", stats=False)[0])
+                continue
             r = self._conv_bn(cat, head + ".0", head + ".1")
             if self._fold():
                 raw, _, _ = self._conv(r[0], head + ".3", stats=False, pre=(r[1], r[2]))
@@ -675,10 +794,14 @@ class HighResolutionNet(nn.Module):
                 drop = (drop_mode, seed, k, None if masks is None else masks[k])
             self._aff(f, out=cat, out_coff=off, size=(h0, w0), drop=drop)   # dropout -> bilinear -> concat slot
             off += f.C
-        r = self._conv_bn(cat, "last_layer.0", "last_layer.1")
-        if self._fold():
+        if self._ev:
+            raw, _, _ = self._conv(self._cba(cat, "last_layer.0", "last_layer.1", relu=True), "last_layer.3", stats=False,
+                                   out_pitch=_softmax_pitch(self.num_classes))
+        elif self._fold():
+            r = self._conv_bn(cat, "last_layer.0", "last_layer.1")
             raw, _, _ = self._conv(r[0], "last_layer.3", stats=False, pre=(r[1], r[2]), out_pitch=_softmax_pitch(self.num_classes))
         else:
+            r = self._conv_bn(cat, "last_layer.0", "last_layer.1")
             raw, _, _ = self._conv(self._aff(r[0], r[1], r[2], relu=True), "last_layer.3", stats=False,
                                    out_pitch=_softmax_pitch(self.num_classes))
         # softmax: `out` receives F.softmax(dim=1) of the upsampled logits (what test_2D.py:300-303 takes of every forward)
@@ -704,6 +827,9 @@ class HighResolutionNet(nn.Module):
         dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
         x = x.detach().to(dev, torch.float32)
         self._pk = self._ensure_packed(dev)
+        self._ev = not self.training
+        if self._ev:
+            self._ensure_affine(dev)
         self._st = _lib.stream_ptr()
         # the previous forward's intermediates were kept until now (its kernels are enqueued ahead of everything this call
         # launches, on streams this call joins before reusing memory): release them BEFORE allocating this forward's, or two
@@ -723,7 +849,8 @@ class HighResolutionNet(nn.Module):
             raise ValueError("forward_samples: the batch must hold `groups` equal groups of images")
         if groups > 1 and n_samples != 1:
             raise ValueError("forward_samples: batched view groups go with n_samples = 1")
-        self._groups = groups
+        # eval mode: the statistics are the checkpoint's, the same for every view -- one table row, no groups
+        self._groups = 1 if self._ev else groups
         try:
             feats = self._backbone(x, nhwc=nhwc)
         except Exception:
@@ -831,6 +958,9 @@ class HighResolutionNet(nn.Module):
         dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
         x = x.detach().to(dev, torch.float32)
         self._pk = self._ensure_packed(dev)
+        self._ev = not self.training
+        if self._ev:
+            self._ensure_affine(dev)
         self._st = _lib.stream_ptr()
         # the previous forward's intermediates were kept until now (its kernels are enqueued ahead of everything this call
         # launches, on streams this call joins before reusing memory): release them BEFORE allocating this forward's, or two
