@@ -662,9 +662,45 @@ int vx_ssn_sample(const float* head, const float* eps_w, const float* eps_d, uin
  *   src_u8 = 0: src = clean, noise0 = noisy, both [B][3][H][W] float32 already normalised (values_amd.predict2d.tta_views_8).
  *   view_code [G] (HOST array): bit 0 HorizontalFlip, bit 1 VerticalFlip, bit 2 noisy, bit 3 the noise field is indexed at
  *     the SOURCE pixel (flip of the noisy image) instead of the view's (noise drawn after the flip, as the dataset does),
- *     bit 4 noise slot (u8 source).  The reference's four views: {0, 1, 4, 1 | 4 | 16}. */
+ *     bit 4 noise slot (u8 source).  The reference's four views: {0, 1, 4, 1 | 4 | 16}.  Codes above 31 are refused (bit 5,
+ *     "generated field", belongs to vx_tta_views_2d_gen below). */
 int vx_tta_views_2d(const void* src, int src_u8, const float* noise0, const float* noise1, const float* mean, const float* std,
                     float max_pixel_value, int B, int H, int W, int G, const int32_t* view_code, float* out, vx_stream_t stream);
+
+/* vx_tta_views_2d with the noise fields of its noisy views DRAWN on the device (uint8 source only).  One more view-code bit:
+ * bit 5 = this view's field is generated (with bit 2; a view without bit 5 behaves as in vx_tta_views_2d, a supplied field
+ * included, so supplied and generated fields mix in one call).  The additive term of a generated view at field element
+ * e = (y * W + x) * 3 + c -- (x, y) the view's pixel, or the SOURCE pixel with bit 3, exactly as a supplied field is indexed --
+ * is sqrt(var[b][k]) * N(0, 1), the normal being element e of stream (image0 + b) * 2 + k of the generator the sampling
+ * kernels use (vx_gauss, keyed by (seed + *seed_dev, stream, element); float64 restatement: tests/noise_ref.py), k the noise
+ * slot of bit 4, and var[b][k] = var_limit[0] + (var_limit[1] - var_limit[0]) * u with ONE uniform u in [0, 1) per (image,
+ * slot) from a stream no element shares.  Then the uint8 path of vx_tta_views_2d: clip to 0..255, truncate, normalise.
+ * This is the DISTRIBUTION of albumentations' GaussNoise(var_limit=(10, 50), mean=0, per_channel=True) on the project's own
+ * stream -- the library's draws come from its own RNG, bit parity with them is out of scope.  image0: global index of the
+ * batch's first image (a view does not depend on how images are batched).  seed_dev: nullable device word added to seed
+ * (as vx_conv3d_args.seed_dev).  var_limit: HOST float[2], 0 <= lo <= hi.  sigma_out: nullable device [B][2], the scale
+ * sqrt(var) of both slots of every image, written when at least one view is generated.  Codes above 63, bit 5 without bit 2
+ * and bit 5 with the f32 source are refused (VX_E_DTYPE). */
+int vx_tta_views_2d_gen(const void* src, int src_u8, const float* noise0, const float* noise1, const float* mean,
+                        const float* std, float max_pixel_value, int B, int H, int W, int G, const int32_t* view_code,
+                        uint32_t seed, const uint32_t* seed_dev, int64_t image0, const float* var_limit, float* sigma_out,
+                        float* out, vx_stream_t stream);
+
+/* The noisy input of the 3D TTA (predict_cases, test_3D.py:428: GaussianNoiseTransform, variance ~ U(0, 0.1)) drawn on the
+ * device:  out[v][r] = x[v][r] + sigma_g * N(0, 1)  for v in [0, V), r in [0, per), per = C * D * H * W < 2^32, the normal
+ * being element r of stream g = index0 + v of vx_gauss under seed + *seed_dev (seed_dev: nullable device word, as
+ * vx_conv3d_args.seed_dev -- a captured graph draws fresh noise per replay).  g is the volume's GLOBAL index: with the seed
+ * it is all that keys the volume's stream, so chunks, shards and batch sizes do not change a view.
+ * var_g = var_lo + (var_hi - var_lo) * u, ONE uniform u in [0, 1) per volume from a stream no element shares;
+ * sigma_law 0: sigma_g = sqrt(var_g) (values_amd.predict.gaussian_noise_view; the default everywhere);
+ * sigma_law 1: sigma_g = var_g (what batchgenerators' augment_gaussian_noise is believed to do -- it hands the drawn
+ * "variance" to numpy's normal() as the scale; UNVERIFIED, the library is not available to this project).
+ * The distribution is the reference's, the stream the project's own (float64 restatement: tests/noise_ref.py).
+ * sigma_out: nullable device [V].  out may be the second half of an [orig | noisy] buffer whose first half is x; x and out
+ * must not overlap partially.  Refused: V <= 0, per >= 2^32, index0 < 0 or index0 + V > 2^32, var_lo < 0, var_hi < var_lo
+ * (VX_E_SHAPE); null x / out (VX_E_NULL); another sigma_law (VX_E_DTYPE).  per == 0 is a no-op. */
+int vx_noise_view_3d(const float* x, float* out, int V, int64_t per, uint32_t seed, const uint32_t* seed_dev, int64_t index0,
+                     float var_lo, float var_hi, int sigma_law, float* sigma_out, vx_stream_t stream);
 
 /* Colour rendering of an arg-max mask (Tester.save_prediction, test_2D.py:124-134): rgb[i] = lut[labels[i]] with
  * labels[i] := unlabeled where ignore[i] != 0 (ignore nullable); lut [256][3] uint8, rgb [n][3]. */

@@ -3,6 +3,7 @@ from .unet3d import UNet3D  # noqa: F401
 from .ssn import SsnUNet3D  # noqa: F401
 from .uncertainty import (calculate_one_minus_msr, calculate_uncertainty, one_minus_msr_batch, softmax_variance,  # noqa: F401
                           uncertainty_maps)
-from .predict import GraphedPredictor, HostPipeline, predict_logits, predict_uncertainty, crop_indices  # noqa: F401
+from .predict import (GraphedPredictor, HostPipeline, crop_indices, noise_view_device, predict_logits,  # noqa: F401
+                      predict_uncertainty)
 from .io import load_models_from_checkpoint, instantiate  # noqa: F401
 from .sliding import predict_image_sliding  # noqa: F401

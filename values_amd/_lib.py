@@ -312,6 +312,9 @@ SIGNATURES = {
     "vx_fuse_sum": (_i, [C.POINTER(FuseArgs), _p]),
     "vx_tta_views_2d": (_i, [_p, _i, _p, _p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i, _i,
                              C.POINTER(C.c_int32), _p, _p]),
+    "vx_tta_views_2d_gen": (_i, [_p, _i, _p, _p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i, _i,
+                                 C.POINTER(C.c_int32), _u32, _p, _i64, C.POINTER(C.c_float), _p, _p, _p]),
+    "vx_noise_view_3d": (_i, [_p, _p, _i, _i64, _u32, _p, _i64, C.c_float, C.c_float, _i, _p, _p]),
     "vx_count_nonzero_batched_workspace_bytes": (_i64, [_i]),
     "vx_count_nonzero_batched": (_i, [C.POINTER(CountItem), _i, _p, _p, _i64, _p]),
     "vx_select_segments_workspace_bytes": (_i64, [_i]),

@@ -5,6 +5,7 @@
 // the same voxels, so sums go through float atomics when `overlap` is set (patch_overlap < 1); with the shipped
 // patch_overlap = 1 every voxel is written once and plain stores are used (bit-reproducible).
 #include "common.h"
+#include "gauss.h"
 
 template <int C>
 __global__ __launch_bounds__(256) void softmax_accumulate_kernel(const float* __restrict__ logits, int B, int T, int P0,
@@ -71,15 +72,7 @@ extern "C" int vx_softmax_accumulate(const float* logits, int B, int T, int C, i
 // Aleatoric-head sampling (predict_cases, test_3D.py:458-469): one forward gives (mu, s) = split(final_aleatoric);
 // sigma = exp(s / 2); sample t: logits_t = mu + sigma * eps_t, eps ~ N(0, 1).  eps is either injected (parity with
 // the reference's torch.randn stream is impossible otherwise) or generated here: Box-Muller on two avalanche
-// hashes of (seed, sample, element).
-__device__ __forceinline__ float vx_gauss(uint32_t seed, uint32_t a, uint32_t b) {
-  const uint32_t h1 = vx_mix32(a * 0x9E3779B1u ^ vx_mix32(seed ^ (b * 0x85EBCA6Bu + 0x165667B1u)));
-  const uint32_t h2 = vx_mix32(h1 ^ 0x27D4EB2Fu ^ (a * 0xC2B2AE35u));
-  const float u1 = ((float)(h1 >> 8) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-  const float u2 = (float)(h2 >> 8) * (1.0f / 16777216.0f);           // [0, 1)
-  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-}
-
+// hashes of (seed, sample, element) -- vx_gauss, gauss.h.
 __global__ __launch_bounds__(256) void aleatoric_sample_kernel(const float* __restrict__ mu_s, const float* __restrict__ eps,
                                                                uint32_t seed, int N, int T, int C, int64_t nvox,
                                                                float* __restrict__ out, float* __restrict__ sigma) {

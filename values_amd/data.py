@@ -5,7 +5,8 @@
                     views [img, HFlip(img), Noise(img), Noise(HFlip(img))] + the transform names test_2D.py uses to
                     un-flip (:304-309).  albumentations' GaussNoise (var_limit (10, 50), per-image RNG) is third-party
                     and absent: the noise field is an INPUT here (parity unpinned for the two noisy views; the flip
-                    views are exact).
+                    views are exact).  tta_views_2d_device(noise_seed=...) draws fields of that DISTRIBUTION on the
+                    device from the project's own generator.
 """
 from __future__ import annotations
 
@@ -52,17 +53,26 @@ def tta_views_2d(img: np.ndarray, mean: Sequence[float], std: Sequence[float], n
 
 
 # view codes of vx_tta_views_2d (include/values_amd.h): bit 0 HorizontalFlip, bit 1 VerticalFlip, bit 2 noisy,
-# bit 3 noise field indexed at the source pixel, bit 4 noise slot
+# bit 3 noise field indexed at the source pixel, bit 4 noise slot, bit 5 (vx_tta_views_2d_gen) the field is generated
 TTA_2D_VIEW_CODES = [0, 1, 4, 1 | 4 | 16]                      # the reference's four views, noise drawn after the flip
 TTA_8_VIEW_CODES = [0, 1, 2, 3, 4 | 8, 5 | 8, 6 | 8, 7 | 8]    # config C4: {id, H, V, HV} of the clean and of the noisy image
 
 
 def tta_views_2d_device(img, mean: Sequence[float], std: Sequence[float], noise=None, noise_flipped=None,
-                        max_pixel_value: float = 255.0, view_codes: Optional[Sequence[int]] = None):
+                        max_pixel_value: float = 255.0, view_codes: Optional[Sequence[int]] = None,
+                        noise_seed: Optional[int] = None, image_index0: int = 0, var_limit=(10.0, 50.0),
+                        return_sigma: bool = False):
     """tta_views_2d on the device, one launch (vx_tta_views_2d): img (B, H, W, 3) or (H, W, 3) uint8 tensor (host or
     device), noise / noise_flipped float fields of the same shape or None.  Returns (views, transforms): views a float32
     device tensor (G, B, H, W, 4) -- channels-last at pitch 4, channel 3 zero: the layout HighResolutionNet's stem stages
-    from (pass it on with nhwc=True) -- bit-exact with the host function's values; transforms as tta_views_2d."""
+    from (pass it on with nhwc=True) -- bit-exact with the host function's values; transforms as tta_views_2d.
+    noise_seed: a noisy view whose field is None is DRAWN on the device (vx_tta_views_2d_gen, view-code bit 5) instead of
+    degenerating to the clean view: sqrt(var) * N(0, 1) per channel with var ~ U(var_limit) per (image, slot) -- the
+    distribution of albumentations' GaussNoise(var_limit=(10, 50), mean=0, per_channel=True), drawn from THIS project's
+    generator (vx_gauss; stream (image_index0 + b) * 2 + slot of the seed), not albumentations' stream: reproducible from
+    the seed and independent of the batching, never bit-equal to the library's draw.  A supplied field still wins for its
+    slot.  With TTA_8_VIEW_CODES the four noisy views are ONE draw flipped four ways.  return_sigma: also a (B, 2) tensor
+    of the scales sqrt(var) of both slots (None when no view was generated)."""
     import ctypes as C
 
     import torch
@@ -90,17 +100,30 @@ def tta_views_2d_device(img, mean: Sequence[float], std: Sequence[float], noise=
             raise ValueError("tta_views_2d_device: noise fields have the image's shape")
         return n.contiguous()
     n0, n1 = field(noise), field(noise_flipped)
-    for g, c in enumerate(codes):      # a noisy view without its field degenerates to the clean one, as the host function's does
+    generated = False
+    for g, c in enumerate(codes):
         if (c & 4) and (n1 if (c & 16) else n0) is None:
-            codes[g] = c & 3
+            if noise_seed is not None:     # drawn on the device
+                codes[g] = c | 32
+                generated = True
+            else:                          # degenerates to the clean view, as the host function's does
+                codes[g] = c & 3
     out = torch.empty((len(codes), B, H, W, 4), dtype=torch.float32, device=dev)
     m3 = (C.c_float * 3)(*[float(v) for v in mean])
     s3 = (C.c_float * 3)(*[float(v) for v in std])
     vc = (C.c_int32 * len(codes))(*codes)
-    _lib.check(lib.vx_tta_views_2d(_lib.ptr(t), 1, _lib.ptr(n0), _lib.ptr(n1), m3, s3, float(max_pixel_value), B, H, W,
-                                   len(codes), vc, _lib.ptr(out), _lib.stream_ptr()), "vx_tta_views_2d")
+    sigma = None
+    if generated:
+        sigma = torch.empty((B, 2), dtype=torch.float32, device=dev) if return_sigma else None
+        vl = (C.c_float * 2)(float(var_limit[0]), float(var_limit[1]))
+        _lib.check(lib.vx_tta_views_2d_gen(_lib.ptr(t), 1, _lib.ptr(n0), _lib.ptr(n1), m3, s3, float(max_pixel_value), B, H, W,
+                                           len(codes), vc, int(noise_seed) & 0xFFFFFFFF, None, int(image_index0), vl,
+                                           _lib.ptr(sigma), _lib.ptr(out), _lib.stream_ptr()), "vx_tta_views_2d_gen")
+    else:
+        _lib.check(lib.vx_tta_views_2d(_lib.ptr(t), 1, _lib.ptr(n0), _lib.ptr(n1), m3, s3, float(max_pixel_value), B, H, W,
+                                       len(codes), vc, _lib.ptr(out), _lib.stream_ptr()), "vx_tta_views_2d")
     names = [[nm for bit, nm in ((1, "HorizontalFlip"), (2, "VerticalFlip"), (4, "GaussNoise")) if c & bit] for c in codes]
-    return out, names
+    return (out, names, sigma) if return_sigma else (out, names)
 
 
 def tta_views_8_device(x, x_noisy, out=None):

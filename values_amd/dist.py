@@ -206,11 +206,16 @@ def passes_per_member(model, n_pred: int = 1, tta: bool = False, n_aleatoric_sam
 
 def ensemble_uncertainty_sharded(models, x: torch.Tensor, world: int, rank: int, n_pred: int = 1, dst: int = 0,
                                  seeds=None, group=None, tta: bool = False, x_noise=None,
-                                 n_aleatoric_samples: int = 10, range_check: str = "fallback") -> Optional[Dict[str, torch.Tensor]]:
+                                 n_aleatoric_samples: int = 10, range_check: str = "fallback",
+                                 noise_seed: Optional[int] = None, variance=(0.0, 0.1),
+                                 sigma_law: str = "sqrt") -> Optional[Dict[str, torch.Tensor]]:
     """models: the FULL member list (every rank holds all checkpoints; only its items run).  x: (V,1,D,H,W), the
     same on every rank.  Returns the maps on `dst` (None elsewhere).  The number of passes of a member is taken from the
     logits it produced (and checked against passes_per_member); the total every rank finalises with is the sum over
     ALL members, whichever rank ran them.
+    noise_seed (tta=True, no x_noise): every item draws the noisy views of its volumes on the device
+    (values_amd.predict.noise_view_device) with noise_index0 = the block's first volume, so a volume's view is the same on
+    whichever rank and in whichever block it runs: the gathered result equals the single-device one.
     range_check: the fp16 range guard (values_amd.predict.guarded) around THIS rank's items, BEFORE the collective: a rank
     whose forwards overflowed recomputes its own statistics on the native-fp32 kernels and then joins the one sum-reduce --
     the ranks never disagree about which collective comes next."""
@@ -238,6 +243,8 @@ def ensemble_uncertainty_sharded(models, x: torch.Tensor, world: int, rank: int,
             kw = {"seeds": [derive_seed(int(seeds[m]), 1, lo)]} if seeds is not None else {}
             if tta:
                 kw["x_noise"] = None if x_noise is None else x_noise[lo:hi]
+                if x_noise is None and noise_seed is not None:
+                    kw.update(noise_seed=noise_seed, noise_index0=lo, variance=variance, sigma_law=sigma_law)
             logits = predict_logits([models[m]], x[lo:hi], n_pred=n_pred, tta=tta, n_aleatoric_samples=n_aleatoric_samples,
                                     **kw).contiguous()  # (hi-lo, T_m, C, ...)
             T_m = int(logits.shape[1])

@@ -49,6 +49,45 @@ def gaussian_noise_view(x: torch.Tensor, generator: Optional[torch.Generator] = 
     return x + noise * var.sqrt().view(-1, *([1] * (x.dim() - 1)))
 
 
+SIGMA_LAWS = {"sqrt": 0, "var": 1}
+
+
+def noise_view_device(x: torch.Tensor, seed: int, index0: int = 0, variance=(0.0, 0.1), sigma_law: str = "sqrt",
+                      out: Optional[torch.Tensor] = None, seed_dev: Optional[torch.Tensor] = None, return_sigma: bool = False):
+    """The noisy TTA input drawn on the device by one launch (vx_noise_view_3d): x (V, C, D, H, W) ->
+    x[v] + sigma_g * N(0, 1), the normals of volume v being stream g = index0 + v of the generator the sampling kernels use
+    (vx_gauss) under `seed` (+ the device word `seed_dev`, an int32 tensor of one element: graph replays).  g is the
+    volume's GLOBAL index: the view of a volume does not depend on how a caller chunks, shards or batches, and it is the
+    same on every torch build.  variance: var_g ~ U(variance), one draw per volume.  sigma_law "sqrt": sigma_g =
+    sqrt(var_g), what gaussian_noise_view does (the default); "var": sigma_g = var_g -- what batchgenerators'
+    augment_gaussian_noise is believed to do, handing the drawn "variance" to numpy as the scale (UNVERIFIED: the library
+    is not available here).  The DISTRIBUTION is the reference's (GaussianNoiseTransform, test_3D.py:428); the stream is
+    this project's, not batchgenerators' / numpy's: bit parity with the reference's views is out of scope.
+    out: write there (the noisy half of an [orig | noisy] input, say) instead of a new tensor.  return_sigma: also the
+    (V,) scales."""
+    _lib.require_gpu()
+    if sigma_law not in SIGMA_LAWS:
+        raise ValueError(f"sigma_law must be one of {sorted(SIGMA_LAWS)}, got {sigma_law!r}")
+    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x = x.to(dev, torch.float32).contiguous()
+    if x.dim() < 2:
+        raise ValueError("noise_view_device: x must be (V, ...)")
+    V = int(x.shape[0])
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("noise_view_device: out must be a contiguous float32 tensor of x's shape on x's device")
+    if seed_dev is not None:
+        if seed_dev.dtype != torch.int32 or not seed_dev.is_cuda:
+            raise ValueError("seed_dev: an int32 device tensor of one element")
+    sigma = torch.empty((V,), dtype=torch.float32, device=dev) if return_sigma else None
+    if V:
+        _lib.check(_lib.load().vx_noise_view_3d(_lib.ptr(x), _lib.ptr(out), V, x[0].numel(), int(seed) & 0xFFFFFFFF,
+                                                _lib.ptr(seed_dev), int(index0), float(variance[0]), float(variance[1]),
+                                                SIGMA_LAWS[sigma_law], _lib.ptr(sigma), _lib.stream_ptr()), "vx_noise_view_3d")
+    return (out, sigma) if return_sigma else out
+
+
 @torch.no_grad()
 def _predict_logits_aleatoric(models, x, n_samples, eps=None, seeds=None):
     lib = _lib.load()
@@ -195,12 +234,16 @@ def _volume_chunks(V: int, n_streams: Optional[int], pinned_inputs: bool, sample
 def predict_logits(models: Sequence, x: torch.Tensor, n_pred: int = 1, tta: bool = False,
                    x_noise: Optional[torch.Tensor] = None, dropout_masks=None, seeds=None,
                    n_aleatoric_samples: int = 10, eps=None, n_streams: Optional[int] = None, _after_chunk=None,
-                   seed_dev: Optional[torch.Tensor] = None, **kw_ssn) -> torch.Tensor:
+                   seed_dev: Optional[torch.Tensor] = None, noise_seed: Optional[int] = None, noise_index0: int = 0,
+                   variance=(0.0, 0.1), sigma_law: str = "sqrt", **kw_ssn) -> torch.Tensor:
     """x: (V,1,D,H,W).  Returns logits (V, n_total, C, D,H,W) f32 on the device, n_total = passes per volume in
     pred_idx order.  dropout_masks: optional [member][pass] -> 17 masks (parity tests).  n_streams: volume chunks
     run concurrently on that many HIP streams (default: VX_STREAMS or 1), each with its own workspace; every chunk
     writes straight into its pred_idx slots of the one logits tensor.  _after_chunk(logits, v0, v1): called on the
-    chunk's stream once its forwards are enqueued (predict_uncertainty reduces the chunk there)."""
+    chunk's stream once its forwards are enqueued (predict_uncertainty reduces the chunk there).
+    noise_seed (tta=True, no x_noise): the noisy half of every chunk's input is drawn by vx_noise_view_3d on the chunk's
+    stream -- volume v is stream noise_index0 + v of the seed (+ seed_dev), whatever the chunking; variance / sigma_law as
+    noise_view_device.  Without noise_seed the view comes from gaussian_noise_view (torch's global generator), as before."""
     _lib.require_gpu()
     dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
     x = x.to(dev, torch.float32)
@@ -218,9 +261,12 @@ def predict_logits(models: Sequence, x: torch.Tensor, n_pred: int = 1, tta: bool
     C = models[0].num_classes
     logits = torch.empty((V, n_total, C, D, H, W), dtype=torch.float32, device=dev)
     flat = logits.view(V * n_total, C, D, H, W)
-    if tta and x_noise is None:
+    gen_noise = tta and x_noise is None and noise_seed is not None
+    if gen_noise:
+        x = x.contiguous()
+    elif tta and x_noise is None:
         x_noise = gaussian_noise_view(x)
-    if tta:
+    if tta and not gen_noise:
         x_noise = x_noise.to(dev, torch.float32)
     chunks, n_side = _volume_chunks(V, n_streams, pinned_inputs=dropout_masks is not None, samples_per_volume=per_model)
     main = torch.cuda.current_stream(dev)
@@ -237,7 +283,13 @@ def predict_logits(models: Sequence, x: torch.Tensor, n_pred: int = 1, tta: bool
     for ci, (v0, v1) in enumerate(chunks):
         with torch.cuda.stream(side[ci % len(side)]):
             xc = x[v0:v1]
-            xin = torch.cat([xc, x_noise[v0:v1]], 0) if tta else None   # volumes [0,Vc) orig, [Vc,2Vc) noisy
+            if gen_noise:       # [orig | noisy] filled in place: a copy and ONE launch that writes the noisy half
+                xin = torch.empty((2 * (v1 - v0),) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
+                xin[:v1 - v0].copy_(xc)
+                noise_view_device(xc, noise_seed, index0=noise_index0 + v0, variance=variance, sigma_law=sigma_law,
+                                  out=xin[v1 - v0:], seed_dev=seed_dev)
+            else:
+                xin = torch.cat([xc, x_noise[v0:v1]], 0) if tta else None   # volumes [0,Vc) orig, [Vc,2Vc) noisy
             for mi, model in enumerate(models):
                 base = mi * per_model
                 src, flip, dst = _slot_indices(dev, v0, v1, n_total, base, per_model, tta)
@@ -269,7 +321,8 @@ def predict_logits(models: Sequence, x: torch.Tensor, n_pred: int = 1, tta: bool
 @torch.no_grad()
 def predict_uncertainty(models: Sequence, x: torch.Tensor, n_pred: int = 1, tta: bool = False,
                         x_noise: Optional[torch.Tensor] = None, ssn: bool = False, want_sample_argmax: bool = False,
-                        range_check: str = "fallback", **kw) -> Dict[str, torch.Tensor]:
+                        range_check: str = "fallback", noise_seed: Optional[int] = None, noise_index0: int = 0,
+                        **kw) -> Dict[str, torch.Tensor]:
     """Forward passes + fused reduction.  Returns device tensors keyed like the reference's results:
     pred_entropy / aleatoric_uncertainty / epistemic_uncertainty (V,D,H,W) f32 (test_3D.py:509-516),
     mean_softmax (V,C,D,H,W), pred_seg_mean (V,D,H,W) u8 (data_carrier_3D.py:254-255), logits; plus
@@ -280,12 +333,18 @@ def predict_uncertainty(models: Sequence, x: torch.Tensor, n_pred: int = 1, tta:
     zeroed in stream order at entry (no read), read once after the batch (the ONE synchronisation of this call) and, if
     the limit was reached, the batch is computed again on the native-fp32 kernels with the same dropout seeds -- NaN maps
     never leave this function; "raise": VxError instead; "off": no read and no reset (pipelined callers -- HostPipeline,
-    bench.py -- read the word where they have waited anyway; it keeps the running maximum)."""
+    bench.py -- read the word where they have waited anyway; it keeps the running maximum).
+    noise_seed / noise_index0 (and variance / sigma_law in **kw), as predict_logits takes them: the TTA noise view drawn on
+    the device from the seed -- reproducible, independent of chunking and batch size."""
     if range_check not in ("fallback", "raise", "off"):
         raise ValueError("range_check must be 'fallback', 'raise' or 'off'")
+    if noise_seed is not None:
+        kw = dict(kw, noise_seed=noise_seed, noise_index0=noise_index0)
     if range_check != "off":
         kw = pin_seeds(models, kw, tta=tta)
-        if tta and x_noise is None:      # the generated noise view is drawn ONCE: a range fallback re-runs the same views
+        # torch's generator: the view is drawn ONCE, a range fallback re-runs the same views (with noise_seed the device
+        # draw is a function of the seed and the fallback regenerates them)
+        if tta and x_noise is None and kw.get("noise_seed") is None:
             x_noise = gaussian_noise_view(x.to(x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device()),
                                                torch.float32))
         return guarded(models, lambda: predict_uncertainty(models, x, n_pred=n_pred, tta=tta, x_noise=x_noise, ssn=ssn,

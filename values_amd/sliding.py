@@ -21,7 +21,8 @@ from .uncertainty import uncertainty_maps
 def predict_image_sliding(models: Sequence, image: torch.Tensor, patch_size: int = 64, patch_overlap: float = 1,
                           n_pred: int = 1, tta: bool = False, patch_batch: int = 8, compat: bool = True,
                           seeds=None, noise_fn=None, n_aleatoric_samples: int = 10, ssn: bool = False,
-                          range_check: str = "fallback", **predict_kw) -> Dict[str, torch.Tensor]:
+                          range_check: str = "fallback", noise_seed: Optional[int] = None,
+                          **predict_kw) -> Dict[str, torch.Tensor]:
     """image: (X, Y, Z) float tensor (the preprocessed .npy of load_image).  Returns device tensors:
     softmax_sum (T, C, X,Y,Z), num_predictions (X,Y,Z), pred_entropy / aleatoric_uncertainty / epistemic_uncertainty
     (X,Y,Z) -- already divided by clip(count,1) like save_data --, mean_softmax (C, X,Y,Z), pred_seg_mean (X,Y,Z) u8.
@@ -29,10 +30,15 @@ def predict_image_sliding(models: Sequence, image: torch.Tensor, patch_size: int
     n_aleatoric_samples for an aleatoric head: test_3D.py:458-469 sets n_pred := n_aleatoric_samples there), times the
     number of members.  ssn=True swaps the aleatoric / epistemic maps like calculate_uncertainty(ssn=True)
     (test_3D.py:510-516).
+    noise_seed (tta=True): the noisy view of every patch is drawn on the device (values_amd.predict.noise_view_device), the
+    patch's index in the crop list being its stream: the result does not depend on patch_batch.  noise_fn(x) -> x_noise, the
+    caller's own draw per patch batch, keeps working; passing both raises ValueError.
     range_check: the fp16 range guard of values_amd.predict.guarded over the WHOLE image -- the range word is zeroed before
     the first patch batch (no read), read once after the last accumulate, and on overflow the image is computed again on
     the native-fp32 kernels with the same seeds ("raise": VxError; "off": the caller checks model.check_range())."""
     _lib.require_gpu()
+    if noise_seed is not None and noise_fn is not None:
+        raise ValueError("predict_image_sliding: pass noise_seed or noise_fn, not both")
     if range_check != "off":
         if seeds is None:
             seeds = pin_seeds(models, {}, tta=tta).get("seeds")
@@ -40,7 +46,7 @@ def predict_image_sliding(models: Sequence, image: torch.Tensor, patch_size: int
                                                              n_pred=n_pred, tta=tta, patch_batch=patch_batch, compat=compat,
                                                              seeds=seeds, noise_fn=noise_fn,
                                                              n_aleatoric_samples=n_aleatoric_samples, ssn=ssn,
-                                                             range_check="off", **predict_kw),
+                                                             range_check="off", noise_seed=noise_seed, **predict_kw),
                        range_check, "predict_image_sliding")
     lib = _lib.load()
     dev = image.device if image.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -59,6 +65,8 @@ def predict_image_sliding(models: Sequence, image: torch.Tensor, patch_size: int
         if seeds is not None:
             kw["seeds"] = [derive_seed(int(s), 1, b0) for s in seeds]   # (one stream per patch batch: predict.derive_seed)
         x_noise = noise_fn(x) if (tta and noise_fn is not None) else None
+        if tta and noise_seed is not None:
+            kw.update(noise_seed=noise_seed, noise_index0=b0)           # (slot = the patch's index in the crop list)
         logits = predict_logits(models, x, n_pred=n_pred, tta=tta, x_noise=x_noise,
                                 n_aleatoric_samples=n_aleatoric_samples, **kw, **predict_kw)  # (B, T, C, P,P,P)
         if ssum is None:
