@@ -756,6 +756,67 @@ int64_t vx_select_segments_workspace_bytes(int n_items);
 int vx_select_segments(const vx_select_item* items /* host */, int n_items, int64_t k, float* out /* device [2] */,
                        int32_t* status /* device */, void* workspace, int64_t ws_bytes, vx_stream_t stream);
 
+/* K41: preprocessing of a 3D data set (datasets/preprocess_datasets_3d.py:135-168) for a whole batch of raw volumes and
+ * their raters' labels, where vx_nifti_decode left them (preprocess.hip).
+ * vx_volume_stats_batched: stats[i] (device, 4 doubles) = {mean, std, min, n} of item i as numpy computes them on the data
+ *   widened to float64: mean = sum(x) / n, std = sqrt(sum((x - mean)^2) / n) (ddof 0, two passes over the data like np.std,
+ *   not a one-pass variance), min as np.min; a NaN anywhere makes all three NaN.  An item is a device pointer, a 64-bit
+ *   element count 1 <= n <= 2^40 and a kind VX_PREP_*: an integer or bool of 1 / 2 / 4 bytes, float32 or float64.  Float
+ *   kinds accumulate in float64.  Integer kinds accumulate sum(x) in 64-bit integers and convert it once: the mean is
+ *   numpy's bit for bit whenever numpy's own float64 sum is exact (|sum(x)| < 2^53; the integer sum itself is exact below
+ *   2^63, that is for every n < 2^31 of a 4-byte kind).  Each item is cut into work blocks of 32 KB counted from its
+ *   first element, the blocks of all items are taken in turn by one grid, every block leaves one partial, and one
+ *   workgroup per item adds the item's partials in an order fixed by its block count.  No floating-point atomics.  The cut,
+ *   the order inside a block and the order of the partials depend on the item's own n and kind only: AN ITEM'S FOUR
+ *   NUMBERS ARE BIT-EQUAL WHETHER IT IS SUBMITTED ALONE OR IN ANY BATCH, AT ANY POSITION (and whatever the grid size).
+ *   The mean stays on the device between the passes: four launches, no wait on the host.
+ * vx_zscore_pad_batched: per item, the source box dims[3] (C order, z innermost) is placed at pad_below[3] of the output
+ *   box out_dims[3].  Mode VX_PREP_ZSCORE: an output voxel inside the source box is (double(x) - mean) / (std + 1e-8), a
+ *   voxel outside it the same expression on min, with {mean, std, min} = stats[stats_row] READ ON THE DEVICE (the rows
+ *   vx_volume_stats_batched wrote on the same stream: the host does not wait between the two calls); IEEE operations,
+ *   correctly rounded -- a true division, no reciprocal, no FMA contraction -- and ONE rounding to out_dtype (VX_F32 |
+ *   VX_F64; VX_PREP_OWN: float32 for a float32 source, else float64, as numpy promotes).  Mode VX_PREP_COPY (labels;
+ *   out_dtype VX_PREP_OWN): inside x unchanged, outside min, both in the source's kind.  The output is cut into work
+ *   blocks of 32 KB that one grid takes in turn, so many small crops and a few large volumes fill the device from one
+ *   launch; lanes run along z, a thread writes 16 bytes of output with one store and reads its source run with one load
+ *   where the run lies inside one source row; chunks that cross a row end or a padding slab, the last chunk of an item
+ *   and a dst off 16 bytes take the per-element path.  What a voxel becomes depends on its item alone.
+ * Both refuse before any device call: a null table, pointer, stats or workspace (VX_E_NULL); n_items outside
+ *   [0, VX_SELECT_MAX_ITEMS], n < 1, a dimension < 1, more than 2^40 elements, out_dims[a] < dims[a] + pad_below[a], a
+ *   negative pad_below, a stats_row outside [0, VX_SELECT_MAX_ITEMS), overlapping src / dst (VX_E_SHAPE); an unknown kind,
+ *   mode or out_dtype (VX_E_DTYPE); a pointer off its element alignment or a workspace off 16 bytes (VX_E_ALIGN); a short
+ *   workspace (VX_E_WORKSPACE).  workspace: vx_*_workspace_bytes(items, n_items) bytes, 0 for what the call refuses (and
+ *   for n_items = 0, which is a no-op).  The item table goes up through a pinned staging buffer inside the call: no wait
+ *   on the stream (only, if it is still in flight, for the previous call's upload), and, like K40, neither call is
+ *   capturable into a hipGraph. */
+enum { VX_PREP_U8 = 0, VX_PREP_I8 = 1, VX_PREP_U16 = 2, VX_PREP_I16 = 3, VX_PREP_U32 = 4, VX_PREP_I32 = 5, VX_PREP_F32 = 6, VX_PREP_F64 = 7 };
+enum { VX_PREP_ZSCORE = 0, VX_PREP_COPY = 1 };
+#define VX_PREP_OWN (-1)
+typedef struct vx_prep_item {
+  const void* ptr; /* device, n elements */
+  int64_t n;
+  int32_t kind; /* VX_PREP_* (bool: VX_PREP_U8) */
+  int32_t reserved;
+} vx_prep_item;
+typedef struct vx_prep_pad_item {
+  const void* src;      /* device [dims[0]][dims[1]][dims[2]] of kind */
+  void* dst;            /* device [out_dims[0]][out_dims[1]][out_dims[2]] */
+  int32_t dims[3];
+  int32_t out_dims[3];
+  int32_t pad_below[3];
+  int32_t kind;         /* VX_PREP_* */
+  int32_t out_dtype;    /* VX_F32 | VX_F64 | VX_PREP_OWN */
+  int32_t mode;         /* VX_PREP_ZSCORE | VX_PREP_COPY */
+  int32_t stats_row;    /* the item's row of stats */
+  int32_t reserved;
+} vx_prep_pad_item;
+int64_t vx_volume_stats_batched_workspace_bytes(const vx_prep_item* items /* host */, int n_items);
+int vx_volume_stats_batched(const vx_prep_item* items /* host */, int n_items, double* stats /* device [n_items][4] */,
+                            void* workspace, int64_t ws_bytes, vx_stream_t stream);
+int64_t vx_zscore_pad_batched_workspace_bytes(const vx_prep_pad_item* items /* host */, int n_items);
+int vx_zscore_pad_batched(const vx_prep_pad_item* items /* host */, int n_items, const double* stats /* device */,
+                          void* workspace, int64_t ws_bytes, vx_stream_t stream);
+
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),
  *   counts[i][j][c] = #{v: mask_i(v) == c and mask_j(v) == c}.  M <= 32, C <= 8.

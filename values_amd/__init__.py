@@ -7,3 +7,4 @@ from .predict import (GraphedPredictor, HostPipeline, crop_indices, noise_view_d
                       predict_uncertainty)
 from .io import load_models_from_checkpoint, instantiate  # noqa: F401
 from .sliding import predict_image_sliding  # noqa: F401
+from .preprocess import load_cases_device, preprocess_dataset  # noqa: F401

@@ -239,6 +239,23 @@ class SelectItem(C.Structure):
     _fields_ = [("ptr", _p), ("n", _i64), ("dtype", _i32), ("reserved", _i32)]
 
 
+VX_PREP_U8, VX_PREP_I8, VX_PREP_U16, VX_PREP_I16, VX_PREP_U32, VX_PREP_I32, VX_PREP_F32, VX_PREP_F64 = range(8)
+VX_PREP_ZSCORE, VX_PREP_COPY = 0, 1
+VX_PREP_OWN = -1
+
+
+class PrepItem(C.Structure):
+    """vx_prep_item: one device array of n elements of kind VX_PREP_* for vx_volume_stats_batched."""
+    _fields_ = [("ptr", _p), ("n", _i64), ("kind", _i32), ("reserved", _i32)]
+
+
+class PrepPadItem(C.Structure):
+    """vx_prep_pad_item: one volume (ZSCORE) or label (COPY) of vx_zscore_pad_batched: the source box dims at pad_below of
+    the output box out_dims, its row of the statistics."""
+    _fields_ = [("src", _p), ("dst", _p), ("dims", _i32 * 3), ("out_dims", _i32 * 3), ("pad_below", _i32 * 3),
+                ("kind", _i32), ("out_dtype", _i32), ("mode", _i32), ("stats_row", _i32), ("reserved", _i32)]
+
+
 VX_MSR_MAX_ITEMS, VX_MSR_MAX_PLANES = 65536, 1 << 22
 
 
@@ -319,6 +336,10 @@ SIGNATURES = {
     "vx_count_nonzero_batched": (_i, [C.POINTER(CountItem), _i, _p, _p, _i64, _p]),
     "vx_select_segments_workspace_bytes": (_i64, [_i]),
     "vx_select_segments": (_i, [C.POINTER(SelectItem), _i, _i64, _p, _p, _p, _i64, _p]),
+    "vx_volume_stats_batched_workspace_bytes": (_i64, [C.POINTER(PrepItem), _i]),
+    "vx_volume_stats_batched": (_i, [C.POINTER(PrepItem), _i, _p, _p, _i64, _p]),
+    "vx_zscore_pad_batched_workspace_bytes": (_i64, [C.POINTER(PrepPadItem), _i]),
+    "vx_zscore_pad_batched": (_i, [C.POINTER(PrepPadItem), _i, _p, _p, _i64, _p]),
     "vx_mask_agreement": (_i, [_p, _i, _i, _i64, _p, _p]),
     "vx_mask_agreement_batched": (_i, [_p, _i, _i, _i, _i64, _i, _p, _p]),
     "vx_soft_metric_workspace_bytes": (_i64, [_i, _i]),
