@@ -363,6 +363,11 @@ int vx_conv3d_k3_tiles(int D, int H, int W);  /* upper bound of ntiles per sampl
 int vx_conv3d_k3_tiles_for(int D, int H, int W, int Cout); /* exact ntiles for a given Cout (finalize) */
 int vx_conv3d_k3(const vx_conv3d_args* a, vx_stream_t stream);
 int vx_conv3d_k3_head_fusable(int Cin, int Cout); /* 1 if the layer's kernel can take head_out */
+/* Dry run of vx_conv3d_k3: every argument check and the choice of the kernel, no launch and no call into the HIP runtime (works
+ * without a GPU; the pointers are only tested for null and alignment).  Returns the VX_E_* code vx_conv3d_k3 would refuse the call
+ * with (message in vx_last_error_string), or VX_OK with the instance name vx_last_kernel_name() would report after the launch in
+ * kernel_name (nullable; at most cap bytes, always terminated). */
+int vx_conv3d_k3_route(const vx_conv3d_args* a, char* kernel_name, int cap);
 
 /* First layer, Cin == 1 (contr_1_1): input is the reference's (V,1,D,H,W) volume batch.
  * Sample n reads volume src[n] (nullable: n / repeat) with flip code flip[n] (nullable: 0;

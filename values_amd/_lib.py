@@ -290,6 +290,7 @@ SIGNATURES = {
     "vx_conv3d_k3_tiles": (_i, [_i, _i, _i]),
     "vx_conv3d_k3_tiles_for": (_i, [_i, _i, _i, _i]),
     "vx_conv3d_k3_head_fusable": (_i, [_i, _i]),
+    "vx_conv3d_k3_route": (_i, [C.POINTER(ConvArgs), C.c_char_p, _i]),
     "vx_conv3d_k3_prologue_ok": (_i, [_i, _i, _i, _i, _i]),
     "vx_conv3d_k3_upfuse_ok": (_i, [_i, _i, _i, _i, _i]),
     "vx_conv3d_k3_poolfuse_ok": (_i, [_i, _i, _i, _i, _i]),
@@ -420,6 +421,8 @@ def load():
     import torch  # noqa: F401  (loads the HIP runtime)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in SIGNATURES.items():
+        if os.environ.get("VX_LIB_PATH") and not hasattr(lib, name):
+            continue  # an A/B build of an older revision lacks the newer entry points
         fn = getattr(lib, name)  # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args
@@ -456,8 +459,8 @@ class config:
 
 
 def pack_mode():
-    """The configuration fields that select the kernel family and with it the PACKED WEIGHT LAYOUT (conv_config() in
-    conv3d_mfma.hip, s16_config() in conv3d_s16.hip, c2_split16() in conv2d_mfma.hip).  Models key their packed-weight
+    """The configuration fields that select the kernel family and with it the PACKED WEIGHT LAYOUT (conv_config() and
+    s16_config() in conv3d_route.h, c2_split16() in conv2d_mfma.hip).  Models key their packed-weight
     cache on it, and every launch carries the family its weights were packed for (w_family): the library refuses a
     mismatch."""
     c = get_config()

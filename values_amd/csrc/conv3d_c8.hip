@@ -19,8 +19,7 @@
 // Work items, staging (global -> registers -> LDS, prefetched one item ahead), tile shapes, the epilogue's fused
 // bias / LeakyReLU / dropout / statistics and the stats partial layout are those of conv3d_mfma.hip.
 // Conv-shaped inner loop alone: 145 TFLOP/s of useful work (tools/micro/mfma_4x4.hip) against 111 for x-pair.
-#include "common.h"
-#include <stdlib.h>
+#include "conv3d_internal.h"
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -35,21 +34,7 @@ struct ConvC8Args {
   unsigned long long* stamps;  // VX_CONV_STAMPS diagnostic builds only
 };
 
-#ifdef VX_CONV_STAMPS
-#define C8_DBG ka.dbg
-#define VX_STAMP(i)                                                                      \
-  do {                                                                                   \
-    unsigned long long t_;                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    st_sum[i] += t_ - st_last;                                                           \
-    st_last = t_;                                                                        \
-  } while (0)
-#else
-#define C8_DBG 0
-#define VX_STAMP(i) do {} while (0)
-#endif
+#define C8_DBG VX_DIAG(ka.dbg)   // (VX_STAMP, VX_DIAG: conv3d_internal.h)
 
 // 8 MFMAs of one 16-byte read: channels 4 Q .. 4 Q + 3 of the chunk, both cout halves
 template <int Q>
@@ -369,8 +354,6 @@ __global__ void pack_conv3d_k3_c8_kernel(const float* __restrict__ w, float* __r
   }
 }
 
-bool vx_conv3d_c8_applies(int Cin, int Cout) { return Cout == 8 && (Cin == 8 || Cin == 16); }
-
 int vx_pack_conv3d_k3_c8(const float* w_torch, float* w_packed, int Cin, hipStream_t s) {
   const int total = 27 * Cin * 8;
   hipLaunchKernelGGL(pack_conv3d_k3_c8_kernel, dim3((total + 255) / 256), dim3(256), 0, s, w_torch, w_packed, Cin, total);
@@ -379,7 +362,7 @@ int vx_pack_conv3d_k3_c8(const float* w_torch, float* w_packed, int Cin, hipStre
 }
 
 template <int NCH, int TXV, int TY, int TZ>
-static int launch_c8(const ConvC8Args& ka, hipStream_t s) {
+static int launch_c8(const ConvC8Args& ka, const Conv3dRoute& r, hipStream_t s) {
   constexpr int NTH = TXV * TY * TZ, NW = NTH / 64;
   constexpr int NHALO = (TXV + 2) * (TY + 2) * (TZ + 2);
   constexpr int PLANE = ((NHALO + 7) / 16) * 16 + 8;
@@ -400,29 +383,24 @@ static int launch_c8(const ConvC8Args& ka, hipStream_t s) {
   if (per_cu < 1) per_cu = 1;
   int gx = 256 * per_cu;
   if (gx > total_tiles) gx = total_tiles;
-  static const char* kname = vx_kname("conv3d_k3_c8_kernel<%d,%d,%d,%d>", NCH, TXV, TY, TZ);
+  static const char* kname = vx_conv3d_kname(r);
   vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(NTH), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv3d_k3(c8)");
   return VX_OK;
 }
 
-// tile = the x-pair kernel's tile (conv3d_mfma.hip tile_config), so vx_conv3d_k3_tiles_for is the same for both
-int vx_conv3d_k3_c8(const vx_conv3d_args& a, int txv, int ty, int tz, hipStream_t s) {
+// tile = the x-pair kernel's tile (conv3d_route.h tile_config), so vx_conv3d_k3_tiles_for is the same for both
+int vx_conv3d_c8_launch(const Conv3dRoute& r, const vx_conv3d_args& a, hipStream_t s) {
   ConvC8Args ka;
   ka.a = a;
-  ka.dbg = 0;   // phase ablation: diagnostic build only (below)
-  ka.stamps = nullptr;
-#ifdef VX_CONV_STAMPS
-  if (const char* e = getenv("VX_CONV_DBG_PTR")) ka.stamps = (unsigned long long*)strtoull(e, nullptr, 0);
-  if (const char* e = getenv("VX_C8_DBG")) ka.dbg = atoi(e);
-#endif
-  ka.tiles_x = (a.W + txv - 1) / txv; ka.tiles_y = (a.H + ty - 1) / ty; ka.tiles_z = (a.D + tz - 1) / tz;
-  ka.mx = (unsigned)((1ull << 32) / (unsigned)ka.tiles_x) + 1u;
-  ka.my = (unsigned)((1ull << 32) / (unsigned)ka.tiles_y) + 1u;
-  ka.mz = (unsigned)((1ull << 32) / (unsigned)ka.tiles_z) + 1u;
-  const int nch = a.Cin / 8;
-  if (txv == 32) return nch == 1 ? launch_c8<1, 32, 4, 4>(ka, s) : launch_c8<2, 32, 4, 4>(ka, s);
-  if (txv == 16) return nch == 1 ? launch_c8<1, 16, 8, 4>(ka, s) : launch_c8<2, 16, 8, 4>(ka, s);
-  return nch == 1 ? launch_c8<1, 8, 4, 4>(ka, s) : launch_c8<2, 8, 4, 4>(ka, s);
+  vx_conv_diag(VX_DIAG_C8_DBG, &ka.stamps, &ka.dbg);   // phase ablation: diagnostic build only
+  ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.tiles_z = r.tiles_z;
+  ka.mx = r.mx; ka.my = r.my; ka.mz = r.mz;
+  switch (conv3d_key_of(r.p, r.np)) {
+#define C8_CASE(...) case conv3d_key(__VA_ARGS__): return launch_c8<__VA_ARGS__>(ka, r, s);
+    C8_INSTANCES(C8_CASE)
+#undef C8_CASE
+  }
+  VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(c8): no such instance");
 }

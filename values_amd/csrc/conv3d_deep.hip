@@ -19,10 +19,11 @@
 // LDS: two images [hi | lo][1080 positions][8 halves] (67.5 KB), two weight chunks [step 7][row tile 2][hi | lo][lane][8
 // halves] (56 KB), statistics slots and the bias vector.
 #include "s16_common.h"
+#include "conv3d_internal.h"
 
 struct DeepArgs {
   vx_conv3d_args a;
-  const float* w;                 // this kernel's block of the packed weights (vx_conv3d_deep_packed_floats)
+  const float* w;                 // this kernel's block of the packed weights (conv3d_deep_packed_floats)
   int tx, ty, tz, ts;             // tile: voxels along x, y, z (powers of two); samples (> 1 only when a tile is whole samples)
   int ltx, lty, ltz;              // their base-2 logarithms
   int tiles_x, tiles_y, tiles_z;
@@ -35,29 +36,14 @@ struct DeepArgs {
   int abl;
 };
 
-#ifdef VX_CONV_STAMPS
-#define DP_STAMP(i)                                                                      \
-  do {                                                                                   \
-    unsigned long long t_;                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    st_sum[i] += t_ - st_last;                                                           \
-    st_last = t_;                                                                        \
-  } while (0)
-#define DP_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define DP_ABL ka.abl
-#else
-#define DP_ABL 0
-#define DP_STAMP(i) do {} while (0)
-#define DP_WAIT_LOADS() do {} while (0)
-#endif
+// phase stamps / ablation word: diagnostic build only (conv3d_internal.h)
+#define DP_STAMP VX_STAMP
+#define DP_WAIT_LOADS VX_STAMP_WAIT_LOADS
+#define DP_ABL VX_DIAG(ka.abl)
 
-constexpr int DEEP_NPOS = 1080;                    // positions of one image (18 x 10 x 6)
+// (DEEP_NPOS, DEEP_W_B, DEEP_MAXC: conv3d_route.h, shared with the routing rules)
 constexpr int DEEP_PREC_B = DEEP_NPOS * 16;
 constexpr int DEEP_IMG_B = 2 * DEEP_PREC_B;
-constexpr int DEEP_W_B = 7 * 2 * 2 * 1024;         // one chunk's weights
-constexpr int DEEP_MAXC = 512;                     // output channels the bias vector in LDS holds
 
 // R: column tiles per multiplying wave (4 / 2).  EPI: 0 bias + statistics + store, 1 LeakyReLU + hash dropout (+ out_split),
 // 3 run-time activation without dropout.  PRE: 1 = InstanceNorm + LeakyReLU + dropout of the producing block on load (dense
@@ -580,13 +566,6 @@ __global__ __launch_bounds__(768) void conv3d_deep_kernel(DeepArgs ka) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-bool vx_conv3d_deep_packs(int Cin, int Cout) { return Cout % 32 == 0 && Cin % 8 == 0 && Cin >= 16 && Cout <= DEEP_MAXC; }
-
-int64_t vx_conv3d_deep_packed_floats(int Cin, int Cout) {
-  if (!vx_conv3d_deep_packs(Cin, Cout)) return 0;
-  return (int64_t)(Cout / 32) * (Cin / 8) * (DEEP_W_B / 4);
-}
-
 // torch (Cout, Cin, 3,3,3) fp32 -> [output group of 32][chunk of 8][step 7][row tile 2][hi | lo][lane 64][8 halves]:
 // lane (m, g) of row tile nt holds row 32 cg + 16 nt + m, tap 4 step + g (zero beyond 26), channels 8 chunk .. + 7
 __global__ void pack_conv3d_deep_kernel(const float* __restrict__ w, _Float16* __restrict__ out, int Cin, int64_t total) {
@@ -606,7 +585,7 @@ __global__ void pack_conv3d_deep_kernel(const float* __restrict__ w, _Float16* _
 }
 
 int vx_pack_conv3d_deep(const float* w_torch, float* w_packed, int Cin, int Cout, hipStream_t s) {
-  const int64_t total = vx_conv3d_deep_packed_floats(Cin, Cout) * 2;
+  const int64_t total = conv3d_deep_packed_floats(Cin, Cout) * 2;
   if (total <= 0) return VX_OK;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
@@ -615,55 +594,8 @@ int vx_pack_conv3d_deep(const float* w_torch, float* w_packed, int Cin, int Cout
   return VX_OK;
 }
 
-// Tile of a layer: 128 R voxels, x first (the whole row up to 16), then y (up to 8), then z; a tile that is a whole sample
-// takes further samples (the last tile of a batch may hold fewer: the kernel masks them).  false = no tile of this size.
-// The geometry is a function of the VOLUME's shape and the channel count only, never of the batch size: a sample's bits must not
-// depend on its batch mates (round-5 advice; tests/test_gpu_kernels.py::test_conv3d_deep_is_batch_independent).
-struct DeepGeo { int tx, ty, tz, ts, tiles_x, tiles_y, tiles_z, npos; };
-static bool deep_geo(int D, int H, int W, int R, DeepGeo* o) {
-  const int vox = 128 * R;
-  const int tx = W < 16 ? W : 16;
-  if (tx < 4 || (tx & (tx - 1)) || W % tx) return false;
-  int ty = H < 8 ? H : 8;
-  while (tx * ty > vox) ty >>= 1;
-  if (ty < 1 || H % ty) return false;
-  int tz = vox / (tx * ty);
-  if (tz > D) tz = D;
-  if (tz < 1 || D % tz) return false;
-  int ts = vox / (tx * ty * tz);
-  if (ts * tx * ty * tz != vox) return false;
-  if ((ty & (ty - 1)) || (tz & (tz - 1))) return false;      // (the kernel decodes a tile's voxels with shifts)
-  if (ts > 1 && (tx != W || ty != H || tz != D || ts > 4 || R != 2)) return false;   // (the kernel masks a partial last tile for R = 2 only)
-  const int npos = ts * (tx + 2) * (ty + 2) * (tz + 2);
-  if (npos > (R == 4 ? DEEP_NPOS : 896)) return false;      // the image's positions; 2 npos pieces in IN_IT x 256
-  o->tx = tx; o->ty = ty; o->tz = tz; o->ts = ts;
-  o->tiles_x = W / tx; o->tiles_y = H / ty; o->tiles_z = D / tz; o->npos = npos;
-  return true;
-}
-
-// the layer's tile: R = 4 wherever it fits, else R = 2.  (Until round 5 the choice also looked at how the batch filled the 256
-// persistent workgroups -- R = 2 for small batches at 8^3 -- which made the fp32 tile sums behind InstanceNorm, and so a sample's
-// bits, a function of the batch size.  At 8^3 x 64 channels and 320 samples the large tile is 2 % faster anyway; at 16^3 the small
-// tile costs 20 %.)
-static int deep_pick(int D, int H, int W, int Cout, DeepGeo* o) {
-  DeepGeo g4, g2;
-  const bool ok4 = deep_geo(D, H, W, 4, &g4), ok2 = deep_geo(D, H, W, 2, &g2);
-  if (!ok4 && !ok2) return 0;
-  const int r = ok4 ? 4 : 2;
-  *o = r == 4 ? g4 : g2;
-  return r;
-}
-
-bool vx_conv3d_deep_applies(int N, int D, int H, int W, int Cin, int Cout) {
-  if (vx_cfg().conv_fp32 != 0 || vx_cfg().s16_no_deep) return false;
-  if (!vx_conv3d_deep_packs(Cin, Cout)) return false;
-  if (W > 32 || H > 32 || D > 32) return false;        // (the larger layers keep the tile kernel's XCD-ordered small tiles)
-  DeepGeo g;
-  return deep_pick(D, H, W, Cout, &g) != 0;
-}
-
 template <int R, int EPI, int PRE>
-static int launch_deep(const DeepArgs& ka, hipStream_t s) {
+static int launch_deep(const DeepArgs& ka, const Conv3dRoute& r, hipStream_t s) {
   constexpr size_t lds = 2 * (size_t)DEEP_IMG_B + 2 * (size_t)DEEP_W_B + 2 * 8 * 32 * 2 * 4 + DEEP_MAXC * 4;
   static_assert(lds <= 160 * 1024, "LDS budget");
   auto kern = conv3d_deep_kernel<R, EPI, PRE>;
@@ -675,72 +607,31 @@ static int launch_deep(const DeepArgs& ka, hipStream_t s) {
   }
   int gx = vx_cu_count();      // one persistent workgroup per CU
   if (gx > ka.npairs) gx = ka.npairs;
-  static const char* kname = vx_kname("conv3d_deep_kernel<%d,%d,%d>", R, EPI, PRE);   // as rocprofv3 prints it
+  static const char* kname = vx_conv3d_kname(r);
   vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(768), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv3d_k3(deep)");
   return VX_OK;
 }
 
-// 1 = not taken (the caller uses the general tile kernel)
-int vx_conv3d_k3_deep(const vx_conv3d_args& a, const float* w_block, int stat_tiles, hipStream_t s) {
-  if (a.head_out || a.in_split || a.in_f16 || a.out_f16 || (a.in_repeat > 1) || a.out_xblk || a.up_in || a.pool_out ||
-      a.in_pool_flags || a.acc_in)
-    return 1;
-  if (a.drop_mode == VX_DROP_MASK || a.in_drop_mode == VX_DROP_MASK) return 1;
-  if (!a.out) return 1;
-  DeepGeo g;
-  const int R = deep_pick(a.D, a.H, a.W, a.Cout, &g);
-  if (!R) return 1;
-  if (a.in_xblk) {
-    const int csrc = a.Cin / 2;
-    if (a.in_mean || csrc % 8 || a.W % a.in_xblk) return 1;
-  } else if (a.in_pitch % 4) {
-    return 1;
-  }
-  if (a.in_mean && (a.in_pitch != a.Cin || g.ts != 1)) return 1;
-  if (a.stats_partial && g.ts != 1) return 1;
+int vx_conv3d_deep_launch(const Conv3dRoute& r, const vx_conv3d_args& a, const float* w_block, hipStream_t s) {
   DeepArgs ka;
   ka.a = a;
   ka.w = w_block;
-  ka.tx = g.tx; ka.ty = g.ty; ka.tz = g.tz; ka.ts = g.ts;
-  ka.ltx = __builtin_ctz((unsigned)g.tx); ka.lty = __builtin_ctz((unsigned)g.ty); ka.ltz = __builtin_ctz((unsigned)g.tz);
-  ka.tiles_x = g.tiles_x; ka.tiles_y = g.tiles_y; ka.tiles_z = g.tiles_z;
-  ka.npos = g.npos;
-  ka.nchunks = a.Cin / 8;
-  ka.ncg = a.Cout / 32;
-  const int tps = g.tiles_x * g.tiles_y * g.tiles_z;
-  const int64_t npairs = (int64_t)((a.N + g.ts - 1) / g.ts) * tps * ka.ncg;
-  if (npairs >= (1ll << 31)) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): too many tiles");
-  ka.npairs = (int)npairs;
-  auto magic = [](int d) { return (unsigned)((1ull << 32) / (unsigned)d) + 1u; };
-  ka.m_cg = magic(ka.ncg); ka.m_tx = magic(g.tiles_x); ka.m_ty = magic(g.tiles_y); ka.m_tz = magic(g.tiles_z);
-  ka.stat_epc = 0;
-  if (a.stats_partial) {
-    // the caller's partials buffer holds stat_tiles entries per sample (the tile kernel's count): this kernel's tiles must divide it,
-    // else the tile kernel takes the launch (round-5 advice: D % 4 == 2 volumes gave 3 tiles against 4 entries and failed here)
-    if (stat_tiles % tps) return 1;
-    if (a.act != VX_ACT_NONE || a.drop_mode != VX_DROP_NONE)
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): statistics go with a plain epilogue");
-    ka.stat_epc = stat_tiles / tps;
-  }
-  ka.stamps = nullptr;
-  ka.abl = 0;
-#ifdef VX_CONV_STAMPS
-  if (const char* e = getenv("VX_CONV_DBG_PTR")) ka.stamps = (unsigned long long*)strtoull(e, nullptr, 0);
-  if (const char* e = getenv("VX_XP_ABL")) ka.abl = atoi(e);
-#endif
-  if ((int64_t)g.ts * a.D * a.H * a.W * a.out_pitch * 4 >= (1ll << 31))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): one tile's samples must stay below 2 GiB");
-  const int pre = a.in_mean ? 1 : 0;
-  int epi;
-  if (a.stats_partial) epi = 0;
-  else if (a.drop_mode == VX_DROP_HASH) { if (a.act != VX_ACT_LRELU) return 1; epi = 1; }
-  else epi = 3;
-  if (a.out_split && a.stats_partial) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): out_split goes with the activation epilogues");
-#define DEEP_CASE(R_, E_, P_) if (R == R_ && epi == E_ && pre == P_) return launch_deep<R_, E_, P_>(ka, s)
-  DEEP_CASE(4, 0, 0); DEEP_CASE(4, 0, 1); DEEP_CASE(4, 1, 0); DEEP_CASE(4, 3, 0);
-  DEEP_CASE(2, 0, 0); DEEP_CASE(2, 0, 1); DEEP_CASE(2, 1, 0); DEEP_CASE(2, 3, 0);
+  ka.tx = r.tx; ka.ty = r.ty; ka.tz = r.tz; ka.ts = r.ts;
+  ka.ltx = __builtin_ctz((unsigned)r.tx); ka.lty = __builtin_ctz((unsigned)r.ty); ka.ltz = __builtin_ctz((unsigned)r.tz);
+  ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.tiles_z = r.tiles_z;
+  ka.npos = r.npos;
+  ka.nchunks = r.nchunks;
+  ka.ncg = r.ncg;
+  ka.npairs = r.nitems;
+  ka.m_cg = r.m_cg; ka.m_tx = r.mx; ka.m_ty = r.my; ka.m_tz = r.mz;
+  ka.stat_epc = r.stat_epc;
+  vx_conv_diag(VX_DIAG_XP_ABL, &ka.stamps, &ka.abl);
+  switch (conv3d_key_of(r.p, r.np)) {
+#define DEEP_CASE(...) case conv3d_key(__VA_ARGS__): return launch_deep<__VA_ARGS__>(ka, r, s);
+    DEEP_INSTANCES(DEEP_CASE)
 #undef DEEP_CASE
-  return 1;
+  }
+  VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): no such instance");
 }

@@ -32,35 +32,9 @@
 //
 // Epilogue (fused): bias, then either (a) raw store + per-workgroup (sum, sumsq) partials for the
 // InstanceNorm that follows (contract blocks), or (b) LeakyReLU/ReLU + dropout (expand / center).
-#include "common.h"
-#include <stdlib.h>
+#include "conv3d_internal.h"
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// conv3d_c8.hip: the Cout = 8, Cin in {8, 16} layers on the 4x4x1 matrix instruction
-bool vx_conv3d_c8_applies(int Cin, int Cout);
-int vx_pack_conv3d_k3_c8(const float* w_torch, float* w_packed, int Cin, hipStream_t s);
-int vx_conv3d_k3_c8(const vx_conv3d_args& a, int txv, int ty, int tz, hipStream_t s);
-// conv3d_s16.hip: split-fp16 schedule for the Cout >= 16 layers
-int64_t vx_conv3d_s16_packed_floats(int Cin, int Cout);
-int vx_pack_conv3d_k3_s16(const float* w_torch, float* w_packed, int Cin, int Cout, hipStream_t s);
-int vx_conv3d_k3_s16(const vx_conv3d_args& a, hipStream_t s);
-bool vx_conv3d_s16_head_fusable(int Cin, int Cout);
-bool vx_conv3d_xp8_applies(int D, int H, int W, int Cin, int Cout);
-int vx_conv3d_k3_xp8(const vx_conv3d_args& a, int stat_tiles, hipStream_t s);   // 1 = not taken
-// conv3d_zc16.hip: the role-split z-column kernel of the Cout = 16 layers
-bool vx_conv3d_zc16_packs(int Cin, int Cout);
-bool vx_conv3d_zc16_applies(int D, int H, int W, int Cin, int Cout);
-int64_t vx_conv3d_zc16_packed_floats(int Cin, int Cout);
-int vx_pack_conv3d_zc16(const float* w_torch, float* w_packed, int Cin, int Cout, hipStream_t s);
-int vx_conv3d_k3_zc16(const vx_conv3d_args& a, const float* w_block, int stat_tiles, hipStream_t s);   // 1 = not taken
-// conv3d_deep.hip: the role-split tile kernel of the deep layers (Cout % 32 == 0, volumes of 32^3 and below)
-bool vx_conv3d_deep_packs(int Cin, int Cout);
-bool vx_conv3d_deep_applies(int N, int D, int H, int W, int Cin, int Cout);
-int64_t vx_conv3d_deep_packed_floats(int Cin, int Cout);
-int vx_pack_conv3d_deep(const float* w_torch, float* w_packed, int Cin, int Cout, hipStream_t s);
-int vx_conv3d_k3_deep(const vx_conv3d_args& a, const float* w_block, int stat_tiles, hipStream_t s);   // 1 = not taken
-void vx_conv3d_s16_tile(int H, int W, int Cout, int* txv, int* ty, int* tz);
 
 struct ConvKArgs {
   vx_conv3d_args a;
@@ -68,20 +42,6 @@ struct ConvKArgs {
   unsigned mx, my, mz;  // floor(2^32 / tiles_*) + 1: exact t / tiles_* = umulhi(t, m) for t * tiles_* < 2^32
   unsigned long long* dbg;  // VX_CONV_STAMPS diagnostic builds only
 };
-
-#ifdef VX_CONV_STAMPS
-#define VX_STAMP(i)                                                                      \
-  do {                                                                                   \
-    unsigned long long t_;                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    st_sum[i] += t_ - st_last;                                                           \
-    st_last = t_;                                                                        \
-  } while (0)
-#else
-#define VX_STAMP(i) do {} while (0)
-#endif
 
 constexpr unsigned VX_OOB = 0xFFFFFFF0u;      // voffset beyond every descriptor's num_records
 constexpr unsigned VX_NUMREC = 0x80000000u;
@@ -467,27 +427,8 @@ __global__ __launch_bounds__(64 * NW) void conv3d_k3_mfma_kernel(ConvKArgs ka) {
 
 // ---------------------------------------------------------------------------------------------
 // weight packing: torch (Cout, Cin, 3,3,3) -> [rowgroup][chunk][tap][nt][lane 64][CPL]
-//   plain : row = cout, tap = (kz,ky,kx)                       (NT fixed per (Cin, Cout) by conv_config())
+//   plain : row = cout, tap = (kz,ky,kx)                       (NT fixed per (Cin, Cout) by s16_config())
 //   x-pair: row = dx*8 + cout, tap = (kz,ky,ix), value W[kx = ix - dx] or 0      (Cout == 8)
-struct ConvCfg { int CB, NT, XP, C8, S16; };
-static inline ConvCfg conv_config(int Cin, int Cout) {
-  ConvCfg c;
-  // Default: the split-fp16 schedule (conv3d_s16.hip) for every layer -- faster AND closer to float64 than the
-  // native fp32 matrix instruction.  VX_CONV_FP32=1 selects the native-fp32 kernels of this
-  // file / conv3d_c8.hip (an exact fmaf chain; the A/B baseline), VX_CONV_FP32=2 keeps fp32 only for Cout = 8.
-  // (vx_config: read once; a launch checks its weights' w_family against what this returns NOW)
-  const int fp32 = vx_cfg().conv_fp32;
-  c.S16 = (fp32 == 0 || (fp32 == 2 && Cout != 8)) ? 1 : 0;
-  c.C8 = (!c.S16 && vx_conv3d_c8_applies(Cin, Cout)) ? 1 : 0;
-  c.NT = (Cout % 32 == 0) ? 2 : 1;
-  c.XP = (Cout == 8) ? 1 : 0;
-  // x-pair layers always go in chunks of 8 channels (same speed as one chunk of 16 here, and the packing the
-  // opt-in LDS-DMA schedule in conv3d_dma.hip needs: all weights + two input images in LDS)
-  c.CB = c.XP ? 8 : ((Cin % 16 == 0) ? 16 : 8);
-  return c;
-}
-static inline int conv_rows_padded(int Cout, int NT) { return ((Cout + 16 * NT - 1) / (16 * NT)) * (16 * NT); }
-
 __global__ void pack_conv3d_k3_kernel(const float* __restrict__ w, float* __restrict__ out, int Cin, int Cout, int CB,
                                       int NT, int XP, int64_t total) {
   const int CPL = CB / 4;
@@ -515,96 +456,17 @@ __global__ void pack_conv3d_k3_kernel(const float* __restrict__ w, float* __rest
   }
 }
 
-// Kernel family = packed layout of a layer under the current configuration (values_amd.h, vx_config):
-//   1 split-fp16 fragments, 2 split-fp16 x-pair blocks, 3 fp32 fragments, 4 fp32 x-pair, 5 fp32 4x4x1 (Cout = 8)
-extern "C" int vx_conv3d_k3_family(int Cin, int Cout) {
-  if (Cin % 8 != 0 || Cout % 8 != 0 || Cin <= 0 || Cout <= 0) return 0;
-  const ConvCfg c = conv_config(Cin, Cout);
-  // 6: the tile kernel's fragments FOLLOWED BY the z-column kernel's (conv3d_zc16.hip: which of the two runs depends on the
-  // volume's shape, known only at launch)
-  // 7: the tile kernel's fragments FOLLOWED BY the deep-layer kernel's (conv3d_deep.hip; Cout % 32 == 0, Cin >= 16)
-  if (c.S16 && !vx_conv3d_s16_head_fusable(Cin, Cout) && vx_conv3d_deep_packs(Cin, Cout)) return 7;
-  if (c.S16) return vx_conv3d_s16_head_fusable(Cin, Cout) ? 2 : (vx_conv3d_zc16_packs(Cin, Cout) ? 6 : 1);   // head-fusable == x-pair packing
-  if (c.C8) return 5;
-  return c.XP ? 4 : 3;
-}
-
-extern "C" int64_t vx_conv3d_k3_packed_floats(int Cin, int Cout) {
-  if (Cin % 8 != 0 || Cout % 8 != 0 || Cin <= 0 || Cout <= 0) return -1;
-  ConvCfg c = conv_config(Cin, Cout);
-  if (c.C8) return (int64_t)27 * Cin * 8;
-  if (c.S16) return vx_conv3d_s16_packed_floats(Cin, Cout) + vx_conv3d_zc16_packed_floats(Cin, Cout) + vx_conv3d_deep_packed_floats(Cin, Cout);
-  if (c.XP) return (int64_t)16 * Cin * 36;
-  return (int64_t)conv_rows_padded(Cout, c.NT) * Cin * 27;
-}
-
-extern "C" int vx_pack_conv3d_k3(const float* w_torch, float* w_packed, int Cin, int Cout, vx_stream_t stream) {
-  if (!w_torch || !w_packed) VX_FAIL(VX_E_NULL, "vx_pack_conv3d_k3: null pointer");
-  int64_t total = vx_conv3d_k3_packed_floats(Cin, Cout);
-  if (total < 0) VX_FAIL(VX_E_SHAPE, "vx_pack_conv3d_k3: Cin=%d Cout=%d must be positive multiples of 8", Cin, Cout);
-  ConvCfg c = conv_config(Cin, Cout);
-  if (c.C8) return vx_pack_conv3d_k3_c8(w_torch, w_packed, Cin, (hipStream_t)stream);
-  if (c.S16) {
-    const int rc = vx_pack_conv3d_k3_s16(w_torch, w_packed, Cin, Cout, (hipStream_t)stream);
-    if (rc != VX_OK) return rc;
-    if (vx_conv3d_deep_packs(Cin, Cout))      // (never both: the z-column kernel packs Cout = 16)
-      return vx_pack_conv3d_deep(w_torch, w_packed + vx_conv3d_s16_packed_floats(Cin, Cout), Cin, Cout, (hipStream_t)stream);
-    if (!vx_conv3d_zc16_packs(Cin, Cout)) return rc;
-    return vx_pack_conv3d_zc16(w_torch, w_packed + vx_conv3d_s16_packed_floats(Cin, Cout), Cin, Cout, (hipStream_t)stream);
-  }
+int vx_pack_conv3d_k3_mfma(const float* w_torch, float* w_packed, int Cin, int Cout, int64_t total, hipStream_t s) {
+  const S16Cfg c = s16_config(Cin, Cout);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_conv3d_k3_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_torch, w_packed, Cin,
-                     Cout, c.CB, c.NT, c.XP, total);
+  hipLaunchKernelGGL(pack_conv3d_k3_kernel, dim3(blocks), dim3(256), 0, s, w_torch, w_packed, Cin, Cout, c.CB, c.NT, c.XP, total);
   VX_CHECK_LAUNCH("vx_pack_conv3d_k3");
   return VX_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// tile shapes: TX = columns per column tile row (x extent in voxels is 2*TX for x-pair)
-struct TileCfg { int TX, TY, TZ, TXV; };
-static inline TileCfg tile_config(int W, int XP) {
-  if (XP) {
-    if (W >= 32) return {16, 4, 4, 32};
-    if (W >= 16) return {8, 8, 4, 16};
-    return {4, 4, 4, 8};
-  }
-  if (W >= 16) return {16, 4, 4, 16};
-  if (W >= 8) return {8, 8, 4, 8};
-  return {4, 4, 4, 4};
-}
-
-static int conv_tiles(int D, int H, int W, int Cout) {
-  if (conv_config(8, Cout).S16) {   // split-fp16 schedule: its own tile choice (larger tiles for large layers)
-    int txv, ty, tz;
-    vx_conv3d_s16_tile(H, W, Cout, &txv, &ty, &tz);
-    return ((W + txv - 1) / txv) * ((H + ty - 1) / ty) * ((D + tz - 1) / tz);
-  }
-  TileCfg t = tile_config(W, Cout == 8);
-  return ((W + t.TXV - 1) / t.TXV) * ((H + t.TY - 1) / t.TY) * ((D + t.TZ - 1) / t.TZ);
-}
-extern "C" int vx_conv3d_k3_tiles(int D, int H, int W) {
-  // upper bound over every packing, Cout and mode (stats_partial sizing).  Neither tiling dominates: for 8 <= W < 16
-  // the x-pair tile (4 pairs x 4 x 4) makes twice the tiles of the plain 8 x 8 x 4 one, for W >= 16 it is the reverse
-  int best = 0;
-  for (int xp = 0; xp < 2; ++xp) {
-    const TileCfg t = tile_config(W, xp);
-    const int n = ((W + t.TXV - 1) / t.TXV) * ((H + t.TY - 1) / t.TY) * ((D + t.TZ - 1) / t.TZ);
-    if (n > best) best = n;
-  }
-  const int couts[3] = {8, 16, 32};   // split-fp16: x-pair / one row tile (large tile) / two row tiles
-  for (int i = 0; i < 3; ++i) {
-    int txv, ty, tz;
-    vx_conv3d_s16_tile(H, W, couts[i], &txv, &ty, &tz);
-    const int n = ((W + txv - 1) / txv) * ((H + ty - 1) / ty) * ((D + tz - 1) / tz);
-    if (n > best) best = n;
-  }
-  return best;
-}
-extern "C" int vx_conv3d_k3_tiles_for(int D, int H, int W, int Cout) { return conv_tiles(D, H, W, Cout); }
-
 template <int CB, int NT, int TX, int TY, int TZ, int NW, int XP>
-static int launch_conv(const ConvKArgs& ka, hipStream_t s) {
+static int launch_conv(const ConvKArgs& ka, const Conv3dRoute& r, hipStream_t s) {
   constexpr int TXV = XP ? 2 * TX : TX;
   constexpr int NPOS = (TXV + 2) * (TY + 2) * (TZ + 2);  // = NPAR * NPP (HX is even for x-pair)
   constexpr int PLANE = CB == 16 ? ((NPOS + 15) / 16) * 16 : ((NPOS + 15) / 32) * 32 + 16;
@@ -630,233 +492,25 @@ static int launch_conv(const ConvKArgs& ka, hipStream_t s) {
   int gx = (256 * per_cu + ygroups - 1) / ygroups;
   if (gx > total_tiles) gx = total_tiles;
   dim3 grid((unsigned)gx, (unsigned)ygroups);
-  static const char* kname = vx_kname("conv3d_k3_mfma_kernel<%d,%d,%d,%d,%d,%d,%d>", CB, NT, TX, TY, TZ, NW, XP);
+  static const char* kname = vx_conv3d_kname(r);
   vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv3d_k3");
   return VX_OK;
 }
 
-template <int CB, int NT>
-static int dispatch_tile(const ConvKArgs& ka, const TileCfg& t, hipStream_t s) {
-  if (t.TX == 16) return launch_conv<CB, NT, 16, 4, 4, 8, 0>(ka, s);
-  if (t.TX == 8) return launch_conv<CB, NT, 8, 8, 4, 8, 0>(ka, s);
-  return launch_conv<CB, NT, 4, 4, 4, 4, 0>(ka, s);
-}
-template <int CB>
-static int dispatch_tile_xp(const ConvKArgs& ka, const TileCfg& t, hipStream_t s) {
-  if (t.TX == 16) return launch_conv<CB, 1, 16, 4, 4, 8, 1>(ka, s);
-  if (t.TX == 8) return launch_conv<CB, 1, 8, 8, 4, 8, 1>(ka, s);
-  return launch_conv<CB, 1, 4, 4, 4, 4, 1>(ka, s);
-}
-
-bool vx_conv3d_s16_prologue_ok(int Cin, int Cout);
-extern "C" int vx_conv3d_k3_prologue_ok(int D, int H, int W, int Cin, int Cout) {
-  if (Cin <= 0 || Cout <= 0 || Cin % 8 || Cout % 8) return 0;
-  if (vx_conv3d_xp8_applies(D, H, W, Cin, Cout)) return 1;
-  // the split-fp16 tile kernel's plain layers (dense input, see vx_conv3d_k3)
-  return conv_config(Cin, Cout).S16 && vx_conv3d_s16_prologue_ok(Cin, Cout) ? 1 : 0;
-}
-
-extern "C" int vx_conv3d_k3_acc_ok(int D, int H, int W, int Cin, int Cout) {
-  return Cin == 16 && Cout == 16 && conv_config(Cin, Cout).S16 && vx_conv3d_zc16_applies(D, H, W, Cin, Cout) ? 1 : 0;
-}
-
-// in_planar / out_planar: the 16 -> 16 layers of the z-column kernel
-extern "C" int vx_conv3d_k3_planar_ok(int D, int H, int W, int Cin, int Cout) {
-  return Cin == 16 && Cout == 16 && conv_config(Cin, Cout).S16 && vx_conv3d_zc16_applies(D, H, W, Cin, Cout) ? 1 : 0;
-}
-
-// in_mean on the SKIP half of an x-blocked concat input (the decoder's first conv reading a contract block's raw output)
-extern "C" int vx_conv3d_k3_skip_prologue_ok(int D, int H, int W, int Cin, int Cout, int xblk) {
-  if (Cin <= 0 || Cout <= 0 || Cin % 16 || Cout % 8 || (xblk != 1 && xblk != 2 && xblk != 4)) return 0;
-  if (Cin == 16 && vx_conv3d_xp8_applies(D, H, W, Cin, Cout)) return 1;      // (16 -> 8 at full resolution: the z-column kernel's prologue)
-  if (Cin % 32) return 0;
-  const ConvCfg c = conv_config(Cin, Cout);
-  const int csrc = Cin / 2;
-  return c.S16 && c.CB == 16 && vx_conv3d_s16_prologue_ok(Cin, Cout) && ((xblk * csrc) & (xblk * csrc - 1)) == 0 ? 1 : 0;
-}
-
-extern "C" int vx_conv3d_k3_upfuse_ok(int D, int H, int W, int Cin, int Cout) {
-  if (vx_cfg().s16_no_upfuse) return 0;
-  if (Cin == 16 && vx_conv3d_xp8_applies(D, H, W, Cin, Cout)) return 1;
-  // 2 (round 5): the 16-channel z-column kernel evaluates ConvTranspose3d(32 -> 16) for ALL 16 of its input channels (`in` is not
-  // read; up_w = vx_pack_convT_zc16, up_pitch >= 32) -- the up half of a decoder conv that runs over its halves (acc_in)
-  if (Cin == 16 && Cout == 16 && conv_config(Cin, Cout).S16 && vx_conv3d_zc16_applies(D, H, W, Cin, Cout)) return 2;
-  return 0;
-}
-
-extern "C" int vx_conv3d_k3_pool_layout(int D, int H, int W, int Cin, int Cout) {
-  if (vx_cfg().s16_no_poolfuse) return 0;
-  if (Cin == 8 && vx_conv3d_xp8_applies(D, H, W, Cin, Cout)) return 1;
-  if (Cin == 16 && Cout == 16 && conv_config(Cin, Cout).S16 && vx_conv3d_zc16_applies(D, H, W, Cin, Cout)) return 2;
-  return 0;
-}
-extern "C" int vx_conv3d_k3_poolfuse_ok(int D, int H, int W, int Cin, int Cout) {
-  return vx_conv3d_k3_pool_layout(D, H, W, Cin, Cout) != 0 ? 1 : 0;
-}
-
-// in_split (vx_prenorm_split's fp16 pairs) is read by the z-column kernel's staging waves only: the tile kernel's prologue
-// takes the raw tensor (in_repeat) -- a caller that pre-splits where this says 0 has overwritten its tensor for nothing
-extern "C" int vx_conv3d_k3_presplit_ok(int D, int H, int W, int Cin, int Cout) {
-  return Cin == 8 && vx_conv3d_xp8_applies(D, H, W, Cin, Cout) ? 1 : 0;
-}
-
-// in_pool_flags: the tile kernel's prologue on a dense 8-channel input (contr_2_1 of the F = 8 networks)
-// (the code lives only in the instances an 8 -> 16 layer of a contract block runs on: 8-channel chunks, plain rows, ONE row
-// tile -- Cout % 32 == 0 takes two row tiles per wave and Cout == 8 the x-pair kernels, neither carries it)
-extern "C" int vx_conv3d_k3_poolfin_ok(int Cin, int Cout) {
-  if (Cin != 8 || Cout <= 0 || Cout % 8 || Cout % 32 == 0) return 0;
-  return conv_config(Cin, Cout).S16 && vx_conv3d_s16_prologue_ok(Cin, Cout) ? 1 : 0;
-}
-
-extern "C" int vx_conv3d_k3_head_fusable(int Cin, int Cout) {
-  if (Cin <= 0 || Cout <= 0 || Cin % 8 || Cout % 8) return 0;
-  const ConvCfg c = conv_config(Cin, Cout);
-  if (c.S16) return vx_conv3d_s16_head_fusable(Cin, Cout) ? 1 : 0;   // x-pair split-fp16 kernel: halves in lanes l, l ^ 16
-  return c.C8;   // the 4x4x1 kernel keeps all channels of a voxel in one lane
-}
-
-extern "C" int vx_conv3d_k3(const vx_conv3d_args* ap, vx_stream_t stream) {
-  if (!ap) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: null args");
-  const vx_conv3d_args& a = *ap;
-  if (!a.in || !a.w_packed || !a.bias || (!a.out && !a.head_out)) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: null tensor pointer");
-  if (a.head_out) {
-    if (!a.head_w || !a.head_b) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: fused head without weights");
-    if (a.head_C < 1 || a.head_C > 8) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: fused head takes 1..8 classes, got %d", a.head_C);
-    if (conv_config(a.Cin, a.Cout).S16 && a.head_C > 4)
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the split-fp16 kernel fuses heads of up to 4 classes, got %d", a.head_C);
-    if (!vx_conv3d_k3_head_fusable(a.Cin, a.Cout))
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: no fused head for Cin=%d Cout=%d (see vx_conv3d_k3_head_fusable)", a.Cin, a.Cout);
-    if (a.stats_partial) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: fused head on a layer with InstanceNorm statistics");
-  }
-  if (a.Cin <= 0 || a.Cout <= 0 || a.Cin % 8 || a.Cout % 8)
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: Cin=%d Cout=%d must be positive multiples of 8", a.Cin, a.Cout);
-  if (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: empty tensor");
-  if (a.w_family != vx_conv3d_k3_family(a.Cin, a.Cout))
-    VX_FAIL(VX_E_DTYPE, "vx_conv3d_k3: weights packed for kernel family %d, the library is configured for family %d "
-            "(vx_conv3d_k3_family(%d, %d)): re-pack them", a.w_family, vx_conv3d_k3_family(a.Cin, a.Cout), a.Cin, a.Cout);
-  if (a.out_xblk && ((a.out_xblk != 1 && a.out_xblk != 2 && a.out_xblk != 4) || a.W % a.out_xblk || (a.out_half != 0 && a.out_half != 1)))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: bad concat output (xblk=%d, half=%d, W=%d)", a.out_xblk, a.out_half, a.W);
-  if ((a.in_mean == nullptr) != (a.in_rstd == nullptr)) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: in_mean / in_rstd must come together");
-  // products: 0 / 3 = the split scheme's three products (default); 1 = the opt-in one-product mode of the full-resolution z-column kernel
-  if (a.products != 0 && a.products != 1 && a.products != 3)
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: products = %d (0 / 3: the default split scheme, 1: one fp16 product)", a.products);
-  if (a.products == 1 && !(conv_config(a.Cin, a.Cout).S16 && vx_conv3d_xp8_applies(a.D, a.H, a.W, a.Cin, a.Cout) &&
-                           a.drop_mode != VX_DROP_MASK && a.in_drop_mode != VX_DROP_MASK))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: products = 1 is taken by the full-resolution z-column kernel only (got %dx%dx%d, %d -> %d)",
-            a.D, a.H, a.W, a.Cin, a.Cout);
-  // the planar hand-over only exists in the 16 -> 16 instances of the z-column kernel: refused before any other kernel can take
-  // the launch and ignore the flags
-  if ((a.in_planar || a.out_planar) && !vx_conv3d_k3_planar_ok(a.D, a.H, a.W, a.Cin, a.Cout))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the planar pre-split hand-over (in_planar / out_planar) is taken where vx_conv3d_k3_planar_ok "
-            "(got %dx%dx%d, %d -> %d)", a.D, a.H, a.W, a.Cin, a.Cout);
-  if (a.up_in) {
-    if (!a.up_w || !a.up_b) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: fused up-convolution without weights");
-    if (!vx_conv3d_k3_upfuse_ok(a.D, a.H, a.W, a.Cin, a.Cout) || a.drop_mode == VX_DROP_MASK || a.stats_partial || a.head_out)
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: no fused up-convolution for this layer (see vx_conv3d_k3_upfuse_ok; hash or no "
-              "dropout, no statistics, no head): %dx%dx%d, %d -> %d", a.D, a.H, a.W, a.Cin, a.Cout);
-    if (a.up_pitch < 16 || a.up_pitch % 4 || !vx_aligned16(a.up_in) || !vx_aligned16(a.up_b))
-      VX_FAIL(VX_E_ALIGN, "vx_conv3d_k3: up_in pitch %d (>= 16, multiple of 4 floats) / alignment", a.up_pitch);
-    if ((int64_t)(a.D / 2 + 2) * (a.H / 2) * (a.W / 2) * a.up_pitch * 4 >= (1ll << 31))
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: one coarse sample must stay below 2 GiB");
-    if (a.up_fused && !vx_aligned16(a.up_fused)) VX_FAIL(VX_E_ALIGN, "vx_conv3d_k3: up_fused alignment");
-  } else if (a.up_fused) {
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: up_fused (composed up-convolution weights) without up_in");
-  }
-  if (a.pool_out) {
-    if (!a.pool_flags || !a.stats_partial) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: pool_out goes with pool_flags and stats_partial");
-    if (!vx_conv3d_k3_poolfuse_ok(a.D, a.H, a.W, a.Cin, a.Cout) || a.drop_mode == VX_DROP_MASK || a.act != VX_ACT_NONE || a.head_out)
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: no pooled output for this layer (see vx_conv3d_k3_poolfuse_ok; hash or no dropout, "
-              "no activation): %dx%dx%d, %d -> %d", a.D, a.H, a.W, a.Cin, a.Cout);
-    if (!vx_aligned16(a.pool_out)) VX_FAIL(VX_E_ALIGN, "vx_conv3d_k3: pool_out alignment");
-  }
-  if (a.in_drop_mode != VX_DROP_NONE && a.in_drop_mode != VX_DROP_HASH) VX_FAIL(VX_E_DTYPE, "vx_conv3d_k3: in_drop_mode %d", a.in_drop_mode);
-  if (a.in_pool_flags) {
-    if (!a.in_mean) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: in_pool_flags goes with in_mean / in_rstd");
-    if (!vx_conv3d_k3_poolfin_ok(a.Cin, a.Cout) || a.in_xblk || a.in_pitch != 8 || a.in_split || a.up_in || a.in_repeat > 1)
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: pool-finish on load takes a dense 8-channel tensor of window maxima (see "
-              "vx_conv3d_k3_poolfin_ok): %d -> %d, pitch %d", a.Cin, a.Cout, a.in_pitch);
-    // the first conv of a contract block: bias + statistics (an InstanceNorm follows) -- the only epilogue whose instances carry
-    // the pool-finish code; with an activation / dropout / head the launch would fall onto an instance that ignores the flag words
-    if (a.act != VX_ACT_NONE || a.drop_mode != VX_DROP_NONE || a.head_out || !a.out)
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: pool-finish on load goes with the plain epilogue (no activation, no dropout, no head): "
-              "act=%d drop_mode=%d", a.act, a.drop_mode);
-  }
-  if (a.out && !a.out_xblk && (a.out_pitch < a.out_coff + a.Cout || a.out_pitch % 4 || a.out_coff % 4))
-    VX_FAIL(VX_E_ALIGN, "vx_conv3d_k3: output pitch/offset must be multiples of 4 floats and cover the channels");
-  if (a.in_xblk) {
-    if (a.in_xblk != 1 && a.in_xblk != 2 && a.in_xblk != 4) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: in_xblk must be 0, 1, 2 or 4");
-    if (a.W % a.in_xblk) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: W=%d not a multiple of in_xblk=%d", a.W, a.in_xblk);
-    if (a.Cin % 16) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: concat input needs Cin %% 16 == 0 (two halves of Cin/2)");
-  } else if (a.in_pitch < (a.up_in ? a.Cin / 2 : a.Cin) || a.in_pitch % 4) {
-    VX_FAIL(VX_E_ALIGN, "vx_conv3d_k3: input pitch must be a multiple of 4 floats and cover the channels");
-  }
-  if (!vx_aligned16(a.in) || !vx_aligned16(a.out) || !vx_aligned16(a.w_packed) || !vx_aligned16(a.bias))
-    VX_FAIL(VX_E_ALIGN, "vx_conv3d_k3: pointers must be 16-byte aligned");
-  if (a.act < 0 || a.act > 2 || a.drop_mode < 0 || a.drop_mode > 2) VX_FAIL(VX_E_DTYPE, "vx_conv3d_k3: bad act/drop enum");
-  if (a.drop_mode == VX_DROP_MASK && !a.drop_mask) VX_FAIL(VX_E_NULL, "vx_conv3d_k3: VX_DROP_MASK without mask");
-  const int64_t inrow = a.in_xblk ? (int64_t)a.Cin : (int64_t)a.in_pitch;
-  if ((int64_t)a.D * a.H * a.W * a.out_pitch * 4 >= (1ll << 31) || ((int64_t)a.D + 2) * a.H * a.W * inrow * 4 >= (1ll << 31))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: one sample must stay below 2 GiB (32-bit buffer offsets)");
-
-  ConvCfg c = conv_config(a.Cin, a.Cout);
-  TileCfg t = tile_config(a.W, c.XP);
+int vx_conv3d_mfma_launch(const Conv3dRoute& r, const vx_conv3d_args& a, hipStream_t s) {
   ConvKArgs ka;
   ka.a = a;
-  ka.tiles_x = (a.W + t.TXV - 1) / t.TXV;
-  ka.tiles_y = (a.H + t.TY - 1) / t.TY;
-  ka.tiles_z = (a.D + t.TZ - 1) / t.TZ;
-  ka.nchunks = a.Cin / c.CB;
-  ka.mx = (unsigned)((1ull << 32) / (unsigned)ka.tiles_x) + 1u;
-  ka.my = (unsigned)((1ull << 32) / (unsigned)ka.tiles_y) + 1u;
-  ka.mz = (unsigned)((1ull << 32) / (unsigned)ka.tiles_z) + 1u;
-  ka.dbg = nullptr;
-#ifdef VX_CONV_STAMPS
-  if (const char* e = getenv("VX_CONV_DBG_PTR")) ka.dbg = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-  hipStream_t s = (hipStream_t)stream;
-  if (c.C8 && !a.in_mean && !a.out_xblk) return vx_conv3d_k3_c8(a, t.TXV, t.TY, t.TZ, s);
-  if (c.S16 && vx_conv3d_xp8_applies(a.D, a.H, a.W, a.Cin, a.Cout) && a.drop_mode != VX_DROP_MASK &&
-      a.in_drop_mode != VX_DROP_MASK) {
-    // the full-resolution layers: z-column walk with a rolling LDS window (conv3d_xp8w.hip)
-    const int rc = vx_conv3d_k3_xp8(a, conv_tiles(a.D, a.H, a.W, a.Cout), s);
-    if (rc != 1) return rc;
-    if (a.products == 1) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: products = 1, but the z-column kernel does not take this launch");
+  ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.tiles_z = r.tiles_z;
+  ka.nchunks = r.nchunks;
+  ka.mx = r.mx; ka.my = r.my; ka.mz = r.mz;
+  int unused;
+  vx_conv_diag(VX_DIAG_NONE, &ka.dbg, &unused);
+  switch (conv3d_key_of(r.p, r.np)) {
+#define MFMA_CASE(...) case conv3d_key(__VA_ARGS__): return launch_conv<__VA_ARGS__>(ka, r, s);
+    MFMA_INSTANCES(MFMA_CASE)
+#undef MFMA_CASE
   }
-  if (c.S16 && vx_conv3d_zc16_applies(a.D, a.H, a.W, a.Cin, a.Cout)) {
-    // the Cout = 16 layers below full resolution: role-split z-column kernel (conv3d_zc16.hip); its weights follow the tile
-    // kernel's in the packed block (family 6)
-    const int rc = vx_conv3d_k3_zc16(a, a.w_packed + vx_conv3d_s16_packed_floats(a.Cin, a.Cout), conv_tiles(a.D, a.H, a.W, a.Cout), s);
-    if (rc != 1) return rc;
-  }
-  if (a.in_planar || a.out_planar)
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the z-column kernel does not take this planar launch (%dx%dx%d, %d -> %d)", a.D, a.H, a.W,
-            a.Cin, a.Cout);
-  if (c.S16 && vx_conv3d_deep_applies(a.N, a.D, a.H, a.W, a.Cin, a.Cout)) {
-    // the deep layers (Cout % 32 == 0 on small volumes): role-split tile kernel (conv3d_deep.hip); its weights follow the tile
-    // kernel's in the packed block (family 7)
-    const int rc = vx_conv3d_k3_deep(a, a.w_packed + vx_conv3d_s16_packed_floats(a.Cin, a.Cout), conv_tiles(a.D, a.H, a.W, a.Cout), s);
-    if (rc != 1) return rc;
-  }
-  // the tile kernel's prologue: a dense input, or (round 5) the skip half of an x-blocked concat input whose halves are whole
-  // 16-channel chunks with xb * Cin / 2 a power of two (the element index of the dropout bits follows from the load offset)
-  const int csrc = a.Cin / 2;
-  const bool xblk_pre = a.in_xblk && c.CB == 16 && csrc % 16 == 0 && ((a.in_xblk * csrc) & (a.in_xblk * csrc - 1)) == 0 &&
-                        !a.in_pool_flags && !(a.in_repeat > 1);
-  const bool tile_pre = a.in_mean && c.S16 && vx_conv3d_s16_prologue_ok(a.Cin, a.Cout) &&
-                        ((!a.in_xblk && a.in_pitch == a.Cin) || xblk_pre) && a.in_drop_mode != VX_DROP_MASK;
-  if ((a.in_mean && !tile_pre) || a.out_xblk || a.up_in || a.pool_out || a.in_split || a.in_f16 || a.out_f16)
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the input prologue / concat output / fused up-convolution are only available where "
-            "vx_conv3d_k3_prologue_ok(D, H, W, Cin, Cout), with hash or no dropout (got %dx%dx%d, %d -> %d)", a.D, a.H, a.W, a.Cin, a.Cout);
-  if (a.up_split) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: up_split goes with the fused up-convolution (up_in)");
-  if (a.acc_in) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: partial sums (acc_in) are taken where vx_conv3d_k3_acc_ok (got %dx%dx%d, %d -> %d)",
-                        a.D, a.H, a.W, a.Cin, a.Cout);
-  if (c.S16) return vx_conv3d_k3_s16(a, s);
-  if (a.out_split) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: out_split is an epilogue of the split-fp16 tile kernel");
-  if (c.XP) return dispatch_tile_xp<8>(ka, t, s);
-  if (c.CB == 16 && c.NT == 1) return dispatch_tile<16, 1>(ka, t, s);
-  if (c.CB == 16 && c.NT == 2) return dispatch_tile<16, 2>(ka, t, s);
-  if (c.CB == 8 && c.NT == 1) return dispatch_tile<8, 1>(ka, t, s);
-  return dispatch_tile<8, 2>(ka, t, s);
+  VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3: no such instance of the fp32 tile kernel");
 }

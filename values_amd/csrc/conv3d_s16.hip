@@ -23,10 +23,8 @@
 // The loop reads (2 NT + 2 R) KiB of LDS per 3 R NT MFMAs.  Around it (x-pair layers on the large tile): two LDS images,
 // one barrier per item, staggered SIMD partners (DB), compile-time epilogues (EPI) -- see the kernel's header below and
 // DESIGN.md section 5, round-1g, for the counters behind each step.
-#include "common.h"
-#include <stdlib.h>
-
 #include "s16_common.h"
+#include "conv3d_internal.h"
 
 struct ConvSArgs {
   vx_conv3d_args a;
@@ -39,25 +37,7 @@ struct ConvSArgs {
   unsigned long long* stamps;   // VX_CONV_STAMPS diagnostic builds only: per wave, cycles spent per phase
 };
 
-// Phase stamps of the item loop (diagnostic build -DVX_CONV_STAMPS, tools/stamp_s16.py): s_memtime deltas summed per
-// wave into st_sum[phase]; the values go to a buffer of their own, never into an output.
-#ifdef VX_CONV_STAMPS
-#define VX_STAMP(i)                                                                      \
-  do {                                                                                   \
-    unsigned long long t_;                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    st_sum[i] += t_ - st_last;                                                           \
-    st_last = t_;                                                                        \
-  } while (0)
-#define VX_STAMP_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define S16_DBG ka.dbg
-#else
-#define VX_STAMP(i) do {} while (0)
-#define VX_STAMP_WAIT_LOADS() do {} while (0)
-#define S16_DBG 0
-#endif
+#define S16_DBG VX_DIAG(ka.dbg)   // (phase stamps VX_STAMP, VX_DIAG: conv3d_internal.h; tools/stamp_s16.py)
 
 // XP (Cout == 8, CB == 8): x-pair packing as in conv3d_mfma.hip -- rows = (dx, cout), columns = voxel pairs
 // (x = 2p, 2p + 1), a K = 32 step = one (kz, ky) row with the four x-offsets ix = 0..3 as the four k-groups
@@ -905,26 +885,9 @@ __global__ void pack_conv3d_k3_s16_kernel(const float* __restrict__ w, _Float16*
   }
 }
 
-struct S16Cfg { int CB, NT, XP; };
-static inline S16Cfg s16_config(int Cin, int Cout) {
-  S16Cfg c;
-  c.NT = (Cout % 32 == 0) ? 2 : 1;
-  c.XP = Cout == 8 ? 1 : 0;
-  c.CB = c.XP ? 8 : ((Cin % 16 == 0) ? 16 : 8);
-  return c;
-}
-static inline int s16_rows_padded(int Cout, int NT) { return ((Cout + 16 * NT - 1) / (16 * NT)) * (16 * NT); }
-
-int64_t vx_conv3d_s16_packed_floats(int Cin, int Cout) {
-  const S16Cfg c = s16_config(Cin, Cout);
-  const int TPS = 32 / c.CB, NSTEP = c.XP ? 9 : (27 + TPS - 1) / TPS;
-  const int64_t halves = (int64_t)(s16_rows_padded(Cout, c.NT) / 16) * (Cin / c.CB) * NSTEP * 2 * (c.XP ? 32 : 64) * 8;
-  return halves / 2;
-}
-
 int vx_pack_conv3d_k3_s16(const float* w_torch, float* w_packed, int Cin, int Cout, hipStream_t s) {
   const S16Cfg c = s16_config(Cin, Cout);
-  const int64_t total = vx_conv3d_s16_packed_floats(Cin, Cout) * 2;
+  const int64_t total = conv3d_s16_packed_floats(Cin, Cout) * 2;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(pack_conv3d_k3_s16_kernel, dim3(blocks), dim3(256), 0, s, w_torch, reinterpret_cast<_Float16*>(w_packed),
@@ -936,7 +899,7 @@ int vx_pack_conv3d_k3_s16(const float* w_torch, float* w_packed, int Cin, int Co
 #endif   // S16_PART == 0
 
 template <int CB, int NT, int TX, int TY, int TZ, int NW, int XP, int DB = 0, int EPI = 3>
-static int launch_s16(const ConvSArgs& ka_in, hipStream_t s) {
+static int launch_s16(const ConvSArgs& ka_in, const Conv3dRoute& r, hipStream_t s) {
   constexpr int TXV = XP ? 2 * TX : TX;
   constexpr int NHALO = (TXV + 2) * (TY + 2) * (TZ + 2);
   constexpr int PLANE = (((XP ? NHALO / 2 : NHALO) + 15) / 16) * 16;
@@ -962,130 +925,47 @@ static int launch_s16(const ConvSArgs& ka_in, hipStream_t s) {
   if (per_cu * NW > 16) per_cu = 16 / NW > 0 ? 16 / NW : 1;
   int gx = (256 * per_cu + ygroups - 1) / ygroups;
   if (gx > total_tiles) gx = total_tiles;
-  static const char* kname = vx_kname("conv3d_k3_s16_kernel<%d,%d,%d,%d,%d,%d,%d,%d,%d>", CB, NT, TX, TY, TZ, NW, XP, DB, EPI);
+  static const char* kname = vx_conv3d_kname(r);
   vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ygroups), dim3(64 * NW), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv3d_k3(s16)");
   return VX_OK;
 }
 
-template <int CB, int NT, int XP>
-static int dispatch_s16(const ConvSArgs& ka, int tx, hipStream_t s) {
-  // epilogue specialisation of the large-tile instances (EPI in the kernel's header)
-  const vx_conv3d_args& a = ka.a;
-  int epi = 3;
-  const bool generic = vx_cfg().s16_generic != 0;   // parity reference: run-time epilogue, one LDS image, two barriers per item
-  if (generic) epi = 3;
-  else if (a.act == VX_ACT_NONE && a.drop_mode == VX_DROP_NONE && !a.head_out && a.out) epi = 0;
-  else if (a.act == VX_ACT_LRELU && a.drop_mode == VX_DROP_HASH && !a.head_out && a.out) epi = 1;
-  else if (a.act == VX_ACT_LRELU && a.drop_mode == VX_DROP_HASH && a.head_out && XP) epi = 2;
-  if constexpr (XP == 1) {   // single-chunk x-pair layers: double-buffered LDS image (one barrier per item)
-    if (tx == 16 && ka.ty8 && ka.nchunks == 1 && !generic) {
-      if (epi == 0) return launch_s16<CB, NT, 16, 8, 4, 8, XP, 2, 0>(ka, s);
-      if (epi == 1) return launch_s16<CB, NT, 16, 8, 4, 8, XP, 2, 1>(ka, s);
-      if (epi == 2) return launch_s16<CB, NT, 16, 8, 4, 8, XP, 2, 2>(ka, s);
-      return launch_s16<CB, NT, 16, 8, 4, 8, XP, 2, 3>(ka, s);
-    }
-    if (tx == 16 && ka.ty8 && ka.nchunks == 2 && !generic) {   // 16 -> 8 channels
-      if (epi == 1) return launch_s16<CB, NT, 16, 8, 4, 8, XP, 3, 1>(ka, s);
-      return launch_s16<CB, NT, 16, 8, 4, 8, XP, 3, 3>(ka, s);
-    }
-  }
-  if constexpr (XP == 0) {
-    // Round 3: single-chunk plain layers on two LDS images with staggered SIMD partners (DB = 2) WHERE THE LAYER'S TILE FITS
-    // TWICE: -11 % on 16 -> 32 at 16^3.  Shrinking the tile to make room loses more than the stagger wins: the 16-channel
-    // chunks at 32^3 on 16 x 4 x 4 instead of 16 x 8 x 4 were 14-15 % SLOWER double-buffered, and 8 -> 16 at 32^3 (whose large
-    // tile does fit twice) measured neutral (same-process A/B)
-    if (tx == 16 && ka.nchunks == 1 && !generic) {
-      if (!ka.ty8) {                             // 16 x 4 x 4 tile (two row tiles, or H < 32)
-        if (epi == 0) return launch_s16<CB, NT, 16, 4, 4, 8, XP, 2, 0>(ka, s);
-        if (epi == 1) return launch_s16<CB, NT, 16, 4, 4, 8, XP, 2, 1>(ka, s);
-        return launch_s16<CB, NT, 16, 4, 4, 8, XP, 2, 3>(ka, s);
-      }
-    }
-  }
-  if constexpr (NT == 1) {   // large layers: 4 column tiles per wave (vx_conv3d_s16_tile: never with two row tiles)
-    if (tx == 16 && ka.ty8) {
-      if (epi == 0) return launch_s16<CB, NT, 16, 8, 4, 8, XP, 0, 0>(ka, s);
-      if (epi == 1) return launch_s16<CB, NT, 16, 8, 4, 8, XP, 0, 1>(ka, s);
-      return launch_s16<CB, NT, 16, 8, 4, 8, XP>(ka, s);
-    }
-  }
-  // (the decoder's LeakyReLU + hash-dropout epilogue as a compile-time instance on the small tiles too: its run-time form
-  // re-tests five flags per column tile)
-  if (tx == 16) {
-    if (epi == 1) return launch_s16<CB, NT, 16, 4, 4, 8, XP, 0, 1>(ka, s);
-    if (epi == 0) return launch_s16<CB, NT, 16, 4, 4, 8, XP, 0, 0>(ka, s);
-    return launch_s16<CB, NT, 16, 4, 4, 8, XP>(ka, s);
-  }
-  if (tx == 8) {
-    if (epi == 1) return launch_s16<CB, NT, 8, 8, 4, 8, XP, 0, 1>(ka, s);
-    if (epi == 0) return launch_s16<CB, NT, 8, 8, 4, 8, XP, 0, 0>(ka, s);
-    return launch_s16<CB, NT, 8, 8, 4, 8, XP>(ka, s);
-  }
-  return launch_s16<CB, NT, 4, 4, 4, 4, XP>(ka, s);
-}
-
-#if S16_PART == 2
-// the 16-channel-chunk instances with two row tiles per wave (this translation unit: conv3d_s16_nt2.o)
-int vx_conv3d_k3_s16_nt2(const ConvSArgs& ka, int tx, hipStream_t s) { return dispatch_s16<16, 2, 0>(ka, tx, s); }
+// This translation unit's share of the instance list (conv3d_route.h): launch_s16<...> is instantiated for these and no others.
+int vx_conv3d_s16_launch_part0(const ConvSArgs& ka, const Conv3dRoute& r, hipStream_t s);   // 16-channel chunks, one row tile
+int vx_conv3d_s16_launch_part1(const ConvSArgs& ka, const Conv3dRoute& r, hipStream_t s);   // 8-channel chunks (x-pair included)
+int vx_conv3d_s16_launch_part2(const ConvSArgs& ka, const Conv3dRoute& r, hipStream_t s);   // 16-channel chunks, two row tiles
+#if S16_PART == 0
+#define S16_LAUNCH_HERE vx_conv3d_s16_launch_part0
+#define S16_INSTANCES_HERE S16_INSTANCES_PART0
 #elif S16_PART == 1
-// the 8-channel-chunk half of the dispatch (this translation unit: conv3d_s16_cb8.o)
-int vx_conv3d_k3_s16_cb8(const ConvSArgs& ka, int nt, int xp, int tx, hipStream_t s) {
-  if (xp) return dispatch_s16<8, 1, 1>(ka, tx, s);
-  if (nt == 1) return dispatch_s16<8, 1, 0>(ka, tx, s);
-  return dispatch_s16<8, 2, 0>(ka, tx, s);
-}
+#define S16_LAUNCH_HERE vx_conv3d_s16_launch_part1
+#define S16_INSTANCES_HERE S16_INSTANCES_PART1
 #else
-int vx_conv3d_k3_s16_cb8(const ConvSArgs& ka, int nt, int xp, int tx, hipStream_t s);
-int vx_conv3d_k3_s16_nt2(const ConvSArgs& ka, int tx, hipStream_t s);
-// tiles = those of conv3d_mfma.hip's tile_config (tx columns per row: 16 / 8 / 4 by W, or by W / 2 for x-pair)
-// Tile of a layer: tx columns per row (16 / 8 / 4 by W, or by W / 2 for x-pair) as in conv3d_mfma.hip; large layers
-// (H >= 32) take 16 x 8 x 4 tiles = 4 column tiles per wave: the halo read per output voxel drops from 2.5x to 2.1x
-// and the per-item costs (barriers, decode, masks) halve -- +14..20 % on the 64^3 layers; small layers keep
-// 16 x 4 x 4 so that the 256 CUs still get enough work items.
-void vx_conv3d_s16_tile(int H, int W, int Cout, int* txv, int* ty, int* tz) {
-  const int xp = s16_config(8, Cout).XP;
-  const int wcols = xp ? W / 2 : W;
-  const int tx = wcols >= 16 ? 16 : (wcols >= 8 ? 8 : 4);
-  // two row tiles per wave (Cout % 32 == 0) on the large tile would need > 256 registers (75 spilled): small tile there
-  // (measured 32->32 @64^3: 321 TFLOP/s on 16x4x4 tiles against 204 on the spilling 16x8x4 instance)
-  const bool nt2 = !xp && Cout % 32 == 0;
-  const bool ty8 = tx == 16 && H >= 32 && !nt2;
-  *txv = xp ? 2 * tx : tx;
-  *ty = (tx == 8 || ty8) ? 8 : 4;
-  *tz = 4;
+#define S16_LAUNCH_HERE vx_conv3d_s16_launch_part2
+#define S16_INSTANCES_HERE S16_INSTANCES_PART2
+#endif
+int S16_LAUNCH_HERE(const ConvSArgs& ka, const Conv3dRoute& r, hipStream_t s) {
+  switch (conv3d_key_of(r.p, r.np)) {
+#define S16_CASE(...) case conv3d_key(__VA_ARGS__): return launch_s16<__VA_ARGS__>(ka, r, s);
+    S16_INSTANCES_HERE(S16_CASE)
+#undef S16_CASE
+  }
+  VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(s16): no such instance");
 }
 
-// +2.6 % end to end over the separate conv1x1 kernel (2088 vs 2036 volumes/s) once the lane's weights are hoisted out of
-// the item loop; a first version with per-piece weight loads measured no gain.  VX_NO_HEAD_FUSION=1 (forward) disables it.
-bool vx_conv3d_s16_head_fusable(int Cin, int Cout) { return s16_config(Cin, Cout).XP != 0; }
-// the tile kernel takes the normalise-on-load prologue on its plain (not x-pair) layers
-bool vx_conv3d_s16_prologue_ok(int Cin, int Cout) { return s16_config(Cin, Cout).XP == 0; }
-int vx_conv3d_s16_head_max_classes() { return 4; }
-
-int vx_conv3d_k3_s16(const vx_conv3d_args& a, hipStream_t s) {
-  const S16Cfg c = s16_config(a.Cin, a.Cout);
-  int txv, ty, tz;
-  vx_conv3d_s16_tile(a.H, a.W, a.Cout, &txv, &ty, &tz);
-  const int tx = c.XP ? txv / 2 : txv;
-  const int ty8 = (tx == 16 && ty == 8) ? 1 : 0;
+#if S16_PART == 0
+int vx_conv3d_s16_launch(const Conv3dRoute& r, const vx_conv3d_args& a, hipStream_t s) {
   ConvSArgs ka;
   ka.a = a;
-  ka.tiles_x = (a.W + txv - 1) / txv; ka.tiles_y = (a.H + ty - 1) / ty; ka.tiles_z = (a.D + tz - 1) / tz;
-  ka.nchunks = a.Cin / c.CB;
-  ka.mx = (unsigned)((1ull << 32) / (unsigned)ka.tiles_x) + 1u;
-  ka.my = (unsigned)((1ull << 32) / (unsigned)ka.tiles_y) + 1u;
-  ka.mz = (unsigned)((1ull << 32) / (unsigned)ka.tiles_z) + 1u;
-  ka.dbg = 0;
-  ka.stamps = nullptr;
-#ifdef VX_CONV_STAMPS
-  if (const char* e = getenv("VX_S16_DBG")) ka.dbg = atoi(e);
-  if (const char* e = getenv("VX_CONV_DBG_PTR")) ka.stamps = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-  ka.ty8 = ty8;
-  if (c.CB == 16 && c.NT == 1) return dispatch_s16<16, 1, 0>(ka, tx, s);
-  if (c.CB == 16 && c.NT == 2) return vx_conv3d_k3_s16_nt2(ka, tx, s);
-  return vx_conv3d_k3_s16_cb8(ka, c.NT, c.XP, tx, s);
+  ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.tiles_z = r.tiles_z;
+  ka.nchunks = r.nchunks;
+  ka.mx = r.mx; ka.my = r.my; ka.mz = r.mz;
+  ka.ty8 = r.ty8;
+  vx_conv_diag(VX_DIAG_S16_DBG, &ka.stamps, &ka.dbg);
+  const int CB = r.p[0], NT = r.p[1];
+  if (CB == 16) return NT == 1 ? vx_conv3d_s16_launch_part0(ka, r, s) : vx_conv3d_s16_launch_part2(ka, r, s);
+  return vx_conv3d_s16_launch_part1(ka, r, s);
 }
-#endif   // S16_PART
+#endif

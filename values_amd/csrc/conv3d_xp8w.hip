@@ -14,6 +14,7 @@
 // wave of the SIMD and issue in the shadow of the consumers' MFMAs; one barrier per item as before.  The roles live in
 // two separate loops (same barrier count) so that the register allocation is the maximum, not the sum, of the two.
 #include "s16_common.h"
+#include "conv3d_internal.h"
 
 struct Xp8wArgs {
   vx_conv3d_args a;
@@ -27,23 +28,10 @@ struct Xp8wArgs {
   int abl;                    // diagnostic build only: phase ablation bits (1 no multiply, 2 no epilogue, 4 no commit, 8 no loads)
 };
 
-#ifdef VX_CONV_STAMPS
-#define XP_STAMP(i)                                                                      \
-  do {                                                                                   \
-    unsigned long long t_;                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    st_sum[i] += t_ - st_last;                                                           \
-    st_last = t_;                                                                        \
-  } while (0)
-#define XP_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define XP_ABL ka.abl
-#else
-#define XP_ABL 0
-#define XP_STAMP(i) do {} while (0)
-#define XP_WAIT_LOADS() do {} while (0)
-#endif
+// phase stamps / ablation word: diagnostic build only (conv3d_internal.h)
+#define XP_STAMP VX_STAMP
+#define XP_WAIT_LOADS VX_STAMP_WAIT_LOADS
+#define XP_ABL VX_DIAG(ka.abl)
 
 // NCH: 8-channel input chunks (1 or 2).  EPI: epilogue (0 bias + statistics + store, 1 LeakyReLU + hash dropout, 2 that + the
 // fused 1x1x1 head, 3 run-time activation, 4 / 5 below).  PRE: normalise-on-load prologue (0 none, 1 InstanceNorm + LeakyReLU +
@@ -1199,14 +1187,8 @@ __global__ __launch_bounds__((8 + NPW) * 64) void conv3d_xp8w_kernel(Xp8wArgs ka
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-bool vx_conv3d_xp8_applies(int D, int H, int W, int Cin, int Cout) {
-  if (vx_cfg().conv_fp32 != 0 || vx_cfg().s16_no_xp8) return false;
-  // D >= 8: a column has at least two items (the statistics hand-off between the wave halves needs the spacing)
-  return Cout == 8 && (Cin == 8 || Cin == 16) && W % 32 == 0 && H % 8 == 0 && D % 4 == 0 && W >= 32 && H >= 8 && D >= 8;
-}
-
 template <int NCH, int EPI, int PRE, int UP, int NPW, int IN16 = 0>
-static int launch_xp8w(const Xp8wArgs& ka, hipStream_t s) {
+static int launch_xp8w(const Xp8wArgs& ka, const Conv3dRoute& r, hipStream_t s) {
   constexpr int TZ = 4 / NCH, NZ = 3 * TZ, ZP = 170;
   constexpr int PP = ((NZ * ZP + 15) / 16) * 16;
   constexpr int NIMG = UP == 2 ? 1 : NCH;      // UP = 2: skip chunk + coarse window + composed weights + bias table
@@ -1222,85 +1204,28 @@ static int launch_xp8w(const Xp8wArgs& ka, hipStream_t s) {
   }
   int gx = vx_cu_count();      // one persistent workgroup per CU (its LDS image fills the CU)
   if (gx > ka.ncols) gx = ka.ncols;
-  static const char* kname = vx_kname("conv3d_xp8w_kernel<%d,%d,%d,%d,%d,%d>", NCH, EPI, PRE, UP, NPW, IN16);   // as rocprofv3 prints it
+  static const char* kname = vx_conv3d_kname(r);
   vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3((8 + NPW) * 64), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv3d_k3(xp8w)");
   return VX_OK;
 }
 
-// 1 = not taken (the caller uses the general tile kernel)
-int vx_conv3d_k3_xp8(const vx_conv3d_args& a, int stat_tiles, hipStream_t s) {
+int vx_conv3d_xp8w_launch(const Conv3dRoute& r, const vx_conv3d_args& a, hipStream_t s) {
   Xp8wArgs ka;
   ka.a = a;
-  const int nch = a.Cin / 8, tz = 4 / nch;
-  ka.tiles_x = a.W / 32; ka.tiles_y = a.H / 8; ka.kz = a.D / tz;
-  const int cps = ka.tiles_x * ka.tiles_y;
-  ka.ncols = a.N * cps;
-  ka.mcps = (unsigned)((1ull << 32) / (unsigned)cps) + 1u;
-  ka.rep = (a.in_mean && a.in_repeat > 1 && a.N % a.in_repeat == 0) ? a.in_repeat : 1;
-  ka.mrep = (unsigned)((1ull << 32) / (unsigned)ka.rep) + 1u;
-  ka.mtx = (unsigned)((1ull << 32) / (unsigned)ka.tiles_x) + 1u;
-  ka.stat_epc = stat_tiles / cps;
-  ka.stamps = nullptr;
-  ka.abl = 0;
-#ifdef VX_CONV_STAMPS
-  if (const char* e = getenv("VX_CONV_DBG_PTR")) ka.stamps = (unsigned long long*)strtoull(e, nullptr, 0);
-  if (const char* e = getenv("VX_XP_ABL")) ka.abl = atoi(e);
-#endif
-  if ((int64_t)a.N * cps >= (1ll << 31)) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): too many columns");
-  if (a.stats_partial && (stat_tiles % cps || a.act != VX_ACT_NONE || (a.drop_mode != VX_DROP_NONE && !a.pool_out) || a.head_out))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): statistics go with a plain epilogue");
-  const int pre = a.in_split ? 2 : (a.in_mean ? 1 : 0);
-  if (a.in_split && (a.Cin != 8 || a.in_xblk || a.in_pitch != 8 || a.up_in || !a.stats_partial))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): a pre-split input (vx_prenorm_split) goes with a dense 8-channel tensor and the "
-            "statistics epilogue (contr_1_2)");
-  int epi;
-  if (a.stats_partial) epi = a.pool_out ? 4 : 0;
-  else if (a.head_out) epi = 2;
-  else if (a.drop_mode == VX_DROP_HASH) epi = 1;
-  else epi = 3;
-  if (epi == 2 && a.act == VX_ACT_LRELU && a.drop_mode == VX_DROP_NONE) epi = 5;        // head without dropout (ensemble members)
-  if (epi == 2 && !(a.act == VX_ACT_LRELU && a.drop_mode == VX_DROP_HASH)) return 1;   // other heads: general kernel
-  if (epi == 1 && a.act != VX_ACT_LRELU) return 1;
-  // 2: the up-convolution composed into the weights (vx_pack_conv3d_upfused), 1: evaluated per step by the staging waves
-  const int up = a.up_in ? (a.up_fused ? 2 : 1) : 0;
-  // producer waves: 8 (two per SIMD) for the two-chunk layers, whose staging is the heavy side; 4 for the one-chunk layers:
-  // their consumers hold R = 4 image rows + accumulators (134-161 VGPRs) and at 16 waves per workgroup (128-VGPR cap) EVERY
-  // one-chunk instance spilled 5-30 VGPRs into its item loop (round-3 verdict; tools/check_spills.sh now fails the build on any
-  // such instance).  The round-3 knob vx_config.s16_pw and the 20 instances behind it are gone.
-  if (a.pool_out && nch != 1) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): the pooled output goes with Cin = 8");
-  if (a.out_split) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): out_split is an epilogue of the tile kernel");
-  if (a.up_split && !up) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): up_split without up_in");
-  if (a.out_f16 && (epi != 1 || a.out_xblk || a.out_coff))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): fp16 output goes with the LeakyReLU + dropout epilogue and a dense output tensor");
-  if (a.in_f16) {
-    if (!(nch == 1 && epi == 2 && pre == 0 && !up && !a.in_xblk))
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): fp16 input goes with the dense 8-channel layer that carries the fused head");
-    if (a.products == 1) return launch_xp8w<1, 2, 0, 0, 4, 3>(ka, s);
-    return launch_xp8w<1, 2, 0, 0, 4, 1>(ka, s);
-  }
-  if (a.products == 1) {
-    // opt-in throughput mode (vx_config.storage16 = 2): one fp16 product per fp32 product on the three full-resolution launches
-    if (nch == 1 && epi == 4 && pre == 2 && up == 0) return launch_xp8w<1, 4, 2, 0, 4, 2>(ka, s);
-    if (nch == 2 && epi == 1 && pre == 1 && up == 2) return launch_xp8w<2, 1, 1, 2, 8, 2>(ka, s);
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): products = 1 exists for the MC-dropout forward's contr_1_2, upscale2 + expand_1_1 and "
-            "expand_1_2 + head (nch %d, epilogue %d, prologue %d, up %d)", nch, epi, pre, up);
-  }
-#define XP8W_CASE(N_, E_, P_, U_)                                                         \
-  if (nch == N_ && epi == E_ && pre == P_ && up == U_)                                    \
-    return launch_xp8w<N_, E_, P_, U_, (N_ == 2 ? 8 : 4)>(ka, s)
-  XP8W_CASE(1, 4, 0, 0); XP8W_CASE(1, 4, 1, 0); XP8W_CASE(1, 4, 2, 0); XP8W_CASE(1, 0, 2, 0);
-  XP8W_CASE(1, 0, 0, 0); XP8W_CASE(1, 0, 1, 0); XP8W_CASE(1, 1, 0, 0); XP8W_CASE(1, 2, 0, 0); XP8W_CASE(1, 3, 0, 0); XP8W_CASE(1, 3, 1, 0);
-  XP8W_CASE(1, 5, 0, 0);
-  XP8W_CASE(2, 1, 0, 0); XP8W_CASE(2, 1, 1, 0); XP8W_CASE(2, 3, 0, 0); XP8W_CASE(2, 3, 1, 0);
-  XP8W_CASE(2, 1, 0, 1); XP8W_CASE(2, 1, 1, 1); XP8W_CASE(2, 3, 0, 1); XP8W_CASE(2, 3, 1, 1);
-  XP8W_CASE(2, 1, 0, 2); XP8W_CASE(2, 1, 1, 2); XP8W_CASE(2, 3, 0, 2); XP8W_CASE(2, 3, 1, 2);
+  ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.kz = r.kz;
+  ka.ncols = r.nitems;
+  ka.mcps = r.mcps; ka.mtx = r.mx;
+  ka.rep = r.rep; ka.mrep = r.mrep;
+  ka.stat_epc = r.stat_epc;
+  vx_conv_diag(VX_DIAG_XP_ABL, &ka.stamps, &ka.abl);
+  switch (conv3d_key_of(r.p, r.np)) {
+#define XP8W_CASE(...) case conv3d_key(__VA_ARGS__): return launch_xp8w<__VA_ARGS__>(ka, r, s);
+    XP8W_INSTANCES(XP8W_CASE)
 #undef XP8W_CASE
-  if (up) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): no fused up-convolution for this epilogue (act=%d, drop_mode=%d, statistics=%d)",
-                  a.act, a.drop_mode, a.stats_partial ? 1 : 0);
-  if (a.pool_out) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): no pooled output for this epilogue");
-  return 1;
+  }
+  VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): no such instance");
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -25,10 +25,11 @@
 // statistics slots.  TZ = 2 output planes per item; three groups of 2 plane slots (a step writes one group while the item
 // in flight reads the other two -- conv3d_xp8w.hip's scheme).
 #include "s16_common.h"
+#include "conv3d_internal.h"
 
 struct Zc16Args {
   vx_conv3d_args a;
-  const float* w;             // this kernel's block of the packed weights (vx_conv3d_zc16_packed_floats)
+  const float* w;             // this kernel's block of the packed weights (conv3d_zc16_packed_floats)
   int tiles_x, tiles_y, kz;   // columns per sample = tiles_x * tiles_y; kz = items per column
   int ncols;                  // columns in the launch
   unsigned mcps, mtx;         // multiply-high magics: / (tiles_x * tiles_y), / tiles_x
@@ -37,23 +38,10 @@ struct Zc16Args {
   int abl;                    // diagnostic build only: phase ablation bits (1 no multiply, 2 no epilogue, 4 no commit, 8 no loads, 16 no LDS writes, 32 no split)
 };
 
-#ifdef VX_CONV_STAMPS
-#define ZC_STAMP(i)                                                                      \
-  do {                                                                                   \
-    unsigned long long t_;                                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                   \
-    st_sum[i] += t_ - st_last;                                                           \
-    st_last = t_;                                                                        \
-  } while (0)
-#define ZC_WAIT_LOADS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define ZC_ABL ka.abl
-#else
-#define ZC_ABL 0
-#define ZC_STAMP(i) do {} while (0)
-#define ZC_WAIT_LOADS() do {} while (0)
-#endif
+// phase stamps / ablation word: diagnostic build only (conv3d_internal.h)
+#define ZC_STAMP VX_STAMP
+#define ZC_WAIT_LOADS VX_STAMP_WAIT_LOADS
+#define ZC_ABL VX_DIAG(ka.abl)
 
 // CIN: input channels (8 or 16).  EPI: 0 bias + statistics + store, 1 LeakyReLU + hash dropout (+ out_split), 3 run-time
 // activation without dropout, 4 = 0 PLUS the (y, x) half of the block's 2 x 2 x 2 max-pool (maximum over the KEPT raw values +
@@ -1034,19 +1022,6 @@ __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-bool vx_conv3d_zc16_packs(int Cin, int Cout) { return Cout == 16 && (Cin == 8 || Cin == 16); }
-
-bool vx_conv3d_zc16_applies(int D, int H, int W, int Cin, int Cout) {
-  if (vx_cfg().conv_fp32 != 0 || vx_cfg().s16_no_zc16) return false;
-  // D >= 4: a column has at least two items (the statistics hand-off between the wave halves needs the spacing)
-  return vx_conv3d_zc16_packs(Cin, Cout) && W % 32 == 0 && H % 8 == 0 && D % 2 == 0 && W >= 32 && H >= 8 && D >= 4;
-}
-
-int64_t vx_conv3d_zc16_packed_floats(int Cin, int Cout) {
-  if (!vx_conv3d_zc16_packs(Cin, Cout)) return 0;
-  return (int64_t)(Cin == 16 ? 14 : 9) * 2 * 64 * 8 / 2;
-}
-
 // torch (16, Cin, 3,3,3) fp32 -> [step][hi | lo][lane 64][8 halves] in the K schedule of the kernel's header
 __global__ void pack_conv3d_zc16_kernel(const float* __restrict__ w, _Float16* __restrict__ out, int Cin, int total) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -1071,7 +1046,7 @@ __global__ void pack_conv3d_zc16_kernel(const float* __restrict__ w, _Float16* _
 }
 
 int vx_pack_conv3d_zc16(const float* w_torch, float* w_packed, int Cin, int Cout, hipStream_t s) {
-  const int total = (int)(vx_conv3d_zc16_packed_floats(Cin, Cout) * 2);
+  const int total = (int)(conv3d_zc16_packed_floats(Cin, Cout) * 2);
   if (total <= 0) return VX_OK;
   hipLaunchKernelGGL(pack_conv3d_zc16_kernel, dim3((total + 255) / 256), dim3(256), 0, s, w_torch, reinterpret_cast<_Float16*>(w_packed), Cin,
                      total);
@@ -1101,7 +1076,7 @@ extern "C" int vx_pack_convT_zc16(const float* w_torch, float* packed, vx_stream
 }
 
 template <int CIN, int EPI, int PRE, int ACC = 0, int UP = 0>
-static int launch_zc16(const Zc16Args& ka, hipStream_t s) {
+static int launch_zc16(const Zc16Args& ka, const Conv3dRoute& r, hipStream_t s) {
   constexpr int PP = ((6 * 340 + 15) / 16) * 16;
   constexpr size_t lds = (size_t)(CIN / 8) * 2 * PP * 16 + (size_t)(CIN == 16 ? 14 : 9) * 2048 + 8 * 16 * 2 * 4 + 64;
   static_assert(lds <= 160 * 1024, "LDS budget");
@@ -1114,94 +1089,26 @@ static int launch_zc16(const Zc16Args& ka, hipStream_t s) {
   }
   int gx = vx_cu_count();      // one persistent workgroup per CU
   if (gx > ka.ncols) gx = ka.ncols;
-  static const char* kname = vx_kname("conv3d_zc16_kernel<%d,%d,%d,%d,%d>", CIN, EPI, PRE, ACC, UP);   // as rocprofv3 prints it
+  static const char* kname = vx_conv3d_kname(r);
   vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(768), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv3d_k3(zc16)");
   return VX_OK;
 }
 
-// 1 = not taken (the caller uses the general tile kernel)
-int vx_conv3d_k3_zc16(const vx_conv3d_args& a, const float* w_block, int stat_tiles, hipStream_t s) {
-  if (a.in_xblk || a.head_out || a.in_split || a.in_f16 || a.out_f16 || (a.in_repeat > 1)) return 1;
-  if ((a.in_planar || a.out_planar) && (a.drop_mode == VX_DROP_MASK || !a.out || a.in_pitch != a.Cin || a.Cout != 16))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the planar pre-split hand-over needs hash or no dropout and dense 16-channel tensors");
-  if (a.up_in && (a.Cin != 16 || a.in_mean || a.stats_partial || a.up_pitch < 32 || a.up_pitch % 4 || a.up_fused))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the fused up-convolution (32 coarse channels -> the conv's 16 input channels) goes with an "
-            "activation epilogue, no prologue, up_pitch >= 32 (got %d), up_w packed by vx_pack_convT_zc16", a.up_pitch);
-  if (a.drop_mode == VX_DROP_MASK || a.in_drop_mode == VX_DROP_MASK) return 1;
-  if (!a.out) return 1;
+int vx_conv3d_zc16_launch(const Conv3dRoute& r, const vx_conv3d_args& a, const float* w_block, hipStream_t s) {
   Zc16Args ka;
   ka.a = a;
   ka.w = w_block;
-  ka.tiles_x = a.W / 32; ka.tiles_y = a.H / 8; ka.kz = a.D / 2;
-  const int cps = ka.tiles_x * ka.tiles_y;
-  ka.ncols = a.N * cps;
-  ka.mcps = (unsigned)((1ull << 32) / (unsigned)cps) + 1u;
-  ka.mtx = (unsigned)((1ull << 32) / (unsigned)ka.tiles_x) + 1u;
-  ka.stat_epc = stat_tiles / cps;
-  ka.stamps = nullptr;
-  ka.abl = 0;
-#ifdef VX_CONV_STAMPS
-  if (const char* e = getenv("VX_CONV_DBG_PTR")) ka.stamps = (unsigned long long*)strtoull(e, nullptr, 0);
-  if (const char* e = getenv("VX_XP_ABL")) ka.abl = atoi(e);
-#endif
-  if ((int64_t)a.N * cps >= (1ll << 31)) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): too many columns");
-  if (a.in_pitch != a.Cin) return 1;
-  if (a.stats_partial && (stat_tiles % cps || a.act != VX_ACT_NONE || (a.drop_mode != VX_DROP_NONE && !a.pool_out)))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): statistics go with a plain epilogue");
-  if (a.pool_out && (!a.stats_partial || a.Cin != 16)) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the pooled output goes with statistics, 16 -> 16");
-  int pre = 0;
-  if (a.in_pool_flags) pre = 3;
-  else if (a.in_mean) pre = 1;
-  if ((pre == 1 && a.Cin != 16) || (pre == 3 && a.Cin != 8)) return 1;
-  if (a.in_planar) {
-    if (a.Cin != 16 || pre != 0 || a.up_in || a.acc_in || a.stats_partial || !vx_aligned16(a.in) ||
-        (int64_t)a.D * a.H * a.W * 64 >= (1ll << 31))
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): a planar pre-split input (in_planar) goes with 16 -> 16, an activation epilogue, no "
-              "prologue / up-convolution / partial sums, a 16-byte aligned tensor, one sample below 2 GiB");
-    pre = 4;
-  }
-  if (a.out_planar && (a.stats_partial || a.out_pitch != 16 || a.out_coff != 0 || a.out_xblk || a.out_split || a.out == a.acc_in ||
-                       (int64_t)a.D * a.H * a.W * 64 >= (1ll << 31)))
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): a planar pre-split output (out_planar) goes with an activation epilogue into a dense "
-            "16-channel tensor that is not the partial sums' (another layout), one sample below 2 GiB");
-  int epi;
-  if (a.stats_partial) epi = a.pool_out ? 4 : 0;
-  else if (a.drop_mode == VX_DROP_HASH) { if (a.act != VX_ACT_LRELU) return 1; epi = 1; }
-  else epi = 3;
-  if (a.out_split && a.stats_partial) VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): out_split goes with the activation epilogues");
-  if (a.out_planar) {
-    // the instances that exist: the decoder's up-half launch (partial sums + fused up-convolution) and the plain 16 -> 16 layer
-    if (a.Cin != 16 || pre != 0 || (epi != 1 && epi != 3) || ((a.acc_in != nullptr) != (a.up_in != nullptr)))
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): out_planar goes with 16 -> 16, an activation epilogue, no prologue, and either partial "
-              "sums + the fused up-convolution together or neither");
-    epi = epi == 1 ? 5 : 6;
-  }
-  if (a.acc_in) {
-    if (a.Cin != 16 || pre != 0 || a.stats_partial || a.acc_pitch < 16 || a.acc_pitch % 4 || !vx_aligned16(a.acc_in) ||
-        (int64_t)a.D * a.H * a.W * a.acc_pitch * 4 >= (1ll << 31))
-      VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): partial sums (acc_in) go with 16 -> 16, no prologue, an activation epilogue, a "
-              "16-byte aligned tensor of pitch >= 16 (pitch %d), one sample below 2 GiB", a.acc_pitch);
-    if (a.up_in) {
-      if (epi == 5) return launch_zc16<16, 5, 0, 1, 1>(ka, s);
-      if (epi == 6) return launch_zc16<16, 6, 0, 1, 1>(ka, s);
-      if (epi == 1) return launch_zc16<16, 1, 0, 1, 1>(ka, s);
-      return launch_zc16<16, 3, 0, 1, 1>(ka, s);
-    }
-    if (epi == 1) return launch_zc16<16, 1, 0, 1>(ka, s);
-    return launch_zc16<16, 3, 0, 1>(ka, s);
-  }
-  if (a.up_in) {
-    if (epi == 1) return launch_zc16<16, 1, 0, 0, 1>(ka, s);
-    if (epi == 3) return launch_zc16<16, 3, 0, 0, 1>(ka, s);
-    VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): no fused up-convolution for this epilogue");
-  }
-#define ZC16_CASE(C_, E_, P_) if (a.Cin == C_ && epi == E_ && pre == P_) return launch_zc16<C_, E_, P_>(ka, s)
-  ZC16_CASE(16, 0, 0); ZC16_CASE(16, 0, 1); ZC16_CASE(16, 4, 0); ZC16_CASE(16, 4, 1);
-  ZC16_CASE(16, 1, 0); ZC16_CASE(16, 1, 1); ZC16_CASE(16, 3, 0); ZC16_CASE(16, 3, 1);
-  ZC16_CASE(16, 1, 4); ZC16_CASE(16, 3, 4); ZC16_CASE(16, 5, 0); ZC16_CASE(16, 6, 0);
-  ZC16_CASE(8, 0, 0); ZC16_CASE(8, 0, 3); ZC16_CASE(8, 3, 0); ZC16_CASE(8, 1, 0);
+  ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.kz = r.kz;
+  ka.ncols = r.nitems;
+  ka.mcps = r.mcps; ka.mtx = r.mx;
+  ka.stat_epc = r.stat_epc;
+  vx_conv_diag(VX_DIAG_XP_ABL, &ka.stamps, &ka.abl);
+  switch (conv3d_key_of(r.p, r.np)) {
+#define ZC16_CASE(...) case conv3d_key(__VA_ARGS__): return launch_zc16<__VA_ARGS__>(ka, r, s);
+    ZC16_INSTANCES(ZC16_CASE)
 #undef ZC16_CASE
-  return 1;
+  }
+  VX_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): no such instance");
 }

@@ -11,10 +11,7 @@
 // torch.cat never happens (K7): CAT_l is the x-blocked buffer [N][D][H][W/xb][2][xb][C_l] (values_amd.h) whose two
 // halves are written as dense blocks by their producers and read by the decoder conv through in_xblk.
 // First layer in MC-dropout mode: computed once per volume (the T samples share input and statistics).
-#include "common.h"
-#include <stdlib.h>
-
-extern "C" int vx_conv3d_k3_c1_tiles(int D, int H, int W);
+#include "conv3d_internal.h"
 
 namespace {
 struct Level { int D, H, W, C; int64_t nvox; };
