@@ -822,6 +822,56 @@ int64_t vx_zscore_pad_batched_workspace_bytes(const vx_prep_pad_item* items /* h
 int vx_zscore_pad_batched(const vx_prep_pad_item* items /* host */, int n_items, const double* stats /* device */,
                           void* workspace, int64_t ws_bytes, vx_stream_t stream);
 
+/* K42: the generator of the toy 3D data sets (datasets/toy_data_generation/dataset_generation.py:144-254, helpers in
+ * stl_to_nifty.py:93-155) on the device, float64 throughout (toydata.hip).  Every entry takes caller-owned memory and an
+ * explicit stream; nothing is uploaded (ranks, thresholds and boxes travel as kernel arguments), so the calls are
+ * capturable.  An image is a C-order [D0][D1][D2] array, axis 2 contiguous.
+ * vx_toy_embed: image = 0 outside the object's box, gray * (double)obj inside it; obj is float32 [obj_dims] placed at
+ *   the signed offset[3] and clipped to the image on both sides (both embed functions of stl_to_nifty.py:93-142).
+ *   flip0 / flip1 reverse axis 0 / axis 1 of the finished image (np.flipud / np.fliplr).
+ * vx_gauss_blur_axis_f64: ONE pass of scipy.ndimage.gaussian_filter's separable filter along `axis` of src into dst,
+ *   in scipy's order of operations (its symmetric correlate1d): x[l] * w[r] first, then for i = r .. 1 the pair
+ *   (x[l - i] + x[l + i]) * w[r - i] added to the sum, every operation rounded once to float64, no FMA, no
+ *   reassociation; mode `reflect` for any extent >= 1 against any radius (index i mod 2n, the second half mirrored).
+ *   weights: DEVICE array of 2 radius + 1 doubles, 0 <= radius <= 128.  Passes over axes 0, 1, 2 in turn with
+ *   scipy's weights give gaussian_filter's result bit for bit.  A pass never runs in place: src and dst may not overlap.
+ *   Lanes run along axis 2 in all three passes; 16-byte loads and stores where the contiguous extent is even and both
+ *   pointers are 16-byte aligned, 8-byte ones elsewhere.
+ * vx_count_ge_f64: *count (device, int64) = #{i: x[i] >= thr}; integer atomics, exact.  n = 0 gives 0.
+ * vx_order_stats_f64: for each 0-based rank ks[i] (HOST array, 1 <= n_k <= 32, 0 <= k < n), out[i] (device, 2 doubles)
+ *   = {the k-th smallest, the (k + 1)-th smallest} value of x[0, n); the second repeats the first when k + 1 == n.
+ *   MSB-first radix select in eight 8-bit digits on the order-preserving 64-bit keys (negative: all bits flipped,
+ *   non-negative: sign bit set; -0.0 sorts directly below +0.0 and compares equal to it): integer arithmetic only, exact
+ *   and independent of the grid.  Up to 16 distinct ranks share a sweep of eight passes, each pass one read of the data:
+ *   vx_order_stats_f64_reads says how many reads a call makes (8 per 16 distinct ranks among {k, k + 1}; 0 for what the
+ *   call refuses).  status (device) = VX_SELECT_NAN when any element is NaN (the outputs are then unspecified), else
+ *   VX_SELECT_OK; +-inf are ordinary values.  workspace: vx_order_stats_f64_workspace_bytes(n_k) bytes, 16-byte aligned.
+ *   vx_select_segments narrows float64 to float32 and cannot serve where the float64 order statistics are needed.
+ * vx_toy_segment: out[r][i] (device int32 [R][n]) = x[i] >= thresholds[r]; thresholds is a HOST array of R doubles,
+ *   1 <= R <= 64; one read of the image for all R (create_segmentations' np.where(image >= threshold, 1, 0)).
+ * vx_toy_noise: in place, where x[i] < 0.1: x[i] = (u_p <= noise_prob) ? 0 : u_n with u_p = (h1 >> 8) * 2^-24 and
+ *   u_n = (h2 >> 8) * 2^-24 from the two hash words of the library's generator for (seed, stream stream_index,
+ *   element i); elements >= 0.1 and NaN are left alone.  An element's value depends on (seed, stream_index, i) only.
+ *   n < 2^32 (the element index is one hash word), 0 <= noise_prob <= 1.  add_noise (stl_to_nifty.py:145-150) with
+ *   this library's generator in place of numpy's stream.
+ * All refuse before any device call: a null pointer (VX_E_NULL); a dimension < 1, more than 2^40 voxels, an axis
+ *   outside 0..2, a radius outside 0..128, overlapping src / dst, n_k, R, n or a rank out of range, a noise_prob outside
+ *   [0, 1] (VX_E_SHAPE); a pointer off its element alignment or a workspace off 16 bytes (VX_E_ALIGN); a short workspace
+ *   (VX_E_WORKSPACE). */
+int vx_toy_embed(const float* obj /* device */, const int32_t* obj_dims /* host [3] */, const int32_t* offset /* host [3] */,
+                 double gray, int flip0, int flip1, double* image /* device */, const int32_t* dims /* host [3] */,
+                 vx_stream_t stream);
+int vx_gauss_blur_axis_f64(const double* src, double* dst, const int32_t* dims /* host [3] */, int axis,
+                           const double* weights /* device [2 radius + 1] */, int radius, vx_stream_t stream);
+int vx_count_ge_f64(const double* x, int64_t n, double thr, int64_t* count /* device */, vx_stream_t stream);
+int64_t vx_order_stats_f64_workspace_bytes(int n_k);
+int vx_order_stats_f64_reads(int64_t n, const int64_t* ks /* host */, int n_k);
+int vx_order_stats_f64(const double* x, int64_t n, const int64_t* ks /* host */, int n_k, double* out /* device [n_k][2] */,
+                       int32_t* status /* device */, void* workspace, int64_t ws_bytes, vx_stream_t stream);
+int vx_toy_segment(const double* x, int64_t n, const double* thresholds /* host [R] */, int R, int32_t* out /* device [R][n] */,
+                   vx_stream_t stream);
+int vx_toy_noise(double* x, int64_t n, uint32_t seed, uint32_t stream_index, double noise_prob, vx_stream_t stream);
+
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),
  *   counts[i][j][c] = #{v: mask_i(v) == c and mask_j(v) == c}.  M <= 32, C <= 8.

@@ -341,6 +341,14 @@ SIGNATURES = {
     "vx_volume_stats_batched": (_i, [C.POINTER(PrepItem), _i, _p, _p, _i64, _p]),
     "vx_zscore_pad_batched_workspace_bytes": (_i64, [C.POINTER(PrepPadItem), _i]),
     "vx_zscore_pad_batched": (_i, [C.POINTER(PrepPadItem), _i, _p, _p, _i64, _p]),
+    "vx_toy_embed": (_i, [_p, C.POINTER(_i32), C.POINTER(_i32), C.c_double, _i, _i, _p, C.POINTER(_i32), _p]),
+    "vx_gauss_blur_axis_f64": (_i, [_p, _p, C.POINTER(_i32), _i, _p, _i, _p]),
+    "vx_count_ge_f64": (_i, [_p, _i64, C.c_double, _p, _p]),
+    "vx_order_stats_f64_workspace_bytes": (_i64, [_i]),
+    "vx_order_stats_f64_reads": (_i, [_i64, C.POINTER(_i64), _i]),
+    "vx_order_stats_f64": (_i, [_p, _i64, C.POINTER(_i64), _i, _p, _p, _p, _i64, _p]),
+    "vx_toy_segment": (_i, [_p, _i64, C.POINTER(C.c_double), _i, _p, _p]),
+    "vx_toy_noise": (_i, [_p, _i64, _u32, _u32, C.c_double, _p]),
     "vx_mask_agreement": (_i, [_p, _i, _i, _i64, _p, _p]),
     "vx_mask_agreement_batched": (_i, [_p, _i, _i, _i, _i64, _i, _p, _p]),
     "vx_soft_metric_workspace_bytes": (_i64, [_i, _i]),

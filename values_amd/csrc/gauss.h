@@ -12,6 +12,12 @@ __device__ __forceinline__ float vx_gauss(uint32_t seed, uint32_t a, uint32_t b)
   return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
 }
 
+// The two hash words of vx_gauss by themselves, for a caller that wants uniforms (toydata.hip: (h >> 8) * 2^-24)
+__device__ __forceinline__ void vx_gauss_words(uint32_t seed, uint32_t a, uint32_t b, uint32_t& h1, uint32_t& h2) {
+  h1 = vx_mix32(a * 0x9E3779B1u ^ vx_mix32(seed ^ (b * 0x85EBCA6Bu + 0x165667B1u)));
+  h2 = vx_mix32(h1 ^ 0x27D4EB2Fu ^ (a * 0xC2B2AE35u));
+}
+
 // The scale of a generated noise view: ONE uniform per stream b, the u2 word of element 0 of the streams of
 // seed ^ VX_NOISE_SCALE_XOR -- no element stream of `seed` shares a key with them (the idiom of the SSN eps_w streams,
 // seed ^ 0x5bd1e995, with a constant of its own).  var = lo + (hi - lo) * u2, u2 in [0, 1), two float32 roundings.
