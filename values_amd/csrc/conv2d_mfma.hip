@@ -385,6 +385,8 @@ static int launch_c2(const Conv2dKArgs& ka, hipStream_t s) {
   if (per_cu > 4) per_cu = 4;
   int gx = (256 * per_cu + ygroups - 1) / ygroups;
   if (gx > total_tiles) gx = total_tiles;
+  static const char* kname = vx_kname("conv2d_mfma_kernel<%d,%d,%d,%d,%d>", KS, S, NT, NSUB, TY);
+  vx_note_kernel(kname);
   hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ygroups), dim3(512), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv2d");
   return VX_OK;
