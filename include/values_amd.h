@@ -872,6 +872,63 @@ int vx_toy_segment(const double* x, int64_t n, const double* thresholds /* host 
                    vx_stream_t stream);
 int vx_toy_noise(double* x, int64_t n, uint32_t seed, uint32_t stream_index, double noise_prob, vx_stream_t stream);
 
+/* K43: preprocessing of the GTA / Cityscapes 2D data sets (datasets/gta_cityscapes/preprocess_gta_cityscapes.py:128-174)
+ * for a whole batch of decoded images and label files, where vx_png_unfilter left them (preprocess2d.hip).
+ * vx_crop_resize_batched: per item, the box [y0, y0 + crop_h) x [x0, x0 + crop_w) of the source [H][W][bpp] (uint8, C
+ *   order, any alignment; bpp 3 = RGB, 4 = RGBA with alpha dropped, 1 = grey, or palette indices when `palette`, device
+ *   256 x 3 RGB bytes, is given: the pixel is then palette[index], gathered in the kernel -- no expanded image exists)
+ *   is shrunk by the even integer `factor` k to out_h x out_w = vx_p2d_out_size(crop_h, k) x vx_p2d_out_size(crop_w, k):
+ *   crop / k rounded half to even on the exact quotient, cv2.resize's saturate_cast<int>(size * fx).  Modes:
+ *   VX_P2D_IMAGE        cv2.resize(INTER_LINEAR) on uint8 at fx = fy = 1 / k: output (y, x) has the taps k y + k/2 - 1 and
+ *                       k y + k/2 on each axis (the second clamped to the crop's last row / column, as OpenCV clamps),
+ *                       each with weight 1/2, and OpenCV's 11-bit fixed point gives exactly (p00 + p01 + p10 + p11 + 2) >> 2
+ *                       per channel.  Only those two rows of every k are read.  out_rgb [out_h][out_w][3].
+ *   VX_P2D_LABEL_IDS    (bpp 1, no palette) INTER_NEAREST: source pixel (k y, k x); out_ids uint8 [out_h][out_w] =
+ *                       id2trainid[pixel], out_rgb = trainid2color[that train id].
+ *   VX_P2D_LABEL_COLOR  (bpp 3 / 4, or 1 with a palette) INTER_NEAREST in RGB: out_rgb is the pixel, out_ids INT64
+ *                       [out_h][out_w] the id of the color2trainid entry whose key is the pixel's 0x00RRGGBB, else
+ *                       default_id (vx_rgb_to_trainid's lookup: of two entries with one key the later counts).
+ *   status[i] (device, zeroed by the call) = the number of pixels of item i whose id is default_id (LABEL_COLOR; integer
+ *   atomics, exact), 0 for the other modes: the reference's `assert 128 not in mask` is the host's to raise.
+ *   ONE launch serves the batch, sizes and modes mixed: every item's OUTPUT is cut into work blocks of 2048 pixels counted
+ *   from its first pixel and one grid takes the blocks of all items in turn.  A pixel's value depends on its item alone:
+ *   AN ITEM'S OUTPUT BYTES ARE EQUAL WHETHER IT IS SUBMITTED ALONE OR IN ANY BATCH, AT ANY POSITION.  Lanes run along
+ *   output x, four pixels per lane and step; the taps are fetched with aligned dword loads that cover them whatever the
+ *   source's alignment (byte loads only within 12 bytes of the source's two ends); a lane's 12 RGB bytes, 4 ids or 4
+ *   int64 ids leave in dword / 16-byte stores where the output address allows it.  No read outside
+ *   [src, src + H * W * bpp), no write outside the outputs.  Plain C++ stores.
+ *   Refused before any device call: a null item table, status, workspace, src or an output or table the mode needs
+ *   (VX_E_NULL); n_items outside [0, VX_SELECT_MAX_ITEMS], H or W < 1, a crop box outside the image or empty, an odd or
+ *   non-positive factor, an output dimension of 0, H * W * bpp >= 2^31, n_color outside 0..256 (VX_E_SHAPE); a bpp other
+ *   than 1 / 3 / 4, a palette with bpp != 1, bpp 1 without a palette in IMAGE or LABEL_COLOR mode, LABEL_IDS with bpp != 1
+ *   or with a palette, an unknown mode, a default_id outside 0..255 (VX_E_DTYPE); an int64 out_ids off 8 bytes or a
+ *   workspace off 16 (VX_E_ALIGN); a short workspace (VX_E_WORKSPACE).  workspace:
+ *   vx_crop_resize_batched_workspace_bytes(items, n_items, tables) bytes, 0 for what the call refuses and for n_items = 0
+ *   (a no-op).  The item table goes up through a pinned staging buffer: no wait on the stream, not capturable. */
+enum { VX_P2D_IMAGE = 0, VX_P2D_LABEL_IDS = 1, VX_P2D_LABEL_COLOR = 2 };
+typedef struct vx_p2d_item {
+  const uint8_t* src;     /* device [H][W][bpp] */
+  const uint8_t* palette; /* device [256][3] RGB, or null */
+  int32_t H, W, bpp;
+  int32_t y0, x0, crop_h, crop_w;
+  int32_t factor;
+  int32_t mode;           /* VX_P2D_* */
+  int32_t reserved;
+  uint8_t* out_rgb;       /* device [out_h][out_w][3] */
+  void* out_ids;          /* device [out_h][out_w]: uint8 (LABEL_IDS), int64 (LABEL_COLOR); IMAGE: not looked at */
+} vx_p2d_item;
+typedef struct vx_p2d_tables {
+  const uint8_t* id2trainid;     /* device [256] */
+  const uint8_t* trainid2color;  /* device [256][3] */
+  const uint32_t* color2trainid; /* device [n_color] pairs (0x00RRGGBB key, id) */
+  int32_t n_color;
+  int32_t default_id;
+} vx_p2d_tables;
+int vx_p2d_out_size(int size, int factor); /* host only; 0 for size < 1 or an odd or non-positive factor */
+int64_t vx_crop_resize_batched_workspace_bytes(const vx_p2d_item* items /* host */, int n_items, const vx_p2d_tables* tables /* host */);
+int vx_crop_resize_batched(const vx_p2d_item* items /* host */, int n_items, const vx_p2d_tables* tables /* host */,
+                           int32_t* status /* device [n_items] */, void* workspace, int64_t ws_bytes, vx_stream_t stream);
+
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),
  *   counts[i][j][c] = #{v: mask_i(v) == c and mask_j(v) == c}.  M <= 32, C <= 8.
@@ -1088,17 +1145,30 @@ int vx_crc32(const void* x, int64_t n, uint32_t* out /* device */, vx_stream_t s
  *   uploads its descriptor table and synchronises the stream before it launches: not capturable into a hipGraph.
  * vx_png_bound: worst-case file size of an H x W item: n = H * (3 W + 1) scanline bytes as stored blocks
  *   (n + 5 per 32 KiB chunk) plus 63 bytes of PNG and zlib framing; host only, -1 for H or W < 1.
- * vx_png_workspace_bytes: 0 for a null table, n < 1 or an item with H or W < 1. */
+ * vx_png_workspace_bytes: 0 for a null table, n < 1 or an item with H or W < 1.
+ * vx_png_encode_rgb: the same files from pixels that are RGB bytes already (rgb: device [H][W][3], any alignment)
+ *   instead of labels through a table -- the vis/ images of the 2D preprocessing (K43).  Layout, filter-0 scanlines, zlib
+ *   framing, limits, refusals and the DEFLATE chunk launch are vx_png_encode's (one host routine serves both); the only
+ *   difference is where a scanline byte comes from.  vx_png_bound serves both; workspace:
+ *   vx_png_encode_rgb_workspace_bytes(items, n). */
 typedef struct vx_png_item {
   const uint8_t* labels;
   const uint8_t* ignore;
   int32_t H, W;
 } vx_png_item;
+typedef struct vx_png_rgb_item {
+  const uint8_t* rgb;
+  int32_t H, W;
+} vx_png_rgb_item;
 int64_t vx_png_bound(int H, int W);
 size_t vx_png_workspace_bytes(const vx_png_item* items /* host array */, int n);
 int vx_png_encode(const vx_png_item* items /* host array */, int n, const uint8_t* lut, int unlabeled, uint8_t* dst,
                   int64_t dst_bytes, int64_t* out_offsets /* device */, int64_t* out_sizes /* device */, void* workspace,
                   size_t ws_bytes, vx_stream_t stream);
+size_t vx_png_encode_rgb_workspace_bytes(const vx_png_rgb_item* items /* host array */, int n);
+int vx_png_encode_rgb(const vx_png_rgb_item* items /* host array */, int n, uint8_t* dst, int64_t dst_bytes,
+                      int64_t* out_offsets /* device */, int64_t* out_sizes /* device */, void* workspace, size_t ws_bytes,
+                      vx_stream_t stream);
 
 /* Reading the results tree back (ExperimentDataloader, aggregate_uncertainties, find_threshold: every consumer of
  * nifti.load; Python: values_amd.gz.gunzip, values_amd.nifti.load_device).

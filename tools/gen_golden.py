@@ -694,6 +694,16 @@ def gen_color2trainid():
     print("cityscapes_color2trainid.json", len(res["color2trainId"]), "colours")
 
 
+def gen_id_tables():
+    """cityscapes_labels.id2trainId and trainId2color (preprocess_gta_cityscapes.py:147-154) as lists of [key, value]"""
+    import uncertainty_modeling.data.cityscapes_labels as cs
+    res = {"id2trainId": [[int(k), int(v)] for k, v in cs.id2trainId.items()],
+           "trainId2color": [[int(k), [int(c) for c in v]] for k, v in cs.trainId2color.items()]}
+    with open(os.path.join(OUT, "cityscapes_id_tables.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print("cityscapes_id_tables.json", len(res["id2trainId"]), "ids", len(res["trainId2color"]), "train ids")
+
+
 def gen_images2d():
     """three small PNG files from a foreign encoder (PIL, adaptive filters) with their decoded arrays: RGB, grey, RGBA"""
     from PIL import Image
@@ -746,3 +756,5 @@ if __name__ == "__main__":
         gen_color2trainid()
     if "images2d" in which:
         gen_images2d()
+    if "id_tables" in which:       # (not in the default list: it rewrites one small file of its own)
+        gen_id_tables()

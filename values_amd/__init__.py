@@ -8,4 +8,5 @@ from .predict import (GraphedPredictor, HostPipeline, crop_indices, noise_view_d
 from .io import load_models_from_checkpoint, instantiate  # noqa: F401
 from .sliding import predict_image_sliding  # noqa: F401
 from .preprocess import load_cases_device, preprocess_dataset  # noqa: F401
+from .preprocess2d import preprocess_dataset_2d, preprocess_images_device  # noqa: F401
 from .toydata import generate_toy_dataset  # noqa: F401

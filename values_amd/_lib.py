@@ -152,6 +152,11 @@ class PngItem(C.Structure):
     _fields_ = [("labels", _p), ("ignore", _p), ("H", _i32), ("W", _i32)]
 
 
+class PngRgbItem(C.Structure):
+    """vx_png_rgb_item: one (H, W, 3) uint8 RGB image to encode as an RGB PNG (device pixels)."""
+    _fields_ = [("rgb", _p), ("H", _i32), ("W", _i32)]
+
+
 class InflateItem(C.Structure):
     """vx_inflate_item: one compressed stream (device src, src_n bytes) and its output window dst[dst_off, +dst_cap)."""
     _fields_ = [("src", _p), ("src_n", _i64), ("dst_off", _i64), ("dst_cap", _i64), ("format", _i32), ("pad", _i32)]
@@ -256,6 +261,22 @@ class PrepPadItem(C.Structure):
                 ("kind", _i32), ("out_dtype", _i32), ("mode", _i32), ("stats_row", _i32), ("reserved", _i32)]
 
 
+VX_P2D_IMAGE, VX_P2D_LABEL_IDS, VX_P2D_LABEL_COLOR = 0, 1, 2
+
+
+class P2dItem(C.Structure):
+    """vx_p2d_item: one decoded image or label file of vx_crop_resize_batched: the source [H][W][bpp] (palette: device
+    256 x 3 bytes for an indexed file, else null), the crop box, the even factor, the mode and its outputs."""
+    _fields_ = [("src", _p), ("palette", _p), ("H", _i32), ("W", _i32), ("bpp", _i32), ("y0", _i32), ("x0", _i32),
+                ("crop_h", _i32), ("crop_w", _i32), ("factor", _i32), ("mode", _i32), ("reserved", _i32), ("out_rgb", _p),
+                ("out_ids", _p)]
+
+
+class P2dTables(C.Structure):
+    """vx_p2d_tables: the device tables of vx_crop_resize_batched (id -> train id, train id -> colour, colour -> train id)."""
+    _fields_ = [("id2trainid", _p), ("trainid2color", _p), ("color2trainid", _p), ("n_color", _i32), ("default_id", _i32)]
+
+
 VX_MSR_MAX_ITEMS, VX_MSR_MAX_PLANES = 65536, 1 << 22
 
 
@@ -341,6 +362,9 @@ SIGNATURES = {
     "vx_volume_stats_batched": (_i, [C.POINTER(PrepItem), _i, _p, _p, _i64, _p]),
     "vx_zscore_pad_batched_workspace_bytes": (_i64, [C.POINTER(PrepPadItem), _i]),
     "vx_zscore_pad_batched": (_i, [C.POINTER(PrepPadItem), _i, _p, _p, _i64, _p]),
+    "vx_p2d_out_size": (_i, [_i, _i]),
+    "vx_crop_resize_batched_workspace_bytes": (_i64, [C.POINTER(P2dItem), _i, C.POINTER(P2dTables)]),
+    "vx_crop_resize_batched": (_i, [C.POINTER(P2dItem), _i, C.POINTER(P2dTables), _p, _p, _i64, _p]),
     "vx_toy_embed": (_i, [_p, C.POINTER(_i32), C.POINTER(_i32), C.c_double, _i, _i, _p, C.POINTER(_i32), _p]),
     "vx_gauss_blur_axis_f64": (_i, [_p, _p, C.POINTER(_i32), _i, _p, _i, _p]),
     "vx_count_ge_f64": (_i, [_p, _i64, C.c_double, _p, _p]),
@@ -389,6 +413,8 @@ SIGNATURES = {
     "vx_png_bound": (_i64, [_i, _i]),
     "vx_png_workspace_bytes": (C.c_size_t, [C.POINTER(PngItem), _i]),
     "vx_png_encode": (_i, [C.POINTER(PngItem), _i, _p, _i, _p, _i64, _p, _p, _p, C.c_size_t, _p]),
+    "vx_png_encode_rgb_workspace_bytes": (C.c_size_t, [C.POINTER(PngRgbItem), _i]),
+    "vx_png_encode_rgb": (_i, [C.POINTER(PngRgbItem), _i, _p, _i64, _p, _p, _p, C.c_size_t, _p]),
     "vx_inflate_workspace_bytes": (_i64, [_i]),
     "vx_inflate": (_i, [C.POINTER(InflateItem), _i, _p, _i64, _p, _p, _p, _i64, _p]),
     "vx_nifti_decode_workspace_bytes": (_i64, [_i]),

@@ -22,6 +22,7 @@
 //   [43 + L, 47 + L) Adler-32  [47 + L, 51 + L) IDAT CRC  [51 + L, 63 + L) IEND
 //
 // Every store in this file is a plain C++ store of a vector register.
+#include <type_traits>
 #include <vector>
 
 #include "deflate_chunk.h"
@@ -43,11 +44,15 @@ struct PngItemDev {
   int32_t first_chunk, nchunks, pad;
 };
 
+// RGB: `labels` holds the item's RGB bytes and a scanline byte is that byte (vx_png_encode_rgb; lut is not looked at)
+template <bool RGB>
 __global__ __launch_bounds__(256) void png_scanline_kernel(const PngItemDev* __restrict__ items, int n_items,
                                                            const uint8_t* __restrict__ lut, int unlabeled) {
   __shared__ uint8_t s_lut[768];
-  for (int i = threadIdx.x; i < 768; i += 256) s_lut[i] = lut[i];
-  __syncthreads();
+  if (!RGB) {
+    for (int i = threadIdx.x; i < 768; i += 256) s_lut[i] = lut[i];
+    __syncthreads();
+  }
   for (int item = blockIdx.y; item < n_items; item += gridDim.y) {
     const PngItemDev it = items[item];
     const uint32_t row = 3u * (uint32_t)it.W + 1u;
@@ -65,9 +70,13 @@ __global__ __launch_bounds__(256) void png_scanline_kernel(const PngItemDev* __r
           const uint32_t p = (c - 1) / 3;
           const uint32_t ch = c - 1 - 3 * p;
           const size_t pix = (size_t)y * (uint32_t)it.W + p;
-          int l = it.labels[pix];
-          if (it.ignore && it.ignore[pix]) l = unlabeled;
-          v |= (uint32_t)s_lut[3 * l + ch] << (8 * j);
+          if (RGB) {
+            v |= (uint32_t)it.labels[3 * pix + ch] << (8 * j);
+          } else {
+            int l = it.labels[pix];
+            if (it.ignore && it.ignore[pix]) l = unlabeled;
+            v |= (uint32_t)s_lut[3 * l + ch] << (8 * j);
+          }
         }
         if (++c == row) { c = 0; ++y; }
       }
@@ -211,7 +220,8 @@ struct PngLayout {
   size_t items, gz_items, chunks, meta, adler, chunk_off, slots, raw, total, head;
 };
 
-PngLayout png_layout(const vx_png_item* items, int n, int64_t nch) {
+template <typename Item>
+PngLayout png_layout(const Item* items, int n, int64_t nch) {
   PngLayout L{};
   size_t o = 0;
   L.items = o; o += vx_align256(sizeof(PngItemDev) * n);
@@ -236,7 +246,10 @@ extern "C" int64_t vx_png_bound(int H, int W) {
   return n + 5 * gz_nchunks(n) + PNG_FRAME;
 }
 
-extern "C" size_t vx_png_workspace_bytes(const vx_png_item* items, int n) {
+namespace {
+
+template <typename Item>
+size_t png_workspace_bytes(const Item* items, int n) {
   if (!items || n < 1) return 0;
   int64_t nch = 0;
   for (int i = 0; i < n; ++i) {
@@ -246,28 +259,35 @@ extern "C" size_t vx_png_workspace_bytes(const vx_png_item* items, int n) {
   return png_layout(items, n, nch).total;
 }
 
-extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut, int unlabeled, uint8_t* dst,
-                             int64_t dst_bytes, int64_t* out_offsets, int64_t* out_sizes, void* workspace,
-                             size_t ws_bytes, vx_stream_t stream) {
-  if (n < 1) VX_FAIL(VX_E_SHAPE, "vx_png_encode: n=%d", n);
-  if (!items || !lut || !dst || !out_offsets || !out_sizes || !workspace) VX_FAIL(VX_E_NULL, "vx_png_encode: null pointer");
-  if (!vx_aligned16(workspace)) VX_FAIL(VX_E_ALIGN, "vx_png_encode: workspace not 16-byte aligned");
-  if (unlabeled < 0 || unlabeled > 255) VX_FAIL(VX_E_SHAPE, "vx_png_encode: unlabeled=%d outside 0..255", unlabeled);
+inline const uint8_t* png_src(const vx_png_item& g) { return g.labels; }
+inline const uint8_t* png_src(const vx_png_rgb_item& g) { return g.rgb; }
+inline const uint8_t* png_ignore(const vx_png_item& g) { return g.ignore; }
+inline const uint8_t* png_ignore(const vx_png_rgb_item&) { return nullptr; }
+
+// vx_png_encode (Item = vx_png_item: labels through lut) and vx_png_encode_rgb (Item = vx_png_rgb_item: RGB bytes)
+template <typename Item>
+int png_encode(const char* who, const Item* items, int n, const uint8_t* lut, int unlabeled, uint8_t* dst, int64_t dst_bytes,
+               int64_t* out_offsets, int64_t* out_sizes, void* workspace, size_t ws_bytes, vx_stream_t stream) {
+  constexpr bool RGB = std::is_same<Item, vx_png_rgb_item>::value;
+  if (n < 1) VX_FAIL(VX_E_SHAPE, "%s: n=%d", who, n);
+  if (!items || (!RGB && !lut) || !dst || !out_offsets || !out_sizes || !workspace) VX_FAIL(VX_E_NULL, "%s: null pointer", who);
+  if (!vx_aligned16(workspace)) VX_FAIL(VX_E_ALIGN, "%s: workspace not 16-byte aligned", who);
+  if (unlabeled < 0 || unlabeled > 255) VX_FAIL(VX_E_SHAPE, "%s: unlabeled=%d outside 0..255", who, unlabeled);
   int64_t need = 0, nch = 0;
   for (int i = 0; i < n; ++i) {
-    const vx_png_item& g = items[i];
-    if (g.H < 1 || g.W < 1) VX_FAIL(VX_E_SHAPE, "vx_png_encode: item %d: H=%d W=%d", i, g.H, g.W);
+    const Item& g = items[i];
+    if (g.H < 1 || g.W < 1) VX_FAIL(VX_E_SHAPE, "%s: item %d: H=%d W=%d", who, i, g.H, g.W);
     if (png_raw_bytes(g.H, g.W) > PNG_RAW_MAX)
-      VX_FAIL(VX_E_SHAPE, "vx_png_encode: item %d: %d x %d has 2^31 or more scanline bytes", i, g.H, g.W);
-    if (!g.labels) VX_FAIL(VX_E_NULL, "vx_png_encode: item %d: null labels", i);
+      VX_FAIL(VX_E_SHAPE, "%s: item %d: %d x %d has 2^31 or more scanline bytes", who, i, g.H, g.W);
+    if (!png_src(g)) VX_FAIL(VX_E_NULL, "%s: item %d: null %s", who, i, RGB ? "rgb" : "labels");
     need += vx_png_bound(g.H, g.W);
     nch += gz_nchunks(png_raw_bytes(g.H, g.W));
   }
-  if (dst_bytes < need) VX_FAIL(VX_E_SHAPE, "vx_png_encode: dst_bytes=%lld < %lld (sum of vx_png_bound)", (long long)dst_bytes,
+  if (dst_bytes < need) VX_FAIL(VX_E_SHAPE, "%s: dst_bytes=%lld < %lld (sum of vx_png_bound)", who, (long long)dst_bytes,
                                 (long long)need);
-  if (nch > 0x7FFFFFFF) VX_FAIL(VX_E_SHAPE, "vx_png_encode: %lld chunks", (long long)nch);
+  if (nch > 0x7FFFFFFF) VX_FAIL(VX_E_SHAPE, "%s: %lld chunks", who, (long long)nch);
   const PngLayout L = png_layout(items, n, nch);
-  if (ws_bytes < L.total) VX_FAIL(VX_E_WORKSPACE, "vx_png_encode: workspace %zu < %zu bytes", ws_bytes, L.total);
+  if (ws_bytes < L.total) VX_FAIL(VX_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, L.total);
 
   // descriptor tables, built in one host block laid out like the head of the workspace and uploaded in one copy
   uint8_t* ws = (uint8_t*)workspace;
@@ -277,10 +297,10 @@ extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut
   size_t raw = L.raw;
   int32_t c = 0, max_words = 1;
   for (int i = 0; i < n; ++i) {
-    const vx_png_item& g = items[i];
+    const Item& g = items[i];
     const int32_t nb = (int32_t)png_raw_bytes(g.H, g.W);
     const int32_t k = (int32_t)gz_nchunks(nb);
-    pi[i] = PngItemDev{g.labels, g.ignore, ws + raw, g.H, g.W, nb, c, k, 0};
+    pi[i] = PngItemDev{png_src(g), png_ignore(g), ws + raw, g.H, g.W, nb, c, k, 0};
     const int64_t row = 3 * (int64_t)g.W + 1;
     // stride hints: the previous pixel and, while within the window, the previous scanline
     recs[i] = vx_gz_item{ws + raw, nb, 0, {3, row <= GZ_CHUNK ? (int32_t)row : 0, 0}, 0};
@@ -291,7 +311,7 @@ extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut
   gz_fill_tables(recs.data(), n, reinterpret_cast<GzItemDev*>(head.data() + L.gz_items),
                  reinterpret_cast<GzChunkDev*>(head.data() + L.chunks));
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = vx_upload_table("vx_png_encode", "descriptor upload", ws, head.data(), L.head, s)) return rc;
+  if (int rc = vx_upload_table(who, "descriptor upload", ws, head.data(), L.head, s)) return rc;
   const PngItemDev* d_items = (const PngItemDev*)(ws + L.items);
   const GzItemDev* d_gz = (const GzItemDev*)(ws + L.gz_items);
   const GzChunkDev* d_chunks = (const GzChunkDev*)(ws + L.chunks);
@@ -301,20 +321,36 @@ extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut
   uint8_t* d_slots = ws + L.slots;
   const unsigned bx = (unsigned)min(1024, (max_words + 255) / 256);
   const unsigned by = (unsigned)min(n, 65535);
-  hipLaunchKernelGGL(png_scanline_kernel, dim3(bx, by), dim3(256), 0, s, d_items, n, lut, unlabeled);
-  VX_CHECK_LAUNCH("vx_png_encode: scanlines");
+  hipLaunchKernelGGL(png_scanline_kernel<RGB>, dim3(bx, by), dim3(256), 0, s, d_items, n, lut, unlabeled);
+  VX_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(png_adler_kernel, dim3((unsigned)nch), dim3(GZ_LANES), 0, s, d_gz, d_chunks, d_adler);
-  VX_CHECK_LAUNCH("vx_png_encode: adler");
-  if (int rc = gz_launch_chunks("vx_png_encode", d_gz, d_chunks, d_meta, d_slots, nch, s)) return rc;
+  VX_CHECK_LAUNCH(who);
+  if (int rc = gz_launch_chunks(who, d_gz, d_chunks, d_meta, d_slots, nch, s)) return rc;
   hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(PNG_SCAN_LANES), 0, s, d_items, n, d_chunks, d_meta, nch, d_off,
                      out_offsets, out_sizes);
-  VX_CHECK_LAUNCH("vx_png_encode: scan");
+  VX_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(png_pack_kernel, dim3((unsigned)nch), dim3(256), 0, s, d_meta, d_off, d_slots, dst);
-  VX_CHECK_LAUNCH("vx_png_encode: pack");
+  VX_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(png_frame_kernel, dim3((unsigned)n), dim3(PNG_FRAME_LANES), 0, s, d_items, d_adler, out_offsets,
                      out_sizes, dst);
-  VX_CHECK_LAUNCH("vx_png_encode: frame");
+  VX_CHECK_LAUNCH(who);
   return VX_OK;
+}
+
+}  // namespace
+
+extern "C" size_t vx_png_workspace_bytes(const vx_png_item* items, int n) { return png_workspace_bytes(items, n); }
+extern "C" size_t vx_png_encode_rgb_workspace_bytes(const vx_png_rgb_item* items, int n) { return png_workspace_bytes(items, n); }
+
+extern "C" int vx_png_encode(const vx_png_item* items, int n, const uint8_t* lut, int unlabeled, uint8_t* dst,
+                             int64_t dst_bytes, int64_t* out_offsets, int64_t* out_sizes, void* workspace,
+                             size_t ws_bytes, vx_stream_t stream) {
+  return png_encode("vx_png_encode", items, n, lut, unlabeled, dst, dst_bytes, out_offsets, out_sizes, workspace, ws_bytes, stream);
+}
+
+extern "C" int vx_png_encode_rgb(const vx_png_rgb_item* items, int n, uint8_t* dst, int64_t dst_bytes, int64_t* out_offsets,
+                                 int64_t* out_sizes, void* workspace, size_t ws_bytes, vx_stream_t stream) {
+  return png_encode("vx_png_encode_rgb", items, n, nullptr, 0, dst, dst_bytes, out_offsets, out_sizes, workspace, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

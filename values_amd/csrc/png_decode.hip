@@ -29,6 +29,7 @@
 //
 // Every store in this file is a plain C++ store of a vector register.
 #include "stream_items.h"   // the [counter | items] table of the launcher
+#include "trainid_lookup.h"
 
 namespace {
 
@@ -210,7 +211,6 @@ __global__ __launch_bounds__(PU_LANES) void png_unfilter_kernel(const PuItemDev*
   });
 }
 
-constexpr int RT_MAX = 256;
 constexpr int RT_BLOCK = 256;
 
 __global__ __launch_bounds__(RT_BLOCK) void rgb_to_trainid_kernel(const uint8_t* __restrict__ rgb, int64_t n,
@@ -218,11 +218,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rgb_to_trainid_kernel(const uint8_t*
                                                                   uint8_t* __restrict__ out, int aligned) {
   __shared__ uint32_t key[RT_MAX];
   __shared__ uint32_t id[RT_MAX];
-  for (int j = threadIdx.x; j < n_table; j += RT_BLOCK) {
-    key[j] = table[2 * j] & 0xFFFFFFu;
-    id[j] = table[2 * j + 1] & 0xFFu;
-  }
-  __syncthreads();
+  rt_stage<RT_BLOCK>(table, n_table, key, id);
   const int64_t groups = (n + 3) >> 2;
   for (int64_t g = (int64_t)blockIdx.x * RT_BLOCK + threadIdx.x; g < groups; g += (int64_t)gridDim.x * RT_BLOCK) {
     const int64_t p0 = 4 * g;
@@ -245,11 +241,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rgb_to_trainid_kernel(const uint8_t*
         }
     }
     uint32_t r[4] = {(uint32_t)default_id, (uint32_t)default_id, (uint32_t)default_id, (uint32_t)default_id};
-    for (int j = 0; j < n_table; ++j) {
-      const uint32_t kj = key[j], ij = id[j];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) r[k] = px[k] == kj ? ij : r[k];
-    }
+    rt_lookup<4>(key, id, n_table, px, r);
     if (aligned && cnt == 4) {
       *reinterpret_cast<uint32_t*>(out + p0) = r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24);
     } else {

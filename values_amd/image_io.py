@@ -67,6 +67,11 @@ def read_png(path) -> np.ndarray:
     with open(path, "rb") as f:
         buf = f.read()
     w, h, _, bpp, spans = png_parse(buf)
+    return _png_unfilter(path, buf, w, h, bpp, spans)
+
+
+def _png_unfilter(path, buf, w, h, bpp, spans) -> np.ndarray:
+    """the IDAT spans of `buf` inflated and their scanlines reconstructed: (h, w) for bpp 1, else (h, w, bpp)"""
     raw = np.frombuffer(zlib.decompress(b"".join(buf[o:o + n] for o, n in spans)), dtype=np.uint8).reshape(h, 1 + w * bpp)
     out = np.zeros((h, w * bpp), dtype=np.uint8)
     prev = np.zeros(w * bpp, dtype=np.int32)
@@ -96,6 +101,56 @@ def read_png(path) -> np.ndarray:
         out[y] = cur
         prev = cur
     return out.reshape(h, w) if bpp == 1 else out.reshape(h, w, bpp)
+
+
+def png_parse_indexed(buf):
+    """The layout of an 8-bit non-interlaced PALETTE PNG (colour type 3) held in `buf`: -> (w, h, palette, [(offset, size)
+    of every IDAT chunk's data]); palette is (256, 3) uint8 RGB, the PLTE chunk's entries padded with black (an index
+    beyond the file's own palette is the file's error).  The inflated stream is h rows of one filter byte and w index
+    bytes: one bpp = 1 image.  A tRNS chunk is not looked at.  Beside png_parse, which keeps refusing these files; the 2D
+    preprocessing (values_amd.preprocess2d) is the only caller."""
+    if bytes(buf[:8]) != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("not a PNG file")
+    pos, idat, hdr, plte = 8, [], None, None
+    while pos + 8 <= len(buf):
+        n, tag = struct.unpack(">I4s", buf[pos:pos + 8])
+        if tag == b"IHDR":
+            hdr = struct.unpack(">IIBBBBB", buf[pos + 8:pos + 8 + n])
+        elif tag == b"PLTE":
+            plte = bytes(buf[pos + 8:pos + 8 + n])
+        elif tag == b"IDAT":
+            idat.append((pos + 8, min(n, len(buf) - pos - 8)))
+        elif tag == b"IEND":
+            break
+        pos += 12 + n
+    if hdr is None:
+        raise ValueError("not a PNG file: no IHDR chunk")
+    w, h, depth, ctype, _, _, interlace = hdr
+    if depth != 8 or interlace != 0 or ctype != 3:
+        raise ValueError("png_parse_indexed: only 8-bit non-interlaced palette files")
+    if plte is None or len(plte) % 3 or not 3 <= len(plte) <= 768:
+        raise ValueError("png_parse_indexed: no PLTE chunk of 1..256 entries")
+    palette = np.zeros((256, 3), dtype=np.uint8)
+    palette[:len(plte) // 3] = np.frombuffer(plte, np.uint8).reshape(-1, 3)
+    return w, h, palette, idat
+
+
+def png_color_type(buf) -> int:
+    """the colour type byte of a PNG file's IHDR (-1: not a PNG file that starts with IHDR)"""
+    if bytes(buf[:8]) != b"\x89PNG\r\n\x1a\n" or bytes(buf[12:16]) != b"IHDR" or len(buf) < 26:
+        return -1
+    return buf[25]
+
+
+def read_png_any(path) -> np.ndarray:
+    """read_png, and palette files besides: those come back expanded to (H, W, 3) RGB, as cv2.imread(path, -1) followed
+    by BGR2RGB gives them."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    if png_color_type(buf) != 3:
+        return read_png(path)
+    w, h, palette, spans = png_parse_indexed(buf)
+    return palette[_png_unfilter(path, buf, w, h, 1, spans)]
 
 
 # ----------------------------------------------------------------------------------------------- TIFF

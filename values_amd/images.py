@@ -73,15 +73,17 @@ def lzw_status_name(st: int) -> str:
     return _lib.LZW_STATUS[st] if 0 <= st < len(_lib.LZW_STATUS) else f"status {st}"
 
 
-def _decode_png(names, raws, device, staging, timing=None):
+def _decode_png(names, raws, device, staging, timing=None, heads=None):
+    """heads: the files' (w, h, ctype, bpp, IDAT spans) where the caller has parsed them already (preprocess2d: a palette
+    file is a bpp = 1 image of indices); None: png_parse"""
     import torch
     from .gz import inflate_into, status_name
-    heads = []
-    for nm, r in zip(names, raws):
+    parsed, heads = heads, []
+    for k, (nm, r) in enumerate(zip(names, raws)):
         if len(r) >= MAX_FILE:
             raise ValueError(f"{nm}: {len(r)} bytes: files of 4 GiB or more are not read on the device")
         try:
-            heads.append(png_parse(r))
+            heads.append(png_parse(r) if parsed is None else parsed[k])
         except ValueError as e:
             raise ValueError(f"{nm}: {e}") from None
     src, soffs, sizes = staging.upload([(r, h[4]) for r, h in zip(raws, heads)], device)

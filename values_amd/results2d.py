@@ -199,6 +199,45 @@ def png_encode(masks: Sequence[torch.Tensor], ignores: Optional[Sequence] = None
     return [host[o:o + k].tobytes() for o, k in zip(pl[:n], pl[n:])]
 
 
+def _png_rgb_table(entries):
+    """the vx_png_rgb_item table of (rgb_ptr, H, W) entries -> (table, sum of vx_png_bound, workspace bytes)"""
+    lib = _lib.load()
+    items = (_lib.PngRgbItem * len(entries))()
+    bound = 0
+    for it, (rgb, H, W) in zip(items, entries):
+        it.rgb, it.H, it.W = rgb, H, W
+        bound += int(lib.vx_png_bound(H, W))
+    return items, bound, int(lib.vx_png_encode_rgb_workspace_bytes(items, len(entries)))
+
+
+def _png_rgb_launch(items, dst, place, ws):
+    """vx_png_encode_rgb of a _png_rgb_table: dst, place and ws as _png_launch takes them"""
+    n = len(items)
+    _lib.check(_lib.load().vx_png_encode_rgb(items, n, dst.data_ptr(), dst.numel(), place.data_ptr(), place[n:].data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "vx_png_encode_rgb")
+
+
+def png_encode_rgb(images: Sequence[torch.Tensor]) -> List[bytes]:
+    """One RGB PNG file per (H, W, 3) uint8 image, all in one vx_png_encode_rgb call; the shapes may differ.  The files
+    have png_encode's layout (filter-0 scanlines, one IDAT) and decode to the images' pixels."""
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    imgs = [_as_device(m, dev).contiguous() for m in images]
+    if not imgs:
+        return []
+    for im in imgs:
+        if im.dim() != 3 or im.shape[2] != 3 or im.dtype != torch.uint8:
+            raise ValueError("png_encode_rgb: (H, W, 3) uint8 images expected")
+    items, bound, ws_bytes = _png_rgb_table([(im.data_ptr(), int(im.shape[0]), int(im.shape[1])) for im in imgs])
+    n = len(imgs)
+    dst = torch.empty(bound, dtype=torch.uint8, device=dev)
+    place = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    _png_rgb_launch(items, dst, place, torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
+    pl = place.cpu().tolist()
+    host = dst[:pl[n - 1] + pl[2 * n - 1]].cpu().numpy()
+    return [host[o:o + k].tobytes() for o, k in zip(pl[:n], pl[n:])]
+
+
 def _encode_images(bufs, image_ids, pred_masks, mean_masks, uncertainty, ignore_index_map, timing=None, tiff=None,
                    tiff_predictor=3, tiff_rows_per_strip=None):
     """vx_png_encode over every mask of the batch, the TIFF stage over every map (_devio.TiffStage: raw, or LZW strips
