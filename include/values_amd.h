@@ -279,7 +279,10 @@ typedef struct vx_conv3d_args {
    * COARSE channels -- K = 192 instead of 288 per x-pair row, and the staging waves copy the coarse tensor into LDS instead
    * of evaluating the transposed conv per step.  The up bias enters through a table of the 27 border classes (a 3x3x3 tap
    * outside the volume sees the zero padding of the concatenated tensor, not the bias).  Same function of the inputs;
-   * weights composed in float64 at pack time, so results differ from the two-stage evaluation by float32 rounding only. */
+   * weights composed in float64 at pack time, so results differ from the two-stage evaluation by float32 rounding only.
+   * Level 1 (the 16-channel z-column kernel, form 2 of vx_conv3d_k3_upfuse_ok; only together with acc_in): the output of
+   * vx_pack_conv3d_upfused_zc16 -- per parity class (z & 1, y & 1, x & 1) a 2 x 2 x 2 tap convolution over the 32 coarse channels,
+   * 8 K-steps instead of 14 + the staging waves' products; up_w is not read then.  Same kernel instance, same name. */
   const float* up_fused;
   /* POOL-FINISH on load (round 4; only where vx_conv3d_k3_poolfin_ok(Cin, Cout)): `in` is the pool_out of the previous block's
    * second conv -- window maxima of RAW values [N][D][H][W][8] -- and in_pool_flags its any-dropped words [N][D][H][W][2];
@@ -325,6 +328,13 @@ int vx_conv3d_k3_upfuse_ok(int D, int H, int W, int Cin, int Cout);   /* != 0 if
    ConvTranspose3d(32 -> 16, k = 2, s = 2)(up_in) + up_b, evaluated while the tiles are staged -- `in` is not read, up_in is
    [N][D/2][H/2][W/2][up_pitch >= 32], up_w the output of vx_pack_convT_zc16, up_split as above; combines with acc_in */
 int64_t vx_convT_zc16_packed_floats(void);
+/* upscale3 composed into expand_2_1's up half.  w1_torch (16, 32, 3,3,3): the layer's FULL weight (its input channels [0, 16) are
+ * the up half); up_w_torch (32, 16, 2,2,2) + up_b (16): the transposed conv (torch layouts, device pointers) -> packed
+ * [8 classes (pz, py, px)][8 taps (a, b, c)][hi | lo][64 lanes][8 halves] + the up-bias table [27 border classes][16] fp32
+ * (vx_conv3d_upfused_zc16_packed_floats() floats, 16-byte aligned).  Composed on the device in float64 (csrc/upcompose16.h), split
+ * and clamped like vx_pack_conv3d_k3's weights.  The layer's bias is not part of it: it rides in the partial sums (acc_in). */
+int64_t vx_conv3d_upfused_zc16_packed_floats(void);
+int vx_pack_conv3d_upfused_zc16(const float* w1_torch, const float* up_w_torch, const float* up_b, float* packed, vx_stream_t stream);
 int vx_pack_convT_zc16(const float* w_torch /* (32, 16, 2,2,2) */, float* packed, vx_stream_t stream);
 /* 1 if vx_conv3d_k3 takes in_mean for the SKIP half of an x-blocked concat input (in_xblk = xblk) of this layer: the decoder's
  * first conv of a level normalising the contract block's raw output on load (round 5: also the tile kernel, Cin % 32 == 0) */
@@ -485,6 +495,8 @@ typedef struct vx_unet3d_weights {
   const float* split_w[2];
   int32_t split_family;    /* vx_conv3d_k3_family(16, 16) at pack time */
   const float* up3_zc16;   /* nullable: vx_pack_convT_zc16(upscale3): the up half's launch evaluates the transposed conv itself */
+  const float* up3_fused;  /* nullable (with up3_zc16): vx_pack_conv3d_upfused_zc16(expand_2_1, upscale3) -- upscale3 composed into the
+                              up half's weights (vx_conv3d_args.up_fused); NULL: evaluated per step by the staging waves */
 } vx_unet3d_weights;
 
 typedef struct vx_unet3d_run {

@@ -122,7 +122,7 @@ class UncOutputs(C.Structure):
 class UNet3DWeights(C.Structure):
     _fields_ = [("conv_w", _p * 18), ("conv_b", _p * 18), ("up_w", _p * 4), ("up_b", _p * 4),
                 ("final_w", _p), ("final_b", _p), ("F", _i32), ("num_classes", _i32), ("conv_family", _i32 * 18),
-                ("in_channels", _i32), ("no_instancenorm", _i32), ("up_fused", _p), ("split_w", _p * 2), ("split_family", _i32), ("up3_zc16", _p)]
+                ("in_channels", _i32), ("no_instancenorm", _i32), ("up_fused", _p), ("split_w", _p * 2), ("split_family", _i32), ("up3_zc16", _p), ("up3_fused", _p)]
 
 
 class UNet3DRun(C.Structure):
@@ -319,6 +319,8 @@ SIGNATURES = {
     "vx_conv3d_k3_poolfin_ok": (_i, [_i, _i]),
     "vx_conv3d_upfused_packed_floats": (_i64, []),
     "vx_pack_conv3d_upfused": (_i, [_p, _p, _p, _p, _p, _p]),
+    "vx_pack_conv3d_upfused_zc16": (_i, [_p, _p, _p, _p, _p]),
+    "vx_conv3d_upfused_zc16_packed_floats": (_i64, []),
     "vx_pool_finish": (_i, [_p, _p, _p, _p, _p, _i, _i, _i64, _i, _p]),
     "vx_pool_finish_z": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i64, _i, _p]),
     "vx_conv3d_k3_pool_layout": (_i, [_i, _i, _i, _i, _i]),

@@ -433,9 +433,10 @@ static inline int route_zc16(const vx_conv3d_args& a, int stat_tiles, Conv3dRout
   if (a.in_xblk || a.head_out || a.in_split || a.in_f16 || a.out_f16 || (a.in_repeat > 1)) return ROUTE_DECLINED;
   if ((a.in_planar || a.out_planar) && (a.drop_mode == VX_DROP_MASK || !a.out || a.in_pitch != a.Cin || a.Cout != 16))
     ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the planar pre-split hand-over needs hash or no dropout and dense 16-channel tensors");
-  if (a.up_in && (a.Cin != 16 || a.in_mean || a.stats_partial || a.up_pitch < 32 || a.up_pitch % 4 || a.up_fused))
+  if (a.up_in && (a.Cin != 16 || a.in_mean || a.stats_partial || a.up_pitch < 32 || a.up_pitch % 4 || (a.up_fused && (!a.acc_in || a.out_xblk || a.out_split))))
     ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the fused up-convolution (32 coarse channels -> the conv's 16 input channels) goes with an "
-               "activation epilogue, no prologue, up_pitch >= 32 (got %d), up_w packed by vx_pack_convT_zc16", a.up_pitch);
+               "activation epilogue, no prologue, up_pitch >= 32 (got %d), up_w packed by vx_pack_convT_zc16; composed weights "
+               "(up_fused: vx_pack_conv3d_upfused_zc16) only together with partial sums (acc_in) and a dense float or planar output", a.up_pitch);
   if (a.drop_mode == VX_DROP_MASK || !a.out) return ROUTE_DECLINED;
   route_columns(r, a, 2, stat_tiles);
   const int cps = r->tiles_x * r->tiles_y;

@@ -26,6 +26,7 @@
 // in flight reads the other two -- conv3d_xp8w.hip's scheme).
 #include "s16_common.h"
 #include "conv3d_internal.h"
+#include "upcompose16.h"
 
 struct Zc16Args {
   vx_conv3d_args a;
@@ -64,6 +65,22 @@ struct Zc16Args {
 // The transposed conv's launch, its 0.67 GB write and the conv's read of it disappear (unet3D_module.py:157-190, 332-356).
 // EPI 5 / 6 (round 6) = 1 / 3 with the PLANAR pre-split output of vx_conv3d_args.out_planar (a compile-time variant: as a run-time
 // branch its address arithmetic and the split's temporaries pushed the partial-sum instances past 168 registers into scratch).
+//
+// COMPOSED up-convolution (ACC = 1, UP = 1 with vx_conv3d_args.up_fused: vx_pack_conv3d_upfused_zc16, upcompose16.h): nothing sits
+// between the transposed conv and this conv, so the pair is ONE 2 x 2 x 2-tap conv over the 32 COARSE channels whose weights depend on
+// the output voxel's parity class (pz, py, px): 8 K-steps of K = 32 (a coarse tap each) instead of 14 + the staging waves' products,
+// 4 096 MACs per fine voxel instead of 7 424.  Chosen per launch by a wave-uniform test of the pointer at the top of each role, which
+// then runs a body of its own (the evaluated bodies are the ones above, bit for bit):
+//   * multiplying wave w owns class (pz, py, px) = (w >> 2, (w >> 1) & 1, w & 1) of the item's two fine planes: the four rows of
+//     parity py, the 16 voxels of parity px of each -- 4 column tiles; its class's 8 hi A fragments are resident in registers, the lo ones are read from LDS (64 KB
+//     for the 8 classes, behind the slots) per (a, c) group, a group ahead: all 64 registers resident spilled.
+//     Tile r, tap (a, b, c) reads coarse (plane k + pz - 1 + a, window row r + py + b, window column m + px + c): for a fixed (a, c)
+//     the four tiles and two b taps share 5 row fragments -- 40 ds_read_b128 per 96 matrix instructions.  The C operand of a
+//     tile's first product is the up bias through the taps inside the volume: btab[class(z)][class(y)][class(x)] (in LDS);
+//   * the staging waves copy ONE coarse plane window per step (6 rows x 18 columns x 32 channels, hi and lo planes of 64 bytes per
+//     position: [hi | lo][108 positions][k-group 4][8 halves]) into a rolling set of 4 slots indexed by the workgroup's running
+//     step number: step s of a column carries coarse plane s (plane D / 2 reads as zeros), item k reads the slots of steps
+//     k - 1 .. k + 1, and the plane before a column's first is the zero plane the previous column (or the start) left.
 template <int CIN, int EPI_, int PRE, int ACC = 0, int UP = 0>
 __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
   constexpr bool PLN = EPI_ == 5 || EPI_ == 6;
@@ -91,6 +108,11 @@ __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
   constexpr int Q = CIN / 4;                       // 16-byte fp32 pieces per voxel
   constexpr bool STATS = EPI == 0 || EPI == 4;
   constexpr bool POOL = EPI == 4;
+  // composed up-convolution: a plane slot is [hi | lo][6 x 18 coarse positions][32 channels] halves; 4 rolling slots
+  constexpr bool CMPI = ACC != 0 && UP != 0;       // the instances that carry the composed bodies
+  constexpr int CW = 18, CPOS = 6 * CW, CPREC_B = CPOS * 64, CSLOT_B = 2 * CPREC_B, CNS = 4;
+  constexpr int CWL_B = 8 * 8 * 1024;              // the lo halves of the composed weights: [class][tap][lane][8 halves], behind the slots
+  static_assert(!CMPI || (CNS * CSLOT_B + CWL_B <= IMG_B && 27 * 16 * 4 <= W_B), "the composed bodies live in the evaluated bodies' LDS");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned char* s_img = smem_raw;
@@ -98,7 +120,12 @@ __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
   float* s_red = reinterpret_cast<float*>(smem_raw + IMG_B + W_B);     // [NW][16][2]
   float* s_bias = s_red + NW * 16 * 2;                                 // [16]: re-read per item (4 registers less across the epilogue)
 
+  unsigned char* s_cwl = smem_raw + CNS * CSLOT_B;
+  float* s_btab = reinterpret_cast<float*>(s_w);                       // composed: [27 border classes][16] in place of the conv's weights
+
   const vx_conv3d_args& a = ka.a;
+  bool cmp = false;                                                    // (a kernel argument: uniform over the launch)
+  if constexpr (CMPI) cmp = a.up_fused != nullptr;
   auto kernarg = [&]() {      // fields used once per item / column are re-read where they are used (conv3d_xp8w.hip)
     typedef const Zc16Args __attribute__((address_space(4))) * kp_t;
     kp_t p = (kp_t)__builtin_amdgcn_kernarg_segment_ptr();
@@ -114,14 +141,24 @@ __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
   // ---- weights: resident for the kernel's life ----
   {
     const f32x4* src = reinterpret_cast<const f32x4*>(ka.w);
-    for (int i = tid; i < W_B / 16; i += NTH) reinterpret_cast<f32x4*>(s_w)[i] = src[i];
+    if (!cmp) {
+      for (int i = tid; i < W_B / 16; i += NTH) reinterpret_cast<f32x4*>(s_w)[i] = src[i];
+    } else {
+      for (int i = tid; i < 27 * 16; i += NTH) s_btab[i] = a.up_fused[VX_UPC16_WHALVES / 2 + i];
+    }
     if (tid < 16) s_bias[tid] = a.bias[tid];
   }
   // the image starts as zeros: a zero-weight k-group (Cin = 16: step 13; Cin = 8: the fourth group) multiplies whatever
   // sits at the position it reads, which must be finite from the first item on
   {
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    for (int i = tid; i < IMG_B / 16; i += NTH) reinterpret_cast<f32x4*>(s_img)[i] = z4;
+    // (composed: the slot a column's first item reads as coarse plane -1 must BE zero)
+    const int zn = cmp ? CNS * CSLOT_B / 16 : IMG_B / 16;
+    for (int i = tid; i < zn; i += NTH) reinterpret_cast<f32x4*>(s_img)[i] = z4;
+    if (cmp) {
+      const f32x4* csrc = reinterpret_cast<const f32x4*>(a.up_fused);
+      for (int i = tid; i < CWL_B / 16; i += NTH) reinterpret_cast<f32x4*>(s_cwl)[i] = csrc[((i >> 6) * 2 + 1) * 64 + (i & 63)];
+    }
   }
   __syncthreads();
 
@@ -167,6 +204,97 @@ __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
     // pooling instance (whose multiplying waves carry the long epilogue) -- not raised there.
     if constexpr ((PRE != 0 && !POOL) || UP != 0) __builtin_amdgcn_s_setprio(2);
     if constexpr (UP != 0) {
+      if (cmp) {
+      // ---- composed up-convolution: copy the coarse window of plane s.  Piece e = 256 i + 64 pw + lane (i < 4) is 16-byte piece
+      // q = e & 7 (channels 4 q .. 4 q + 3) of window position e >> 3 = (Yi, Xi) of 6 x 18: coarse (Yc0 - 1 + Yi, Xc0 - 1 + Xi); its
+      // fp16 pairs [hi0..3 | lo0..3] (up_split: as the producer stored them) go to the hi and the lo plane of the step's slot.
+      constexpr int UT = 4;
+      const int Hc = a.H >> 1, Wc = a.W >> 1;
+      const int up = a.up_pitch;
+      const int urow = Wc * up;
+      const int ubiasf = urow + up;                                 // keeps (Y = -1, X = -1) offsets non-negative
+      unsigned t_voff[UT];
+      int t_lds[UT];
+      unsigned tb_always = 0, tb_xlo = 0, tb_xhi = 0, tb_ylo = 0, tb_yhi = 0;     // bit i: piece i's voxel is ... (per lane)
+#pragma unroll
+      for (int i = 0; i < UT; ++i) {
+        const int e = 256 * i + 64 * pw + lane;
+        const int pos = e >> 3, q = e & 7;
+        const int Yi = pos / CW, Xi = pos % CW;
+        t_voff[i] = (unsigned)((((Yi - 1) * Wc + Xi - 1) * up + 4 * q + ubiasf) * 4);
+        t_lds[i] = pos * 64 + q * 8;
+        if (pos >= CPOS) tb_always |= 1u << i;                      // (no such position: neither loaded nor written)
+        if (Xi == 0) tb_xlo |= 1u << i;
+        if (Xi == CW - 1) tb_xhi |= 1u << i;
+        if (Yi == 0) tb_ylo |= 1u << i;
+        if (Yi == 5) tb_yhi |= 1u << i;
+      }
+      const size_t up_sample = (size_t)(a.D >> 1) * Hc * urow;
+      f32x4 ubuf[UT];
+      bool cs_have = false;
+      unsigned cs_bad = 0xFFFFFFFFu, cs_usoff = 0;
+      __amdgpu_buffer_rsrc_t cs_usrd = __builtin_amdgcn_make_buffer_rsrc((void*)a.up_in, 0, 0, 0x00020000);
+      auto column_state = [&](int ci) {
+        const bool have = ci < ncol_wg;
+        int n = 0, ty = 0, tx = 0;
+        if (have) col_of(ci, n, ty, tx);
+        cs_have = have;
+        unsigned b = tb_always;
+        if (tx == 0) b |= tb_xlo;
+        if (tx == ka.tiles_x - 1) b |= tb_xhi;
+        if (ty == 0) b |= tb_ylo;
+        if (ty == ka.tiles_y - 1) b |= tb_yhi;
+        cs_bad = b;
+        cs_usoff = (unsigned)(((ty * 4) * urow + tx * 16 * up) * 4);
+        cs_usrd = __builtin_amdgcn_make_buffer_rsrc((void*)(a.up_in + (size_t)n * up_sample - ubiasf), 0, VX_NUMREC, 0x00020000);
+      };
+      auto prefetch = [&](const Cur& c) {
+        if (c.s == 0) column_state(c.ci);
+        unsigned b = cs_bad;
+        if (!cs_have || c.s == KZ) b = 0xFFFFFFFFu;                 // coarse plane D / 2: zeros
+        const unsigned usoff = cs_usoff + (unsigned)((c.s * Hc) * urow * 4);
+#pragma unroll
+        for (int i = 0; i < UT; ++i) {
+          const unsigned v0 = ((b >> i) & 1u) ? VX_OOB : t_voff[i];
+          ubuf[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(cs_usrd, (int)v0, (int)usoff, 0));
+        }
+      };
+      auto commit = [&](int slot) {
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        unsigned char* base = s_img + slot * CSLOT_B;
+#pragma unroll
+        for (int i = 0; i < UT; ++i) {
+          u32x2 h2, l2;
+          if (a.up_split) {
+            const u32x4 d = __builtin_bit_cast(u32x4, ubuf[i]);
+            h2 = (u32x2){d[0], d[1]};
+            l2 = (u32x2){d[2], d[3]};
+          } else {
+            f16x4 hi, lo;
+            vx_split4_s(ubuf[i], hi, lo);
+            h2 = __builtin_bit_cast(u32x2, hi);
+            l2 = __builtin_bit_cast(u32x2, lo);
+          }
+          if (!((tb_always >> i) & 1u)) {
+            *reinterpret_cast<u32x2*>(base + t_lds[i]) = h2;
+            *reinterpret_cast<u32x2*>(base + t_lds[i] + CPREC_B) = l2;
+          }
+        }
+      };
+      Cur cx = {0, 0}, cc = {0, 0}, cp = {0, 0};
+      prefetch(cp); advance(cp);
+      commit(0);    advance(cc);          // S_0 -> slot 0; S_j -> slot j & 3
+      prefetch(cp); advance(cp);
+      int sl_x = 0;
+      while (cx.ci < ncol_wg) {
+        __syncthreads();
+        const int sl_c = (sl_x + 1) & (CNS - 1);
+        if (cc.ci < ncol_wg) commit(sl_c);
+        prefetch(cp);
+        advance(cx); advance(cc); advance(cp);
+        sl_x = sl_c;
+      }
+      } else {
       // ---- fused up-convolution.  A wave owns a plane of the step (u_pz; fine plane 2 s - 1 + u_pz: odd -> dz = 1 of coarse
       // plane s - 1, even -> dz = 0 of coarse plane s) and HALF of that plane's coarse window (6 rows x 18 columns = 108 coarse
       // voxels = 7 column tiles of 16: tiles 0..3 / 4..6), and evaluates all FOUR (dy, dx) classes on each tile it loads: every
@@ -312,6 +440,7 @@ __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
         advance(cx); advance(cc); advance(cp);
         grp_x = grp_c;
       }
+      }   // evaluated
     } else if constexpr (PRE == 4) {
       // ---- planar pre-split input, LDS-DMA.  Wave pw owns plane (octet pw >> 1, precision pw & 1) of the image: the slot group of
       // a step is NPOS = 680 consecutive positions of that plane, moved by NI = 11 instructions of 64 positions (the last one
@@ -648,362 +777,20 @@ __global__ __launch_bounds__(768) void conv3d_zc16_kernel(Zc16Args ka) {
     if (STATS) __syncthreads();
   } else {
     // =============================================== MULTIPLYING ===============================================
-    const int lz = wave >> 2, xh = (wave >> 1) & 1, ly0 = (wave & 1) * R, x0 = 16 * xh;
-    const bool late = wave >= NW / 2;
-    // ---- compute-phase constants (byte offsets into the LDS image) ----
-    // type-1 fragment of input row (slot, ly0 + j): lane (m, g) -> position x0 + m + kx, octet g & 1 (Cin = 16: kx = g >> 1;
-    // Cin = 8: kx = g, the zero group g = 3 re-reads kx = 2: finite data under a zero weight)
-    const int kxP = CIN == 16 ? (g >> 1) : (g < 2 ? g : 2);
-    const int bP = (CIN == 16 ? (g & 1) * OCT_B : 0) + (ly0 * HX + x0 + m + kxP) * 16;
-    const int bQ = (g & 1) * OCT_B + (ly0 * HX + x0 + m + 2) * 16;      // Cin = 16: the kx = 2 taps
-    const unsigned char* wlane = s_w + lane * 16;
-
-    // ---- epilogue constants: this lane stores voxel x0 + m of row ly0 + r, channels 4 g .. 4 g + 3 ----
-    const int lx = x0 + m, oc = 4 * g;
-    // (row r of the wave sits r output rows further: a scalar added to the store's soffset, one offset register per lane)
-    unsigned ovoff0;
-    if (a.out_xblk) {
-      const int oxb = a.out_xblk;
-      ovoff0 = (unsigned)((((lz * a.H + ly0) * (2 * a.W * 16)) + ((lx / oxb) * 2 + a.out_half) * oxb * 16 + (lx % oxb) * 16 + oc) * 4);
-    } else {
-      ovoff0 = (unsigned)((((lz * a.H + ly0) * a.W + lx) * a.out_pitch + a.out_coff + oc) * 4);
+    // (one body per evaluation of the up-convolution, chosen here by the wave-uniform test; conv3d_zc16_mult.h)
+    bool evaluated = true;
+    if constexpr (CMPI) {
+      if (cmp) {
+        evaluated = false;
+#define ZC_CMP 1
+#include "conv3d_zc16_mult.h"
+#undef ZC_CMP
+      }
     }
-    const unsigned orow = (unsigned)(a.W * (a.out_xblk ? 32 : a.out_pitch) * 4);   // bytes between two output rows
-    // ONE hash round per item serves the wave's R rows (16 channels: a keep-word = 2 voxels, a half row = 8 words): lane i
-    // computes word i & 7 of row i >> 3, a row's lanes fetch theirs with ds_bpermute.  Same bits as vx_drop_bits4(key, e).
-    unsigned hword_l;
-    {
-      const int rr_ = (lane >> 3) < R ? (lane >> 3) : 0;
-      hword_l = (unsigned)((((lz * a.H + ly0 + rr_) * a.W + x0) >> 1) + (lane & 7));
-    }
-    const int out_voxf = a.out_xblk ? 32 : a.out_pitch;
-    const size_t out_sample = (size_t)a.D * a.H * a.W * out_voxf;
-    const bool f_lrelu = EPI == 3 ? a.act == VX_ACT_LRELU : EPI == 1;
-    const bool f_relu = EPI == 3 && a.act == VX_ACT_RELU;
-
-    f32x4 acc[R], accx[R];
-    f32x4 accin[ACC ? R : 1];
-    float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
-    const unsigned avoff0 = ACC ? (unsigned)((((lz * a.H + ly0) * a.W + lx) * a.acc_pitch + oc) * 4) : 0u;
-    const unsigned arow = ACC ? (unsigned)(a.W * a.acc_pitch * 4) : 0u;
-    const size_t acc_sample = (size_t)a.D * a.H * a.W * (ACC ? a.acc_pitch : 0);
-
-    // the multiply phase of the item whose first input plane (z0 - 1) sits in slot rb (item k of column ci)
-    auto multiply = [&](int rb, int ci, int k) {
-      if constexpr (ACC != 0) {
-        int n_, ty_, tx_;
-        col_of(ci, n_, ty_, tx_);
-        const unsigned asoff = (unsigned)(((k * TZ) * a.H + ty_ * 8) * a.W + tx_ * 32) * (unsigned)a.acc_pitch * 4u;
-        const __amdgpu_buffer_rsrc_t asrd = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(const_cast<float*>(kernarg()->a.acc_in) + (size_t)n_ * acc_sample), 0, VX_NUMREC, 0x00020000);
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-          accin[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(asrd, (int)avoff0, (int)(asoff + (unsigned)r * arow), 0));
-      }
-      const f32x4 bias4 = *reinterpret_cast<const f32x4*>(s_bias + oc);
-      int sl[3];
-#pragma unroll
-      for (int kz = 0; kz < 3; ++kz) {
-        int s_ = rb + lz + kz;
-        if (s_ >= NZ) s_ -= NZ;
-        sl[kz] = s_ * PLN_B;
-      }
-      // phases = groups of steps that share their row fragments.  Cin = 16: phases 0..2 (type 1, kz = phase) and 3 (the kx = 2 taps
-      // of kz = 0 / 1) have three steps (ky) over 6 rows -- tile r of step ky reads row r + ky; phase 4 is the ONE step that holds
-      // the kx = 2 taps of (kz = 2, ky = 0 / 1) as its two k-group pairs: its fragment of tile r mixes rows r and r + 1 by lane
-      // (4 fragments, no reuse); phase 5 the half-empty step of (kz = 2, ky = 2): rows 2..5.  14 steps for 13.5 (round 5, second
-      // version: the first ran the kz = 2 taps as three half-empty steps, 15).  Cin = 8: three phases of three steps.
-      constexpr int NPH = CIN == 16 ? 6 : 3;
-      auto ph_of = [](int t) { return t < 12 ? t / 3 : t - 8; };           // step -> phase
-      auto ky_of = [](int t) { return t < 12 ? t % 3 : 0; };               // step -> row offset of tile r within the phase's rows
-      auto nrows = [](int ph) { return ph < 4 ? R + 2 : R; };
-      const unsigned char* rowp[NPH];
-#pragma unroll
-      for (int ph = 0; ph < NPH; ++ph) {
-        if (ph < 3) rowp[ph] = s_img + bP + sl[ph];
-        else if (ph == 3) rowp[ph] = s_img + bQ + ((g >> 1) ? sl[1] : sl[0]);
-        else if (ph == 4) rowp[ph] = s_img + bQ + sl[2] + (g >> 1) * ROW_B;
-        else rowp[ph] = s_img + bQ + sl[2] + 2 * ROW_B;
-      }
-#ifndef ZC_NO_PIPE
-      if constexpr (!POOL)      // (the pooling instance holds 8 statistics registers + its window state across the loop: 168 + scratch)
-      // ONE software pipeline over the NSTEP K-steps, 12 matrix instructions each.  Left alone hipcc sinks every ds_read_b128 to
-      // just before its consumer (ds_read; s_waitcnt lgkmcnt(0..1); v_mfma).  Here every step requests, behind its own matrix
-      // instructions and pinned there (sched_group_barrier), fragments of LATER steps:
-      //   step (phase p, ky = 0): the weights of (p, 1) + rows 4, 5 of phase p          (needed at ky = 1 / ky = 2)
-      //   step (p, 1):            the weights of (p, 2) + rows 0, 1 of phase p + 1
-      //   step (p, 2):            the weights of (p + 1, 0) + rows 2, 3 of phase p + 1
-      //   step 12 (phase 4):      the weights of step 13 + the four rows of phase 5
-      // -- 0.5 reads per matrix instruction over the item.  Measured -2 .. -3.5 % (same-process A/B against the plain loop).
-      {
-        f16x8 rh[NPH][R + 2], rl[NPH][R + 2], wh[NSTEP], wl[NSTEP];
-        auto ld_row = [&](int ph, int jr) {
-          rh[ph][jr] = *reinterpret_cast<const f16x8*>(rowp[ph] + jr * ROW_B);
-          rl[ph][jr] = *reinterpret_cast<const f16x8*>(rowp[ph] + jr * ROW_B + PREC_B);
-        };
-        auto ld_w = [&](int t) {
-          wh[t] = *reinterpret_cast<const f16x8*>(wlane + t * 2048);
-          wl[t] = *reinterpret_cast<const f16x8*>(wlane + t * 2048 + 1024);
-        };
-        ld_w(0);
-#pragma unroll
-        for (int jr = 0; jr < R; ++jr) ld_row(0, jr);
-        __builtin_amdgcn_sched_group_barrier(0x100, 3 + 2 * R, 0);      // (+ the bias vector)
-#pragma unroll
-        for (int t = 0; t < NSTEP; ++t) {
-          const int ph = ph_of(t), ky = ky_of(t);
-          int nrd = 0;
-          if (t + 1 < NSTEP) { ld_w(t + 1); nrd += 2; }
-          if (t < 12) {
-            if (ky == 0) { ld_row(ph, R); ld_row(ph, R + 1); nrd += 4; }
-            else if (ph + 1 < NPH) { ld_row(ph + 1, 2 * (ky - 1)); ld_row(ph + 1, 2 * (ky - 1) + 1); nrd += 4; }
-          } else if (t == 12) {
-#pragma unroll
-            for (int jr = 0; jr < R; ++jr) ld_row(5, jr);
-            nrd += 2 * R;
-          }
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const bool fresh = t == 0;      // the bias is the first product's C operand
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], rh[ph][r + ky], fresh ? (ACC ? zero : bias4) : acc[r], 0, 0, 0);
-            accx[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], rl[ph][r + ky], fresh ? zero : accx[r], 0, 0, 0);
-            accx[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], rh[ph][r + ky], accx[r], 0, 0, 0);
-          }
-#pragma unroll
-          for (int i = 0; i < 3 * R; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (i < nrd) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
-        }
-        return;
-      }
-#endif
-#pragma unroll
-      for (int ph = 0; ph < NPH; ++ph) {
-        f16x8 bh[R + 2], bl[R + 2];
-#pragma unroll
-        for (int jr = 0; jr < R + 2; ++jr) {
-          if (jr < nrows(ph)) {
-            bh[jr] = *reinterpret_cast<const f16x8*>(rowp[ph] + jr * ROW_B);
-            bl[jr] = *reinterpret_cast<const f16x8*>(rowp[ph] + jr * ROW_B + PREC_B);
-          }
-        }
-#pragma unroll
-        for (int ky = 0; ky < (ph < 4 ? 3 : 1); ++ky) {
-          const int step = ph < 4 ? ph * 3 + ky : 8 + ph;
-          const f16x8 ah = *reinterpret_cast<const f16x8*>(wlane + step * 2048);
-          const f16x8 al = *reinterpret_cast<const f16x8*>(wlane + step * 2048 + 1024);
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const bool fresh = ph == 0 && ky == 0;      // the bias is the first product's C operand
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[r + ky], fresh ? (ACC ? zero : bias4) : acc[r], 0, 0, 0);
-            accx[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[r + ky], fresh ? zero : accx[r], 0, 0, 0);
-            accx[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[r + ky], accx[r], 0, 0, 0);
-          }
-        }
-      }
-    };
-
-    // ---- epilogue state of THIS wave (column it is storing) ----
-    int e_ci = -1, e_n = 0, e_ty = 0, e_tx = 0;
-    vx_dkey e_key = {0u, 0u};
-
-    auto epilogue = [&](int ci, int k) {
-      if (ci != e_ci) {
-        e_ci = ci;
-        col_of(ci, e_n, e_ty, e_tx);
-        if (EPI == 1 || EPI == 4) e_key = vx_drop_key(seed_out, kernarg()->a.drop_layer, (uint32_t)e_n);
-      }
-      const unsigned vox0 = (unsigned)(((k * TZ) * a.H + e_ty * 8) * a.W + e_tx * 32);
-      const unsigned osoff = a.out_xblk ? (unsigned)((((k * TZ) * a.H + e_ty * 8) * (2 * a.W * 16) + e_tx * 32 * 32) * 4)
-                                        : vox0 * (unsigned)a.out_pitch * 4u;
-      const int hbp = 4 * (m >> 1);                               // (recomputed per item: two registers less across the matrix loop)
-      const unsigned hsh = (unsigned)((m & 1) * 16 + oc);
-      const bool e_hash = (EPI == 1) || (EPI == 4 && a.drop_mode == VX_DROP_HASH);
-      const uint32_t hw_item = e_hash ? vx_drop_word(e_key, (vox0 >> 1) + hword_l) : 0u;
-      const __amdgpu_buffer_rsrc_t osrd = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(reinterpret_cast<char*>(kernarg()->a.out) + (size_t)e_n * out_sample * 4), 0, VX_NUMREC, 0x00020000);
-      float pl_max[4];
-      uint32_t pl_any = 0u;
-      __amdgpu_buffer_rsrc_t psrd = osrd, fsrd = osrd;
-      if constexpr (POOL) {
-        const auto kp = kernarg();
-        const size_t pvs = (size_t)a.D * (a.H >> 1) * (a.W >> 1);      // pooled (y, x) voxels per sample
-        psrd = __builtin_amdgcn_make_buffer_rsrc((void*)(kp->a.pool_out + (size_t)e_n * pvs * 16), 0, VX_NUMREC, 0x00020000);
-        fsrd = __builtin_amdgcn_make_buffer_rsrc((void*)(kp->a.pool_flags + (size_t)e_n * pvs * 4), 0, VX_NUMREC, 0x00020000);
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        f32x4 v;       // main + cross * 2^-11: one fma per element (exact scaling)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = fmaf(accx[r][j], 1.0f / 2048.f, acc[r][j]);
-        if constexpr (ACC != 0) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] += accin[r][j];
-        }
-        if (STATS) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { ssum[j] += v[j]; ssq[j] = fmaf(v[j], v[j], ssq[j]); }
-        }
-        if constexpr (POOL) {
-          uint32_t bits = 0xFu;
-          if (e_hash) bits = ((uint32_t)__builtin_amdgcn_ds_bpermute(hbp + 32 * r, (int)hw_item) >> hsh) & 0xFu;
-          pl_any = (r & 1) ? (pl_any | (~bits & 0xFu)) : (~bits & 0xFu);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float kept = ((bits >> j) & 1u) ? v[j] : -INFINITY;
-            pl_max[j] = (r & 1) ? fmaxf(pl_max[j], kept) : kept;
-          }
-        }
-        if (f_lrelu) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.01f * v[j]);
-        } else if (f_relu) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
-        if (EPI == 1) {
-          const uint32_t bits = ((uint32_t)__builtin_amdgcn_ds_bpermute(hbp + 32 * r, (int)hw_item) >> hsh) & 0xFu;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] *= __uint_as_float((bits << (30 - j)) & 0x40000000u);
-        }
-        if (!STATS) rmax = fmaxf(fmaxf(rmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        u32x4 sv = __builtin_bit_cast(u32x4, v);
-        if (EPI == 1 || EPI == 3) {
-          if constexpr (PLN) {
-            // the consumer stages by LDS-DMA: its image rows are [octet][hi | lo][x][8 halves] -- this lane's 4 channels are one half
-            // of a 16-byte entry of the hi plane and of the lo plane of octet g >> 1 (the lane pair g, g ^ 1 fills the entry)
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            f16x4 hi, lo;
-            vx_split4_s(v, hi, lo);
-            const unsigned rowB = (unsigned)a.W * 64u, plB = (unsigned)a.W * 16u;
-            int ln = lane;
-            asm volatile("" : "+v"(ln));          // (keeps this address arithmetic inside the epilogue: one register less across the matrix loop)
-            const int g_ = ln >> 4, m_ = ln & 15;
-            const unsigned pvo = (unsigned)(lz * a.H + ly0) * rowB + (unsigned)((g_ >> 1) * 2) * plB + (unsigned)(x0 + m_) * 16u + (unsigned)(g_ & 1) * 8u;
-            const unsigned pso = (unsigned)((k * TZ) * a.H + e_ty * 8 + r) * rowB + (unsigned)(e_tx * 32) * 16u;
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), osrd, (int)pvo, (int)pso, 0);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), osrd, (int)pvo, (int)(pso + plB), 0);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_nop 3" ::: "memory");      // (the store-data hazard with an SGPR soffset, below)
-            __builtin_amdgcn_sched_barrier(0);
-            continue;
-          }
-          if (a.out_split) {   // the consumer is the fused up-convolution: hand the piece over as the fp16 pairs it multiplies
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            f16x4 hi, lo;
-            vx_split4_s(v, hi, lo);      // (plain instructions: packed fp32 beside the partner wave's matrix stream costs three)
-            const u32x2 h2 = __builtin_bit_cast(u32x2, hi), l2 = __builtin_bit_cast(u32x2, lo);
-            sv = (u32x4){h2[0], h2[1], l2[0], l2[1]};
-          }
-        }
-        __builtin_amdgcn_raw_buffer_store_b128(sv, osrd, (int)ovoff0, (int)(osoff + (unsigned)r * orow), 0);
-        // gfx950 store-data hazard with an SGPR soffset (conv3d_mfma.hip)
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 3" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (POOL) {
-          if (r & 1) {
-            // a row pair is complete.  The x-neighbour (same channels) is the adjacent lane: quad_perm [1, 0, 3, 2]; even lanes
-            // store the window of their z-plane: pool_out [N][D][H/2][W/2][16], pool_flags [N][D][H/2][W/2][4] (the flag word of a
-            // 16-byte piece sits at a quarter of the piece's byte offset); odd lanes are steered out of the descriptor's range
-            const int Hp = a.H >> 1, Wp = a.W >> 1;
-            u32x4 mx;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const int o = __builtin_amdgcn_update_dpp(0, __float_as_int(pl_max[j]), 0xB1, 0xF, 0xF, true);
-              mx[j] = __float_as_uint(fmaxf(pl_max[j], __int_as_float(o)));
-            }
-            const uint32_t oany = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pl_any, 0xB1, 0xF, 0xF, true);
-            // lane part: ((lz Hp + ly0 / 2) Wp + lx / 2) 64 + 16 g bytes; scalar part: item, column, row pair
-            const unsigned pvo = (m & 1) ? VX_OOB : (unsigned)((((lz * Hp + (ly0 >> 1)) * Wp + (lx >> 1)) * 16 + oc) * 4);
-            const unsigned pso = (unsigned)(((((k * TZ) * Hp + e_ty * 4 + (r >> 1)) * Wp) + e_tx * 16) * 64);
-            __builtin_amdgcn_raw_buffer_store_b128(mx, psrd, (int)pvo, (int)pso, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(pl_any | oany, fsrd, (int)((m & 1) ? VX_OOB : (pvo >> 2)), (int)(pso >> 2), 0);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_nop 3" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
-      if (STATS && k == KZ - 1) {
-        // the column is complete for this wave: sum over its 16 voxel columns and leave the 4 x 2 values of row group g
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float s = ssum[j], q = ssq[j];
-#pragma unroll
-          for (int rot = 8; rot >= 1; rot >>= 1) { s += vx_row_ror(s, rot); q += vx_row_ror(q, rot); }
-          if (m == 0) {
-            s_red[(wave * 16 + g * 4 + j) * 2 + 0] = s;
-            s_red[(wave * 16 + g * 4 + j) * 2 + 1] = q;
-          }
-          ssum[j] = 0.f; ssq[j] = 0.f;
-        }
-      }
-    };
-
-    // statistics of a complete column: entry 0 of the column's block is real, the other stat_epc - 1 are zero
-    // (vx_instnorm_finalize sums vx_conv3d_k3_tiles_for entries per sample)
-    auto flush_col = [&](int ci) {
-      int n, ty, tx;
-      col_of(ci, n, ty, tx);
-      const auto kp = kernarg();
-      const int epc = kp->stat_epc;
-      const int ntile = cps * epc;
-      float* dst = kp->a.stats_partial + (((size_t)n * ntile + (size_t)(ty * ka.tiles_x + tx) * epc) * 16) * 2;
-      if (tid < 16) {
-        float s = 0.f, q = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          s += s_red[(w * 16 + tid) * 2 + 0];
-          q += s_red[(w * 16 + tid) * 2 + 1];
-        }
-        dst[tid * 2 + 0] = s;
-        dst[tid * 2 + 1] = q;
-      }
-      for (int i = 32 + tid; i < epc * 32; i += 256) {
-        if (tid < 256) dst[i] = 0.f;
-      }
-    };
-
-    Cur cx = {0, 0};
-    int j = 0;                                   // S_j = cx;  its slot group is j % 3
-    int grp_x = 0;
-    int prev_ci = -1, prev_k = 0;                // waves 4..7: the item still to store
-    int fl_ci = -1, fl_at = 0;                   // column whose statistics are complete after barrier fl_at
-    while (cx.ci < ncol_wg) {
-      __syncthreads();
-      ZC_STAMP(0);
-      if (STATS && fl_ci >= 0 && j >= fl_at && !late) { flush_col(fl_ci); fl_ci = -1; }
-      const bool comp = cx.s >= 1;
-      const int item_k = cx.s - 1;
-      int grp_c = grp_x + 1; if (grp_c == 3) grp_c = 0;
-      const int rb = (grp_x == 0 ? 2 : grp_x - 1) * TZ + (TZ - 2);           // first plane of the item: group of S_{j-1}, plane TZ - 2
-      if (late) {
-        if (prev_ci >= 0 && !(ZC_ABL & 2)) { epilogue(prev_ci, prev_k); prev_ci = -1; }
-        ZC_STAMP(2);
-        if (comp) { if (!(ZC_ABL & 1)) multiply(rb, cx.ci, item_k); prev_ci = cx.ci; prev_k = item_k; }
-        ZC_STAMP(1);
-      } else {
-        if (comp && !(ZC_ABL & 1)) multiply(rb, cx.ci, item_k);
-        ZC_STAMP(1);
-        if (comp && !(ZC_ABL & 2)) epilogue(cx.ci, item_k);
-        ZC_STAMP(2);
-      }
-      if (STATS && comp && item_k == KZ - 1) { fl_ci = cx.ci; fl_at = j + 2; }
-#ifdef VX_CONV_STAMPS
-      ++st_iters;
-#endif
-      advance(cx);
-      grp_x = grp_c;
-      ++j;
-    }
-    if (late && prev_ci >= 0) epilogue(prev_ci, prev_k);
-    if (STATS) {
-      __syncthreads();
-      if (fl_ci >= 0 && !late) flush_col(fl_ci);
+    if (evaluated) {
+#define ZC_CMP 0
+#include "conv3d_zc16_mult.h"
+#undef ZC_CMP
     }
   }
   if (!STATS && a.range_flag) {
@@ -1072,6 +859,36 @@ extern "C" int vx_pack_convT_zc16(const float* w_torch, float* packed, vx_stream
   if (!vx_aligned16(packed)) VX_FAIL(VX_E_ALIGN, "vx_pack_convT_zc16: packed must be 16-byte aligned");
   hipLaunchKernelGGL(pack_convT_zc16_kernel, dim3(32), dim3(256), 0, (hipStream_t)stream, w_torch, reinterpret_cast<_Float16*>(packed));
   VX_CHECK_LAUNCH("vx_pack_convT_zc16");
+  return VX_OK;
+}
+
+// upscale3 composed into expand_2_1's up half (upcompose16.h): float64 on the device, split as pack_conv3d_zc16_kernel splits
+__global__ void pack_upfused_zc16_kernel(const float* __restrict__ w1, const float* __restrict__ uw, const float* __restrict__ ub,
+                                         float* __restrict__ out) {
+  _Float16* oh = reinterpret_cast<_Float16*>(out);
+  constexpr int NWE = VX_UPC16_WHALVES / 2;      // weight elements: one thread writes an element's hi and lo
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NWE + 27 * 16; i += gridDim.x * blockDim.x) {
+    if (i < NWE) {
+      const int j = i & 7, lane = (i >> 3) & 63, tap = (i >> 9) & 7, cls = i >> 12;
+      const int co = lane & 15, ci = 8 * (lane >> 4) + j;
+      const double v = vx_upc16_weff(w1, 32, uw, cls, tap, ci, co);
+      const _Float16 h = (_Float16)(float)fmin(fmax(v, -65504.0), 65504.0);
+      const _Float16 l = (_Float16)(float)((v - (double)(float)h) * 2048.0);
+      oh[(((cls * 8 + tap) * 2 + 0) * 64 + lane) * 8 + j] = h;
+      oh[(((cls * 8 + tap) * 2 + 1) * 64 + lane) * 8 + j] = l;
+    } else {
+      const int t = i - NWE, co = t & 15, bc = t >> 4;
+      out[NWE + t] = (float)vx_upc16_btab(w1, 32, ub, bc / 9, (bc / 3) % 3, bc % 3, co);
+    }
+  }
+}
+extern "C" int64_t vx_conv3d_upfused_zc16_packed_floats(void) { return VX_UPC16_FLOATS; }
+extern "C" int vx_pack_conv3d_upfused_zc16(const float* w1_torch, const float* up_w_torch, const float* up_b, float* packed,
+                                           vx_stream_t stream) {
+  if (!w1_torch || !up_w_torch || !up_b || !packed) VX_FAIL(VX_E_NULL, "vx_pack_conv3d_upfused_zc16: null pointer");
+  if (!vx_aligned16(packed)) VX_FAIL(VX_E_ALIGN, "vx_pack_conv3d_upfused_zc16: packed must be 16-byte aligned");
+  hipLaunchKernelGGL(pack_upfused_zc16_kernel, dim3(130), dim3(256), 0, (hipStream_t)stream, w1_torch, up_w_torch, up_b, packed);
+  VX_CHECK_LAUNCH("vx_pack_conv3d_upfused_zc16");
   return VX_OK;
 }
 

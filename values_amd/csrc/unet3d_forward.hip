@@ -452,6 +452,7 @@ extern "C" int vx_unet3d_forward(const vx_unet3d_weights* w, const vx_unet3d_run
       if (f.fuse_up1) {
         b.in = p.B[l + 1]; b.up_in = p.B[l + 1]; b.up_pitch = 2 * C; b.up_w = w->up3_zc16; b.up_b = w->up_b[2];
         b.up_split = 1;
+        b.up_fused = w->up3_fused;   // (nullable) upscale3 composed into the up half's weights: same instance, composed bodies
       }
       // the planar tensor goes into the up half of CAT_l, free since upscale3 lives inside this launch (it cannot overwrite A_l
       // in place: the partial sums there have the float layout)

@@ -164,6 +164,14 @@ class UNet3D(nn.Module):
             _lib.check(lib.vx_pack_convT_zc16(_lib.ptr(sd["upscale3.weight"]), _lib.ptr(u3), st), "vx_pack_convT_zc16")
             keep.append(u3)
             w.up3_zc16 = u3.data_ptr()
+            # upscale3 composed into the up half's weights (vx_unet3d_weights.up3_fused): the level-1 launch then runs 8 K-steps
+            # over the coarse tensor instead of evaluating the transposed conv per step
+            if hasattr(lib, "vx_pack_conv3d_upfused_zc16"):      # (absent only in an A/B build of an older revision: _lib.load)
+                u3f = torch.empty(lib.vx_conv3d_upfused_zc16_packed_floats(), dtype=torch.float32, device=device)
+                _lib.check(lib.vx_pack_conv3d_upfused_zc16(_lib.ptr(w2), _lib.ptr(sd["upscale3.weight"]), _lib.ptr(sd["upscale3.bias"]),
+                                                           _lib.ptr(u3f), st), "vx_pack_conv3d_upfused_zc16")
+                keep.append(u3f)
+                w.up3_fused = u3f.data_ptr()
         fw, fb = self._head_params(sd)
         keep += [fw, fb]
         w.final_w = fw.data_ptr()
