@@ -566,6 +566,17 @@ int64_t vx_conv2d_packed_floats(int Cin, int Cout, int KS);
 int vx_pack_conv2d(const float* w_torch /* (Cout,Cin,KS,KS) */, float* w_packed, int Cin, int Cout, int KS, vx_stream_t stream);
 int vx_conv2d_tiles(int H, int W, int KS, int S); /* tiles per image (stats_partial has N * this entries) */
 int vx_conv2d(const vx_conv2d_args* a, vx_stream_t stream);
+/* Dry run of vx_conv2d: every argument check, the choice of the kernel and its launch geometry, no launch and no call into the HIP
+ * runtime (works without a GPU; the pointers are only tested for null and alignment).  Returns the VX_E_* code vx_conv2d would
+ * refuse the call with (message in vx_last_error_string), or VX_OK with the instance name vx_last_kernel_name() would report after
+ * the launch in kernel_name (nullable; at most cap bytes, always terminated) and the geometry in info (nullable). */
+typedef struct vx_conv2d_route_info {
+  int32_t nchunks;    /* work items per tile (input chunks) */
+  int32_t w_all;      /* 1: all chunks' weights stay in LDS for the kernel's life */
+  int32_t lds_bytes;  /* dynamic LDS of the launch */
+  int32_t grid_x, grid_y; /* persistent workgroups per output-channel group; output-channel groups */
+} vx_conv2d_route_info;
+int vx_conv2d_route(const vx_conv2d_args* a, char* kernel_name, int cap, vx_conv2d_route_info* info);
 
 /* K16: BatchNorm2d in training mode: partials -> scale = gamma * rstd, shift = beta - mean * scale
  * (biased variance over count = N*OH*OW, eps 1e-5; hrnet_module.py:30, BN_MOMENTUM side effect not reproduced). */

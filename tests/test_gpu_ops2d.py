@@ -12,7 +12,6 @@ import ctypes as C
 import importlib.util
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -628,32 +627,12 @@ def affine_dev(xd, c, scale, shift, relu, gi):
     return out
 
 
-def c2s_lds(ks, s, nt, nsub, oct_, nchunks):
-    """the launcher's LDS budget, restated: (bytes without weights, bytes of one chunk's weights, whether all chunks' weights
-    stay resident).  A COPY of values_amd/csrc/conv2d_s16.hip, launch_c2s: the constexpr block HX .. `rest` and the line
-    `ka.w_all = ...`; the library reports the instance name only, so that w_all 0 and 1 are both covered rests on this copy.  If
-    the launcher's LDS layout changes, the chunks / wall columns of PROLOGUE_CASES fail here: update both together."""
-    hx = hy = 15 * s + ks
-    npp = -(-hx // s) * -(-hy // s)
-    plane = r16(s * s * npp)
-    img_h = (oct_ or 2 * nsub) * plane * 8
-    nstep = ((9 * oct_ + 3) // 4 if oct_ else 5 * nsub) if ks == 3 else nsub // 2
-    tabc = r16(oct_ * 8) if oct_ else nsub * 16
-    wch = nstep * nt * 2 * 64 * 8 * 2
-    rest = img_h * 4 + 8 * nt * 16 * 2 * 4 + 2 * tabc * 4
-    return rest, wch, int(nchunks > 1 and rest + nchunks * wch <= 160 * 1024)
-
-
-def c2s_workgroups(name, cin_pad, cout, total_tiles):
-    """(chunks per tile, weights resident, workgroups per output-channel group) the launcher derives for the instance `name`: a
-    copy of vx_conv2d_s16 (nchunks) and of launch_c2s (per_cu, ygroups, gx) in values_amd/csrc/conv2d_s16.hip"""
-    ks, s, nt, nsub, _, oct_ = map(int, re.fullmatch(r"conv2d_s16_kernel<(\d+),(\d+),(\d+),(\d+),(\d+),(\d+)>", name).groups())
-    nchunks = 1 if oct_ or (ks == 3 and nsub > 1) else -(-(cin_pad // 16) // nsub)
-    rest, wch, w_all = c2s_lds(ks, s, nt, nsub, oct_, nchunks)
-    lds = rest + (nchunks if w_all else 1) * wch
-    per_cu = min(2, max(1, 160 * 1024 // lds))
-    ygroups = -(-cout // (16 * nt))
-    return nchunks, w_all, min(-(-256 * per_cu // ygroups), total_tiles)
+def conv2d_dry_run(a):
+    """vx_conv2d_route of the arguments `a`: (kernel name, nchunks, w_all, grid_x) of the launch they make"""
+    lib = _lib.load()
+    buf, info = C.create_string_buffer(128), _lib.Conv2dRouteInfo()
+    _lib.check(lib.vx_conv2d_route(C.byref(a), buf, len(buf), C.byref(info)), "vx_conv2d_route")
+    return buf.value.decode(), info.nchunks, info.w_all, info.grid_x
 
 
 def prologue_case(cin, cout, ks, s, n, h, w, *, narrow=False, gi=0, relu=True, cpitch_extra=0, tag=900, name=None, nchunks=None,
@@ -685,11 +664,13 @@ def prologue_case(cin, cout, ks, s, n, h, w, *, narrow=False, gi=0, relu=True, c
     w2 = torch.from_numpy(R.f32_tensor((cout, cin, ks, ks), tag + 4, (1.0 / (ks * ks * cin)) ** 0.5))
     pre = dict(scale=scale, shift=shift, cpitch=cpitch, gi=gi, relu=relu)
     out_pitch = r4(cout) + 8
-    fused, stf, kname = run_conv2d(y1, cin, w2, ks, s, out_pitch=out_pitch, pre=pre, fill=SENT)
+    route = []                                           # the dry run of the very arguments the launch below takes
+    fused, stf, kname = run_conv2d(y1, cin, w2, ks, s, out_pitch=out_pitch, pre=pre, fill=SENT, args_hook=lambda a: route.append(conv2d_dry_run(a)))
     if name is not None:
         assert kname == name, kname
     total_tiles = n * lib.vx_conv2d_tiles(h, w, ks, s)
-    got_chunks, got_w_all, wgs = c2s_workgroups(kname, r16(cin), cout, total_tiles)
+    dry_name, got_chunks, got_w_all, wgs = route[0]
+    assert dry_name == kname, (dry_name, kname)
     if nchunks is not None:
         assert (got_chunks, got_w_all) == (nchunks, w_all), (got_chunks, got_w_all)
     if multi_item:                                       # more tiles than workgroups: persistent workgroups take several

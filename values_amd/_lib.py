@@ -70,6 +70,11 @@ class Conv2dArgs(C.Structure):
                 ("out_scale", _p), ("out_shift", _p), ("out_add", _p), ("out_add_pitch", _i32), ("out_act", _i32)]
 
 
+class Conv2dRouteInfo(C.Structure):
+    """vx_conv2d_route_info: the launch geometry vx_conv2d_route reports."""
+    _fields_ = [("nchunks", _i32), ("w_all", _i32), ("lds_bytes", _i32), ("grid_x", _i32), ("grid_y", _i32)]
+
+
 class BnAffineItem(C.Structure):
     """vx_bn_affine_item: one BatchNorm layer of vx_bn_running_affine (running statistics -> scale / shift rows)."""
     _fields_ = [("gamma", _p), ("beta", _p), ("running_mean", _p), ("running_var", _p), ("scale", _p), ("shift", _p),
@@ -389,6 +394,7 @@ SIGNATURES = {
     "vx_pack_conv2d": (_i, [_p, _p, _i, _i, _i, _p]),
     "vx_conv2d_tiles": (_i, [_i, _i, _i, _i]),
     "vx_conv2d": (_i, [C.POINTER(Conv2dArgs), _p]),
+    "vx_conv2d_route": (_i, [C.POINTER(Conv2dArgs), C.c_char_p, _i, C.POINTER(Conv2dRouteInfo)]),
     "vx_bn_finalize": (_i, [_p, _i, _i, _i64, C.c_float, _p, _p, _p, _p, _p]),
     "vx_bn_finalize_groups": (_i, [_p, _i, _i, _i, _i, _i64, C.c_float, _p, _p, _p, _p, _p]),
     "vx_bn_running_affine": (_i, [_p, _i, C.c_float, _p]),
@@ -496,7 +502,7 @@ class config:
 
 def pack_mode():
     """The configuration fields that select the kernel family and with it the PACKED WEIGHT LAYOUT (conv_config() and
-    s16_config() in conv3d_route.h, c2_split16() in conv2d_mfma.hip).  Models key their packed-weight
+    s16_config() in conv3d_route.h, conv2d_family() in conv2d_route.h).  Models key their packed-weight
     cache on it, and every launch carries the family its weights were packed for (w_family): the library refuses a
     mismatch."""
     c = get_config()

@@ -13,22 +13,13 @@
 // Epilogue: optional bias, raw store, and per-workgroup (sum, sum of squares) partials per channel for the
 // TRAINING-mode BatchNorm that follows every conv (batch statistics over N,H,W) -- deterministic, no
 // atomics; vx_bn_finalize reduces them.
-#include "common.h"
-#include <stdlib.h>
+#include "conv2d_internal.h"
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// conv2d_s16.hip: the split-fp16 schedule (default; VX_CONV_FP32=1 selects the native-fp32 kernels of this file)
-int64_t vx_conv2d_s16_packed_floats(int Cin, int Cout, int KS);
-int vx_pack_conv2d_s16(const float* w_torch, float* w_packed, int Cin, int Cout, int KS, hipStream_t s);
-int vx_conv2d_s16(const vx_conv2d_args& a, hipStream_t s);
-int vx_conv2d_s16_row_tiles(int KS, int Cout);
-int vx_conv2d_s16_octets(int Cin, int KS);
-static inline bool c2_split16() { return vx_cfg().conv_fp32 == 0; }
-
 struct Conv2dKArgs {
   vx_conv2d_args a;
-  int OH, OW, tiles_x, tiles_y, nchunks;   // nchunks = ceil(Cin/16 / NSUB)
+  int OH, OW, tiles_x, tiles_y, nchunks;   // Conv2dRoute's (nchunks = ceil(Cin/16 / NSUB))
   unsigned mx, my;
 };
 
@@ -41,15 +32,10 @@ template <int KS, int S, int NT, int NSUB, int TY>
 __global__ __launch_bounds__(512) void conv2d_mfma_kernel(Conv2dKArgs ka) {
   constexpr int NW = 8, NTH = 512, TX = 16;
   constexpr int R = TY / NW;
-  constexpr int HX = (TX - 1) * S + KS, HY = (TY - 1) * S + KS;   // input halo tile
-  constexpr int NPAR = S * S;                                     // parity planes (stride 2: 4)
-  constexpr int PXW = (HX + S - 1) / S, PYH = (HY + S - 1) / S;   // positions per parity plane
-  constexpr int NPP = PXW * PYH;
-  constexpr int PLANE = ((NPAR * NPP + 15) / 16) * 16;            // positions per (sub, g) plane, 16-aligned
-  constexpr int IN_FLOATS = NSUB * 4 * PLANE * 4;
-  constexpr int NTAP = KS * KS;
-  constexpr int W_SUB = NTAP * NT * 64 * 4;                       // weight floats per sub-block
-  constexpr int W_FLOATS = NSUB * W_SUB;
+  // the instance's LDS layout (conv2d_route.h, where the launch geometry reads the same numbers)
+  constexpr C2Geo G = c2_geo(KS, S, NT, NSUB, TY);
+  constexpr int HX = G.t.HX, HY = G.t.HY, PXW = G.t.PXW, NPP = G.t.NPP, PLANE = G.t.PLANE;
+  constexpr int IN_FLOATS = G.IN_FLOATS, NTAP = KS * KS, W_SUB = G.W_SUB, W_FLOATS = G.W_FLOATS;
   constexpr int NPIECE = HX * HY * 4 * NSUB;                      // 16-byte pieces of the input tile
   constexpr int IN_IT = (NPIECE + NTH - 1) / NTH;
   constexpr int W_IT = (W_FLOATS / 4 + NTH - 1) / NTH;
@@ -293,15 +279,7 @@ __global__ __launch_bounds__(512) void conv2d_mfma_kernel(Conv2dKArgs ka) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct C2Cfg { int NT, NSUB, TY; };
-static inline C2Cfg c2_config(int KS, int S, int Cout) {
-  C2Cfg c;
-  c.NT = (Cout % 48 == 0) ? 3 : ((Cout % 32 == 0) ? 2 : 1);
-  c.NSUB = KS == 1 ? 4 : 1;
-  c.TY = 16;
-  return c;
-}
-
+// torch (Cout, Cin, KS, KS) fp32 -> [row group][sub-block][tap][nt][lane][4 floats]
 __global__ void pack_conv2d_kernel(const float* __restrict__ w, float* __restrict__ out, int Cin, int Cin_pad, int Cout,
                                    int KS, int NT, int64_t total) {
   const int ntap = KS * KS, nsub = Cin_pad / 16;
@@ -321,146 +299,43 @@ __global__ void pack_conv2d_kernel(const float* __restrict__ w, float* __restric
   }
 }
 
-static inline int c2_rows_padded(int Cout, int NT) { return ((Cout + 16 * NT - 1) / (16 * NT)) * (16 * NT); }
-
-// Kernel family = packed layout under the current configuration: 1 split-fp16, 2 split-fp16 with five row tiles
-// (wide 1x1 layers), 3 native fp32
-extern "C" int vx_conv2d_family(int Cin, int Cout, int KS) {
-  if (Cin <= 0 || Cout <= 0 || (KS != 1 && KS != 3)) return 0;
-  if (!c2_split16()) return 3;
-  // the packed layout is [row group][...][row tile]: bound to the tile count; + 100 x the octets of the octet-granular K
-  // schedule when the layer's REAL input channel count is packed for it (vx_conv2d_s16_octets)
-  return 10 + vx_conv2d_s16_row_tiles(KS, Cout) + 100 * vx_conv2d_s16_octets(Cin, KS);
-}
-
-extern "C" int64_t vx_conv2d_packed_floats(int Cin, int Cout, int KS) {
-  if (Cin <= 0 || Cout <= 0 || (KS != 1 && KS != 3)) return -1;
-  if (c2_split16()) return vx_conv2d_s16_packed_floats(Cin, Cout, KS);
-  const int cin_pad = (Cin + 15) / 16 * 16;
-  C2Cfg c = c2_config(KS, 1, Cout);
-  return (int64_t)c2_rows_padded(Cout, c.NT) * cin_pad * KS * KS;
-}
-
-extern "C" int vx_pack_conv2d(const float* w_torch, float* w_packed, int Cin, int Cout, int KS, vx_stream_t stream) {
-  if (!w_torch || !w_packed) VX_FAIL(VX_E_NULL, "vx_pack_conv2d: null pointer");
-  const int64_t total = vx_conv2d_packed_floats(Cin, Cout, KS);
-  if (total < 0) VX_FAIL(VX_E_SHAPE, "vx_pack_conv2d: Cin=%d Cout=%d KS=%d", Cin, Cout, KS);
-  if (c2_split16()) return vx_pack_conv2d_s16(w_torch, w_packed, Cin, Cout, KS, (hipStream_t)stream);
-  C2Cfg c = c2_config(KS, 1, Cout);
+int vx_pack_conv2d_mfma(const float* w_torch, float* w_packed, int Cin, int Cout, int KS, int64_t total, hipStream_t s) {
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_conv2d_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_torch, w_packed, Cin,
-                     (Cin + 15) / 16 * 16, Cout, KS, c.NT, total);
+  hipLaunchKernelGGL(pack_conv2d_kernel, dim3(blocks), dim3(256), 0, s, w_torch, w_packed, Cin, (int)conv2d_cin_padded(Cin), Cout, KS,
+                     c2_config(KS, Cout).NT, total);
   VX_CHECK_LAUNCH("vx_pack_conv2d");
   return VX_OK;
 }
 
-extern "C" int vx_conv2d_tiles(int H, int W, int KS, int S) {
-  const int OH = (H + 2 * (KS / 2) - KS) / S + 1, OW = (W + 2 * (KS / 2) - KS) / S + 1;
-  const int TY = 16;
-  return ((OW + 15) / 16) * ((OH + TY - 1) / TY);
-}
-
 template <int KS, int S, int NT, int NSUB, int TY>
-static int launch_c2(const Conv2dKArgs& ka, hipStream_t s) {
-  constexpr int HX = 15 * S + KS, HY = (TY - 1) * S + KS;
-  constexpr int NPP = ((HX + S - 1) / S) * ((HY + S - 1) / S);
-  constexpr int PLANE = ((S * S * NPP + 15) / 16) * 16;
-  constexpr int IN_FLOATS = NSUB * 4 * PLANE * 4;
-  constexpr int W_FLOATS = NSUB * KS * KS * NT * 64 * 4;
-  constexpr size_t lds = (size_t)(IN_FLOATS + W_FLOATS + 8 * NT * 16 * 2) * sizeof(float);
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
+static int launch_c2(const Conv2dRoute& r, const vx_conv2d_args& a, hipStream_t s) {
+  static_assert(c2_geo(KS, S, NT, NSUB, TY).lds_bytes <= C2_LDS_BYTES, "LDS budget");
+  Conv2dKArgs ka;
+  ka.a = a;
+  ka.OH = r.OH; ka.OW = r.OW; ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.nchunks = r.nchunks;
+  ka.mx = r.mx; ka.my = r.my;
+  const size_t lds = (size_t)r.lds_bytes;
+  static size_t attr_lds = 0;
   auto kern = conv2d_mfma_kernel<KS, S, NT, NSUB, TY>;
-  if (!attr_set) {
+  if (lds > attr_lds) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) VX_FAIL((int)e, "vx_conv2d: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-    attr_set = true;
+    attr_lds = lds;
   }
-  const vx_conv2d_args& a = ka.a;
-  const int total_tiles = ka.tiles_x * ka.tiles_y * a.N;
-  const int ygroups = (a.Cout + 16 * NT - 1) / (16 * NT);
-  int per_cu = (int)((160 * 1024) / lds);
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 4) per_cu = 4;
-  int gx = (256 * per_cu + ygroups - 1) / ygroups;
-  if (gx > total_tiles) gx = total_tiles;
-  static const char* kname = vx_kname("conv2d_mfma_kernel<%d,%d,%d,%d,%d>", KS, S, NT, NSUB, TY);
+  static const char* kname = vx_conv2d_kname(r);
   vx_note_kernel(kname);
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ygroups), dim3(512), lds, s, ka);
+  hipLaunchKernelGGL(kern, dim3((unsigned)r.grid_x, (unsigned)r.grid_y), dim3(512), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv2d");
   return VX_OK;
 }
 
-template <int KS, int S, int NSUB, int TY>
-static int dispatch_c2(const Conv2dKArgs& ka, int NT, hipStream_t s) {
-  if (NT == 3) return launch_c2<KS, S, 3, NSUB, TY>(ka, s);
-  if (NT == 2) return launch_c2<KS, S, 2, NSUB, TY>(ka, s);
-  return launch_c2<KS, S, 1, NSUB, TY>(ka, s);
-}
-
-extern "C" int vx_conv2d(const vx_conv2d_args* ap, vx_stream_t stream) {
-  if (!ap) VX_FAIL(VX_E_NULL, "vx_conv2d: null args");
-  const vx_conv2d_args& a = *ap;
-  if (!a.in || !a.w_packed || !a.out) VX_FAIL(VX_E_NULL, "vx_conv2d: null tensor pointer");
-  if (a.N <= 0 || a.H <= 0 || a.W <= 0) VX_FAIL(VX_E_SHAPE, "vx_conv2d: empty tensor");
-  if (a.Cin <= 0 || a.Cin % 16 || a.Cout <= 0)
-    VX_FAIL(VX_E_SHAPE, "vx_conv2d: Cin=%d must be a positive multiple of 16 (pad the input), Cout=%d positive", a.Cin, a.Cout);
-  if ((a.KS != 1 && a.KS != 3) || (a.S != 1 && a.S != 2) || (a.KS == 1 && a.S != 1))
-    VX_FAIL(VX_E_SHAPE, "vx_conv2d: kernel %d stride %d unsupported (3x3 s1/s2, 1x1 s1)", a.KS, a.S);
-  {
-    // a.Cin is the PADDED channel count; weights packed for the octet-granular schedule carry their octet count in the
-    // family (the real count was 8 oct - 7 .. 8 oct): accepted when it pads to this Cin
-    const int fam = vx_conv2d_family(a.Cin, a.Cout, a.KS), oct = a.w_family / 100;
-    const bool octet_ok = oct > 0 && c2_split16() && a.KS == 3 && (oct * 8 + 15) / 16 * 16 == a.Cin &&
-                          vx_conv2d_s16_octets(oct * 8, a.KS) == oct && a.w_family % 100 == fam % 100;
-    if (a.w_family != fam && !octet_ok)
-      VX_FAIL(VX_E_DTYPE, "vx_conv2d: weights packed for kernel family %d, the library is configured for family %d: re-pack them",
-              a.w_family, fam);
+// arguments validated and the instance chosen by conv2d_route
+int vx_conv2d_mfma_launch(const Conv2dRoute& r, const vx_conv2d_args& a, hipStream_t s) {
+  switch (conv2d_key_of(r.p)) {
+#define C2_CASE(...) case conv2d_key(__VA_ARGS__): return launch_c2<__VA_ARGS__>(r, a, s);
+    C2_INSTANCES(C2_CASE)
+#undef C2_CASE
   }
-  // outputs leave as 16-byte groups of 4 channels: a Cout that is not a multiple of 4 writes its last group up to
-  // round4(Cout) (zeros beyond Cout), which the pitch must cover
-  if (a.in_pitch <= a.Cin - 16 || a.in_pitch % 4 || a.out_pitch < a.out_coff + (a.Cout + 3) / 4 * 4 || a.out_pitch % 4 || a.out_coff % 4)
-    VX_FAIL(VX_E_ALIGN, "vx_conv2d: pitches/offsets must be multiples of 4 floats and cover the channels");
-  if (!vx_aligned16(a.in) || !vx_aligned16(a.out) || !vx_aligned16(a.w_packed) || (a.bias && !vx_aligned16(a.bias)))
-    VX_FAIL(VX_E_ALIGN, "vx_conv2d: pointers must be 16-byte aligned");
-  Conv2dKArgs ka;
-  ka.a = a;
-  ka.OH = (a.H + 2 * (a.KS / 2) - a.KS) / a.S + 1;
-  ka.OW = (a.W + 2 * (a.KS / 2) - a.KS) / a.S + 1;
-  if ((int64_t)(a.H + 2) * a.W * a.in_pitch * 4 >= (1ll << 31) || (int64_t)ka.OH * ka.OW * a.out_pitch * 4 >= (1ll << 31))
-    VX_FAIL(VX_E_SHAPE, "vx_conv2d: one image must stay below 2 GiB");
-  if ((a.in_scale == nullptr) != (a.in_shift == nullptr)) VX_FAIL(VX_E_NULL, "vx_conv2d: in_scale / in_shift must come together");
-  if (a.in_scale && (a.in_cpitch < a.Cin - 15 || a.in_group_images < 0 || !c2_split16()))
-    VX_FAIL(VX_E_SHAPE, "vx_conv2d: the input prologue needs rows of in_cpitch >= the real channel count and the split-fp16 "
-            "kernels (vx_config.conv_fp32 = 0)");
-  // output epilogue (fixed affine + residual + ReLU as the conv stores): refused before any launch where it has no meaning
-  if ((a.out_scale == nullptr) != (a.out_shift == nullptr)) VX_FAIL(VX_E_NULL, "vx_conv2d: out_scale / out_shift must come together");
-  if (!a.out_scale && a.out_add) VX_FAIL(VX_E_NULL, "vx_conv2d: out_add needs out_scale / out_shift (the output epilogue)");
-  if (!a.out_scale && a.out_act != VX_ACT_NONE) VX_FAIL(VX_E_DTYPE, "vx_conv2d: out_act needs out_scale / out_shift (the output epilogue)");
-  if (a.out_scale) {
-    if (a.stats_partial)
-      VX_FAIL(VX_E_DTYPE, "vx_conv2d: out_scale together with stats_partial (batch statistics belong to the raw output, which the "
-              "epilogue does not write)");
-    if (!c2_split16())
-      VX_FAIL(VX_E_DTYPE, "vx_conv2d: the output epilogue (out_scale) needs the split-fp16 kernels (vx_config.conv_fp32 = 0): run "
-              "the raw conv and vx_affine_gather");
-    if (a.out_act != VX_ACT_NONE && a.out_act != VX_ACT_RELU) VX_FAIL(VX_E_DTYPE, "vx_conv2d: out_act must be none or relu");
-    if (a.out_add && (a.out_add_pitch % 4 || a.out_add_pitch < (a.Cout + 3) / 4 * 4))
-      VX_FAIL(VX_E_ALIGN, "vx_conv2d: out_add_pitch must be a multiple of 4 floats and cover the channels");
-    if (a.out_add && (int64_t)ka.OH * ka.OW * a.out_add_pitch * 4 >= (1ll << 31))
-      VX_FAIL(VX_E_SHAPE, "vx_conv2d: one image of out_add must stay below 2 GiB");
-    if (!vx_aligned16(a.out_add)) VX_FAIL(VX_E_ALIGN, "vx_conv2d: out_add must be 16-byte aligned");
-  }
-  if (c2_split16()) return vx_conv2d_s16(a, (hipStream_t)stream);
-  C2Cfg c = c2_config(a.KS, a.S, a.Cout);
-  ka.tiles_x = (ka.OW + 15) / 16;
-  ka.tiles_y = (ka.OH + c.TY - 1) / c.TY;
-  ka.nchunks = (a.Cin / 16 + c.NSUB - 1) / c.NSUB;
-  ka.mx = (unsigned)((1ull << 32) / (unsigned)ka.tiles_x) + 1u;
-  ka.my = (unsigned)((1ull << 32) / (unsigned)ka.tiles_y) + 1u;
-  hipStream_t s = (hipStream_t)stream;
-  if (a.KS == 3 && a.S == 1) return dispatch_c2<3, 1, 1, 16>(ka, c.NT, s);
-  if (a.KS == 3 && a.S == 2) return dispatch_c2<3, 2, 1, 16>(ka, c.NT, s);
-  return dispatch_c2<1, 1, 4, 16>(ka, c.NT, s);
+  VX_FAIL(VX_E_SHAPE, "vx_conv2d: no such instance");
 }

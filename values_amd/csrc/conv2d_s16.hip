@@ -10,55 +10,19 @@
 //   weights:      [row group][chunk][step][row tile][hi | lo][lane][8 halves]
 // Everything else (work items, register prefetch, stride-2 parity planes, epilogue with BatchNorm batch-statistics
 // partials) is conv2d_mfma.hip's.
-#include "common.h"
-#include <stdlib.h>
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+#include "conv2d_internal.h"
+#include "s16_common.h"
 
 struct Conv2dSArgs {
   vx_conv2d_args a;
-  int OH, OW, tiles_x, tiles_y, nchunks;   // nchunks = ceil(Cin/16 / NSUB)
-  int w_all;                               // every chunk's weights stay in LDS for the kernel's life (launch_c2s: they fit)
+  int OH, OW, tiles_x, tiles_y, nchunks;   // Conv2dRoute's (nchunks: work items per tile)
+  int w_all;                               // every chunk's weights stay in LDS for the kernel's life (conv2d_route: they fit)
   unsigned mx, my;
 };
 
 namespace {
 constexpr unsigned K_OOB = 0xFFFFFFF0u;
 constexpr unsigned K_NUMREC = 0x80000000u;
-
-__device__ __forceinline__ void split4(const f32x4 v, f16x4& hi, f16x4& lo) {   // conv3d_s16.hip: vx_split4
-#pragma unroll
-  for (int j = 0; j < 4; j += 2) {
-    const f32x2 x = {v[j], v[j + 1]};
-    const f16x2 h = __builtin_convertvector(x, f16x2);
-    // lo = fp16(2048 x - 2048 hi): one mixed-precision fma per element (same bits as the cvt / sub / mul / cvt form)
-    const f32x2 xs = x * 2048.f;
-    const float m2048 = -2048.f;
-    const uint32_t hv = __builtin_bit_cast(uint32_t, h);
-    uint32_t lv = 0;
-    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(lv) : "v"(hv), "v"(m2048), "v"(xs[0]));
-    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lv) : "v"(hv), "v"(m2048), "v"(xs[1]));
-    const f16x2 l = __builtin_bit_cast(f16x2, lv);
-    hi[j] = h[0]; hi[j + 1] = h[1];
-    lo[j] = l[0]; lo[j + 1] = l[1];
-  }
-}
-}
-
-// lane i of every 16-lane row <- lane (i + rot) % 16 of the same row (DPP; conv3d_s16.hip: vx_row_ror)
-__device__ __forceinline__ float row_ror(float x, int rot) {
-  const int v = __builtin_bit_cast(int, x);
-  int r;
-  switch (rot) {
-    case 8: r = __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, true); break;
-    case 4: r = __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, true); break;
-    case 2: r = __builtin_amdgcn_update_dpp(0, v, 0x122, 0xF, 0xF, true); break;
-    default: r = __builtin_amdgcn_update_dpp(0, v, 0x121, 0xF, 0xF, true); break;
-  }
-  return __builtin_bit_cast(float, r);
 }
 
 // OCT > 0 (3x3 only, round 3): OCTET-granular K.  The legacy schedule spends a K = 32 step on two taps x one 16-channel
@@ -75,20 +39,12 @@ template <int KS, int S, int NT, int NSUB, int TY, int OCT = 0, bool EPI = false
 __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
   constexpr int NW = 8, NTH = 512, TX = 16;
   constexpr int R = TY / NW;
-  constexpr int HX = (TX - 1) * S + KS, HY = (TY - 1) * S + KS;   // input halo tile
-  constexpr int NPAR = S * S;                                     // parity planes (stride 2: 4)
-  constexpr int PXW = (HX + S - 1) / S, PYH = (HY + S - 1) / S;   // positions per parity plane
-  constexpr int NPP = PXW * PYH;
-  constexpr int PLANE = ((NPAR * NPP + 15) / 16) * 16;            // positions per (sub, octet) plane, 16-aligned
   static_assert(OCT == 0 || (KS == 3 && NSUB == 1), "octet-granular K: 3x3 layers, one item per tile");
-  constexpr int NOCTP = OCT ? OCT : 2 * NSUB;                     // octet planes of the LDS image
-  constexpr int QPP = 2 * NOCTP;                                  // 16-byte quads staged per pixel
-  constexpr int IMG_H = NOCTP * PLANE * 8;                        // halves per precision plane
-  constexpr int IN_FLOATS = IMG_H;                                // (hi + lo planes = 2 * IMG_H halves = IMG_H floats)
-  constexpr int NSTEP = KS == 3 ? (OCT ? (9 * OCT + 3) / 4 : 5 * NSUB) : NSUB / 2;   // K = 32 steps per item
-  constexpr int TABC = OCT ? ((OCT * 8 + 15) / 16) * 16 : NSUB * 16;                 // channels of the prologue table
-  constexpr int W_STEP = NT * 2 * 64 * 8;                         // weight halves per step
-  constexpr int W_FLOATS = NSTEP * W_STEP / 2;                    // per item (chunk), in floats
+  // the instance's LDS layout and K steps (conv2d_route.h, where the launch geometry reads the same numbers)
+  constexpr C2SGeo G = c2s_geo(KS, S, NT, NSUB, TY, OCT, EPI);
+  constexpr int HX = G.t.HX, HY = G.t.HY, PXW = G.t.PXW, NPP = G.t.NPP, PLANE = G.t.PLANE;
+  constexpr int QPP = 2 * G.NOCTP;                                // 16-byte quads staged per pixel
+  constexpr int IMG_H = G.IMG_H, IN_FLOATS = G.IMG_H, NSTEP = G.NSTEP, TABC = G.TABC, W_STEP = G.W_STEP, W_FLOATS = G.W_FLOATS;
   static_assert(KS == 3 || NSUB % 2 == 0, "1x1: sub-blocks are consumed in pairs");
   constexpr int NPIECE = HX * HY * QPP;                           // 16-byte pieces of the input tile
   constexpr int IN_IT = (NPIECE + NTH - 1) / NTH;
@@ -179,7 +135,7 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
   };
 
   const float* w_cg = a.w_packed + (size_t)cg * ka.nchunks * W_FLOATS;
-  // whole-Cin items (3x3, NSUB > 1: vx_conv2d_s16 runs them with ONE chunk): the weights are copied once, no weight
+  // whole-Cin items (3x3, NSUB > 1: conv2d_route runs them with ONE chunk): the weights are copied once, no weight
   // prefetch registers live across the multiply phase
   constexpr bool WRES = (KS == 3 && NSUB > 1) || OCT > 0;
   f32x4 ibuf[IN_IT], wbuf[WRES ? 1 : W_IT];
@@ -268,7 +224,7 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
           }
           ibuf[it] = v;
         }
-        split4(ibuf[it], hi, lo);
+        vx_split4(ibuf[it], hi, lo);
         *reinterpret_cast<f16x4*>(s_hi + (ldst[it] & 0xFFFFFF)) = hi;
         *reinterpret_cast<f16x4*>(s_lo + (ldst[it] & 0xFFFFFF)) = lo;
       }
@@ -485,7 +441,7 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
           for (int j = 0; j < 4; ++j) {
             float s = ssum[nt][j], q = ssq[nt][j];
 #pragma unroll
-            for (int rot = 8; rot >= 1; rot >>= 1) { s += row_ror(s, rot); q += row_ror(q, rot); }
+            for (int rot = 8; rot >= 1; rot >>= 1) { s += vx_row_ror(s, rot); q += vx_row_ror(q, rot); }
             if (m == 0) {
               s_red[((wave * NT + nt) * 16 + g * 4 + j) * 2 + 0] = s;
               s_red[((wave * NT + nt) * 16 + g * 4 + j) * 2 + 1] = q;
@@ -505,47 +461,11 @@ __global__ __launch_bounds__(512) void conv2d_s16_kernel(Conv2dSArgs ka) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct C2SCfg { int NT, NSUB, TY; };
-static inline C2SCfg c2s_config(int KS, int S, int Cout) {
-  C2SCfg c;
-  // row tiles (16 output channels each) per workgroup: every workgroup of a row group stages the SAME input tile and
-  // reads the same image fragments, so fewer groups are better as long as the padding they need (rows beyond Cout hold
-  // zero weights and are not stored) costs less: minimise groups x (staging + tiles) with the staging of a 1x1 layer
-  // weighing ~3 tiles of products and that of a 3x3 layer ~0.7.  HRNet-W18: 18 -> 2 tiles, 36 -> 3, 72 -> 5, 144 -> 3 x 3,
-  // the 270 -> 270 head conv 4 groups of 5 (it ran as 17 groups of one tile: 4.8 ms of a 43 ms step); W48: 48 / 96 /
-  // 192 / 384 -> 3 tiles, the 720 -> 720 head conv 9 x 5.  Five tiles only on 1x1 layers: the 3x3 instance needs 256
-  // VGPRs plus scratch.
-  const int r16 = (Cout + 15) / 16;
-  const float cs = KS == 1 ? 3.0f : 0.7f;
-  float bestc = 1e30f;
-  c.NT = 1;
-  for (int nt : {1, 2, 3, 5}) {
-    if (nt == 5 && KS == 3) continue;   // 3x3 with five tiles: 256 VGPRs and scratch
-    const float cost = (float)((r16 + nt - 1) / nt) * (cs + (float)nt);
-    if (cost < bestc) { bestc = cost; c.NT = nt; }   // ties: the smaller tile count (less padding)
-  }
-  c.NSUB = KS == 1 ? 4 : 1;
-  c.TY = 16;
-  return c;
-}
-int vx_conv2d_s16_row_tiles(int KS, int Cout) { return c2s_config(KS, 1, Cout).NT; }
-// octets of the octet-granular K schedule (conv2d_s16_kernel's OCT) a 3x3 layer of Cin REAL input channels is packed for;
-// 0 = the sub-block schedule.  1: up to 8 channels (the image: 3 instead of 5 K steps); 3: 17..24 channels (HRNet-W18's
-// full-resolution branch: 7 instead of 10).  Two octets are one sub-block (the same 5 steps), 4 and 6 save one step of 10 /
-// 15, and five octets (36 channels) would save 3 of 15 but do not fit beside the stride-2 parity planes: not built.
-int vx_conv2d_s16_octets(int Cin, int KS) {
-  if (KS != 3 || vx_cfg().c2s_no_oct) return 0;
-  if (Cin <= 8) return 1;
-  if (Cin > 16 && Cin <= 24) return 3;
-  return 0;
-}
-static inline int c2s_rows_padded(int Cout, int NT) { return ((Cout + 16 * NT - 1) / (16 * NT)) * (16 * NT); }
-
 // torch (Cout, Cin, KS, KS) fp32 -> [row group][chunk][step][nt][hi | lo][lane][8 halves]; OCT > 0: one chunk, k-group kg of
 // step s = unit u = 4 s + kg -> (tap u / OCT, octet u % OCT), units beyond 9 OCT are zeros
 __global__ void pack_conv2d_s16_kernel(const float* __restrict__ w, _Float16* __restrict__ out, int Cin, int Cout, int KS,
                                        int NT, int NSUB, int nchunks, int64_t total, int OCT) {
-  const int nstep = OCT ? (9 * OCT + 3) / 4 : (KS == 3 ? 5 * NSUB : NSUB / 2), ntap = KS * KS;
+  const int nstep = c2s_nstep(KS, NSUB, OCT), ntap = KS * KS;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t r = i;
     const int j = r % 8; r /= 8;
@@ -574,42 +494,26 @@ __global__ void pack_conv2d_s16_kernel(const float* __restrict__ w, _Float16* __
   }
 }
 
-int64_t vx_conv2d_s16_packed_floats(int Cin, int Cout, int KS) {
-  const C2SCfg c = c2s_config(KS, 1, Cout);
-  const int oct = vx_conv2d_s16_octets(Cin, KS);
-  const int nsub_all = (Cin + 15) / 16, nchunks = oct ? 1 : (nsub_all + c.NSUB - 1) / c.NSUB;
-  const int nstep = oct ? (9 * oct + 3) / 4 : (KS == 3 ? 5 * c.NSUB : c.NSUB / 2);
-  return (int64_t)(c2s_rows_padded(Cout, c.NT) / 16 / c.NT) * nchunks * nstep * c.NT * 2 * 64 * 8 / 2;
-}
-
-int vx_pack_conv2d_s16(const float* w_torch, float* w_packed, int Cin, int Cout, int KS, hipStream_t s) {
-  const C2SCfg c = c2s_config(KS, 1, Cout);
-  const int oct = vx_conv2d_s16_octets(Cin, KS);
-  const int nsub_all = (Cin + 15) / 16, nchunks = oct ? 1 : (nsub_all + c.NSUB - 1) / c.NSUB;
-  const int64_t total = vx_conv2d_s16_packed_floats(Cin, Cout, KS) * 2;
+int vx_pack_conv2d_s16(const float* w_torch, float* w_packed, int Cin, int Cout, int KS, const C2SPack& k, hipStream_t s) {
+  const int64_t total = k.floats * 2;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(pack_conv2d_s16_kernel, dim3(blocks), dim3(256), 0, s, w_torch, reinterpret_cast<_Float16*>(w_packed), Cin,
-                     Cout, KS, c.NT, c.NSUB, nchunks, total, oct);
+                     Cout, KS, k.NT, k.NSUB, k.nchunks, total, k.OCT);
   VX_CHECK_LAUNCH("vx_pack_conv2d(s16)");
   return VX_OK;
 }
 
-template <int KS, int S, int NT, int NSUB, int TY, int OCT = 0, bool EPI = false>
-static int launch_c2s(const Conv2dSArgs& ka_in, hipStream_t s) {
-  constexpr int HX = 15 * S + KS, HY = (TY - 1) * S + KS;
-  constexpr int NPP = ((HX + S - 1) / S) * ((HY + S - 1) / S);
-  constexpr int PLANE = ((S * S * NPP + 15) / 16) * 16;
-  constexpr int IMG_H = (OCT ? OCT : 2 * NSUB) * PLANE * 8;
-  constexpr int NSTEP = KS == 3 ? (OCT ? (9 * OCT + 3) / 4 : 5 * NSUB) : NSUB / 2;
-  constexpr int TABC = OCT ? ((OCT * 8 + 15) / 16) * 16 : NSUB * 16;
-  constexpr size_t wch = (size_t)NSTEP * NT * 2 * 64 * 8 * 2;
-  constexpr size_t rest = (size_t)IMG_H * 4 + (size_t)8 * NT * 16 * 2 * 4 + (size_t)2 * TABC * 4 +   // image, statistics, prologue table,
-                          (EPI ? (size_t)2 * NT * 16 * 4 : 0);                                       // epilogue table
-  static_assert(rest + wch <= 160 * 1024, "LDS budget");
-  Conv2dSArgs ka = ka_in;
-  ka.w_all = (ka.nchunks > 1 && rest + ka.nchunks * wch <= 160 * 1024) ? 1 : 0;
-  const size_t lds = rest + (ka.w_all ? ka.nchunks : 1) * wch;
+template <int KS, int S, int NT, int NSUB, int TY, int OCT, bool EPI>
+static int launch_c2s(const Conv2dRoute& r, const vx_conv2d_args& a, hipStream_t s) {
+  constexpr C2SGeo G = c2s_geo(KS, S, NT, NSUB, TY, OCT, EPI);
+  static_assert(G.rest_bytes + G.w_bytes <= (size_t)C2_LDS_BYTES, "LDS budget");
+  Conv2dSArgs ka;
+  ka.a = a;
+  ka.OH = r.OH; ka.OW = r.OW; ka.tiles_x = r.tiles_x; ka.tiles_y = r.tiles_y; ka.nchunks = r.nchunks;
+  ka.w_all = r.w_all;
+  ka.mx = r.mx; ka.my = r.my;
+  const size_t lds = (size_t)r.lds_bytes;
   static size_t attr_lds = 0;
   auto kern = conv2d_s16_kernel<KS, S, NT, NSUB, TY, OCT, EPI>;
   if (lds > attr_lds) {
@@ -617,68 +521,20 @@ static int launch_c2s(const Conv2dSArgs& ka_in, hipStream_t s) {
     if (e != hipSuccess) VX_FAIL((int)e, "vx_conv2d(s16): hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
     attr_lds = lds;
   }
-  const vx_conv2d_args& a = ka.a;
-  const int total_tiles = ka.tiles_x * ka.tiles_y * a.N;
-  const int ygroups = (a.Cout + 16 * NT - 1) / (16 * NT);
-  int per_cu = (int)((160 * 1024) / lds);
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 2) per_cu = 2;
-  int gx = (256 * per_cu + ygroups - 1) / ygroups;
-  if (gx > total_tiles) gx = total_tiles;
-  // every template argument, defaulted ones included: the list rocprofv3 prints for the instance
-  // (the epilogue instances carry a seventh argument, 1; the others keep the six-argument name they always reported)
-  static const char* kname = EPI ? vx_kname("conv2d_s16_kernel<%d,%d,%d,%d,%d,%d,1>", KS, S, NT, NSUB, TY, OCT)
-                                 : vx_kname("conv2d_s16_kernel<%d,%d,%d,%d,%d,%d>", KS, S, NT, NSUB, TY, OCT);
+  static const char* kname = vx_conv2d_kname(r);
   vx_note_kernel(kname);
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ygroups), dim3(512), lds, s, ka);
+  hipLaunchKernelGGL(kern, dim3((unsigned)r.grid_x, (unsigned)r.grid_y), dim3(512), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv2d(s16)");
   return VX_OK;
 }
 
-template <int KS, int S, int NSUB, int TY, int OCT, bool EPI>
-static int dispatch_c2s_e(const Conv2dSArgs& ka, int NT, hipStream_t s) {
-  if constexpr (KS == 1) {
-    if (NT == 5) return launch_c2s<KS, S, 5, NSUB, TY, OCT, EPI>(ka, s);
+// arguments validated and the instance chosen by conv2d_route
+int vx_conv2d_s16_launch(const Conv2dRoute& r, const vx_conv2d_args& a, hipStream_t s) {
+  switch (conv2d_key_of(r.p)) {
+#define C2S_CASE(KS, S, NT, NSUB, TY, OCT, EPI) \
+  case conv2d_key(KS, S, NT, NSUB, TY, OCT, EPI): return launch_c2s<KS, S, NT, NSUB, TY, OCT, EPI != 0>(r, a, s);
+    C2S_INSTANCES(C2S_CASE)
+#undef C2S_CASE
   }
-  if (NT == 3) return launch_c2s<KS, S, 3, NSUB, TY, OCT, EPI>(ka, s);
-  if (NT == 2) return launch_c2s<KS, S, 2, NSUB, TY, OCT, EPI>(ka, s);
-  return launch_c2s<KS, S, 1, NSUB, TY, OCT, EPI>(ka, s);
-}
-// every instance family exists with and without the output epilogue (vx_conv2d_args.out_scale)
-template <int KS, int S, int NSUB, int TY, int OCT = 0>
-static int dispatch_c2s(const Conv2dSArgs& ka, int NT, hipStream_t s) {
-  if (ka.a.out_scale) return dispatch_c2s_e<KS, S, NSUB, TY, OCT, true>(ka, NT, s);
-  return dispatch_c2s_e<KS, S, NSUB, TY, OCT, false>(ka, NT, s);
-}
-
-// arguments validated by vx_conv2d (conv2d_mfma.hip)
-int vx_conv2d_s16(const vx_conv2d_args& a, hipStream_t s) {
-  Conv2dSArgs ka;
-  ka.a = a;
-  ka.OH = (a.H + 2 * (a.KS / 2) - a.KS) / a.S + 1;
-  ka.OW = (a.W + 2 * (a.KS / 2) - a.KS) / a.S + 1;
-  const C2SCfg c = c2s_config(a.KS, a.S, a.Cout);
-  ka.tiles_x = (ka.OW + 15) / 16;
-  ka.tiles_y = (ka.OH + c.TY - 1) / c.TY;
-  ka.nchunks = (a.Cin / 16 + c.NSUB - 1) / c.NSUB;
-  ka.mx = (unsigned)((1ull << 32) / (unsigned)ka.tiles_x) + 1u;
-  ka.my = (unsigned)((1ull << 32) / (unsigned)ka.tiles_y) + 1u;
-  // 3x3 layers of 2 / 3 input sub-blocks (HRNet: 18 / 36 / 48 channels): ONE item per tile with all sub-blocks staged
-  // together -- a third / half of the barriers, prefetches and commits, and the weights resident.  The packed layout does
-  // not change ([chunk][step] with five steps per sub-block is the same sequence either way).  Stride 2 with three
-  // sub-blocks does not fit (120 KB of parity planes + 92 KB of weights).
-  const int oct = a.w_family / 100;     // octet-granular K: the weights were packed for it (vx_conv2d checked the family)
-  if (oct) {
-    ka.nchunks = 1;
-    if (oct == 1) return a.S == 1 ? dispatch_c2s<3, 1, 1, 16, 1>(ka, c.NT, s) : dispatch_c2s<3, 2, 1, 16, 1>(ka, c.NT, s);
-    return a.S == 1 ? dispatch_c2s<3, 1, 1, 16, 3>(ka, c.NT, s) : dispatch_c2s<3, 2, 1, 16, 3>(ka, c.NT, s);
-  }
-  const int nsub = a.Cin / 16;
-  if (a.KS == 3 && a.S == 1 && !vx_cfg().c2s_no_wide && (nsub == 2 || nsub == 3)) {
-    ka.nchunks = 1;
-    return nsub == 2 ? dispatch_c2s<3, 1, 2, 16>(ka, c.NT, s) : dispatch_c2s<3, 1, 3, 16>(ka, c.NT, s);
-  }
-  if (a.KS == 3 && a.S == 1) return dispatch_c2s<3, 1, 1, 16>(ka, c.NT, s);
-  if (a.KS == 3 && a.S == 2) return dispatch_c2s<3, 2, 1, 16>(ka, c.NT, s);
-  return dispatch_c2s<1, 1, 4, 16>(ka, c.NT, s);
+  VX_FAIL(VX_E_SHAPE, "vx_conv2d(s16): no such instance");
 }
