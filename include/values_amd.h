@@ -895,6 +895,29 @@ int vx_toy_segment(const double* x, int64_t n, const double* thresholds /* host 
                    vx_stream_t stream);
 int vx_toy_noise(double* x, int64_t n, uint32_t seed, uint32_t stream_index, double noise_prob, vx_stream_t stream);
 
+/* K44: triangle meshes to a label volume, the toy generator's first step (the reference's meshes_to_numpy,
+ * datasets/toy_data_generation/stl_to_nifty.py:82-90) under this project's own rule (values_amd/stl.py, voxelize.hip,
+ * DESIGN 4.53).  Caller-owned memory and an explicit stream; nothing is uploaded (origin, h, dims and the mesh offsets
+ * travel as kernel arguments), so the call is capturable.
+ * vx_voxelize_meshes: tris holds the float32 triangles [n_tri][vertex 3][xyz 3] of all meshes, mesh m being triangles
+ *   [mesh_offsets[m], mesh_offsets[m + 1]).  Voxel (k, j, i) of out [n_z][n_y][n_x] has the sample point
+ *   c_a(t) = origin_a + (t + 0.5) * h (float64, in that order) and is inside mesh m when an odd number of m's triangles are
+ *   hit by the column (c_x(i), c_y(j)) at a depth z_hit < c_z(k).  out = 0 outside all meshes, m + 1 inside mesh m, later
+ *   meshes overwriting earlier ones.  A triangle (float32 widened to float64) is hit when its projected area
+ *   E(v0, v1; v2) is not 0, the column lies in its closed xy box, and for each edge (v1,v2), (v2,v0), (v0,v1) the
+ *   weight w_e = Ec * m is > 0, or == 0 with m > 0, where Ec = (q.x - p.x) * (s.y - p.y) - (q.y - p.y) * (s.x - p.x) on the
+ *   endpoints ordered p < q by (x, then y) and m = sign(area) * (the edge came as (q, p) ? -1 : +1): a point on an edge
+ *   belongs to the triangle on the positive side of the ordered edge, so a closed mesh is crossed an even number of
+ *   times by every column.  z_hit = ((w0 z0 + w1 z1) + w2 z2) / ((w0 + w1) + w2).  Every operation is rounded once to
+ *   float64: no FMA, no reassociation.  *odd_columns (device, zeroed by the call) = the number of (mesh, column) pairs
+ *   hit an odd number of times: 0 for closed meshes; integer atomics, exact.
+ *   Refused before any device call: a null pointer (VX_E_NULL); n_meshes outside 1..16, a dimension outside 1..1024,
+ *   n_tri outside 1..2^20, offsets not increasing from 0 to n_tri, h not finite and positive, a non-finite origin
+ *   (VX_E_SHAPE); a pointer off its element alignment (VX_E_ALIGN). */
+int vx_voxelize_meshes(const float* tris /* device [n_tri][3][3] */, const int64_t* mesh_offsets /* host [n_meshes + 1] */,
+                       int n_meshes, const double* origin /* host [3] xyz */, double h, const int32_t* dims /* host [3]: n_z, n_y, n_x */,
+                       float* out /* device [n_z][n_y][n_x] */, int64_t* odd_columns /* device (1,) */, vx_stream_t stream);
+
 /* K43: preprocessing of the GTA / Cityscapes 2D data sets (datasets/gta_cityscapes/preprocess_gta_cityscapes.py:128-174)
  * for a whole batch of decoded images and label files, where vx_png_unfilter left them (preprocess2d.hip).
  * vx_crop_resize_batched: per item, the box [y0, y0 + crop_h) x [x0, x0 + crop_w) of the source [H][W][bpp] (uint8, C

@@ -10,3 +10,4 @@ from .sliding import predict_image_sliding  # noqa: F401
 from .preprocess import load_cases_device, preprocess_dataset  # noqa: F401
 from .preprocess2d import preprocess_dataset_2d, preprocess_images_device  # noqa: F401
 from .toydata import generate_toy_dataset  # noqa: F401
+from .stl import generate_toy_dataset_from_config  # noqa: F401

@@ -380,6 +380,7 @@ SIGNATURES = {
     "vx_order_stats_f64": (_i, [_p, _i64, C.POINTER(_i64), _i, _p, _p, _p, _i64, _p]),
     "vx_toy_segment": (_i, [_p, _i64, C.POINTER(C.c_double), _i, _p, _p]),
     "vx_toy_noise": (_i, [_p, _i64, _u32, _u32, C.c_double, _p]),
+    "vx_voxelize_meshes": (_i, [_p, C.POINTER(_i64), _i, C.POINTER(C.c_double), C.c_double, C.POINTER(_i32), _p, _p, _p]),
     "vx_mask_agreement": (_i, [_p, _i, _i, _i64, _p, _p]),
     "vx_mask_agreement_batched": (_i, [_p, _i, _i, _i, _i64, _i, _p, _p]),
     "vx_soft_metric_workspace_bytes": (_i64, [_i, _i]),

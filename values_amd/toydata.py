@@ -11,8 +11,13 @@ results.MapsWriter, so sample i is written while sample i + 1 is computed.
 
 Pinned: the blur to scipy.ndimage.gaussian_filter bit for bit; the placements, flips and gray values to the reference's
 calls on Python's `random` for the same seed and object shapes; the thresholds to np.quantile in float64.
-Not pinned: the STL voxeliser (numpy-stl and stltovoxel are absent: `object_fn(resolution)` stands for meshes_to_numpy),
-SimpleITK's header bytes (the files are nifti.save's), and, on the device route, numpy's noise stream: the noise is
+The object of a sample comes from `object_fn(resolution)`: stl.mesh_object(input_files) voxelises the reference's STL
+meshes (meshes_to_numpy) under this project's own rule, on the host or, with device_io, on the device, where the
+volume stays as a tensor from the voxeliser to the embed (stl.py, voxelize.hip, DESIGN 4.53);
+stl.generate_toy_dataset_from_config runs one of the reference's JSON configs.  sphere_object / box_object are
+mesh-free stand-ins.
+Not pinned: parity of the voxeliser with stl-to-voxel 0.9.1 (numpy-stl and stltovoxel are absent; that package paints
+the perimeter of each slice, so its surface voxels are fatter and its shape may differ by one), SimpleITK's header bytes (the files are nifti.save's), and, on the device route, numpy's noise stream: the noise is
 drawn by this library's generator from (seed, sample index, voxel), so a data set generated here has other noise values
 than the reference's for the same seed -- the same distribution, not the same numbers.
 """
@@ -30,7 +35,11 @@ from .thresholds import _lerp
 
 
 # ---------------------------------------------------------------------------------------------
-# objects (stand-ins for meshes_to_numpy: float32 occupancy volumes of about `resolution` voxels per axis)
+# objects (mesh-free stand-ins for meshes_to_numpy: float32 occupancy volumes of about `resolution` voxels per axis)
+
+def _is_tensor(obj):
+    return type(obj).__module__.split(".")[0] == "torch"
+
 
 def sphere_object(resolution: int):
     r = int(resolution)
@@ -50,7 +59,7 @@ def box_object(resolution: int):
 
 def plan_samples(object_fn, n_samples, image_size, min_object_ratio=10, max_object_ratio=2, object_over_border=False,
                  object_gray=False, seed=22):
-    """-> one dict per sample: object (float32), offset, image_size, negative (which embed function), fliplr, flipud,
+    """-> one dict per sample: object (float32 array, or the device tensor object_fn returned), offset, image_size, negative (which embed function), fliplr, flipud,
     gray (None: the object keeps its values).  Seeds Python's `random` as the reference's __main__ does."""
     image_size = (int(image_size),) * 3 if np.isscalar(image_size) else tuple(int(s) for s in image_size)
     if len(image_size) != 3:
@@ -59,7 +68,8 @@ def plan_samples(object_fn, n_samples, image_size, min_object_ratio=10, max_obje
     plan = []
     for _ in range(n_samples):
         resolution = random.randint(int(max(image_size) / min_object_ratio), int(max(image_size) / max_object_ratio))
-        obj = np.asarray(object_fn(resolution))
+        obj = object_fn(resolution)
+        obj = obj if _is_tensor(obj) else np.asarray(obj)   # a device tensor stays where it is: only its shape is used here
         max_offset = [image_size[a] - obj.shape[a] for a in range(3)]
         item = {"object": obj, "image_size": image_size, "negative": bool(object_over_border), "fliplr": False, "flipud": False,
                 "gray": None}
@@ -196,7 +206,10 @@ def embed_device(item, device=None):
     import torch
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    obj = torch.from_numpy(np.ascontiguousarray(item["object"], dtype=np.float32)).to(dev)
+    if _is_tensor(item["object"]):
+        obj = item["object"].to(device=dev, dtype=torch.float32).contiguous()   # the voxeliser's tensor: no host round trip
+    else:
+        obj = torch.from_numpy(np.ascontiguousarray(item["object"], dtype=np.float32)).to(dev)
     image = torch.empty(tuple(item["image_size"]), dtype=torch.float64, device=dev)
     gray = 1.0 if item["gray"] is None else float(item["gray"])
     _lib.check(_lib.load().vx_toy_embed(_lib.ptr(obj), _dims(obj.shape), _dims(item["offset"]), gray, int(item["flipud"]),
