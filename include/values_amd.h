@@ -415,7 +415,10 @@ typedef struct vx_norm_args {
                                  itself, vx_conv3d_args.in_mean) */
   const uint32_t* seed_dev;   /* as in vx_conv3d_args */
   uint32_t* range_flag;       /* nullable, as in vx_conv3d_args: set where this pass does NOT normalise (do_instancenorm=False:
-                                 the first layer's activation / dropout pass feeds a split-fp16 conv un-normalised) */
+                                 the first layer's activation / dropout pass feeds a split-fp16 conv un-normalised).  The
+                                 per-sample kernels report the largest |stored value| (the dropout's 2 included, a dropped
+                                 element counts as 0); vx_norm_act_drop_pool_bcast without pooling reports twice the largest
+                                 |activation| whatever the masks hold: an upper bound of what its samples store */
 } vx_norm_args;
 int vx_norm_act_drop_pool(const vx_norm_args* a, vx_stream_t stream);
 /* Round 5: a streaming pass that takes its InstanceNorm statistics from the producing conv's PARTIALS instead of from a
@@ -440,7 +443,8 @@ int vx_pool_finish_z_stats(const float* pool_raw, const uint32_t* pool_flags, co
                            int N, int Dp, int64_t plane_voxels, int drop_scale2, vx_stream_t stream);
 /* Same, but sample n of the OUTPUT reads sample n / x_repeat of x / mean / rstd: the T MC-dropout samples of a
  * volume share contr_1_1's conv output and statistics (test_3D.py:462-472 feeds the same input T times; dropout
- * is the first thing that differs), so that conv runs once per volume and this kernel fans it out. */
+ * is the first thing that differs), so that conv runs once per volume and this kernel fans it out.  At most 65535 samples per
+ * launch; without pooling (the fan-out kernel) the limit is on the N / x_repeat SOURCE samples. */
 int vx_norm_act_drop_pool_bcast(const vx_norm_args* a, int x_repeat, vx_stream_t stream);
 
 /* K6: ConvTranspose3d(k=2, s=2) (+ReLU+Dropout for center.4), unet3D_module.py:113-120, 157-190;

@@ -7,6 +7,8 @@ sys.path.insert(0, ROOT)
 import torch
 torch.set_num_threads(16)
 from tests import test_gpu_kernels as T
+from tests import test_gpu_stream3d as S3
+from tests import ops3d_ref as R3
 from values_amd._lib import VxError
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 150
@@ -22,16 +24,23 @@ for case in range(cases):
             tag = f"convT {cin}->{cout} {shape}"
             T.test_convT_matches_oracle(cin, cout, shape)
         elif kind == "norm":
-            c = rng.choice([4, 8, 16, 32, 64, 128, 256, 12])
-            pool = rng.random() < 0.5
+            # instance, activation, dropout mode, concat input / output, pool-only and the _stats form, through the body of
+            # tests/test_gpu_stream3d.py::test_norm_matrix (bits against the float32 restatement, float64 against its bound)
+            inst = rng.choice(sorted(R3.INSTANCES))
+            pool = R3.INSTANCES[inst][1]
+            c = rng.choice(R3.C_WIDE if inst.startswith("wide") else R3.C_SHUFFLE if pool else R3.C_NOPOOL + (256, 12))
+            layout = rng.choice(R3._POOL_LAYOUTS if pool else R3._COMMON_LAYOUTS)
+            lay = R3.parse_layout(layout)
+            xb = max(lay["out_xblk"], lay["x_xblk"], 1)
             if pool:
-                shape = (rng.randint(1, 3), 2 * rng.randint(1, 4), 2 * rng.randint(1, 6), 2 * rng.randint(1, 10))
+                shape = (rng.randint(1, 3), 2 * rng.randint(1, 4), 2 * rng.randint(1, 6), 2 * xb * rng.randint(1, 5))
             else:
-                shape = (rng.randint(1, 3), rng.randint(1, 7), rng.randint(1, 11), rng.randint(1, 21))
-                if shape[1] * shape[2] * shape[3] == 1:      # one element per (sample, channel): torch's instance_norm (the oracle) refuses it,
-                    shape = shape[:3] + (2,)                 # as the reference's InstanceNorm3d does at 1^3; seed 23, case 142
-            tag = f"norm C={c} {shape} pool={pool}"
-            T.test_instnorm_lrelu_drop_pool_matches_oracle(c, shape, pool)
+                shape = (rng.randint(1, 3), rng.randint(1, 7), rng.randint(1, 11), xb * rng.randint(1, 21 // xb))
+            act, drop = rng.randint(0, 2), rng.randint(0, 2)
+            repeat = rng.choice([2, 3, 5]) if inst == "fanout" else 1
+            tiles = rng.choice([1, 2, 5, 37, 300])
+            tag = f"norm {inst} C={c} {shape} act={act} drop={drop} {layout} tiles={tiles} x{repeat}"
+            S3.norm_case_body(inst, c, shape, act, drop, layout, tiles, repeat)
         else:
             cout = rng.choice([8, 16, 32])
             shape = (rng.randint(1, 3), rng.randint(1, 9), rng.randint(1, 20), rng.randint(1, 40))

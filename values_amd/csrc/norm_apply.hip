@@ -344,8 +344,10 @@ static int norm_act_drop_pool_impl(const vx_norm_args* ap, int x_repeat, const v
     const int C4 = a.C / 4, PW = (wide ? a.W / 2 : a.W) * C4, RH = pool ? a.H / 2 : a.H, RD = pool ? a.D / 2 : a.D;
     const int64_t per = (int64_t)RD * RH * PW;
     const int64_t dmax = PW > RH ? PW : RH;
-    if (per * dmax >= (1ll << 32) || a.N > 65535)
-      VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: sample too large for the 32-bit index decode (%lld pieces) or N > 65535", (long long)per);
+    // grid y = samples: N, or the N / x_repeat source samples of the fan-out kernel
+    const int grid_y = (!pool && x_repeat > 1) ? a.N / x_repeat : a.N;
+    if (per * dmax >= (1ll << 32) || grid_y > 65535)
+      VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: sample too large for the 32-bit index decode (%lld pieces) or more than 65535 samples in the grid (%d)", (long long)per, grid_y);
     NormDecode dc;
     dc.per_sample = (unsigned)per;
     auto magic = [](int d) { return d == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d) + 1u; };
