@@ -901,7 +901,7 @@ int vx_toy_noise(double* x, int64_t n, uint32_t seed, uint32_t stream_index, dou
 
 /* K44: triangle meshes to a label volume, the toy generator's first step (the reference's meshes_to_numpy,
  * datasets/toy_data_generation/stl_to_nifty.py:82-90) under this project's own rule (values_amd/stl.py, voxelize.hip,
- * DESIGN 4.53).  Caller-owned memory and an explicit stream; nothing is uploaded (origin, h, dims and the mesh offsets
+ * DESIGN 4.54).  Caller-owned memory and an explicit stream; nothing is uploaded (origin, h, dims and the mesh offsets
  * travel as kernel arguments), so the call is capturable.
  * vx_voxelize_meshes: tris holds the float32 triangles [n_tri][vertex 3][xyz 3] of all meshes, mesh m being triangles
  *   [mesh_offsets[m], mesh_offsets[m + 1]).  Voxel (k, j, i) of out [n_z][n_y][n_x] has the sample point
@@ -978,6 +978,59 @@ int vx_p2d_out_size(int size, int factor); /* host only; 0 for size < 1 or an od
 int64_t vx_crop_resize_batched_workspace_bytes(const vx_p2d_item* items /* host */, int n_items, const vx_p2d_tables* tables /* host */);
 int vx_crop_resize_batched(const vx_p2d_item* items /* host */, int n_items, const vx_p2d_tables* tables /* host */,
                            int32_t* status /* device [n_items] */, void* workspace, int64_t ws_bytes, vx_stream_t stream);
+
+/* K44: the raters of the 2D test split (uncertainty_modeling/augmentations.py:9-50, StochasticLabelSwitches.apply_to_mask)
+ * and the label-switch variance map (evaluation/utils/gta.py:15-35) for a whole batch of label maps, where the loader
+ * left them (label_switch.hip).
+ * vx_label_switch_batched: per item, a label map [H][W] (device; kind VX_COUNT_B1 / B2 / B4 / B8: an integer of 1 / 2 /
+ *   4 / 8 bytes; H, W >= 1 and H * W < 2^31; sizes may differ within a batch; pointers need only the alignment of their
+ *   elements) gives
+ *     refs     [R][H * W] uint8 (or null): refs[r][i] = rows[k].to where label[i] == rows[k].from and decision(item, r, k),
+ *              else (uint8)label[i] -- 255 (ignore) and every class without a row pass through;
+ *     variance [W][H] float32 (or null), THE FIRST TWO AXES SWAPPED as gta.py:34 returns it: var_table[label[y][x]] at
+ *              [x][y].  var_table (host, 256 floats) is the caller's: built as gta.py builds its values, the map is
+ *              bit-equal to the host hook's.
+ *   A label outside 0..255 gives 255 in refs, var_table[255] in variance, and is counted in status[i] (device, zeroed by
+ *   the call; integer atomics, exact): the host turns a non-zero count into its error.
+ *   rows (host, 1 <= n_switch <= VX_LSWITCH_MAX_ROWS): {from, to, thr}, labels in 0..255, thr = (uint32)(p * 2^24) <= 2^24.
+ *   All `from` are distinct and no `to` equals a `from` (so the result does not depend on the order of the rows, and
+ *   the table is what the reference's sequential in-place moves compute); anything else is VX_E_SHAPE.
+ *   Decisions: given -- decisions (host) [n_items][R][n_switch], values 0 / 1 -- or, with decisions == NULL, drawn on the
+ *   device: decision(item, r, k) = (h1 >> 8) < rows[k].thr with h1 the first word of the generator of the sampling
+ *   kernels (gauss.h: vx_gauss_words) for seed ^ VX_LSWITCH_XOR, element r * n_switch + k, stream item.index.  An
+ *   integer compare: values_amd.dataset2d.switch_decisions restates it exactly.  index is the image's position in its
+ *   split, so an image's raters do not depend on the batching.
+ *   ONE launch serves the batch: every item is cut into tiles of 32 rows x 128 columns and one grid takes the tiles of
+ *   all items in turn.  A workgroup builds the R 256-entry remap tables of its item in LDS once, loads the tile in
+ *   aligned 16-byte pieces, narrows it to bytes in LDS, stores every rater plane in aligned 16-byte pieces (element
+ *   stores only in the pieces that hold a row's two ends) and writes the swapped-axes variance from the LDS tile with
+ *   lanes along H.  AN ITEM'S OUTPUT BYTES ARE EQUAL WHETHER IT IS SUBMITTED ALONE OR IN ANY BATCH, AT ANY POSITION.
+ *   No read outside [labels, labels + H * W elements), no write outside the outputs.  Plain C++ stores.
+ *   Refused before any device call: a null item table, switch table, labels, status or workspace, or a variance map
+ *   without var_table (VX_E_NULL); n_items outside [1, VX_SELECT_MAX_ITEMS], R outside [1, VX_LSWITCH_MAX_R], n_switch
+ *   out of range, H or W < 1, H * W >= 2^31, a bad switch table, a decision other than 0 / 1 (VX_E_SHAPE); an unknown
+ *   kind (VX_E_DTYPE); labels off their element alignment, variance off 4 bytes or a workspace off 16 (VX_E_ALIGN); a
+ *   short workspace (VX_E_WORKSPACE).  workspace: vx_label_switch_batched_workspace_bytes(n_items, R) bytes, 0 for what
+ *   the call refuses.  The tables go up through a pinned staging buffer: no wait on the stream, not capturable. */
+#define VX_LSWITCH_MAX_R 31
+#define VX_LSWITCH_MAX_ROWS 8
+typedef struct vx_lswitch_item {
+  const void* labels; /* device [H][W] */
+  uint8_t* refs;      /* device [R][H * W], or null */
+  float* variance;    /* device [W][H], or null */
+  int32_t H, W;
+  int32_t kind;       /* VX_COUNT_B1 | B2 | B4 | B8 */
+  uint32_t index;     /* position of the image in its split: keys the item's random streams */
+} vx_lswitch_item;
+typedef struct vx_lswitch_row {
+  int32_t from, to;
+  uint32_t thr;
+} vx_lswitch_row;
+int64_t vx_label_switch_batched_workspace_bytes(int n_items, int R);
+int vx_label_switch_batched(const vx_lswitch_item* items /* host */, int n_items, int R, const vx_lswitch_row* rows /* host */,
+                            int n_switch, const uint8_t* decisions /* host [n_items][R][n_switch], or null: drawn */, uint32_t seed,
+                            const float* var_table /* host [256], or null */, int32_t* status /* device [n_items] */,
+                            void* workspace, int64_t ws_bytes, vx_stream_t stream);
 
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),

@@ -282,6 +282,20 @@ class P2dTables(C.Structure):
     _fields_ = [("id2trainid", _p), ("trainid2color", _p), ("color2trainid", _p), ("n_color", _i32), ("default_id", _i32)]
 
 
+VX_LSWITCH_MAX_R, VX_LSWITCH_MAX_ROWS = 31, 8
+
+
+class LswitchItem(C.Structure):
+    """vx_lswitch_item: one label map [H][W] of vx_label_switch_batched (kind VX_COUNT_B1 .. B8), its rater planes
+    [R][H * W] uint8 and / or its variance map [W][H] float32, and the image's split index."""
+    _fields_ = [("labels", _p), ("refs", _p), ("variance", _p), ("H", _i32), ("W", _i32), ("kind", _i32), ("index", _u32)]
+
+
+class LswitchRow(C.Structure):
+    """vx_lswitch_row: one label switch from -> to, drawn with thr = (uint32)(p * 2^24)."""
+    _fields_ = [("from_", _i32), ("to", _i32), ("thr", _u32)]
+
+
 VX_MSR_MAX_ITEMS, VX_MSR_MAX_PLANES = 65536, 1 << 22
 
 
@@ -372,6 +386,9 @@ SIGNATURES = {
     "vx_p2d_out_size": (_i, [_i, _i]),
     "vx_crop_resize_batched_workspace_bytes": (_i64, [C.POINTER(P2dItem), _i, C.POINTER(P2dTables)]),
     "vx_crop_resize_batched": (_i, [C.POINTER(P2dItem), _i, C.POINTER(P2dTables), _p, _p, _i64, _p]),
+    "vx_label_switch_batched_workspace_bytes": (_i64, [_i, _i]),
+    "vx_label_switch_batched": (_i, [C.POINTER(LswitchItem), _i, _i, C.POINTER(LswitchRow), _i, _p, _u32, C.POINTER(C.c_float), _p,
+                                     _p, _i64, _p]),
     "vx_toy_embed": (_i, [_p, C.POINTER(_i32), C.POINTER(_i32), C.c_double, _i, _i, _p, C.POINTER(_i32), _p]),
     "vx_gauss_blur_axis_f64": (_i, [_p, _p, C.POINTER(_i32), _i, _p, _i, _p]),
     "vx_count_ge_f64": (_i, [_p, _i64, C.c_double, _p, _p]),

@@ -28,3 +28,8 @@ __device__ __forceinline__ float vx_noise_var(uint32_t seed, uint32_t b, float l
   const float u2 = (float)(h2 >> 8) * (1.0f / 16777216.0f);           // [0, 1)
   return lo + (hi - lo) * u2;
 }
+
+// The label-switch decisions of the 2D test split (label_switch.hip): the h1 word of element r * n_switch + k of stream
+// `image index` of seed ^ VX_LSWITCH_XOR -- the same idiom, a constant of its own: no stream is shared with the dropout,
+// SSN or noise draws of the same seed.
+#define VX_LSWITCH_XOR 0xA54FF53Au

@@ -371,9 +371,16 @@ class DeviceExperimentDataloader(ExperimentDataloader):
     def get_pred_segs(self, image_id):
         return self._load_many(self.get_pred_seg_paths(image_id))
 
+    def _device_loader_2d(self):
+        """the datamodule's loader when it is a dataset2d.DeviceTestLoader2D (datamodule config with device_io=True), else None"""
+        from .dataset2d import DeviceTestLoader2D
+        return self.dataloader if isinstance(self.dataloader, DeviceTestLoader2D) else None
+
     def get_reference_segs(self, image_id):
         import torch
         if self.dataloader is not None:
+            if self._device_loader_2d() is not None:   # the raters drawn on the device, keyed by the image's split index
+                return self.dataloader.reference_segs(image_id)
             return super().get_reference_segs(image_id)
         end = self.exp_version.image_ending
         return torch.stack(self._load_many([self.ref_seg_dir / f"{image_id}_{i:02d}{end}"
@@ -393,7 +400,10 @@ class DeviceExperimentDataloader(ExperimentDataloader):
     def get_gt_unc_map(self, image_id):
         if self.exp_version.gt_unc_map_loading is None:
             return super().get_gt_unc_map(image_id)
-        return instantiate(self._device_hook(self.exp_version.gt_unc_map_loading), image_id=image_id, dataloader=self.dataloader)
+        cfg = self._device_hook(self.exp_version.gt_unc_map_loading)
+        if cfg["_target_"] == "values_amd.gta.gt_unc_map_device" and self._device_loader_2d() is not None:
+            return self.dataloader.gt_unc_map(image_id)   # the label goes up as it is: no map is made on the host
+        return instantiate(cfg, image_id=image_id, dataloader=self.dataloader)
 
     def get_gt_unc_map_device(self, image_id):
         """get_gt_unc_map without the host: in the file branch the variance over the device-read reference segmentations

@@ -25,6 +25,11 @@ TARGET_MAP = {
     "utils.gta.pred_seg_loading": "values_amd.gta.pred_seg_loading",
     "evaluation.utils.gta.gt_unc_map": "values_amd.gta.gt_unc_map",
     "utils.gta.gt_unc_map": "values_amd.gta.gt_unc_map",
+    # the 2D test split's datamodule and dataset (uncertainty_modeling/configs/datamodule/gta_torch_config.yaml)
+    "uncertainty_modeling.data.torch_dataloader.BaseDataModule": "values_amd.dataset2d.TestDataModule2D",
+    "data.torch_dataloader.BaseDataModule": "values_amd.dataset2d.TestDataModule2D",
+    "uncertainty_modeling.data.cityscapes_dataset.Cityscapes_dataset": "values_amd.dataset2d.CityscapesTestSet",
+    "data.cityscapes_dataset.Cityscapes_dataset": "values_amd.dataset2d.CityscapesTestSet",
 }
 
 

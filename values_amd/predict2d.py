@@ -47,15 +47,31 @@ class NhwcViews:
 @torch.no_grad()
 def predict_logits_2d(models: Sequence, data, n_pred: int = 1, tta: bool = False, hflip_views: Optional[Sequence[bool]] = None,
                       dropout_masks=None, seeds=None, vflip_views: Optional[Sequence[bool]] = None,
-                      batch_views: bool = True, softmax: bool = False) -> torch.Tensor:
+                      batch_views: bool = True, softmax: bool = False, nhwc: bool = False) -> torch.Tensor:
     """data: (B,3,H,W) tensor, or with tta a list of view tensors (the dataset's 4 views, cityscapes_dataset.py:76-99,
     or the 8 of tta_views_8) and hflip_views[i] = "HorizontalFlip" in transforms of view i (vflip_views likewise).
     Returns logits (B, Npred_total, C, H, W) -- with softmax=True their class softmax (F.softmax(output, dim=1) of every
     forward, test_2D.py:300-303), taken inside the model's final upsampling pass so that the full-resolution logits are
     never written (not for SSN members: their draws are logits); process_output_2d(probs=...) takes it.  batch_views: the TTA views travel as ONE batch whose BatchNorm statistics
-    are kept per view (vx_bn_finalize_groups) -- the same numbers as one forward per view, an eighth of the launches."""
+    are kept per view (vx_bn_finalize_groups) -- the same numbers as one forward per view, an eighth of the launches.
+    nhwc (without tta): data is ONE view as vx_tta_views_2d writes it, (B, H, W, 4) channels-last or (1, B, H, W, 4) -- what
+    dataset2d.DeviceTestLoader2D yields -- staged by the n_pred forwards as it is (deterministic / dropout members)."""
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
+    if nhwc:
+        if tta or isinstance(data, NhwcViews) or dropout_masks is not None or any(getattr(m, "ssn", False) for m in models):
+            raise ValueError("predict_logits_2d: nhwc=True is one channels-last view of deterministic / dropout members without tta")
+        x = data[0] if data.dim() == 5 and data.shape[0] == 1 else data
+        if x.dim() != 4 or x.shape[-1] != 4:
+            raise ValueError(f"predict_logits_2d: nhwc=True takes a (B, H, W, 4) tensor, got {tuple(data.shape)}")
+        B, H, W, _ = x.shape
+        total = n_pred * len(models)
+        C = models[0].num_classes
+        out = torch.empty((B * total, C, H, W), dtype=torch.float32, device=dev)
+        for mi, model in enumerate(models):
+            model.forward_samples(x.contiguous(), n_pred, seeds=None if seeds is None else [seeds[mi] * 131 + t for t in range(n_pred)],
+                                  out=out, slot_stride=total, slot_offset=mi * n_pred, softmax_out=softmax, nhwc=True)
+        return out.view(B, total, C, H, W)
     if isinstance(data, NhwcViews):
         if not tta or dropout_masks is not None or any(getattr(m, "ssn", False) for m in models):
             raise ValueError("predict_logits_2d: NhwcViews are the batched TTA views of deterministic / dropout members")
@@ -201,3 +217,46 @@ def process_output_2d(logits: Optional[torch.Tensor], ssn: bool = False, probs: 
         uncertainty.one_minus_msr_batch([probs[b, 0] for b in range(B)], out=list(msr.unbind(0)))
         out["pred_entropy"] = msr
     return out
+
+
+@torch.no_grad()
+def run_test_2d(models: Sequence, loader, save_dir: str, n_pred: int = 1, tta: bool = False, ssn: bool = False,
+                ged_only: bool = True, tiff=None, workers: int = 4) -> Dict[str, Dict]:
+    """Tester.predict_cases + save_results_dict (test_2D.py:258-319) over a whole test split: per batch of `loader` (a
+    dataset2d.DeviceTestLoader2D or the host mirror's loader) predict_logits_2d, process_output_2d, process_metrics_2d and
+    the device results writer; then <save_dir>/metrics.json with each image's dataset.  Returns the written dict.
+    The batches of the device loader are consumed where they are: the views tensor is staged as it is and `seg` never
+    leaves the device."""
+    from . import results2d
+    from .data import hflip_flags
+    from .metrics import process_metrics_2d
+    from .uncertainty import uncertainty_maps
+    _lib.require_gpu()
+    results: Dict[str, Dict] = {}
+    with results2d.ResultsWriter2D(workers=workers, tiff=tiff) as writer:
+        for batch in loader:
+            data, ids = batch["data"], list(batch["image_id"])
+            device_batch = isinstance(data, torch.Tensor) and data.dim() == 5
+            if tta:
+                flips = hflip_flags(batch["transforms"])
+                views = NhwcViews(data, flips) if device_batch else list(data)
+                logits = predict_logits_2d(models, views, n_pred=n_pred, tta=True, hflip_views=flips)
+            elif device_batch and not any(getattr(m, "ssn", False) for m in models):
+                logits = predict_logits_2d(models, data, n_pred=n_pred, nhwc=True)
+            else:
+                x = data[0, ..., :3].permute(0, 3, 1, 2).contiguous() if device_batch else data
+                logits = predict_logits_2d(models, x, n_pred=n_pred)
+            out = process_output_2d(logits, ssn=ssn)
+            B, T, C, H, W = out["softmax_pred"].shape
+            sample_argmax = uncertainty_maps(out["softmax_pred"].reshape(B, T, C, -1), from_logits=False,
+                                             want_sample_argmax=True)["sample_argmax"].reshape(B, T, H, W)
+            seg = batch["seg"]
+            gt = seg if seg.dim() == 4 else seg.unsqueeze(1)   # (the host collate leaves out the rater axis of one rater)
+            metrics = process_metrics_2d(out, gt, ged_only=ged_only, image_ids=ids, sample_argmax=sample_argmax)
+            for image_id, dataset in zip(ids, batch["dataset"]):
+                results[image_id] = {"dataset": dataset, "metrics": metrics[image_id]}
+            gt_dev = gt.to(out["pred_seg"].device)
+            unc = {k: out[k] for k in ("pred_entropy", "aleatoric_uncertainty", "epistemic_uncertainty") if k in out}
+            writer.submit(save_dir, ids, sample_argmax, out["pred_seg"] if T > 1 else None, unc,
+                          ignore_index_map=(gt_dev[:, 0] == 255))
+    return results2d.save_results_dict(save_dir, results)
