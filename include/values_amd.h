@@ -449,7 +449,7 @@ int vx_norm_act_drop_pool_bcast(const vx_norm_args* a, int x_repeat, vx_stream_t
 
 /* K6: ConvTranspose3d(k=2, s=2) (+ReLU+Dropout for center.4), unet3D_module.py:113-120, 157-190;
  * writes channels [out_coff, out_coff+Cout) of the concat buffer (K7: torch.cat disappears).
- * Cin in {64, 128} with Cout % 8 == 0 (% 4 for 128) under vx_config.conv_fp32 == 0 (round 5): the products run on the fp16 matrix
+ * Cin in {64, 128} (any Cout the entry point takes: a multiple of 8) under vx_config.conv_fp32 == 0 (round 5): the products run on the fp16 matrix
  * cores by operand splitting, like the 3x3x3 convolutions -- same accuracy, and the same contract on the INPUT: |x| < 65504
  * (the producers inside vx_unet3d_forward record it in their range_flag).  A WEIGHT past 65504 is reported through this launch's
  * range_flag (infinity).  conv_fp32 != 0 keeps the native-fp32 instruction. */
@@ -464,6 +464,14 @@ typedef struct vx_convT_args {
   const uint32_t* seed_dev;   /* as in vx_conv3d_args */
 } vx_convT_args;
 int vx_convT_k2s2(const vx_convT_args* a, vx_stream_t stream);
+/* Dry run of vx_convT_k2s2: every argument check, the choice of the kernel and its grid, no launch and no call into the HIP runtime
+ * (works without a GPU; the pointers are only tested for null).  Returns the VX_E_* code vx_convT_k2s2 would refuse the call with
+ * (message in vx_last_error_string), or VX_OK with the name vx_last_kernel_name() would report after the launch in kernel_name
+ * (nullable; at most cap bytes, always terminated) and the grid in info (nullable). */
+typedef struct vx_convT_route_info {
+  int32_t grid_x, grid_y; /* workgroups walking the input (grid stride); groups of output rows */
+} vx_convT_route_info;
+int vx_convT_k2s2_route(const vx_convT_args* a, char* kernel_name, int cap, vx_convT_route_info* info);
 
 /* K8 (+K13): final 1x1x1 conv (unet3D_module.py:199, 365) -> logits in the reference's NCDHW
  * layout, sample n written to slot dst[n] (nullable: n) of out [slots][C][D][H][W], un-flipped by

@@ -1,5 +1,6 @@
-"""Shared helpers for the parity tests (fixture loading, mask unpacking)."""
+"""Shared helpers for the parity tests (fixture loading, mask unpacking) and the sanitizer build of the stand-alone host programs."""
 import os
+import subprocess
 
 import numpy as np
 import torch
@@ -7,6 +8,12 @@ import torch
 from tests.formula import formula_unet3d_state_dict
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def build_host_program(src, out, extra=()):
+    """Compile a stand-alone host program (its own main, nothing loaded into Python) under ASan + UBSan, every finding fatal."""
+    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17", "-O1", "-g", "-Wall",
+                           *extra, str(src), "-o", str(out)])
 
 
 def load_npz(name):

@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from tests import conv3d_route_cases as rc
+from tests.helpers import build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NULL, E_SHAPE, E_DTYPE, E_ALIGN = -1, -2, -3, -5
@@ -77,8 +78,7 @@ def test_dry_run_returns_the_refusals_of_the_launch(lib, vxcfg):
 
 def test_routing_header_under_asan_ubsan(golden, tmp_path):
     exe = str(tmp_path / "conv3d_route_host")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17", "-O1", "-g", "-Wall",
-                           os.path.join(ROOT, "tests", "conv3d_route_host.cpp"), "-o", exe])
+    build_host_program(os.path.join(ROOT, "tests", "conv3d_route_host.cpp"), exe)
     lines = "".join("%s %d %d %d %d %d %d %s %d\n" % ((c["id"],) + tuple(c["shape"]) + (c["cin"], c["cout"], rc.LAYER_N, c["epilogue"],
                                                                                    c["cfg"].get("conv_fp32", 0))) for c in rc.LAYER_CASES)
     res = subprocess.run([exe], input=lines, capture_output=True, text=True)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from tests import png_build, prep2d_ref, prep2d_trees
-from tests.helpers import GOLDEN
+from tests.helpers import GOLDEN, build_host_program
 from values_amd import gta, image_io
 from values_amd import preprocess2d as p2d
 from values_amd.preprocess import npy_header
@@ -345,8 +345,7 @@ def test_refusals_without_a_device():
 
 def test_host_plan_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "prep2d_plan_host")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17", "-O1", "-g", "-Wall",
-                           os.path.join(ROOT, "tests", "prep2d_plan_host.cpp"), "-o", exe])
+    build_host_program(os.path.join(ROOT, "tests", "prep2d_plan_host.cpp"), exe)
     res = subprocess.run([exe], capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
     assert "BAD-BLOCKS" not in res.stdout and "NO-MESSAGE" not in res.stdout

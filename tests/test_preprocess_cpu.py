@@ -9,6 +9,7 @@ import subprocess
 
 import numpy as np
 import pytest
+from tests.helpers import build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NULL, E_SHAPE, E_DTYPE, E_WORKSPACE, E_ALIGN = -1, -2, -3, -4, -5
@@ -288,8 +289,7 @@ def test_device_entry_points_fail_loudly_without_a_gpu():
 def test_host_plan_under_asan_ubsan(lib, tmp_path):
     from values_amd import _lib
     exe = str(tmp_path / "prep_plan_host")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17", "-O1", "-g", "-Wall",
-                           os.path.join(ROOT, "tests", "prep_plan_host.cpp"), "-o", exe])
+    build_host_program(os.path.join(ROOT, "tests", "prep_plan_host.cpp"), exe)
     res = subprocess.run([exe], capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
     assert "BAD-BLOCKS" not in res.stdout

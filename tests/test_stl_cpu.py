@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import voxel_ref as vr
+from tests.helpers import build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NULL, E_SHAPE, E_DTYPE, E_WORKSPACE, E_ALIGN = -1, -2, -3, -4, -5
@@ -340,8 +341,7 @@ def test_refusals_without_a_gpu(lib):
 
 def test_host_plan_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "voxel_plan_host")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17", "-O1", "-g", "-Wall",
-                           os.path.join(ROOT, "tests", "voxel_plan_host.cpp"), "-o", exe])
+    build_host_program(os.path.join(ROOT, "tests", "voxel_plan_host.cpp"), exe)
     res = subprocess.run([exe], capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
     assert "BAD-" not in res.stdout

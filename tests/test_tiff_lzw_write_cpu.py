@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import lzw_build as lb
+from tests.helpers import build_host_program
 
 ROOT = lb.ROOT
 NO_ROOM = 3
@@ -152,9 +153,7 @@ def test_the_serial_core_as_a_sanitized_program(tmp_path, corpus):
     behaviour sanitizers and run as a program: every payload with a window of exactly the strip, a larger one, one byte
     too small (VX_LZW_NO_ROOM, the strip's first bytes, nothing more) and an empty one"""
     exe = str(tmp_path / "lzw_enc_host")
-    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-std=c++17", "-O1", "-g", "-Wall",
-                           "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "lzw_enc_host.cpp"),
-                           "-o", exe])
+    build_host_program(os.path.join(ROOT, "tests", "lzw_enc_host.cpp"), exe, extra=("-Werror", "-I", os.path.join(ROOT, "include")))
     items = []
     for name, (data, strip) in corpus.items():
         items += [(name, data, len(strip), 0, strip), (name, data, len(strip) + 7, 0, strip),

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from tests.formula import formula_tensor
 from tests.upcompose16_ref import apply_composed, formula_weights, weff_btab
+from tests.helpers import build_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,8 +25,7 @@ def tables():
 def test_host_function_matches_the_float64_restatement(tables, tmp_path):
     w1, uw, ub, weff, btab = tables
     exe = str(tmp_path / "upcompose16_host")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "upcompose16_host.cpp"), "-o", exe])
+    build_host_program(os.path.join(ROOT, "tests", "upcompose16_host.cpp"), exe)
     blob = tmp_path / "w.bin"
     np.concatenate([w1.numpy().ravel(), uw.numpy().ravel(), ub.numpy().ravel()]).astype(np.float32).tofile(blob)
     lines = subprocess.check_output([exe, str(blob)]).decode().split("\n")

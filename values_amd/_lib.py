@@ -61,6 +61,11 @@ class ConvTArgs(C.Structure):
                 ("out_xblk", _i32), ("out_half", _i32), ("range_flag", _p), ("seed_dev", _p)]
 
 
+class ConvTRouteInfo(C.Structure):
+    """vx_convT_route_info: the grid vx_convT_k2s2_route reports."""
+    _fields_ = [("grid_x", _i32), ("grid_y", _i32)]
+
+
 class Conv2dArgs(C.Structure):
     _fields_ = [("in_", _p), ("in_pitch", _i32), ("w_packed", _p), ("bias", _p),
                 ("out", _p), ("out_pitch", _i32), ("out_coff", _i32),
@@ -361,6 +366,7 @@ SIGNATURES = {
     "vx_prenorm_split_stats": (_i, [_p, C.POINTER(StatSrc), _i, _i64, C.c_float, _p]),
     "vx_pool_finish_z_stats": (_i, [_p, _p, C.POINTER(StatSrc), _p, _i, _i, _i, _i64, _i, _p]),
     "vx_convT_k2s2": (_i, [C.POINTER(ConvTArgs), _p]),
+    "vx_convT_k2s2_route": (_i, [C.POINTER(ConvTArgs), C.c_char_p, _i, C.POINTER(ConvTRouteInfo)]),
     "vx_conv1x1_ncdhw": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "vx_unet3d_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "vx_unet3d_forward": (_i, [C.POINTER(UNet3DWeights), C.POINTER(UNet3DRun), _p]),

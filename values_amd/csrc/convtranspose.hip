@@ -5,10 +5,11 @@
 // producing the dx = 0,1 pair => 64 contiguous output bytes per lane when Cout == 8.
 // The output goes straight into channels [out_coff, out_coff + Cout) of the decoder's concat buffer,
 // which removes torch.cat (K7).  Optional ReLU + dropout epilogue for center.4.
+// This file: the kernels, the pack kernel and the launching.  Which kernel runs a launch, its grid and every argument check are
+// convT_route.h (host only; CT_CO, the output channels per thread of the generic kernel, comes from there).
 #include "common.h"
 #include <stdlib.h>
-
-constexpr int CT_CO = 8;  // output channels per thread
+#include "convT_route.h"
 
 // address of channel c of output voxel (row, ox): plain pitched tensor or one half of a concat buffer
 __device__ __forceinline__ float* convT_out_ptr(const vx_convT_args& a, size_t orow, int ox, int OW, int c) {
@@ -417,56 +418,32 @@ __global__ __launch_bounds__(256) void convT_k2s2_s16_kernel(vx_convT_args a, in
   }
 }
 
-template <int CIN, int RT>
-static int launch_convT_s16(const vx_convT_args& a, hipStream_t s) {
-  const int64_t nvox = (int64_t)a.N * a.D * a.H * a.W;
-  const int ncoltiles = (int)((nvox + 15) / 16);
-  const int groups = (a.Cout / 2) / RT;
-  int bx = (ncoltiles + 3) / 4;
-  // 512 workgroups (two per CU at these instances' registers), each wave walking its share of the column tiles: the weight gather
-  // of the prologue is paid once per wave.  Measured at 320 samples (tools/ab_convT.py): upscale4 0.108 -> 0.056 ms, center.4
-  // 0.052 -> 0.033; with one column tile per wave (the fp32 kernel's grid) the same kernel is 20-30 % SLOWER than the fp32 one,
-  // and <64,8> / <128,4> (256 registers, one workgroup per CU) reach 0.076 / 0.034.
-  const int cap = (512 + groups - 1) / groups;
-  if (bx > cap) bx = cap;
-  auto magic = [](int d) { return d == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d) + 1u; };
-  ConvTDecode dc;
-  dc.mW = magic(a.W); dc.mH = magic(a.H); dc.mD = magic(a.D);
-  static const char* kname = vx_kname("convT_k2s2_s16_kernel<%d,%d,false>", CIN, RT);
-  static const char* kname_m = vx_kname("convT_k2s2_s16_kernel<%d,%d,true>", CIN, RT);
-  vx_note_kernel(a.drop_mode == VX_DROP_MASK ? kname_m : kname);
-  if (a.drop_mode == VX_DROP_MASK)
-    hipLaunchKernelGGL((convT_k2s2_s16_kernel<CIN, RT, true>), dim3((unsigned)bx, (unsigned)groups), dim3(256), 0, s, a, ncoltiles,
-                       (int)nvox, dc);
-  else
-    hipLaunchKernelGGL((convT_k2s2_s16_kernel<CIN, RT, false>), dim3((unsigned)bx, (unsigned)groups), dim3(256), 0, s, a, ncoltiles,
-                       (int)nvox, dc);
-  VX_CHECK_LAUNCH("vx_convT_k2s2(s16)");
-  return VX_OK;
+// ---- launching: the arguments are validated and the instance, the grid and the decode magics chosen by convT_route --------------
+// the route's name, formatted once per instance (a function-local static at each call) and kept for the process
+static const char* convT_kname(const ConvTRoute& r) {
+  char buf[128];
+  convT_route_name(r, buf, (int)sizeof(buf));
+  return vx_kname("%s", buf);
 }
 
-template <int CIN, int RT>
-static int launch_convT_mfma(const vx_convT_args& a, hipStream_t s) {
-  const int64_t nvox = (int64_t)a.N * a.D * a.H * a.W;
-  const int ncoltiles = (int)((nvox + 15) / 16);
-  const int groups = (a.Cout / 2) / RT;          // 8 * Cout rows = Cout / 2 row tiles
-  int bx = (ncoltiles + 3) / 4;
-  int per = 32;   // workgroups per CU in the grid: more, shorter address streams write faster (fill: 5.1 TB/s at 2048 WGs, 6.5 at 32768)
-  const int cap = (256 * per + groups - 1) / groups;
-  if (bx > cap) bx = cap;
-  auto magic = [](int d) { return d == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d) + 1u; };
-  ConvTDecode dc;
-  dc.mW = magic(a.W); dc.mH = magic(a.H); dc.mD = magic(a.D);
-  static const char* kname = vx_kname("convT_k2s2_mfma_kernel<%d,%d,false>", CIN, RT);
-  static const char* kname_m = vx_kname("convT_k2s2_mfma_kernel<%d,%d,true>", CIN, RT);
-  vx_note_kernel(a.drop_mode == VX_DROP_MASK ? kname_m : kname);
-  if (a.drop_mode == VX_DROP_MASK)
-    hipLaunchKernelGGL((convT_k2s2_mfma_kernel<CIN, RT, true>), dim3((unsigned)bx, (unsigned)groups), dim3(256), 0, s, a,
-                       ncoltiles, (int)nvox, dc);
+template <int FAMILY, int CIN, int RT, bool MASK>
+static void launch_convT_instance(const ConvTRoute& r, const vx_convT_args& a, hipStream_t s) {
+  static const char* kname = convT_kname(r);
+  vx_note_kernel(kname);
+  const ConvTDecode dc = {r.mW, r.mH, r.mD};
+  const dim3 grid((unsigned)r.grid_x, (unsigned)r.grid_y);
+  if constexpr (FAMILY == CONVT_S16)
+    hipLaunchKernelGGL((convT_k2s2_s16_kernel<CIN, RT, MASK>), grid, dim3(256), 0, s, a, r.ncoltiles, (int)r.nvox, dc);
   else
-    hipLaunchKernelGGL((convT_k2s2_mfma_kernel<CIN, RT, false>), dim3((unsigned)bx, (unsigned)groups), dim3(256), 0, s, a,
-                       ncoltiles, (int)nvox, dc);
-  VX_CHECK_LAUNCH("vx_convT_k2s2(mfma)");
+    hipLaunchKernelGGL((convT_k2s2_mfma_kernel<CIN, RT, MASK>), grid, dim3(256), 0, s, a, r.ncoltiles, (int)r.nvox, dc);
+}
+
+// both tile families; the injected-mask dropout is its own instance (see convT_k2s2_mfma_kernel)
+template <int FAMILY, int CIN, int RT>
+static int launch_convT_tiles(const ConvTRoute& r, const vx_convT_args& a, hipStream_t s) {
+  if (r.mask) launch_convT_instance<FAMILY, CIN, RT, true>(r, a, s);
+  else launch_convT_instance<FAMILY, CIN, RT, false>(r, a, s);
+  VX_CHECK_LAUNCH(FAMILY == CONVT_S16 ? "vx_convT_k2s2(s16)" : "vx_convT_k2s2(mfma)");
   return VX_OK;
 }
 
@@ -483,75 +460,64 @@ __global__ void pack_convT_kernel(const float* __restrict__ w, float* __restrict
   }
 }
 
-extern "C" int64_t vx_convT_k2s2_packed_floats(int Cin, int Cout) {
-  if (Cin <= 0 || Cout <= 0 || Cin % 4 || Cout % 8) return -1;
-  return (int64_t)Cin * Cout * 8;
-}
+extern "C" int64_t vx_convT_k2s2_packed_floats(int Cin, int Cout) { return convT_packed_floats(Cin, Cout); }
 
 extern "C" int vx_pack_convT_k2s2(const float* w_torch, float* w_packed, int Cin, int Cout, vx_stream_t stream) {
   if (!w_torch || !w_packed) VX_FAIL(VX_E_NULL, "vx_pack_convT_k2s2: null pointer");
-  const int64_t total = vx_convT_k2s2_packed_floats(Cin, Cout);
+  const int64_t total = convT_packed_floats(Cin, Cout);
   if (total < 0) VX_FAIL(VX_E_SHAPE, "vx_pack_convT_k2s2: Cin=%d (mult of 4) Cout=%d (mult of 8)", Cin, Cout);
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_convT_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_torch, w_packed, Cin, Cout,
-                     total);
+  const int64_t nb = (total - 1) / 256 + 1;
+  const int blocks = nb > 4096 ? 4096 : (int)nb;
+  hipLaunchKernelGGL(pack_convT_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_torch, w_packed, Cin, Cout, total);
   VX_CHECK_LAUNCH("vx_pack_convT_k2s2");
   return VX_OK;
 }
 
-extern "C" int vx_convT_k2s2(const vx_convT_args* ap, vx_stream_t stream) {
+static int route_or_fail(const vx_convT_args* ap, ConvTRoute* r) {
   if (!ap) VX_FAIL(VX_E_NULL, "vx_convT_k2s2: null args");
-  const vx_convT_args& a = *ap;
-  if (!a.in || !a.w_packed || !a.bias || !a.out) VX_FAIL(VX_E_NULL, "vx_convT_k2s2: null tensor");
-  if (a.Cin <= 0 || a.Cout <= 0 || a.Cin % 4 || a.Cout % 8)
-    VX_FAIL(VX_E_SHAPE, "vx_convT_k2s2: Cin=%d (mult of 4) Cout=%d (mult of 8)", a.Cin, a.Cout);
-  if (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0) VX_FAIL(VX_E_SHAPE, "vx_convT_k2s2: empty tensor");
-  if (a.in_pitch % 4 || a.in_pitch < a.Cin) VX_FAIL(VX_E_ALIGN, "vx_convT_k2s2: input pitch");
-  if (a.out_xblk) {
-    if ((a.out_xblk != 1 && a.out_xblk != 2 && a.out_xblk != 4) || (2 * a.W) % a.out_xblk || (a.out_half != 0 && a.out_half != 1))
-      VX_FAIL(VX_E_SHAPE, "vx_convT_k2s2: bad concat layout (xblk=%d, half=%d)", a.out_xblk, a.out_half);
-  } else if (a.out_pitch % 4 || a.out_coff % 4 || a.out_pitch < a.out_coff + a.Cout) {
-    VX_FAIL(VX_E_ALIGN, "vx_convT_k2s2: pitches/offsets must be multiples of 4 floats");
-  }
-  if (a.drop_mode == VX_DROP_MASK && !a.drop_mask) VX_FAIL(VX_E_NULL, "vx_convT_k2s2: mask mode without mask");
-  if ((int64_t)a.D * a.H * a.W * 8 * a.Cout >= (1ll << 32)) VX_FAIL(VX_E_SHAPE, "vx_convT_k2s2: sample too large");
-  // matrix-core kernel for the channel counts the networks use (row tiles per workgroup: weights stay in <= 128 VGPRs)
-  // (flat voxel index * largest dimension < 2^32: the multiply-high divisions of the index decode are then exact)
-  const int64_t dmax = a.W > a.H ? (a.W > a.D ? a.W : a.D) : (a.H > a.D ? a.H : a.D);
-  if ((int64_t)a.N * a.D * a.H * a.W < (1ll << 27) && (int64_t)a.N * a.D * a.H * a.W * dmax < (1ll << 32)) {
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles = a.Cout / 2;
-    if (a.Cin == 16 && tiles % 4 == 0) return tiles % 8 ? launch_convT_mfma<16, 4>(a, s) : launch_convT_mfma<16, 8>(a, s);
-    if (a.Cin == 32 && tiles % 4 == 0) return tiles % 8 ? launch_convT_mfma<32, 4>(a, s) : launch_convT_mfma<32, 8>(a, s);
-    // the deep up-convolutions on the split-fp16 products (vx_config.conv_fp32 == 0: the family the convolutions run in)
-    if (vx_cfg().conv_fp32 == 0) {
-      if (a.Cin == 64 && tiles % 4 == 0) return launch_convT_s16<64, 4>(a, s);
-      if (a.Cin == 128 && tiles % 2 == 0) return launch_convT_s16<128, 2>(a, s);
-    }
-    if (a.Cin == 64 && tiles % 4 == 0) return tiles % 8 ? launch_convT_mfma<64, 4>(a, s) : launch_convT_mfma<64, 8>(a, s);
-    if (a.Cin == 128 && tiles % 4 == 0) return launch_convT_mfma<128, 4>(a, s);
-  }
-  // large, shallow up-convolutions: row-streaming kernel (needs 256 % (2*Cout/4) == 0 and Cout <= 128)
-  if ((a.Cin == 16 || a.Cin == 32) && a.Cout <= 128 && 256 % (2 * (a.Cout / 4)) == 0) {
-    const int64_t total = (int64_t)a.N * a.D * a.H * (2 * a.W) * (a.Cout / 4);
-    int bx = (int)((total + 255) / 256);
-    if (bx > 4096) bx = 4096;
-    dim3 grid((unsigned)bx, 4);
-    vx_note_kernel("convT_k2s2_rows_kernel");
-    if (a.Cin == 16)
-      hipLaunchKernelGGL(convT_k2s2_rows_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, a, total);
-    else
-      hipLaunchKernelGGL(convT_k2s2_rows_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, a, total);
-    VX_CHECK_LAUNCH("vx_convT_k2s2");
-    return VX_OK;
-  }
-  const int64_t nvox = (int64_t)a.N * a.D * a.H * a.W;
-  int bx = (int)((nvox + 255) / 256);
-  if (bx > 8192) bx = 8192;
-  dim3 grid((unsigned)bx, (unsigned)(4 * (a.Cout / CT_CO)));
-  vx_note_kernel("convT_k2s2_kernel");
-  hipLaunchKernelGGL(convT_k2s2_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, nvox);
-  VX_CHECK_LAUNCH("vx_convT_k2s2");
+  const int rc = convT_route(*ap, vx_cfg(), r);
+  if (rc != VX_OK) VX_FAIL(rc, "%s", r->err);
   return VX_OK;
+}
+
+extern "C" int vx_convT_k2s2_route(const vx_convT_args* ap, char* kernel_name, int cap, vx_convT_route_info* info) {
+  ConvTRoute r;
+  const int rc = route_or_fail(ap, &r);
+  if (rc != VX_OK) return rc;
+  if (kernel_name && cap > 0) convT_route_name(r, kernel_name, cap);
+  if (info) *info = {r.grid_x, r.grid_y};
+  return VX_OK;
+}
+
+extern "C" int vx_convT_k2s2(const vx_convT_args* ap, vx_stream_t stream) {
+  ConvTRoute r;
+  const int rc = route_or_fail(ap, &r);
+  if (rc != VX_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)r.grid_x, (unsigned)r.grid_y);
+#define CONVT_LAUNCH_MFMA(CIN, RT) case convT_key(CIN, RT): return launch_convT_tiles<CONVT_MFMA, CIN, RT>(r, *ap, s);
+#define CONVT_LAUNCH_S16(CIN, RT) case convT_key(CIN, RT): return launch_convT_tiles<CONVT_S16, CIN, RT>(r, *ap, s);
+#define CONVT_LAUNCH_ROWS(CIN) case convT_key(CIN): hipLaunchKernelGGL(convT_k2s2_rows_kernel<CIN>, grid, dim3(256), 0, s, *ap, r.total); break;
+  switch (r.kernel) {
+    case CONVT_MFMA: switch (convT_key(r.cin, r.rt)) { CONVT_MFMA_INSTANCES(CONVT_LAUNCH_MFMA) } break;
+    case CONVT_S16: switch (convT_key(r.cin, r.rt)) { CONVT_S16_INSTANCES(CONVT_LAUNCH_S16) } break;
+    case CONVT_ROWS: {
+      static const char* kname = convT_kname(r);
+      vx_note_kernel(kname);
+      switch (convT_key(r.cin)) { CONVT_ROWS_INSTANCES(CONVT_LAUNCH_ROWS) }
+      VX_CHECK_LAUNCH("vx_convT_k2s2");
+      return VX_OK;
+    }
+    case CONVT_GENERIC: {
+      static const char* kname = convT_kname(r);
+      vx_note_kernel(kname);
+      hipLaunchKernelGGL(convT_k2s2_kernel, grid, dim3(256), 0, s, *ap, r.nvox);
+      VX_CHECK_LAUNCH("vx_convT_k2s2");
+      return VX_OK;
+    }
+  }
+#undef CONVT_LAUNCH_MFMA
+#undef CONVT_LAUNCH_S16
+#undef CONVT_LAUNCH_ROWS
+  VX_FAIL(VX_E_SHAPE, "vx_convT_k2s2: no such instance");   // (not reached: convT_route names listed instances only)
 }
