@@ -446,6 +446,18 @@ int vx_pool_finish_z_stats(const float* pool_raw, const uint32_t* pool_flags, co
  * is the first thing that differs), so that conv runs once per volume and this kernel fans it out.  At most 65535 samples per
  * launch; without pooling (the fan-out kernel) the limit is on the N / x_repeat SOURCE samples. */
 int vx_norm_act_drop_pool_bcast(const vx_norm_args* a, int x_repeat, vx_stream_t stream);
+/* Dry run of vx_norm_act_drop_pool (x_repeat 1, st NULL), _bcast (x_repeat) and _stats (st): every argument check, the choice of the
+ * kernel instance, its grid and its index decode, no launch and no call into the HIP runtime (works without a GPU; the pointers are only
+ * tested for null).  Returns the VX_E_* code the entry point would refuse the call with (message in vx_last_error_string), or VX_OK
+ * with the name vx_last_kernel_name() would report after the launch in kernel_name (nullable; at most cap bytes, always terminated) and
+ * the geometry in info (nullable). */
+typedef struct vx_norm_route_info {
+  int32_t grid_x, grid_y;        /* workgroups walking a sample's pieces (grid stride); samples (the fan-out kernel: source samples) */
+  uint32_t per_sample;           /* 16-byte pieces (work items) of one sample */
+  uint32_t magic_pw, magic_c4, magic_rh; /* multiply-high magics of the piece decode: / pieces per row, / (C / 4), / rows per plane (0: divisor 1) */
+} vx_norm_route_info;
+int vx_norm_act_drop_pool_route(const vx_norm_args* a, int x_repeat, const vx_stat_src* st, char* kernel_name, int cap,
+                                vx_norm_route_info* info);
 
 /* K6: ConvTranspose3d(k=2, s=2) (+ReLU+Dropout for center.4), unet3D_module.py:113-120, 157-190;
  * writes channels [out_coff, out_coff+Cout) of the concat buffer (K7: torch.cat disappears).

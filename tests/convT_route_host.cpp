@@ -38,7 +38,7 @@ static std::set<std::string> g_named;      // kernels accepted routes named
 static bool route_is_sound(const ConvTRoute& r, const vx_convT_args& a) {
   if (r.kernel < 0 || r.kernel >= CONVT_NKERNELS || !convT_instance_exists(r.kernel, r.cin, r.rt, r.mask)) return false;
   if (r.grid_x < 1 || r.grid_y < 1 || r.nvox < 1) return false;
-  if (r.nvox != (int64_t)((convT_wide)a.N * a.D * a.H * a.W)) return false;
+  if (r.nvox != (int64_t)((vx_wide)a.N * a.D * a.H * a.W)) return false;
   if (r.mask != (a.drop_mode == VX_DROP_MASK) && r.kernel <= CONVT_S16) return false;
   if (r.kernel == CONVT_MFMA || r.kernel == CONVT_S16) {
     if (r.cin != a.Cin || r.nvox >= (1ll << 27) || r.ncoltiles < 1 || (int64_t)r.ncoltiles * 16 < r.nvox || (int64_t)r.ncoltiles * 16 >= r.nvox + 16) return false;
@@ -46,17 +46,17 @@ static bool route_is_sound(const ConvTRoute& r, const vx_convT_args& a) {
     const int d[3] = {a.W, a.H, a.D};
     const unsigned m[3] = {r.mW, r.mH, r.mD};
     for (int i = 0; i < 3; ++i) {
-      if ((convT_wide)r.nvox * d[i] >= ((convT_wide)1 << 32)) return false;
+      if ((vx_wide)r.nvox * d[i] >= ((vx_wide)1 << 32)) return false;
       // the decode at the largest index it meets: exact
       const unsigned v = (unsigned)(r.nvox - 1), q = m[i] ? (unsigned)(((uint64_t)v * m[i]) >> 32) : v;
       if (q != v / (unsigned)d[i]) return false;
     }
   } else {
     if ((int64_t)a.N * 2 * a.D >= (1ll << 31)) return false;
-    if (r.kernel == CONVT_ROWS && (r.cin != a.Cin || r.total != (int64_t)((convT_wide)r.nvox * 2 * (a.Cout / 4)) || r.grid_y != 4 || r.grid_x > CONVT_ROWS_MAX_WGS)) return false;
+    if (r.kernel == CONVT_ROWS && (r.cin != a.Cin || r.total != (int64_t)((vx_wide)r.nvox * 2 * (a.Cout / 4)) || r.grid_y != 4 || r.grid_x > CONVT_ROWS_MAX_WGS)) return false;
     if (r.kernel == CONVT_GENERIC && (r.grid_y != a.Cout / 2 || r.grid_x > CONVT_GENERIC_MAX_WGS)) return false;
   }
-  if ((convT_wide)a.D * a.H * a.W * 8 * a.Cout >= ((convT_wide)1 << 32)) return false;
+  if ((vx_wide)a.D * a.H * a.W * 8 * a.Cout >= ((vx_wide)1 << 32)) return false;
   char name[128];
   const int n = convT_route_name(r, name, sizeof name);
   if (n <= 0 || n >= (int)sizeof name) return false;

@@ -124,9 +124,14 @@ def launch_norm(x, *, entry="plain", repeat=1, mean=None, rstd=None, part=None, 
         assert repeat == 1
         rc = lib.vx_norm_act_drop_pool(C.byref(a), _lib.stream_ptr())
     assert rc == expect_rc, (rc, lib.vx_last_error_string())
+    # the dry run, given the arguments just launched: the same code, and the name of the kernel that ran
+    dry_name = C.create_string_buffer(96)
+    dry = lib.vx_norm_act_drop_pool_route(C.byref(a), repeat, C.byref(st) if entry == "stats" else None, dry_name, len(dry_name), None)
+    assert dry == rc, (dry, rc, lib.vx_last_error_string())
     if rc != 0:
         return None
     name = _kernel()
+    assert dry_name.value.decode() == name
     torch.cuda.synchronize()
     res = SimpleNamespace()
     res.kernel = name

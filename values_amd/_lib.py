@@ -53,6 +53,11 @@ class StatSrc(C.Structure):
     _fields_ = [("stats_partial", _p), ("tiles", _i32), ("eps", C.c_float), ("count", _i64), ("mean_out", _p), ("rstd_out", _p)]
 
 
+class NormRouteInfo(C.Structure):
+    """vx_norm_route_info: the launch geometry and index decode vx_norm_act_drop_pool_route reports."""
+    _fields_ = [("grid_x", _i32), ("grid_y", _i32), ("per_sample", _u32), ("magic_pw", _u32), ("magic_c4", _u32), ("magic_rh", _u32)]
+
+
 class ConvTArgs(C.Structure):
     _fields_ = [("in_", _p), ("in_pitch", _i32), ("w_packed", _p), ("bias", _p),
                 ("out", _p), ("out_pitch", _i32), ("out_coff", _i32),
@@ -363,6 +368,7 @@ SIGNATURES = {
     "vx_norm_act_drop_pool": (_i, [C.POINTER(NormArgs), _p]),
     "vx_norm_act_drop_pool_bcast": (_i, [C.POINTER(NormArgs), _i, _p]),
     "vx_norm_act_drop_pool_stats": (_i, [C.POINTER(NormArgs), C.POINTER(StatSrc), _p]),
+    "vx_norm_act_drop_pool_route": (_i, [C.POINTER(NormArgs), _i, C.POINTER(StatSrc), C.c_char_p, _i, C.POINTER(NormRouteInfo)]),
     "vx_prenorm_split_stats": (_i, [_p, C.POINTER(StatSrc), _i, _i64, C.c_float, _p]),
     "vx_pool_finish_z_stats": (_i, [_p, _p, C.POINTER(StatSrc), _p, _i, _i, _i, _i64, _i, _p]),
     "vx_convT_k2s2": (_i, [C.POINTER(ConvTArgs), _p]),

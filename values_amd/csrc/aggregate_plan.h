@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"
 
 #define VX_AGG_MAX_SPECS 8
 #define VX_AGG_MAX_ITEMS 4096
@@ -44,12 +45,10 @@ struct agg_plan {
   char err[160] = {0};
 };
 
-static inline size_t agg_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // LDS of one tile: the float input rows with their halo, the row sums along W as doubles, and (pd > 1) the last pd slices
 // of the sums along H for the sum along D
 static inline size_t agg_tile_lds(int TH, int TW, int pd, int ph, int pw) {
-  const size_t in = agg_align256((size_t)(TH + ph - 1) * (TW + pw - 1) * sizeof(float));
+  const size_t in = vx_align256((size_t)(TH + ph - 1) * (TW + pw - 1) * sizeof(float));
   const size_t ws = (size_t)(TH + ph - 1) * TW * sizeof(double);
   const size_t ring = pd > 1 ? (size_t)pd * TH * TW * sizeof(double) : 0;
   return in + ws + ring;
@@ -67,32 +66,27 @@ static inline bool agg_fit_tile(size_t budget, int min_th, int min_tw, int pd, i
 
 // VX_OK and a filled plan, or a VX_E_* code and plan->err
 static inline int agg_make_plan(const vx_agg_item* items, int n_items, const vx_agg_spec* specs, int n_specs, agg_plan* p) {
-#define AGG_REFUSE(code, ...)                        \
-  do {                                               \
-    snprintf(p->err, sizeof(p->err), __VA_ARGS__);   \
-    return (code);                                   \
-  } while (0)
-  if (!items || !specs) AGG_REFUSE(VX_E_NULL, "vx_aggregate_batched: null items or specs");
-  if (n_items < 1 || n_items > VX_AGG_MAX_ITEMS) AGG_REFUSE(VX_E_SHAPE, "vx_aggregate_batched: n_items %d outside 1..%d", n_items, VX_AGG_MAX_ITEMS);
-  if (n_specs < 1 || n_specs > VX_AGG_MAX_SPECS) AGG_REFUSE(VX_E_SHAPE, "vx_aggregate_batched: n_specs %d outside 1..%d", n_specs, VX_AGG_MAX_SPECS);
+  if (!items || !specs) VX_REFUSE(p, VX_E_NULL, "vx_aggregate_batched: null items or specs");
+  if (n_items < 1 || n_items > VX_AGG_MAX_ITEMS) VX_REFUSE(p, VX_E_SHAPE, "vx_aggregate_batched: n_items %d outside 1..%d", n_items, VX_AGG_MAX_ITEMS);
+  if (n_specs < 1 || n_specs > VX_AGG_MAX_SPECS) VX_REFUSE(p, VX_E_SHAPE, "vx_aggregate_batched: n_specs %d outside 1..%d", n_specs, VX_AGG_MAX_SPECS);
   for (int s = 0; s < n_specs; ++s) {
     const vx_agg_spec& sp = specs[s];
     if (sp.kind == VX_AGG_IMAGE || sp.kind == VX_AGG_THRESHOLD) p->any_sum = true;
-    else if (sp.kind != VX_AGG_PATCH) AGG_REFUSE(VX_E_DTYPE, "vx_aggregate_batched: spec %d: kind %d", s, sp.kind);
-    else if (sp.pd < 1 || sp.ph < 1 || sp.pw < 1) AGG_REFUSE(VX_E_SHAPE, "vx_aggregate_batched: spec %d: patch (%d,%d,%d)", s, sp.pd, sp.ph, sp.pw);
+    else if (sp.kind != VX_AGG_PATCH) VX_REFUSE(p, VX_E_DTYPE, "vx_aggregate_batched: spec %d: kind %d", s, sp.kind);
+    else if (sp.pd < 1 || sp.ph < 1 || sp.pw < 1) VX_REFUSE(p, VX_E_SHAPE, "vx_aggregate_batched: spec %d: patch (%d,%d,%d)", s, sp.pd, sp.ph, sp.pw);
   }
   int64_t hw_tiles = 0;
   for (int i = 0; i < n_items; ++i) {
     const vx_agg_item& it = items[i];
-    if (!it.map) AGG_REFUSE(VX_E_NULL, "vx_aggregate_batched: item %d: null map", i);
-    if (it.dtype != VX_F32 && it.dtype != VX_F64) AGG_REFUSE(VX_E_DTYPE, "vx_aggregate_batched: item %d: dtype %d", i, it.dtype);
-    if (it.D < 1 || it.H < 1 || it.W < 1) AGG_REFUSE(VX_E_SHAPE, "vx_aggregate_batched: item %d: map (%d,%d,%d)", i, it.D, it.H, it.W);
+    if (!it.map) VX_REFUSE(p, VX_E_NULL, "vx_aggregate_batched: item %d: null map", i);
+    if (it.dtype != VX_F32 && it.dtype != VX_F64) VX_REFUSE(p, VX_E_DTYPE, "vx_aggregate_batched: item %d: dtype %d", i, it.dtype);
+    if (it.D < 1 || it.H < 1 || it.W < 1) VX_REFUSE(p, VX_E_SHAPE, "vx_aggregate_batched: item %d: map (%d,%d,%d)", i, it.D, it.H, it.W);
     if (p->any_sum) p->sums.push_back(agg_sum_item{it.map, (int64_t)it.D * it.H * it.W, it.dtype, 0});
     for (int s = 0; s < n_specs; ++s) {
       const vx_agg_spec& sp = specs[s];
       if (sp.kind != VX_AGG_PATCH) continue;
       if (sp.pd > it.D || sp.ph > it.H || sp.pw > it.W)
-        AGG_REFUSE(VX_E_SHAPE, "vx_aggregate_batched: item %d: patch (%d,%d,%d) of spec %d must fit map (%d,%d,%d)", i, sp.pd, sp.ph,
+        VX_REFUSE(p, VX_E_SHAPE, "vx_aggregate_batched: item %d: patch (%d,%d,%d) of spec %d must fit map (%d,%d,%d)", i, sp.pd, sp.ph,
                    sp.pw, s, it.D, it.H, it.W);
       agg_pair q;
       memset(&q, 0, sizeof(q));
@@ -104,7 +98,7 @@ static inline int agg_make_plan(const vx_agg_item* items, int n_items, const vx_
       if (TH > q.oh) TH = q.oh;
       if (!agg_fit_tile(VX_AGG_LDS_SHARED, TH < 4 ? TH : 4, TW < 16 ? TW : 16, sp.pd, sp.ph, sp.pw, &TH, &TW) &&
           !agg_fit_tile(VX_AGG_LDS_WHOLE, 1, 1, sp.pd, sp.ph, sp.pw, &TH, &TW))
-        AGG_REFUSE(VX_E_SHAPE, "vx_aggregate_batched: item %d: patch (%d,%d,%d) of spec %d leaves no LDS tile (%zu bytes at 1x1)", i,
+        VX_REFUSE(p, VX_E_SHAPE, "vx_aggregate_batched: item %d: patch (%d,%d,%d) of spec %d leaves no LDS tile (%zu bytes at 1x1)", i,
                    sp.pd, sp.ph, sp.pw, s, agg_tile_lds(1, 1, sp.pd, sp.ph, sp.pw));
       q.TH = TH;
       for (q.tw_log2 = 0; (1 << q.tw_log2) < TW; ++q.tw_log2) {}
@@ -128,11 +122,10 @@ static inline int agg_make_plan(const vx_agg_item* items, int n_items, const vx_
     q.tile0 = p->tiles;
     p->tiles += (int64_t)q.ntd * q.nth * q.ntw;
   }
-  p->off_pairs = agg_align256(p->sums.size() * sizeof(agg_sum_item));
-  p->off_tmax = p->off_pairs + agg_align256(p->pairs.size() * sizeof(agg_pair));
-  p->off_first = p->off_tmax + agg_align256((size_t)p->tiles * sizeof(double));
-  p->bytes = p->off_first + agg_align256((size_t)p->tiles * sizeof(int64_t));
+  p->off_pairs = vx_align256(p->sums.size() * sizeof(agg_sum_item));
+  p->off_tmax = p->off_pairs + vx_align256(p->pairs.size() * sizeof(agg_pair));
+  p->off_first = p->off_tmax + vx_align256((size_t)p->tiles * sizeof(double));
+  p->bytes = p->off_first + vx_align256((size_t)p->tiles * sizeof(int64_t));
   if (p->bytes == 0) p->bytes = 256;
   return VX_OK;
-#undef AGG_REFUSE
 }

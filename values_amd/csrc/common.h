@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"   // vx_aligned16, vx_align256, the magic forms (host)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -32,8 +33,8 @@ const char* vx_kname(const char* fmt, ...);   // lib.cpp: the environment is rea
     }                                                              \
   } while (0)
 
-static inline bool vx_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
-static inline size_t vx_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// exact n / d by multiply-high with the host's vx_magic_or0(d) (host_checks.h): magic 0 = divisor 1
+__device__ __forceinline__ unsigned vx_magic_div(unsigned n, unsigned m) { return m ? __umulhi(n, m) : n; }
 
 // Copies a launcher's host-built table into (the head of) its workspace.  The table is the launcher's own host copy,
 // freed when it returns, and hipMemcpyAsync from pageable memory may return before the bytes have left it: wait for the

@@ -19,6 +19,7 @@
 #include <stdio.h>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"
 
 enum Conv2dKernel { CONV2D_MFMA = 0, CONV2D_S16, CONV2D_NKERNELS };
 
@@ -149,10 +150,7 @@ struct Conv2dRoute {
   char err[400];                 // the refusal's message (vx_last_error_string) when conv2d_route returns < 0
 };
 
-static inline unsigned conv2d_magic(int d) { return (unsigned)((1ull << 32) / (unsigned)d) + 1u; }
-static inline bool conv2d_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 // the 32-bit offset guards: bytes of an image, as a product no argument can overflow
-typedef __int128 conv2d_bytes;
 constexpr int64_t CONV2D_2GIB = 1ll << 31;
 
 // ---- channel and tile rules ---------------------------------------------------------------------------------------------------
@@ -215,7 +213,7 @@ static inline int conv2d_family(int Cin, int Cout, int KS, const vx_config& cfg)
 
 // ---- packed weights -----------------------------------------------------------------------------------------------------------
 // a packed size as a product no layer can overflow: -1 (no such layer) beyond int64
-static inline int64_t conv2d_floats(conv2d_bytes v) { return v > (conv2d_bytes)INT64_MAX ? -1 : (int64_t)v; }
+static inline int64_t conv2d_floats(vx_wide v) { return v > (vx_wide)INT64_MAX ? -1 : (int64_t)v; }
 // split-fp16: [row group][chunk][step][row tile][hi | lo][lane][8 halves] for a layer of Cin REAL input channels
 struct C2SPack { int NT, NSUB, OCT, nchunks, nstep; int64_t floats; };
 static inline C2SPack conv2d_s16_pack(int Cin, int Cout, int KS, const vx_config& cfg) {
@@ -226,7 +224,7 @@ static inline C2SPack conv2d_s16_pack(int Cin, int Cout, int KS, const vx_config
   const int nsub_all = (int)(((int64_t)Cin + 15) / 16);
   k.nchunks = k.OCT ? 1 : (nsub_all + c.NSUB - 1) / c.NSUB;
   k.nstep = c2s_nstep(KS, c.NSUB, k.OCT);
-  k.floats = conv2d_floats((conv2d_bytes)conv2d_ygroups(Cout, c.NT) * k.nchunks * k.nstep * c.NT * 2 * 64 * 8 / 2);
+  k.floats = conv2d_floats((vx_wide)conv2d_ygroups(Cout, c.NT) * k.nchunks * k.nstep * c.NT * 2 * 64 * 8 / 2);
   return k;
 }
 // native fp32: [row group][sub-block][tap][row tile][lane][4 floats]
@@ -234,7 +232,7 @@ static inline int64_t conv2d_cin_padded(int Cin) { return (((int64_t)Cin + 15) /
 static inline int64_t conv2d_packed_floats(int Cin, int Cout, int KS, const vx_config& cfg) {
   if (!conv2d_layer_ok(Cin, Cout, KS)) return -1;
   if (conv2d_split16(cfg)) return conv2d_s16_pack(Cin, Cout, KS, cfg).floats;
-  return conv2d_floats((conv2d_bytes)conv2d_rows_padded(Cout, c2_config(KS, Cout).NT) * conv2d_cin_padded(Cin) * KS * KS);
+  return conv2d_floats((vx_wide)conv2d_rows_padded(Cout, c2_config(KS, Cout).NT) * conv2d_cin_padded(Cin) * KS * KS);
 }
 
 // ---- tiles ------------------------------------------------------------------------------------------------------------------
@@ -248,23 +246,18 @@ static inline int conv2d_tiles(int H, int W, int KS, int S) {
 }
 
 // ---- the route ----------------------------------------------------------------------------------------------------------------
-#define ROUTE2D_FAIL(code, ...)                        \
-  do {                                                 \
-    snprintf(r->err, sizeof(r->err), __VA_ARGS__);     \
-    return (code);                                     \
-  } while (0)
 
 // Every argument check of vx_conv2d, then the instance and its launch geometry.  Returns VX_OK with *r filled, or the VX_E_* code
 // of the refusal with its message in r->err.
 static inline int conv2d_route(const vx_conv2d_args& a, const vx_config& cfg, Conv2dRoute* r) {
   r->err[0] = 0;
   const bool split16 = conv2d_split16(cfg);
-  if (!a.in || !a.w_packed || !a.out) ROUTE2D_FAIL(VX_E_NULL, "vx_conv2d: null tensor pointer");
-  if (a.N <= 0 || a.H <= 0 || a.W <= 0) ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d: empty tensor");
+  if (!a.in || !a.w_packed || !a.out) VX_REFUSE(r, VX_E_NULL, "vx_conv2d: null tensor pointer");
+  if (a.N <= 0 || a.H <= 0 || a.W <= 0) VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d: empty tensor");
   if (a.Cin <= 0 || a.Cin % 16 || a.Cout <= 0)
-    ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d: Cin=%d must be a positive multiple of 16 (pad the input), Cout=%d positive", a.Cin, a.Cout);
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d: Cin=%d must be a positive multiple of 16 (pad the input), Cout=%d positive", a.Cin, a.Cout);
   if ((a.KS != 1 && a.KS != 3) || (a.S != 1 && a.S != 2) || (a.KS == 1 && a.S != 1))
-    ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d: kernel %d stride %d unsupported (3x3 s1/s2, 1x1 s1)", a.KS, a.S);
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d: kernel %d stride %d unsupported (3x3 s1/s2, 1x1 s1)", a.KS, a.S);
   // a.Cin is the PADDED channel count; weights packed for the octet-granular schedule carry their octet count in the
   // family (the real count was 8 oct - 7 .. 8 oct): accepted when it pads to this Cin
   const int fam = conv2d_family(a.Cin, a.Cout, a.KS, cfg), oct = a.w_family / 100;
@@ -272,41 +265,41 @@ static inline int conv2d_route(const vx_conv2d_args& a, const vx_config& cfg, Co
     const bool octet_ok = oct > 0 && split16 && a.KS == 3 && ((int64_t)oct * 8 + 15) / 16 * 16 == a.Cin &&
                           conv2d_s16_octets(oct * 8, a.KS, cfg) == oct && a.w_family % 100 == fam % 100;
     if (a.w_family != fam && !octet_ok)
-      ROUTE2D_FAIL(VX_E_DTYPE, "vx_conv2d: weights packed for kernel family %d, the library is configured for family %d: re-pack them",
+      VX_REFUSE(r, VX_E_DTYPE, "vx_conv2d: weights packed for kernel family %d, the library is configured for family %d: re-pack them",
                    a.w_family, fam);
   }
   // outputs leave as 16-byte groups of 4 channels: a Cout that is not a multiple of 4 writes its last group up to
   // round4(Cout) (zeros beyond Cout), which the pitch must cover
   const int64_t cout4 = ((int64_t)a.Cout + 3) / 4 * 4;
   if (a.in_pitch <= a.Cin - 16 || a.in_pitch % 4 || a.out_pitch < a.out_coff + cout4 || a.out_pitch % 4 || a.out_coff % 4)
-    ROUTE2D_FAIL(VX_E_ALIGN, "vx_conv2d: pitches/offsets must be multiples of 4 floats and cover the channels");
-  if (!conv2d_aligned16(a.in) || !conv2d_aligned16(a.out) || !conv2d_aligned16(a.w_packed) || (a.bias && !conv2d_aligned16(a.bias)))
-    ROUTE2D_FAIL(VX_E_ALIGN, "vx_conv2d: pointers must be 16-byte aligned");
+    VX_REFUSE(r, VX_E_ALIGN, "vx_conv2d: pitches/offsets must be multiples of 4 floats and cover the channels");
+  if (!vx_aligned16(a.in) || !vx_aligned16(a.out) || !vx_aligned16(a.w_packed) || (a.bias && !vx_aligned16(a.bias)))
+    VX_REFUSE(r, VX_E_ALIGN, "vx_conv2d: pointers must be 16-byte aligned");
   r->OH = conv2d_out_size(a.H, a.KS, a.S);
   r->OW = conv2d_out_size(a.W, a.KS, a.S);
-  if (((conv2d_bytes)a.H + 2) * a.W * a.in_pitch * 4 >= CONV2D_2GIB || (conv2d_bytes)r->OH * r->OW * a.out_pitch * 4 >= CONV2D_2GIB)
-    ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d: one image must stay below 2 GiB");
-  if ((a.in_scale == nullptr) != (a.in_shift == nullptr)) ROUTE2D_FAIL(VX_E_NULL, "vx_conv2d: in_scale / in_shift must come together");
+  if (((vx_wide)a.H + 2) * a.W * a.in_pitch * 4 >= CONV2D_2GIB || (vx_wide)r->OH * r->OW * a.out_pitch * 4 >= CONV2D_2GIB)
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d: one image must stay below 2 GiB");
+  if ((a.in_scale == nullptr) != (a.in_shift == nullptr)) VX_REFUSE(r, VX_E_NULL, "vx_conv2d: in_scale / in_shift must come together");
   if (a.in_scale && (a.in_cpitch < a.Cin - 15 || a.in_group_images < 0 || !split16))
-    ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d: the input prologue needs rows of in_cpitch >= the real channel count and the split-fp16 "
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d: the input prologue needs rows of in_cpitch >= the real channel count and the split-fp16 "
                  "kernels (vx_config.conv_fp32 = 0)");
   // output epilogue (fixed affine + residual + ReLU as the conv stores): refused before any launch where it has no meaning
-  if ((a.out_scale == nullptr) != (a.out_shift == nullptr)) ROUTE2D_FAIL(VX_E_NULL, "vx_conv2d: out_scale / out_shift must come together");
-  if (!a.out_scale && a.out_add) ROUTE2D_FAIL(VX_E_NULL, "vx_conv2d: out_add needs out_scale / out_shift (the output epilogue)");
-  if (!a.out_scale && a.out_act != VX_ACT_NONE) ROUTE2D_FAIL(VX_E_DTYPE, "vx_conv2d: out_act needs out_scale / out_shift (the output epilogue)");
+  if ((a.out_scale == nullptr) != (a.out_shift == nullptr)) VX_REFUSE(r, VX_E_NULL, "vx_conv2d: out_scale / out_shift must come together");
+  if (!a.out_scale && a.out_add) VX_REFUSE(r, VX_E_NULL, "vx_conv2d: out_add needs out_scale / out_shift (the output epilogue)");
+  if (!a.out_scale && a.out_act != VX_ACT_NONE) VX_REFUSE(r, VX_E_DTYPE, "vx_conv2d: out_act needs out_scale / out_shift (the output epilogue)");
   if (a.out_scale) {
     if (a.stats_partial)
-      ROUTE2D_FAIL(VX_E_DTYPE, "vx_conv2d: out_scale together with stats_partial (batch statistics belong to the raw output, which the "
+      VX_REFUSE(r, VX_E_DTYPE, "vx_conv2d: out_scale together with stats_partial (batch statistics belong to the raw output, which the "
                    "epilogue does not write)");
     if (!split16)
-      ROUTE2D_FAIL(VX_E_DTYPE, "vx_conv2d: the output epilogue (out_scale) needs the split-fp16 kernels (vx_config.conv_fp32 = 0): run "
+      VX_REFUSE(r, VX_E_DTYPE, "vx_conv2d: the output epilogue (out_scale) needs the split-fp16 kernels (vx_config.conv_fp32 = 0): run "
                    "the raw conv and vx_affine_gather");
-    if (a.out_act != VX_ACT_NONE && a.out_act != VX_ACT_RELU) ROUTE2D_FAIL(VX_E_DTYPE, "vx_conv2d: out_act must be none or relu");
+    if (a.out_act != VX_ACT_NONE && a.out_act != VX_ACT_RELU) VX_REFUSE(r, VX_E_DTYPE, "vx_conv2d: out_act must be none or relu");
     if (a.out_add && (a.out_add_pitch % 4 || a.out_add_pitch < cout4))
-      ROUTE2D_FAIL(VX_E_ALIGN, "vx_conv2d: out_add_pitch must be a multiple of 4 floats and cover the channels");
-    if (a.out_add && (conv2d_bytes)r->OH * r->OW * a.out_add_pitch * 4 >= CONV2D_2GIB)
-      ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d: one image of out_add must stay below 2 GiB");
-    if (!conv2d_aligned16(a.out_add)) ROUTE2D_FAIL(VX_E_ALIGN, "vx_conv2d: out_add must be 16-byte aligned");
+      VX_REFUSE(r, VX_E_ALIGN, "vx_conv2d: out_add_pitch must be a multiple of 4 floats and cover the channels");
+    if (a.out_add && (vx_wide)r->OH * r->OW * a.out_add_pitch * 4 >= CONV2D_2GIB)
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d: one image of out_add must stay below 2 GiB");
+    if (!vx_aligned16(a.out_add)) VX_REFUSE(r, VX_E_ALIGN, "vx_conv2d: out_add must be 16-byte aligned");
   }
 
   // ---- the instance ----
@@ -314,8 +307,8 @@ static inline int conv2d_route(const vx_conv2d_args& a, const vx_config& cfg, Co
   const int nsub_all = a.Cin / 16;
   r->tiles_x = (int)(((int64_t)r->OW + 15) / 16);
   r->tiles_y = (int)(((int64_t)r->OH + c.TY - 1) / c.TY);
-  r->mx = conv2d_magic(r->tiles_x);
-  r->my = conv2d_magic(r->tiles_y);
+  r->mx = vx_magic_raw(r->tiles_x);
+  r->my = vx_magic_raw(r->tiles_y);
   r->nchunks = (nsub_all + c.NSUB - 1) / c.NSUB;
   r->w_all = 0;
   int per_cu_max;
@@ -330,7 +323,7 @@ static inline int conv2d_route(const vx_conv2d_args& a, const vx_config& cfg, Co
     const int p[7] = {a.KS, a.S, c.NT, nsub, c.TY, oct, a.out_scale ? 1 : 0};
     r->kernel = CONV2D_S16;
     for (int i = 0; i < 7; ++i) r->p[i] = p[i];
-    if (!conv2d_instance_exists(CONV2D_S16, r->p)) ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d(s16): no such instance");   // (not reached)
+    if (!conv2d_instance_exists(CONV2D_S16, r->p)) VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d(s16): no such instance");   // (not reached)
     const C2SGeo g = c2s_geo(a.KS, a.S, c.NT, nsub, c.TY, oct, a.out_scale != nullptr);
     r->w_all = (r->nchunks > 1 && g.rest_bytes + r->nchunks * g.w_bytes <= (size_t)C2_LDS_BYTES) ? 1 : 0;
     r->lds_bytes = (int)(g.rest_bytes + (r->w_all ? r->nchunks : 1) * g.w_bytes);
@@ -339,7 +332,7 @@ static inline int conv2d_route(const vx_conv2d_args& a, const vx_config& cfg, Co
     const int p[7] = {a.KS, a.S, c.NT, c.NSUB, c.TY, 0, 0};
     r->kernel = CONV2D_MFMA;
     for (int i = 0; i < 7; ++i) r->p[i] = p[i];
-    if (!conv2d_instance_exists(CONV2D_MFMA, r->p)) ROUTE2D_FAIL(VX_E_SHAPE, "vx_conv2d: no such instance");         // (not reached)
+    if (!conv2d_instance_exists(CONV2D_MFMA, r->p)) VX_REFUSE(r, VX_E_SHAPE, "vx_conv2d: no such instance");         // (not reached)
     r->lds_bytes = c2_geo(a.KS, a.S, c.NT, c.NSUB, c.TY).lds_bytes;
     per_cu_max = 4;
   }
@@ -354,7 +347,6 @@ static inline int conv2d_route(const vx_conv2d_args& a, const vx_config& cfg, Co
   r->grid_x = gx;
   return VX_OK;
 }
-#undef ROUTE2D_FAIL
 
 // the instance's name as rocprofv3 prints it (vx_last_kernel_name): every template argument, defaulted ones included -- the
 // epilogue instances carry a seventh argument, 1; the others keep the six-argument name they always reported.  Returns the length

@@ -17,6 +17,7 @@
 #include <stdio.h>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"
 
 // ---- constants shared with the kernel files ---------------------------------------------------------------------------------
 constexpr int DEEP_NPOS = 1080;                    // conv3d_deep: positions of one LDS image (18 x 10 x 6), the R = 4 tile's cap
@@ -111,11 +112,8 @@ struct Conv3dRoute {
   char err[400];                   // the refusal's message (vx_last_error_string) when conv3d_route returns < 0
 };
 
-static inline unsigned conv3d_magic(int d) { return (unsigned)((1ull << 32) / (unsigned)d) + 1u; }
-static inline bool conv3d_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 static inline bool conv3d_pow2(int64_t v) { return (v & (v - 1)) == 0; }
 // the 32-bit offset guards: bytes of a sample, as a product no argument can overflow (four int factors and a small constant)
-typedef __int128 conv3d_bytes;
 constexpr int64_t CONV3D_2GIB = 1ll << 31;
 
 // ---- channel rules ------------------------------------------------------------------------------------------------------------
@@ -358,11 +356,6 @@ static inline int conv3d_poolfin_ok(int Cin, int Cout, const vx_config& cfg) {
 }
 
 // ---- the route ----------------------------------------------------------------------------------------------------------------
-#define ROUTE_FAIL(code, ...)                          \
-  do {                                                 \
-    snprintf(r->err, sizeof(r->err), __VA_ARGS__);     \
-    return (code);                                     \
-  } while (0)
 constexpr int ROUTE_DECLINED = 1;   // a family's step: not taken, the next family is asked
 
 static inline void route_instance(Conv3dRoute* r, int kernel, int np, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0, int f = 0,
@@ -373,14 +366,14 @@ static inline void route_instance(Conv3dRoute* r, int kernel, int np, int a = 0,
 }
 static inline void route_tiles(Conv3dRoute* r, const vx_conv3d_args& a, int txv, int ty, int tz) {
   r->tiles_x = conv3d_tiles_along(a.W, txv); r->tiles_y = conv3d_tiles_along(a.H, ty); r->tiles_z = conv3d_tiles_along(a.D, tz);
-  r->mx = conv3d_magic(r->tiles_x); r->my = conv3d_magic(r->tiles_y); r->mz = conv3d_magic(r->tiles_z);
+  r->mx = vx_magic_raw(r->tiles_x); r->my = vx_magic_raw(r->tiles_y); r->mz = vx_magic_raw(r->tiles_z);
 }
 // columns of the z-column kernels: 32 x 8 voxels, tz planes per item
 static inline void route_columns(Conv3dRoute* r, const vx_conv3d_args& a, int tz, int stat_tiles) {
   r->tiles_x = a.W / 32; r->tiles_y = a.H / 8; r->tiles_z = 1; r->kz = a.D / tz;
   const int cps = r->tiles_x * r->tiles_y;
   r->nitems = (int)((int64_t)a.N * cps);
-  r->mcps = conv3d_magic(cps); r->mx = conv3d_magic(r->tiles_x);
+  r->mcps = vx_magic_raw(cps); r->mx = vx_magic_raw(r->tiles_x);
   r->stat_epc = stat_tiles / cps;
 }
 
@@ -390,13 +383,13 @@ static inline int route_xp8w(const vx_conv3d_args& a, int stat_tiles, Conv3dRout
   route_columns(r, a, 4 / nch, stat_tiles);
   const int cps = r->tiles_x * r->tiles_y;
   r->rep = (a.in_mean && a.in_repeat > 1 && a.N % a.in_repeat == 0) ? a.in_repeat : 1;
-  r->mrep = conv3d_magic(r->rep);
-  if ((int64_t)a.N * cps >= (1ll << 31)) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): too many columns");
+  r->mrep = vx_magic_raw(r->rep);
+  if ((int64_t)a.N * cps >= (1ll << 31)) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): too many columns");
   if (a.stats_partial && (stat_tiles % cps || a.act != VX_ACT_NONE || (a.drop_mode != VX_DROP_NONE && !a.pool_out) || a.head_out))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): statistics go with a plain epilogue");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): statistics go with a plain epilogue");
   const int pre = a.in_split ? 2 : (a.in_mean ? 1 : 0);
   if (a.in_split && (a.Cin != 8 || a.in_xblk || a.in_pitch != 8 || a.up_in || !a.stats_partial))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): a pre-split input (vx_prenorm_split) goes with a dense 8-channel tensor and the "
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): a pre-split input (vx_prenorm_split) goes with a dense 8-channel tensor and the "
                "statistics epilogue (contr_1_2)");
   int epi;
   if (a.stats_partial) epi = a.pool_out ? 4 : 0;
@@ -408,23 +401,23 @@ static inline int route_xp8w(const vx_conv3d_args& a, int stat_tiles, Conv3dRout
   if (epi == 1 && a.act != VX_ACT_LRELU) return ROUTE_DECLINED;
   // 2: the up-convolution composed into the weights (vx_pack_conv3d_upfused), 1: evaluated per step by the staging waves
   const int up = a.up_in ? (a.up_fused ? 2 : 1) : 0;
-  if (a.pool_out && nch != 1) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): the pooled output goes with Cin = 8");
-  if (a.out_split) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): out_split is an epilogue of the tile kernel");
-  if (a.up_split && !up) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): up_split without up_in");
+  if (a.pool_out && nch != 1) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): the pooled output goes with Cin = 8");
+  if (a.out_split) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): out_split is an epilogue of the tile kernel");
+  if (a.up_split && !up) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): up_split without up_in");
   if (a.out_f16 && (epi != 1 || a.out_xblk || a.out_coff))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): fp16 output goes with the LeakyReLU + dropout epilogue and a dense output tensor");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): fp16 output goes with the LeakyReLU + dropout epilogue and a dense output tensor");
   if (a.in_f16 && !(nch == 1 && epi == 2 && pre == 0 && !up && !a.in_xblk))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): fp16 input goes with the dense 8-channel layer that carries the fused head");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): fp16 input goes with the dense 8-channel layer that carries the fused head");
   // IN16: bit 0 the fp16 input, bit 1 the opt-in throughput mode (vx_config.storage16 = 2): one fp16 product per fp32 product
   const int in16 = (a.in_f16 ? 1 : 0) | (a.products == 1 ? 2 : 0);
   route_instance(r, CONV3D_XP8W, 6, nch, epi, pre, up, nch == 2 ? 8 : 4, in16);
   if (conv3d_instance_exists(CONV3D_XP8W, r->p, 6)) return VX_OK;
   if (a.products == 1 && !a.in_f16)
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): products = 1 exists for the MC-dropout forward's contr_1_2, upscale2 + expand_1_1 and "
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): products = 1 exists for the MC-dropout forward's contr_1_2, upscale2 + expand_1_1 and "
                "expand_1_2 + head (nch %d, epilogue %d, prologue %d, up %d)", nch, epi, pre, up);
-  if (up) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): no fused up-convolution for this epilogue (act=%d, drop_mode=%d, statistics=%d)",
+  if (up) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): no fused up-convolution for this epilogue (act=%d, drop_mode=%d, statistics=%d)",
                      a.act, a.drop_mode, a.stats_partial ? 1 : 0);
-  if (a.pool_out) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(xp8w): no pooled output for this epilogue");
+  if (a.pool_out) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(xp8w): no pooled output for this epilogue");
   return ROUTE_DECLINED;
 }
 
@@ -432,53 +425,53 @@ static inline int route_xp8w(const vx_conv3d_args& a, int stat_tiles, Conv3dRout
 static inline int route_zc16(const vx_conv3d_args& a, int stat_tiles, Conv3dRoute* r) {
   if (a.in_xblk || a.head_out || a.in_split || a.in_f16 || a.out_f16 || (a.in_repeat > 1)) return ROUTE_DECLINED;
   if ((a.in_planar || a.out_planar) && (a.drop_mode == VX_DROP_MASK || !a.out || a.in_pitch != a.Cin || a.Cout != 16))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the planar pre-split hand-over needs hash or no dropout and dense 16-channel tensors");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): the planar pre-split hand-over needs hash or no dropout and dense 16-channel tensors");
   if (a.up_in && (a.Cin != 16 || a.in_mean || a.stats_partial || a.up_pitch < 32 || a.up_pitch % 4 || (a.up_fused && (!a.acc_in || a.out_xblk || a.out_split))))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the fused up-convolution (32 coarse channels -> the conv's 16 input channels) goes with an "
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): the fused up-convolution (32 coarse channels -> the conv's 16 input channels) goes with an "
                "activation epilogue, no prologue, up_pitch >= 32 (got %d), up_w packed by vx_pack_convT_zc16; composed weights "
                "(up_fused: vx_pack_conv3d_upfused_zc16) only together with partial sums (acc_in) and a dense float or planar output", a.up_pitch);
   if (a.drop_mode == VX_DROP_MASK || !a.out) return ROUTE_DECLINED;
   route_columns(r, a, 2, stat_tiles);
   const int cps = r->tiles_x * r->tiles_y;
-  if ((int64_t)a.N * cps >= (1ll << 31)) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): too many columns");
+  if ((int64_t)a.N * cps >= (1ll << 31)) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): too many columns");
   if (a.in_pitch != a.Cin) return ROUTE_DECLINED;
   if (a.stats_partial && (stat_tiles % cps || a.act != VX_ACT_NONE || (a.drop_mode != VX_DROP_NONE && !a.pool_out)))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): statistics go with a plain epilogue");
-  if (a.pool_out && (!a.stats_partial || a.Cin != 16)) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): the pooled output goes with statistics, 16 -> 16");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): statistics go with a plain epilogue");
+  if (a.pool_out && (!a.stats_partial || a.Cin != 16)) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): the pooled output goes with statistics, 16 -> 16");
   int pre = 0;
   if (a.in_pool_flags) pre = 3;
   else if (a.in_mean) pre = 1;
   if ((pre == 1 && a.Cin != 16) || (pre == 3 && a.Cin != 8)) return ROUTE_DECLINED;
   if (a.in_planar) {
-    if (a.Cin != 16 || pre != 0 || a.up_in || a.acc_in || a.stats_partial || !conv3d_aligned16(a.in) ||
-        (conv3d_bytes)a.D * a.H * a.W * 64 >= CONV3D_2GIB)
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): a planar pre-split input (in_planar) goes with 16 -> 16, an activation epilogue, no "
+    if (a.Cin != 16 || pre != 0 || a.up_in || a.acc_in || a.stats_partial || !vx_aligned16(a.in) ||
+        (vx_wide)a.D * a.H * a.W * 64 >= CONV3D_2GIB)
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): a planar pre-split input (in_planar) goes with 16 -> 16, an activation epilogue, no "
                  "prologue / up-convolution / partial sums, a 16-byte aligned tensor, one sample below 2 GiB");
     pre = 4;
   }
   if (a.out_planar && (a.stats_partial || a.out_pitch != 16 || a.out_coff != 0 || a.out_xblk || a.out_split || a.out == a.acc_in ||
-                       (conv3d_bytes)a.D * a.H * a.W * 64 >= CONV3D_2GIB))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): a planar pre-split output (out_planar) goes with an activation epilogue into a dense "
+                       (vx_wide)a.D * a.H * a.W * 64 >= CONV3D_2GIB))
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): a planar pre-split output (out_planar) goes with an activation epilogue into a dense "
                "16-channel tensor that is not the partial sums' (another layout), one sample below 2 GiB");
   int epi;
   if (a.stats_partial) epi = a.pool_out ? 4 : 0;
   else if (a.drop_mode == VX_DROP_HASH) { if (a.act != VX_ACT_LRELU) return ROUTE_DECLINED; epi = 1; }
   else epi = 3;
-  if (a.out_split && a.stats_partial) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): out_split goes with the activation epilogues");
+  if (a.out_split && a.stats_partial) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): out_split goes with the activation epilogues");
   if (a.out_planar) {
     // the instances that exist: the decoder's up-half launch (partial sums + fused up-convolution) and the plain 16 -> 16 layer
     if (a.Cin != 16 || pre != 0 || (epi != 1 && epi != 3) || ((a.acc_in != nullptr) != (a.up_in != nullptr)))
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): out_planar goes with 16 -> 16, an activation epilogue, no prologue, and either partial "
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): out_planar goes with 16 -> 16, an activation epilogue, no prologue, and either partial "
                  "sums + the fused up-convolution together or neither");
     epi = epi == 1 ? 5 : 6;
   }
-  if (a.acc_in && (a.Cin != 16 || pre != 0 || a.stats_partial || a.acc_pitch < 16 || a.acc_pitch % 4 || !conv3d_aligned16(a.acc_in) ||
-                   (conv3d_bytes)a.D * a.H * a.W * a.acc_pitch * 4 >= CONV3D_2GIB))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): partial sums (acc_in) go with 16 -> 16, no prologue, an activation epilogue, a "
+  if (a.acc_in && (a.Cin != 16 || pre != 0 || a.stats_partial || a.acc_pitch < 16 || a.acc_pitch % 4 || !vx_aligned16(a.acc_in) ||
+                   (vx_wide)a.D * a.H * a.W * a.acc_pitch * 4 >= CONV3D_2GIB))
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): partial sums (acc_in) go with 16 -> 16, no prologue, an activation epilogue, a "
                "16-byte aligned tensor of pitch >= 16 (pitch %d), one sample below 2 GiB", a.acc_pitch);
   route_instance(r, CONV3D_ZC16, 5, a.Cin, epi, pre, a.acc_in ? 1 : 0, a.up_in ? 1 : 0);
   if (conv3d_instance_exists(CONV3D_ZC16, r->p, 5)) return VX_OK;
-  if (a.up_in && !a.acc_in) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(zc16): no fused up-convolution for this epilogue");
+  if (a.up_in && !a.acc_in) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(zc16): no fused up-convolution for this epilogue");
   return ROUTE_DECLINED;
 }
 
@@ -505,24 +498,24 @@ static inline int route_deep(const vx_conv3d_args& a, int stat_tiles, Conv3dRout
   r->ncg = a.Cout / 32;
   const int tps = g.tiles_x * g.tiles_y * g.tiles_z;
   const int64_t npairs = (((int64_t)a.N + g.ts - 1) / g.ts) * tps * r->ncg;
-  if (npairs >= (1ll << 31)) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): too many tiles");
+  if (npairs >= (1ll << 31)) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(deep): too many tiles");
   r->nitems = (int)npairs;
-  r->m_cg = conv3d_magic(r->ncg); r->mx = conv3d_magic(g.tiles_x); r->my = conv3d_magic(g.tiles_y); r->mz = conv3d_magic(g.tiles_z);
+  r->m_cg = vx_magic_raw(r->ncg); r->mx = vx_magic_raw(g.tiles_x); r->my = vx_magic_raw(g.tiles_y); r->mz = vx_magic_raw(g.tiles_z);
   r->stat_epc = 0;
   if (a.stats_partial) {
     // the caller's partials buffer holds stat_tiles entries per sample (the tile kernel's count): this kernel's tiles must divide it,
     // else the tile kernel takes the launch (D % 4 == 2 volumes give 3 tiles against 4 entries)
     if (stat_tiles % tps) return ROUTE_DECLINED;
-    if (a.act != VX_ACT_NONE || a.drop_mode != VX_DROP_NONE) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): statistics go with a plain epilogue");
+    if (a.act != VX_ACT_NONE || a.drop_mode != VX_DROP_NONE) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(deep): statistics go with a plain epilogue");
     r->stat_epc = stat_tiles / tps;
   }
-  if ((conv3d_bytes)g.ts * a.D * a.H * a.W * a.out_pitch * 4 >= CONV3D_2GIB)
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): one tile's samples must stay below 2 GiB");
+  if ((vx_wide)g.ts * a.D * a.H * a.W * a.out_pitch * 4 >= CONV3D_2GIB)
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(deep): one tile's samples must stay below 2 GiB");
   int epi;
   if (a.stats_partial) epi = 0;
   else if (a.drop_mode == VX_DROP_HASH) { if (a.act != VX_ACT_LRELU) return ROUTE_DECLINED; epi = 1; }
   else epi = 3;
-  if (a.out_split && a.stats_partial) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(deep): out_split goes with the activation epilogues");
+  if (a.out_split && a.stats_partial) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(deep): out_split goes with the activation epilogues");
   route_instance(r, CONV3D_DEEP, 3, R, epi, a.in_mean ? 1 : 0);
   return conv3d_instance_exists(CONV3D_DEEP, r->p, 3) ? VX_OK : ROUTE_DECLINED;
 }
@@ -556,7 +549,7 @@ static inline int route_s16(const vx_conv3d_args& a, const vx_config& cfg, Conv3
   if (db == 3 && epi == 0) epi = 3;
   if (tx == 4) epi = 3;
   route_instance(r, CONV3D_S16, 9, c.CB, c.NT, tx, ty, tz, tx == 4 ? 4 : 8, c.XP, db, epi);
-  if (!conv3d_instance_exists(CONV3D_S16, r->p, 9)) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3(s16): no instance for this tile");   // (not reached)
+  if (!conv3d_instance_exists(CONV3D_S16, r->p, 9)) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(s16): no instance for this tile");   // (not reached)
   return VX_OK;
 }
 
@@ -565,86 +558,86 @@ static inline int route_s16(const vx_conv3d_args& a, const vx_config& cfg, Conv3
 static inline int conv3d_route(const vx_conv3d_args& a, const vx_config& cfg, Conv3dRoute* r) {
   r->err[0] = 0;
   r->w_off = 0;
-  if (!a.in || !a.w_packed || !a.bias || (!a.out && !a.head_out)) ROUTE_FAIL(VX_E_NULL, "vx_conv3d_k3: null tensor pointer");
+  if (!a.in || !a.w_packed || !a.bias || (!a.out && !a.head_out)) VX_REFUSE(r, VX_E_NULL, "vx_conv3d_k3: null tensor pointer");
   const ConvCfg c = conv_config(a.Cin, a.Cout, cfg);
   if (a.head_out) {
-    if (!a.head_w || !a.head_b) ROUTE_FAIL(VX_E_NULL, "vx_conv3d_k3: fused head without weights");
-    if (a.head_C < 1 || a.head_C > 8) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: fused head takes 1..8 classes, got %d", a.head_C);
+    if (!a.head_w || !a.head_b) VX_REFUSE(r, VX_E_NULL, "vx_conv3d_k3: fused head without weights");
+    if (a.head_C < 1 || a.head_C > 8) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: fused head takes 1..8 classes, got %d", a.head_C);
     if (c.S16 && a.head_C > S16_HEAD_MAXC)
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the split-fp16 kernel fuses heads of up to 4 classes, got %d", a.head_C);
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: the split-fp16 kernel fuses heads of up to 4 classes, got %d", a.head_C);
     if (!conv3d_head_fusable(a.Cin, a.Cout, cfg))
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: no fused head for Cin=%d Cout=%d (see vx_conv3d_k3_head_fusable)", a.Cin, a.Cout);
-    if (a.stats_partial) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: fused head on a layer with InstanceNorm statistics");
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: no fused head for Cin=%d Cout=%d (see vx_conv3d_k3_head_fusable)", a.Cin, a.Cout);
+    if (a.stats_partial) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: fused head on a layer with InstanceNorm statistics");
   }
   if (!conv3d_channels_ok(a.Cin, a.Cout))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: Cin=%d Cout=%d must be positive multiples of 8", a.Cin, a.Cout);
-  if (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: empty tensor");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: Cin=%d Cout=%d must be positive multiples of 8", a.Cin, a.Cout);
+  if (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: empty tensor");
   if (a.w_family != conv3d_family(a.Cin, a.Cout, cfg))
-    ROUTE_FAIL(VX_E_DTYPE, "vx_conv3d_k3: weights packed for kernel family %d, the library is configured for family %d "
+    VX_REFUSE(r, VX_E_DTYPE, "vx_conv3d_k3: weights packed for kernel family %d, the library is configured for family %d "
                "(vx_conv3d_k3_family(%d, %d)): re-pack them", a.w_family, conv3d_family(a.Cin, a.Cout, cfg), a.Cin, a.Cout);
   if (a.out_xblk && ((a.out_xblk != 1 && a.out_xblk != 2 && a.out_xblk != 4) || a.W % a.out_xblk || (a.out_half != 0 && a.out_half != 1)))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: bad concat output (xblk=%d, half=%d, W=%d)", a.out_xblk, a.out_half, a.W);
-  if ((a.in_mean == nullptr) != (a.in_rstd == nullptr)) ROUTE_FAIL(VX_E_NULL, "vx_conv3d_k3: in_mean / in_rstd must come together");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: bad concat output (xblk=%d, half=%d, W=%d)", a.out_xblk, a.out_half, a.W);
+  if ((a.in_mean == nullptr) != (a.in_rstd == nullptr)) VX_REFUSE(r, VX_E_NULL, "vx_conv3d_k3: in_mean / in_rstd must come together");
   // products: 0 / 3 = the split scheme's three products (default); 1 = the opt-in one-product mode of the full-resolution z-column kernel
   if (a.products != 0 && a.products != 1 && a.products != 3)
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: products = %d (0 / 3: the default split scheme, 1: one fp16 product)", a.products);
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: products = %d (0 / 3: the default split scheme, 1: one fp16 product)", a.products);
   const bool xp8 = c.S16 && conv3d_xp8_applies(a.D, a.H, a.W, a.Cin, a.Cout, cfg) && a.drop_mode != VX_DROP_MASK;
   if (a.products == 1 && !(xp8 && a.in_drop_mode != VX_DROP_MASK))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: products = 1 is taken by the full-resolution z-column kernel only (got %dx%dx%d, %d -> %d)",
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: products = 1 is taken by the full-resolution z-column kernel only (got %dx%dx%d, %d -> %d)",
                a.D, a.H, a.W, a.Cin, a.Cout);
   // the planar hand-over only exists in the 16 -> 16 instances of the z-column kernel: refused before any other kernel can take
   // the launch and ignore the flags
   if ((a.in_planar || a.out_planar) && !conv3d_zc16_16to16(a.D, a.H, a.W, a.Cin, a.Cout, cfg))
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the planar pre-split hand-over (in_planar / out_planar) is taken where vx_conv3d_k3_planar_ok "
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: the planar pre-split hand-over (in_planar / out_planar) is taken where vx_conv3d_k3_planar_ok "
                "(got %dx%dx%d, %d -> %d)", a.D, a.H, a.W, a.Cin, a.Cout);
   if (a.up_in) {
-    if (!a.up_w || !a.up_b) ROUTE_FAIL(VX_E_NULL, "vx_conv3d_k3: fused up-convolution without weights");
+    if (!a.up_w || !a.up_b) VX_REFUSE(r, VX_E_NULL, "vx_conv3d_k3: fused up-convolution without weights");
     if (!conv3d_upfuse_ok(a.D, a.H, a.W, a.Cin, a.Cout, cfg) || a.drop_mode == VX_DROP_MASK || a.stats_partial || a.head_out)
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: no fused up-convolution for this layer (see vx_conv3d_k3_upfuse_ok; hash or no "
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: no fused up-convolution for this layer (see vx_conv3d_k3_upfuse_ok; hash or no "
                  "dropout, no statistics, no head): %dx%dx%d, %d -> %d", a.D, a.H, a.W, a.Cin, a.Cout);
-    if (a.up_pitch < 16 || a.up_pitch % 4 || !conv3d_aligned16(a.up_in) || !conv3d_aligned16(a.up_b))
-      ROUTE_FAIL(VX_E_ALIGN, "vx_conv3d_k3: up_in pitch %d (>= 16, multiple of 4 floats) / alignment", a.up_pitch);
-    if ((conv3d_bytes)(a.D / 2 + 2) * (a.H / 2) * (a.W / 2) * a.up_pitch * 4 >= CONV3D_2GIB)
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: one coarse sample must stay below 2 GiB");
-    if (a.up_fused && !conv3d_aligned16(a.up_fused)) ROUTE_FAIL(VX_E_ALIGN, "vx_conv3d_k3: up_fused alignment");
+    if (a.up_pitch < 16 || a.up_pitch % 4 || !vx_aligned16(a.up_in) || !vx_aligned16(a.up_b))
+      VX_REFUSE(r, VX_E_ALIGN, "vx_conv3d_k3: up_in pitch %d (>= 16, multiple of 4 floats) / alignment", a.up_pitch);
+    if ((vx_wide)(a.D / 2 + 2) * (a.H / 2) * (a.W / 2) * a.up_pitch * 4 >= CONV3D_2GIB)
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: one coarse sample must stay below 2 GiB");
+    if (a.up_fused && !vx_aligned16(a.up_fused)) VX_REFUSE(r, VX_E_ALIGN, "vx_conv3d_k3: up_fused alignment");
   } else if (a.up_fused) {
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: up_fused (composed up-convolution weights) without up_in");
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: up_fused (composed up-convolution weights) without up_in");
   }
   if (a.pool_out) {
-    if (!a.pool_flags || !a.stats_partial) ROUTE_FAIL(VX_E_NULL, "vx_conv3d_k3: pool_out goes with pool_flags and stats_partial");
+    if (!a.pool_flags || !a.stats_partial) VX_REFUSE(r, VX_E_NULL, "vx_conv3d_k3: pool_out goes with pool_flags and stats_partial");
     if (!conv3d_pool_layout(a.D, a.H, a.W, a.Cin, a.Cout, cfg) || a.drop_mode == VX_DROP_MASK || a.act != VX_ACT_NONE || a.head_out)
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: no pooled output for this layer (see vx_conv3d_k3_poolfuse_ok; hash or no dropout, "
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: no pooled output for this layer (see vx_conv3d_k3_poolfuse_ok; hash or no dropout, "
                  "no activation): %dx%dx%d, %d -> %d", a.D, a.H, a.W, a.Cin, a.Cout);
-    if (!conv3d_aligned16(a.pool_out)) ROUTE_FAIL(VX_E_ALIGN, "vx_conv3d_k3: pool_out alignment");
+    if (!vx_aligned16(a.pool_out)) VX_REFUSE(r, VX_E_ALIGN, "vx_conv3d_k3: pool_out alignment");
   }
-  if (a.in_drop_mode != VX_DROP_NONE && a.in_drop_mode != VX_DROP_HASH) ROUTE_FAIL(VX_E_DTYPE, "vx_conv3d_k3: in_drop_mode %d", a.in_drop_mode);
+  if (a.in_drop_mode != VX_DROP_NONE && a.in_drop_mode != VX_DROP_HASH) VX_REFUSE(r, VX_E_DTYPE, "vx_conv3d_k3: in_drop_mode %d", a.in_drop_mode);
   if (a.in_pool_flags) {
-    if (!a.in_mean) ROUTE_FAIL(VX_E_NULL, "vx_conv3d_k3: in_pool_flags goes with in_mean / in_rstd");
+    if (!a.in_mean) VX_REFUSE(r, VX_E_NULL, "vx_conv3d_k3: in_pool_flags goes with in_mean / in_rstd");
     if (!conv3d_poolfin_ok(a.Cin, a.Cout, cfg) || a.in_xblk || a.in_pitch != 8 || a.in_split || a.up_in || a.in_repeat > 1)
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: pool-finish on load takes a dense 8-channel tensor of window maxima (see "
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: pool-finish on load takes a dense 8-channel tensor of window maxima (see "
                  "vx_conv3d_k3_poolfin_ok): %d -> %d, pitch %d", a.Cin, a.Cout, a.in_pitch);
     // the first conv of a contract block: bias + statistics (an InstanceNorm follows) -- the only epilogue whose instances carry
     // the pool-finish code; with an activation / dropout / head the launch would fall onto an instance that ignores the flag words
     if (a.act != VX_ACT_NONE || a.drop_mode != VX_DROP_NONE || a.head_out || !a.out)
-      ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: pool-finish on load goes with the plain epilogue (no activation, no dropout, no head): "
+      VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: pool-finish on load goes with the plain epilogue (no activation, no dropout, no head): "
                  "act=%d drop_mode=%d", a.act, a.drop_mode);
   }
   if (a.out && !a.out_xblk && (a.out_pitch < (int64_t)a.out_coff + a.Cout || a.out_pitch % 4 || a.out_coff % 4))
-    ROUTE_FAIL(VX_E_ALIGN, "vx_conv3d_k3: output pitch/offset must be multiples of 4 floats and cover the channels");
+    VX_REFUSE(r, VX_E_ALIGN, "vx_conv3d_k3: output pitch/offset must be multiples of 4 floats and cover the channels");
   if (a.in_xblk) {
-    if (a.in_xblk != 1 && a.in_xblk != 2 && a.in_xblk != 4) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: in_xblk must be 0, 1, 2 or 4");
-    if (a.W % a.in_xblk) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: W=%d not a multiple of in_xblk=%d", a.W, a.in_xblk);
-    if (a.Cin % 16) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: concat input needs Cin %% 16 == 0 (two halves of Cin/2)");
+    if (a.in_xblk != 1 && a.in_xblk != 2 && a.in_xblk != 4) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: in_xblk must be 0, 1, 2 or 4");
+    if (a.W % a.in_xblk) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: W=%d not a multiple of in_xblk=%d", a.W, a.in_xblk);
+    if (a.Cin % 16) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: concat input needs Cin %% 16 == 0 (two halves of Cin/2)");
   } else if (a.in_pitch < (a.up_in ? a.Cin / 2 : a.Cin) || a.in_pitch % 4) {
-    ROUTE_FAIL(VX_E_ALIGN, "vx_conv3d_k3: input pitch must be a multiple of 4 floats and cover the channels");
+    VX_REFUSE(r, VX_E_ALIGN, "vx_conv3d_k3: input pitch must be a multiple of 4 floats and cover the channels");
   }
-  if (!conv3d_aligned16(a.in) || !conv3d_aligned16(a.out) || !conv3d_aligned16(a.w_packed) || !conv3d_aligned16(a.bias))
-    ROUTE_FAIL(VX_E_ALIGN, "vx_conv3d_k3: pointers must be 16-byte aligned");
-  if (a.act < 0 || a.act > 2 || a.drop_mode < 0 || a.drop_mode > 2) ROUTE_FAIL(VX_E_DTYPE, "vx_conv3d_k3: bad act/drop enum");
-  if (a.drop_mode == VX_DROP_MASK && !a.drop_mask) ROUTE_FAIL(VX_E_NULL, "vx_conv3d_k3: VX_DROP_MASK without mask");
+  if (!vx_aligned16(a.in) || !vx_aligned16(a.out) || !vx_aligned16(a.w_packed) || !vx_aligned16(a.bias))
+    VX_REFUSE(r, VX_E_ALIGN, "vx_conv3d_k3: pointers must be 16-byte aligned");
+  if (a.act < 0 || a.act > 2 || a.drop_mode < 0 || a.drop_mode > 2) VX_REFUSE(r, VX_E_DTYPE, "vx_conv3d_k3: bad act/drop enum");
+  if (a.drop_mode == VX_DROP_MASK && !a.drop_mask) VX_REFUSE(r, VX_E_NULL, "vx_conv3d_k3: VX_DROP_MASK without mask");
   const int64_t inrow = a.in_xblk ? (int64_t)a.Cin : (int64_t)a.in_pitch;
-  if ((conv3d_bytes)a.D * a.H * a.W * a.out_pitch * 4 >= CONV3D_2GIB || ((conv3d_bytes)a.D + 2) * a.H * a.W * inrow * 4 >= CONV3D_2GIB)
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: one sample must stay below 2 GiB (32-bit buffer offsets)");
+  if ((vx_wide)a.D * a.H * a.W * a.out_pitch * 4 >= CONV3D_2GIB || ((vx_wide)a.D + 2) * a.H * a.W * inrow * 4 >= CONV3D_2GIB)
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: one sample must stay below 2 GiB (32-bit buffer offsets)");
 
   // ---- the families, in order ----
   const TileCfg t = tile_config(a.W, c.XP);
@@ -659,14 +652,14 @@ static inline int conv3d_route(const vx_conv3d_args& a, const vx_config& cfg, Co
     r->w_off = 0;
     const int rc = route_xp8w(a, stat_tiles, r);
     if (rc != ROUTE_DECLINED) return rc;
-    if (a.products == 1) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: products = 1, but the z-column kernel does not take this launch");
+    if (a.products == 1) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: products = 1, but the z-column kernel does not take this launch");
   }
   if (c.S16 && conv3d_zc16_applies(a.D, a.H, a.W, a.Cin, a.Cout, cfg)) {
     const int rc = route_zc16(a, stat_tiles, r);
     if (rc != ROUTE_DECLINED) return rc;
   }
   if (a.in_planar || a.out_planar)
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the z-column kernel does not take this planar launch (%dx%dx%d, %d -> %d)", a.D, a.H, a.W,
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: the z-column kernel does not take this planar launch (%dx%dx%d, %d -> %d)", a.D, a.H, a.W,
                a.Cin, a.Cout);
   if (c.S16 && conv3d_deep_applies(a.D, a.H, a.W, a.Cin, a.Cout, cfg)) {
     const int rc = route_deep(a, stat_tiles, r);
@@ -677,19 +670,18 @@ static inline int conv3d_route(const vx_conv3d_args& a, const vx_config& cfg, Co
   const bool xblk_pre = a.in_xblk && conv3d_tile_xblk_prologue(a.Cin, a.Cout, a.in_xblk) && !a.in_pool_flags && !(a.in_repeat > 1);
   const bool tile_pre = a.in_mean && conv3d_tile_prologue(a.Cin, a.Cout, cfg) && ((!a.in_xblk && a.in_pitch == a.Cin) || xblk_pre);
   if ((a.in_mean && !tile_pre) || a.out_xblk || a.up_in || a.pool_out || a.in_split || a.in_f16 || a.out_f16)
-    ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: the input prologue / concat output / fused up-convolution are only available where "
+    VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: the input prologue / concat output / fused up-convolution are only available where "
                "vx_conv3d_k3_prologue_ok(D, H, W, Cin, Cout), with hash or no dropout (got %dx%dx%d, %d -> %d)", a.D, a.H, a.W, a.Cin, a.Cout);
-  if (a.up_split) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: up_split goes with the fused up-convolution (up_in)");
-  if (a.acc_in) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: partial sums (acc_in) are taken where vx_conv3d_k3_acc_ok (got %dx%dx%d, %d -> %d)",
+  if (a.up_split) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: up_split goes with the fused up-convolution (up_in)");
+  if (a.acc_in) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: partial sums (acc_in) are taken where vx_conv3d_k3_acc_ok (got %dx%dx%d, %d -> %d)",
                            a.D, a.H, a.W, a.Cin, a.Cout);
   if (c.S16) return route_s16(a, cfg, r);
-  if (a.out_split) ROUTE_FAIL(VX_E_SHAPE, "vx_conv3d_k3: out_split is an epilogue of the split-fp16 tile kernel");
+  if (a.out_split) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3: out_split is an epilogue of the split-fp16 tile kernel");
   route_tiles(r, a, t.TXV, t.TY, t.TZ);
   r->nchunks = a.Cin / c.CB;
   route_instance(r, CONV3D_MFMA, 7, c.CB, c.NT, t.TX, t.TY, t.TZ, t.TX == 4 ? 4 : 8, c.XP);
   return VX_OK;
 }
-#undef ROUTE_FAIL
 
 // the instance's name as rocprofv3 prints it (vx_last_kernel_name); returns the length snprintf reports
 static inline int conv3d_route_name(const Conv3dRoute& r, char* buf, int cap) {

@@ -18,6 +18,7 @@
 #include <stdio.h>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"
 
 enum ConvTKernel { CONVT_MFMA = 0, CONVT_S16, CONVT_ROWS, CONVT_GENERIC, CONVT_NKERNELS };
 
@@ -59,14 +60,12 @@ constexpr int64_t CONVT_DECODE_PRODUCT = 1ll << 32;     // nvox * max(D, H, W) b
 constexpr int CONVT_GRID_CUS = 256, CONVT_MFMA_PER_CU = 32, CONVT_S16_WGS = 512;
 constexpr int CONVT_ROWS_MAX_WGS = 4096, CONVT_GENERIC_MAX_WGS = 8192;
 
-typedef __int128 convT_wide;   // byte and index guards: products no argument can overflow
-
 static inline bool convT_layer_ok(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % 4 == 0 && Cout % CT_CO == 0; }
 // packed weights [dz][dy][ci][dx][co]; -1: no such layer (or a size beyond int64)
 static inline int64_t convT_packed_floats(int Cin, int Cout) {
   if (!convT_layer_ok(Cin, Cout)) return -1;
-  const convT_wide v = (convT_wide)Cin * Cout * 8;
-  return v > (convT_wide)INT64_MAX ? -1 : (int64_t)v;
+  const vx_wide v = (vx_wide)Cin * Cout * 8;
+  return v > (vx_wide)INT64_MAX ? -1 : (int64_t)v;
 }
 
 // The channel rule of the tile kernels (8 Cout rows = Cout / 2 row tiles of 16; Cout % 8 == 0 is checked before): family and row
@@ -98,32 +97,24 @@ struct ConvTRoute {
   char err[200];           // the refusal's message (vx_last_error_string) when convT_route returns < 0
 };
 
-static inline unsigned convT_magic(int d) { return d == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d) + 1u; }
-
-#define ROUTET_FAIL(code, ...)                         \
-  do {                                                 \
-    snprintf(r->err, sizeof(r->err), __VA_ARGS__);     \
-    return (code);                                     \
-  } while (0)
-
 // Every argument check of vx_convT_k2s2, then the kernel and its launch geometry.  Returns VX_OK with *r filled, or the VX_E_* code
 // of the refusal with its message in r->err.
 static inline int convT_route(const vx_convT_args& a, const vx_config& cfg, ConvTRoute* r) {
   r->err[0] = 0;
-  if (!a.in || !a.w_packed || !a.bias || !a.out) ROUTET_FAIL(VX_E_NULL, "vx_convT_k2s2: null tensor");
-  if (!convT_layer_ok(a.Cin, a.Cout)) ROUTET_FAIL(VX_E_SHAPE, "vx_convT_k2s2: Cin=%d (mult of 4) Cout=%d (mult of 8)", a.Cin, a.Cout);
-  if (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0) ROUTET_FAIL(VX_E_SHAPE, "vx_convT_k2s2: empty tensor");
-  if (a.in_pitch % 4 || a.in_pitch < a.Cin) ROUTET_FAIL(VX_E_ALIGN, "vx_convT_k2s2: input pitch");
+  if (!a.in || !a.w_packed || !a.bias || !a.out) VX_REFUSE(r, VX_E_NULL, "vx_convT_k2s2: null tensor");
+  if (!convT_layer_ok(a.Cin, a.Cout)) VX_REFUSE(r, VX_E_SHAPE, "vx_convT_k2s2: Cin=%d (mult of 4) Cout=%d (mult of 8)", a.Cin, a.Cout);
+  if (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0) VX_REFUSE(r, VX_E_SHAPE, "vx_convT_k2s2: empty tensor");
+  if (a.in_pitch % 4 || a.in_pitch < a.Cin) VX_REFUSE(r, VX_E_ALIGN, "vx_convT_k2s2: input pitch");
   if (a.out_xblk) {
     if ((a.out_xblk != 1 && a.out_xblk != 2 && a.out_xblk != 4) || (2 * (int64_t)a.W) % a.out_xblk || (a.out_half != 0 && a.out_half != 1))
-      ROUTET_FAIL(VX_E_SHAPE, "vx_convT_k2s2: bad concat layout (xblk=%d, half=%d)", a.out_xblk, a.out_half);
+      VX_REFUSE(r, VX_E_SHAPE, "vx_convT_k2s2: bad concat layout (xblk=%d, half=%d)", a.out_xblk, a.out_half);
   } else if (a.out_pitch % 4 || a.out_coff % 4 || a.out_pitch < (int64_t)a.out_coff + a.Cout) {
-    ROUTET_FAIL(VX_E_ALIGN, "vx_convT_k2s2: pitches/offsets must be multiples of 4 floats");
+    VX_REFUSE(r, VX_E_ALIGN, "vx_convT_k2s2: pitches/offsets must be multiples of 4 floats");
   }
-  if (a.drop_mode == VX_DROP_MASK && !a.drop_mask) ROUTET_FAIL(VX_E_NULL, "vx_convT_k2s2: mask mode without mask");
+  if (a.drop_mode == VX_DROP_MASK && !a.drop_mask) VX_REFUSE(r, VX_E_NULL, "vx_convT_k2s2: mask mode without mask");
   // All four kernels: the dropout element index ((oz OH + oy) OW + ox) Cout + co of one sample is a 32-bit word, and the offset
   // inside an interleaved output row, < 4 W Cout, an int.  (What follows from it: D H W < 2^26, so nvox and total fit an int64.)
-  if ((convT_wide)a.D * a.H * a.W * 8 * a.Cout >= ((convT_wide)1 << 32)) ROUTET_FAIL(VX_E_SHAPE, "vx_convT_k2s2: sample too large");
+  if ((vx_wide)a.D * a.H * a.W * 8 * a.Cout >= ((vx_wide)1 << 32)) VX_REFUSE(r, VX_E_SHAPE, "vx_convT_k2s2: sample too large");
   r->nvox = (int64_t)a.N * a.D * a.H * a.W;
   r->kernel = -1;
   r->cin = r->rt = r->ncoltiles = 0;
@@ -135,27 +126,27 @@ static inline int convT_route(const vx_convT_args& a, const vx_config& cfg, Conv
   // sample index n = v / (D H W) goes on as size_t ----
   const int64_t dmax = a.W > a.H ? (a.W > a.D ? a.W : a.D) : (a.H > a.D ? a.H : a.D);
   ConvTTiles t = {-1, 0};
-  if (r->nvox < CONVT_DECODE_NVOX && (convT_wide)r->nvox * dmax < CONVT_DECODE_PRODUCT && convT_tile_rule(a.Cin, a.Cout, cfg, &t)) {
+  if (r->nvox < CONVT_DECODE_NVOX && (vx_wide)r->nvox * dmax < CONVT_DECODE_PRODUCT && convT_tile_rule(a.Cin, a.Cout, cfg, &t)) {
     r->kernel = t.kernel; r->cin = a.Cin; r->rt = t.rt;
     r->mask = a.drop_mode == VX_DROP_MASK;
-    if (!convT_instance_exists(r->kernel, r->cin, r->rt, r->mask)) ROUTET_FAIL(VX_E_SHAPE, "vx_convT_k2s2: no such instance");   // (not reached)
+    if (!convT_instance_exists(r->kernel, r->cin, r->rt, r->mask)) VX_REFUSE(r, VX_E_SHAPE, "vx_convT_k2s2: no such instance");   // (not reached)
     r->ncoltiles = (int)((r->nvox + 15) / 16);
     r->grid_y = (a.Cout / 2) / t.rt;   // groups of RT row tiles
     const int wgs = t.kernel == CONVT_S16 ? CONVT_S16_WGS : CONVT_GRID_CUS * CONVT_MFMA_PER_CU;
     const int cap = (wgs + r->grid_y - 1) / r->grid_y;
     r->grid_x = (r->ncoltiles + 3) / 4;   // one column tile per wave ...
     if (r->grid_x > cap) r->grid_x = cap; // ... or a grid stride
-    r->mW = convT_magic(a.W); r->mH = convT_magic(a.H); r->mD = convT_magic(a.D);
+    r->mW = vx_magic_or0(a.W); r->mH = vx_magic_or0(a.H); r->mD = vx_magic_or0(a.D);
     return VX_OK;
   }
   // ---- rows and generic kernels: flat indices are int64, but the output plane n * 2D + oz (and the input plane n * D + z) is an
   // int before it is widened ----
-  if ((int64_t)a.N * 2 * a.D >= (1ll << 31)) ROUTET_FAIL(VX_E_SHAPE, "vx_convT_k2s2: N * 2 D must stay below 2^31");
+  if ((int64_t)a.N * 2 * a.D >= (1ll << 31)) VX_REFUSE(r, VX_E_SHAPE, "vx_convT_k2s2: N * 2 D must stay below 2^31");
   if (convT_rows_rule(a.Cin, a.Cout)) {
     // large, shallow up-convolutions.  Pieces per output row 2 W Cout / 4 < 2^28 (sample guard): an int
     r->kernel = CONVT_ROWS; r->cin = a.Cin;
-    if (!convT_instance_exists(r->kernel, r->cin, 0, 0)) ROUTET_FAIL(VX_E_SHAPE, "vx_convT_k2s2: no such instance");             // (not reached)
-    r->total = (int64_t)((convT_wide)r->nvox * 2 * (a.Cout / 4));
+    if (!convT_instance_exists(r->kernel, r->cin, 0, 0)) VX_REFUSE(r, VX_E_SHAPE, "vx_convT_k2s2: no such instance");             // (not reached)
+    r->total = (int64_t)((vx_wide)r->nvox * 2 * (a.Cout / 4));
     const int64_t bx = (r->total + 255) / 256;
     r->grid_x = bx > CONVT_ROWS_MAX_WGS ? CONVT_ROWS_MAX_WGS : (int)bx;
     r->grid_y = 4;   // (dz, dy)
@@ -167,7 +158,6 @@ static inline int convT_route(const vx_convT_args& a, const vx_config& cfg, Conv
   r->grid_y = 4 * (a.Cout / CT_CO);   // (dz, dy) x groups of CT_CO channels
   return VX_OK;
 }
-#undef ROUTET_FAIL
 
 // the name vx_last_kernel_name() reports after the launch.  Returns the length snprintf reports
 static inline int convT_route_name(const ConvTRoute& r, char* buf, int cap) {

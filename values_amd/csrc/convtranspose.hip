@@ -152,7 +152,6 @@ __global__ __launch_bounds__(256) void convT_k2s2_rows_kernel(vx_convT_args a, i
 // (blockIdx.y picks which) in registers for its whole life and walks column tiles with a grid stride.  The VALU
 // work left is the bias/activation/dropout epilogue, which leaves the kernel HBM-store-bound.
 struct ConvTDecode { unsigned mW, mH, mD; };   // 2^32 / d + 1 (0: d == 1); exact while v * d < 2^32 (launcher checks)
-__device__ __forceinline__ unsigned ct_div(unsigned n, unsigned m) { return m ? __umulhi(n, m) : n; }
 
 // MASK: the injected-mask dropout of the parity tests as its own instance -- a (run-time) branch around its mask load made
 // hipcc put an `s_waitcnt vmcnt(0)` at the join, on EVERY path: each column tile then waited for the stores of the tile
@@ -226,9 +225,9 @@ __global__ __launch_bounds__(256) void convT_k2s2_mfma_kernel(vx_convT_args a, i
       load_x(ct, xv);
     }
     unsigned r = (unsigned)vc, q;
-    q = ct_div(r, dc.mW); const int x = (int)(r - q * (unsigned)a.W); r = q;
-    q = ct_div(r, dc.mH); const int y = (int)(r - q * (unsigned)a.H); r = q;
-    q = ct_div(r, dc.mD); const int z = (int)(r - q * (unsigned)a.D);
+    q = vx_magic_div(r, dc.mW); const int x = (int)(r - q * (unsigned)a.W); r = q;
+    q = vx_magic_div(r, dc.mH); const int y = (int)(r - q * (unsigned)a.H); r = q;
+    q = vx_magic_div(r, dc.mD); const int z = (int)(r - q * (unsigned)a.D);
     const int n = (int)q;
     const vx_dkey dkey = vx_drop_key(seed0, a.drop_layer, (uint32_t)n);
 #pragma unroll
@@ -364,9 +363,9 @@ __global__ __launch_bounds__(256) void convT_k2s2_s16_kernel(vx_convT_args a, in
     asm volatile("s_nop 7" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     unsigned r = (unsigned)vc, qq;
-    qq = ct_div(r, dc.mW); const int x = (int)(r - qq * (unsigned)a.W); r = qq;
-    qq = ct_div(r, dc.mH); const int y = (int)(r - qq * (unsigned)a.H); r = qq;
-    qq = ct_div(r, dc.mD); const int z = (int)(r - qq * (unsigned)a.D);
+    qq = vx_magic_div(r, dc.mW); const int x = (int)(r - qq * (unsigned)a.W); r = qq;
+    qq = vx_magic_div(r, dc.mH); const int y = (int)(r - qq * (unsigned)a.H); r = qq;
+    qq = vx_magic_div(r, dc.mD); const int z = (int)(r - qq * (unsigned)a.D);
     const int n = (int)qq;
     const vx_dkey dkey = vx_drop_key(seed0, a.drop_layer, (uint32_t)n);
 #pragma unroll

@@ -255,14 +255,8 @@ struct em_plan {
   char err[160] = {0};
 };
 
-#define EM_REFUSE(code, ...)                       \
-  do {                                             \
-    snprintf(p->err, sizeof(p->err), __VA_ARGS__); \
-    return (code);                                 \
-  } while (0)
-
 int em_layout(const char* who, int n_items, size_t entry, int K, em_plan* p) {
-  if (n_items < 1 || n_items > VX_EM_MAX_ITEMS) EM_REFUSE(VX_E_SHAPE, "%s: n_items %d outside 1..%d", who, n_items, VX_EM_MAX_ITEMS);
+  if (n_items < 1 || n_items > VX_EM_MAX_ITEMS) VX_REFUSE(p, VX_E_SHAPE, "%s: n_items %d outside 1..%d", who, n_items, VX_EM_MAX_ITEMS);
   p->table_bytes = (size_t)n_items * entry;
   p->off_partial = vx_align256(p->table_bytes);
   p->bytes = p->off_partial + (size_t)n_items * EM_BLOCKS * K * sizeof(double);
@@ -270,38 +264,37 @@ int em_layout(const char* who, int n_items, size_t entry, int K, em_plan* p) {
 }
 
 int em_plan_raters(const char* who, const vx_em_item* items, int n_items, size_t entry, int K, em_plan* p) {
-  if (!items) EM_REFUSE(VX_E_NULL, "%s: null items", who);
+  if (!items) VX_REFUSE(p, VX_E_NULL, "%s: null items", who);
   const int rc = em_layout(who, n_items, entry, K, p);
   if (rc != VX_OK) return rc;
   for (int i = 0; i < n_items; ++i) {
     const vx_em_item& it = items[i];
-    if (!it.unc || !it.ref || !it.pred) EM_REFUSE(VX_E_NULL, "%s: item %d: null map, reference or prediction", who, i);
-    if (it.dtype != VX_F32 && it.dtype != VX_F64) EM_REFUSE(VX_E_DTYPE, "%s: item %d: dtype %d", who, i, it.dtype);
+    if (!it.unc || !it.ref || !it.pred) VX_REFUSE(p, VX_E_NULL, "%s: item %d: null map, reference or prediction", who, i);
+    if (it.dtype != VX_F32 && it.dtype != VX_F64) VX_REFUSE(p, VX_E_DTYPE, "%s: item %d: dtype %d", who, i, it.dtype);
     if (it.R < 1 || it.nvox < 1 || it.nvox > INT64_MAX / it.R)
-      EM_REFUSE(VX_E_SHAPE, "%s: item %d: R %d, nvox %lld", who, i, it.R, (long long)it.nvox);
+      VX_REFUSE(p, VX_E_SHAPE, "%s: item %d: R %d, nvox %lld", who, i, it.R, (long long)it.nvox);
   }
   return VX_OK;
 }
 
 int em_plan_ncc(const vx_ncc_item* items, int n_items, em_plan* p) {
   const char* who = "vx_ncc_batched";
-  if (!items) EM_REFUSE(VX_E_NULL, "%s: null items", who);
+  if (!items) VX_REFUSE(p, VX_E_NULL, "%s: null items", who);
   const int rc = em_layout(who, n_items, sizeof(vx_ncc_item), 3, p);
   if (rc != VX_OK) return rc;
   for (int i = 0; i < n_items; ++i) {
     const vx_ncc_item& it = items[i];
-    if (!it.gt || !it.pred) EM_REFUSE(VX_E_NULL, "%s: item %d: null map", who, i);
-    if (it.gt_R < 0) EM_REFUSE(VX_E_SHAPE, "%s: item %d: gt_R %d", who, i, it.gt_R);
+    if (!it.gt || !it.pred) VX_REFUSE(p, VX_E_NULL, "%s: item %d: null map", who, i);
+    if (it.gt_R < 0) VX_REFUSE(p, VX_E_SHAPE, "%s: item %d: gt_R %d", who, i, it.gt_R);
     if ((it.gt_R == 0 && it.gt_dtype != VX_F32 && it.gt_dtype != VX_F64) || (it.pred_dtype != VX_F32 && it.pred_dtype != VX_F64))
-      EM_REFUSE(VX_E_DTYPE, "%s: item %d: dtypes %d, %d", who, i, it.gt_dtype, it.pred_dtype);
-    if (it.n_gt < 1 || it.n_pred < 1) EM_REFUSE(VX_E_SHAPE, "%s: item %d: empty map", who, i);
+      VX_REFUSE(p, VX_E_DTYPE, "%s: item %d: dtypes %d, %d", who, i, it.gt_dtype, it.pred_dtype);
+    if (it.n_gt < 1 || it.n_pred < 1) VX_REFUSE(p, VX_E_SHAPE, "%s: item %d: empty map", who, i);
     if (it.n_gt != it.n_pred)
-      EM_REFUSE(VX_E_SHAPE, "%s: item %d: maps of different size (%lld, %lld)", who, i, (long long)it.n_gt, (long long)it.n_pred);
-    if (it.gt_R > 0 && it.n_gt > INT64_MAX / it.gt_R) EM_REFUSE(VX_E_SHAPE, "%s: item %d: gt_R %d x %lld", who, i, it.gt_R, (long long)it.n_gt);
+      VX_REFUSE(p, VX_E_SHAPE, "%s: item %d: maps of different size (%lld, %lld)", who, i, (long long)it.n_gt, (long long)it.n_pred);
+    if (it.gt_R > 0 && it.n_gt > INT64_MAX / it.gt_R) VX_REFUSE(p, VX_E_SHAPE, "%s: item %d: gt_R %d x %lld", who, i, it.gt_R, (long long)it.n_gt);
   }
   return VX_OK;
 }
-#undef EM_REFUSE
 
 int em_check_buffers(const char* who, const em_plan& p, const void* out, const void* workspace, size_t workspace_bytes) {
   if (!out || !workspace) VX_FAIL(VX_E_NULL, "%s: null out or workspace", who);

@@ -4,7 +4,22 @@
 //   vx_norm_act_drop_pool: y = Dropout(LeakyReLU((x - mean) * rstd)); writes y with an arbitrary
 //                          channel pitch/offset (the skip half of the decoder concat buffer) and the
 //                          2x2x2 max-pool of y.  Pure streaming: 16-byte vectors, HBM-bound.
+// Host side: every argument check, instance choice and launch geometry is in stream3d_route.h; an entry point is its route, then
+// the kernel family's launcher with the descriptor.
 #include "s16_common.h"
+#include "stream3d_route.h"
+
+// a route's refusal becomes the library's error
+static int routed(int rc, const Stream3dRoute& r) {
+  if (rc != VX_OK) vx_set_error("%s", r.err);
+  return rc;
+}
+// the route's name, formatted once per launcher instance (a function-local static at each call) and kept for the process
+static const char* s3_kname(const Stream3dRoute& r) {
+  char buf[96];
+  stream3d_route_name(r, buf, (int)sizeof(buf));
+  return vx_kname("%s", buf);
+}
 
 __global__ __launch_bounds__(64) void instnorm_finalize_kernel(const float* __restrict__ partial, int ntiles, int C,
                                                                double inv_count, float eps, float* __restrict__ mean,
@@ -32,10 +47,11 @@ __global__ __launch_bounds__(64) void instnorm_finalize_kernel(const float* __re
 
 extern "C" int vx_instnorm_finalize(const float* stats_partial, int N, int ntiles, int C, int64_t nvox, float eps,
                                     float* mean, float* rstd, vx_stream_t stream) {
-  if (!stats_partial || !mean || !rstd) VX_FAIL(VX_E_NULL, "vx_instnorm_finalize: null pointer");
-  if (N <= 0 || ntiles <= 0 || C <= 0 || nvox <= 0) VX_FAIL(VX_E_SHAPE, "vx_instnorm_finalize: empty");
-  vx_note_kernel("instnorm_finalize_kernel");
-  hipLaunchKernelGGL(instnorm_finalize_kernel, dim3((unsigned)(N * C)), dim3(64), 0, (hipStream_t)stream,
+  Stream3dRoute r;
+  if (const int rc = routed(stream3d_finalize_route(stats_partial, N, ntiles, C, nvox, mean, rstd, &r), r)) return rc;
+  static const char* kname = s3_kname(r);
+  vx_note_kernel(kname);
+  hipLaunchKernelGGL(instnorm_finalize_kernel, dim3((unsigned)r.grid_x), dim3(64), 0, (hipStream_t)stream,
                      stats_partial, ntiles, C, 1.0 / (double)nvox, eps, mean, rstd);
   VX_CHECK_LAUNCH("vx_instnorm_finalize");
   return VX_OK;
@@ -49,7 +65,6 @@ extern "C" int vx_instnorm_finalize(const float* stats_partial, int N, int ntile
 // The four instnorm_finalize launches in front of these passes (first block's pre-split, vx_pool_finish_z, the two normalise +
 // pool passes of the deep levels) are gone: 33 -> 29 launches per forward.
 struct StatSrc { const float* partial; int tiles; double inv_count; float eps; float* mean_out; float* rstd_out; };
-constexpr int VX_STAT_MAXC = 512;
 __device__ __forceinline__ void vx_block_instnorm(const StatSrc& st, int n, int C, bool write, float* s_mu, float* s_rs, double* s_part) {
   const float* p = st.partial + (size_t)n * st.tiles * C * 2;
   const int tid = threadIdx.x;
@@ -96,12 +111,10 @@ __device__ __forceinline__ void vx_block_instnorm(const StatSrc& st, int n, int 
     __syncthreads();
   }
 }
-static int vx_stat_src_check(const vx_stat_src* st, int C, const char* who, StatSrc* o) {
-  if (!st || !st->stats_partial) VX_FAIL(VX_E_NULL, "%s: null statistics source", who);
-  if (st->tiles <= 0 || st->count <= 0 || C > VX_STAT_MAXC) VX_FAIL(VX_E_SHAPE, "%s: %d tiles, %lld values per channel, C = %d (<= %d)", who, st->tiles, (long long)st->count, C, VX_STAT_MAXC);
-  o->partial = st->stats_partial; o->tiles = st->tiles; o->inv_count = 1.0 / (double)st->count; o->eps = st->eps;
-  o->mean_out = st->mean_out; o->rstd_out = st->rstd_out;
-  return VX_OK;
+// the device's form of a checked vx_stat_src (null: the pass takes mean / rstd tables)
+static StatSrc stat_src(const vx_stat_src* st) {
+  if (!st) return StatSrc{};
+  return StatSrc{st->stats_partial, st->tiles, 1.0 / (double)st->count, st->eps, st->mean_out, st->rstd_out};
 }
 
 // One thread = one 16-byte piece (4 channels of one voxel) of a full-resolution ROW; consecutive lanes hold
@@ -123,7 +136,6 @@ __device__ __forceinline__ void vx_range_report(uint32_t* flag, float rmax) {
   for (int off = 32; off >= 1; off >>= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, off, 64));
   if ((threadIdx.x & 63) == 0 && !(rmax < 32768.f)) atomicMax(flag, __float_as_uint(rmax));
 }
-__device__ __forceinline__ unsigned vx_magic_div(unsigned n, unsigned m) { return m ? __umulhi(n, m) : n; }
 // WIDE (pooling with more than 128 channels): the x-neighbour's piece would sit in another wave, so a thread takes
 // BOTH voxels of an x-pair (a row then has W/2 * C/4 work items) and no shuffle is needed.
 template <bool POOL, bool WIDE = false, bool FOLD = false>
@@ -288,106 +300,53 @@ __global__ __launch_bounds__(256) void norm_act_drop_fanout_kernel(vx_norm_args 
   vx_range_report(a.range_flag, rmax);
 }
 
-static int norm_act_drop_pool_impl(const vx_norm_args* ap, int x_repeat, const vx_stat_src* stsrc, vx_stream_t stream);
-extern "C" int vx_norm_act_drop_pool(const vx_norm_args* ap, vx_stream_t stream) {
-  return norm_act_drop_pool_impl(ap, 1, nullptr, stream);
+template <bool POOL, bool WIDE, bool FOLD>
+static void launch_norm_instance(const Stream3dRoute& r, const vx_norm_args& a, int x_repeat, const NormDecode& dc, const StatSrc& st, hipStream_t s) {
+  static const char* kname = s3_kname(r);
+  vx_note_kernel(kname);
+  hipLaunchKernelGGL((norm_act_drop_pool_kernel<POOL, WIDE, FOLD>), dim3(r.grid_x, r.grid_y), dim3(256), 0, s, a, x_repeat, dc, st);
 }
+
+static int norm_route_or_fail(const vx_norm_args* ap, int x_repeat, const vx_stat_src* stsrc, Stream3dRoute* r) {
+  if (!ap) VX_FAIL(VX_E_NULL, "vx_norm_act_drop_pool: null args");
+  return routed(stream3d_norm_route(*ap, x_repeat, stsrc, r), *r);
+}
+
+// the three forms of the pass: one route, one launcher
+static int launch_norm(const vx_norm_args* ap, int x_repeat, const vx_stat_src* stsrc, vx_stream_t stream) {
+  Stream3dRoute r;
+  if (const int rc = norm_route_or_fail(ap, x_repeat, stsrc, &r)) return rc;
+  const vx_norm_args& a = *ap;
+  hipStream_t s = (hipStream_t)stream;
+  const NormDecode dc = {r.pieces, r.mPW, r.mC4, r.mH};
+  const StatSrc st = stat_src(stsrc);
+  if (r.kernel == S3_FANOUT) {
+    static const char* kname = s3_kname(r);
+    vx_note_kernel(kname);
+    hipLaunchKernelGGL(norm_act_drop_fanout_kernel, dim3(r.grid_x, r.grid_y), dim3(256), 0, s, a, x_repeat, dc);
+  } else {
+#define NORM_LAUNCH_CASE(P, W, F) case stream3d_key(P, W, F): launch_norm_instance<P != 0, W != 0, F != 0>(r, a, x_repeat, dc, st, s); break;
+    switch (stream3d_key(r.pool, r.wide, r.fold)) { STREAM3D_NORM_INSTANCES(NORM_LAUNCH_CASE) }
+#undef NORM_LAUNCH_CASE
+  }
+  VX_CHECK_LAUNCH("vx_norm_act_drop_pool");
+  return VX_OK;
+}
+
+extern "C" int vx_norm_act_drop_pool(const vx_norm_args* ap, vx_stream_t stream) { return launch_norm(ap, 1, nullptr, stream); }
 extern "C" int vx_norm_act_drop_pool_bcast(const vx_norm_args* ap, int x_repeat, vx_stream_t stream) {
-  return norm_act_drop_pool_impl(ap, x_repeat, nullptr, stream);
+  return launch_norm(ap, x_repeat, nullptr, stream);
 }
 extern "C" int vx_norm_act_drop_pool_stats(const vx_norm_args* ap, const vx_stat_src* st, vx_stream_t stream) {
   if (!st) VX_FAIL(VX_E_NULL, "vx_norm_act_drop_pool_stats: null statistics source");
-  return norm_act_drop_pool_impl(ap, 1, st, stream);
+  return launch_norm(ap, 1, st, stream);
 }
-
-static int norm_act_drop_pool_impl(const vx_norm_args* ap, int x_repeat, const vx_stat_src* stsrc, vx_stream_t stream) {
-  if (!ap) VX_FAIL(VX_E_NULL, "vx_norm_act_drop_pool: null args");
-  StatSrc st = {};
-  if (stsrc) {
-    const int rc = vx_stat_src_check(stsrc, ap->C, "vx_norm_act_drop_pool_stats", &st);
-    if (rc != VX_OK) return rc;
-    if (ap->mean || ap->rstd) VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool_stats: the statistics come from the source, mean / rstd must be NULL");
-  }
-  if (x_repeat < 1) VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: x_repeat must be >= 1");
-  const vx_norm_args& a = *ap;
-  if (!a.x || (!a.out && !a.pool_out)) VX_FAIL(VX_E_NULL, "vx_norm_act_drop_pool: null tensor");
-  if (a.x_xblk && ((a.x_xblk != 1 && a.x_xblk != 2 && a.x_xblk != 4) || a.W % a.x_xblk || (a.x_half != 0 && a.x_half != 1)))
-    VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: bad concat input (xblk=%d, half=%d, W=%d)", a.x_xblk, a.x_half, a.W);
-  if (a.x_xblk && (x_repeat > 1 || !a.pool_out)) VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: a concat input goes with pooling, x_repeat 1");
-  if ((a.mean == nullptr) != (a.rstd == nullptr)) VX_FAIL(VX_E_NULL, "vx_norm_act_drop_pool: mean/rstd must come together");
-  if (a.N <= 0 || a.D <= 0 || a.H <= 0 || a.W <= 0 || a.C <= 0 || a.C % 4)
-    VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: bad shape (C must be a multiple of 4)");
-  if (!a.x_xblk && (a.x_pitch % 4 || a.x_pitch < a.C)) VX_FAIL(VX_E_ALIGN, "vx_norm_act_drop_pool: input pitch");
-  if (!a.out) {
-    // pooled tensor only
-  } else if (a.out_xblk) {
-    if ((a.out_xblk != 1 && a.out_xblk != 2 && a.out_xblk != 4) || a.W % a.out_xblk || (a.out_half != 0 && a.out_half != 1))
-      VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: bad concat layout (xblk=%d, half=%d, W=%d)", a.out_xblk, a.out_half, a.W);
-  } else if (a.out_pitch % 4 || a.out_coff % 4 || a.out_pitch < a.out_coff + a.C) {
-    VX_FAIL(VX_E_ALIGN, "vx_norm_act_drop_pool: pitches/offsets must be multiples of 4 floats");
-  }
-  if (a.drop_mode == VX_DROP_MASK && !a.drop_mask) VX_FAIL(VX_E_NULL, "vx_norm_act_drop_pool: mask mode without mask");
-  if ((int64_t)a.D * a.H * a.W * a.C >= (1ll << 32)) VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: sample too large");
-  hipStream_t s = (hipStream_t)stream;
-  if (a.pool_out) {
-    if (a.D % 2 || a.H % 2 || a.W % 2) VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: pooling needs even dims");
-    if (a.pool_pitch % 4 || a.pool_pitch < a.C) VX_FAIL(VX_E_ALIGN, "vx_norm_act_drop_pool: pool pitch");
-    // the x-pair exchange is a shuffle over C/4 lanes: both voxels of a pair must sit in one wave, i.e. the
-    // pieces of a row must not straddle a 64-lane boundary mid-pair: (W*C/4) % (2*C/4) == 0 always holds (W even)
-    // and a wave starts at a multiple of 64 pieces, which is a multiple of 2*C/4 when C/4 divides 32
-    if (a.C / 4 <= 32 && (32 % (a.C / 4)) != 0)
-      VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: pooling needs C/4 to divide 32, or C > 128 (C = %d)", a.C);
-  }
-  {
-    const int pool = a.pool_out ? 1 : 0;
-    const int wide = pool && a.C / 4 > 32;
-    const int C4 = a.C / 4, PW = (wide ? a.W / 2 : a.W) * C4, RH = pool ? a.H / 2 : a.H, RD = pool ? a.D / 2 : a.D;
-    const int64_t per = (int64_t)RD * RH * PW;
-    const int64_t dmax = PW > RH ? PW : RH;
-    // grid y = samples: N, or the N / x_repeat source samples of the fan-out kernel
-    const int grid_y = (!pool && x_repeat > 1) ? a.N / x_repeat : a.N;
-    if (per * dmax >= (1ll << 32) || grid_y > 65535)
-      VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: sample too large for the 32-bit index decode (%lld pieces) or more than 65535 samples in the grid (%d)", (long long)per, grid_y);
-    NormDecode dc;
-    dc.per_sample = (unsigned)per;
-    auto magic = [](int d) { return d == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d) + 1u; };
-    dc.mPW = magic(PW); dc.mC4 = magic(C4); dc.mH = magic(RH);
-    int bx = (int)((per + 255) / 256);
-    const int cap = (16384 + a.N - 1) / a.N;
-    if (!pool && bx > cap) bx = cap > 0 ? cap : 1;
-    if (!pool && x_repeat > 1) {
-      if (a.N % x_repeat) VX_FAIL(VX_E_SHAPE, "vx_norm_act_drop_pool: N=%d is not a multiple of x_repeat=%d", a.N, x_repeat);
-      const int ns = a.N / x_repeat;
-      int fx = (int)((per + 255) / 256);
-      const int fcap = (32768 + ns - 1) / ns;
-      if (fx > fcap) fx = fcap;
-      vx_note_kernel("norm_act_drop_fanout_kernel");
-      hipLaunchKernelGGL(norm_act_drop_fanout_kernel, dim3(fx, ns), dim3(256), 0, s, a, x_repeat, dc);
-    } else if (stsrc) {
-      // (four pieces per thread: the workgroup's reduction of the partials is paid once per 1 024 pieces instead of 256)
-      bx = (bx + 3) / 4;
-      if (wide) {
-        vx_note_kernel("norm_act_drop_pool_kernel<true,true,true>");
-        hipLaunchKernelGGL((norm_act_drop_pool_kernel<true, true, true>), dim3(bx, a.N), dim3(256), 0, s, a, x_repeat, dc, st);
-      } else if (pool) {
-        vx_note_kernel("norm_act_drop_pool_kernel<true,false,true>");
-        hipLaunchKernelGGL((norm_act_drop_pool_kernel<true, false, true>), dim3(bx, a.N), dim3(256), 0, s, a, x_repeat, dc, st);
-      } else {
-        vx_note_kernel("norm_act_drop_pool_kernel<false,false,true>");
-        hipLaunchKernelGGL((norm_act_drop_pool_kernel<false, false, true>), dim3(bx, a.N), dim3(256), 0, s, a, x_repeat, dc, st);
-      }
-    } else if (wide) {
-      vx_note_kernel("norm_act_drop_pool_kernel<true,true>");
-      hipLaunchKernelGGL((norm_act_drop_pool_kernel<true, true>), dim3(bx, a.N), dim3(256), 0, s, a, x_repeat, dc, st);
-    } else if (pool) {
-      vx_note_kernel("norm_act_drop_pool_kernel<true,false>");
-      hipLaunchKernelGGL(norm_act_drop_pool_kernel<true>, dim3(bx, a.N), dim3(256), 0, s, a, x_repeat, dc, st);
-    } else {
-      vx_note_kernel("norm_act_drop_pool_kernel<false,false>");
-      hipLaunchKernelGGL(norm_act_drop_pool_kernel<false>, dim3(bx, a.N), dim3(256), 0, s, a, x_repeat, dc, st);
-    }
-  }
-  VX_CHECK_LAUNCH("vx_norm_act_drop_pool");
+extern "C" int vx_norm_act_drop_pool_route(const vx_norm_args* ap, int x_repeat, const vx_stat_src* st, char* kernel_name, int cap,
+                                           vx_norm_route_info* info) {
+  Stream3dRoute r;
+  if (const int rc = norm_route_or_fail(ap, x_repeat, st, &r)) return rc;
+  if (kernel_name && cap > 0) stream3d_route_name(r, kernel_name, cap);
+  if (info) *info = {r.grid_x, r.grid_y, r.pieces, r.mPW, r.mC4, r.mH};
   return VX_OK;
 }
 
@@ -409,14 +368,9 @@ __global__ __launch_bounds__(256) void drop_hash_mask_kernel(uint32_t seed, uint
 
 extern "C" int vx_drop_hash_mask(uint32_t seed, uint32_t layer, int N, int64_t elems_per_sample, uint8_t* mask,
                                  vx_stream_t stream) {
-  if (N <= 0 || elems_per_sample <= 0 || elems_per_sample % 4 || elems_per_sample >= (1ll << 32))
-    VX_FAIL(VX_E_SHAPE, "vx_drop_hash_mask: N=%d, %lld elements per sample (a positive multiple of 4 below 2^32)", N,
-            (long long)elems_per_sample);
-  if (!mask || (((uintptr_t)mask) & 3u)) VX_FAIL(VX_E_ALIGN, "vx_drop_hash_mask: mask must be a 4-byte aligned device pointer");
-  const int64_t total = (int64_t)N * (elems_per_sample / 4);
-  int bx = (int)((total + 255) / 256);
-  if (bx > 16384) bx = 16384;
-  hipLaunchKernelGGL(drop_hash_mask_kernel, dim3(bx), dim3(256), 0, (hipStream_t)stream, seed, layer, N, elems_per_sample, mask);
+  Stream3dRoute r;
+  if (const int rc = routed(stream3d_hash_mask_route(N, elems_per_sample, mask, &r), r)) return rc;
+  hipLaunchKernelGGL(drop_hash_mask_kernel, dim3(r.grid_x), dim3(256), 0, (hipStream_t)stream, seed, layer, N, elems_per_sample, mask);
   VX_CHECK_LAUNCH("vx_drop_hash_mask");
   return VX_OK;
 }
@@ -513,92 +467,63 @@ __global__ __launch_bounds__(256) void prenorm_split_kernel(float* __restrict__ 
   }
 }
 
-extern "C" int vx_prenorm_split(float* x, const float* mean, const float* rstd, int N, int64_t nvox, float scale,
-                                vx_stream_t stream) {
-  if (!x || !mean || !rstd) VX_FAIL(VX_E_NULL, "vx_prenorm_split: null pointer");
-  if (N <= 0 || N >= 65536 || nvox <= 0 || nvox >= (1ll << 30)) VX_FAIL(VX_E_SHAPE, "vx_prenorm_split: empty / too large");
-  if (!vx_aligned16(x) || !vx_aligned16(mean) || !vx_aligned16(rstd)) VX_FAIL(VX_E_ALIGN, "vx_prenorm_split: alignment");
-  const unsigned pieces = (unsigned)(nvox * 2);
-  unsigned bx = (pieces + 255u) / 256u;
-  if (bx > 512u) bx = 512u;
-  vx_note_kernel("prenorm_split_kernel<false>");
-  hipLaunchKernelGGL(prenorm_split_kernel<false>, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, pieces, scale, StatSrc{});
-  VX_CHECK_LAUNCH("vx_prenorm_split");
+// ---- the small passes: the plain and the _stats form of a pass are one route and one launcher, FOLD the kernel's own switch ----
+template <bool FOLD>
+static int launch_split(const char* who, float* x, const float* mean, const float* rstd, const vx_stat_src* stsrc, int N, int64_t nvox,
+                        float scale, vx_stream_t stream) {
+  Stream3dRoute r;
+  if (const int rc = routed(stream3d_split_route(who, x, mean, rstd, FOLD, stsrc, N, nvox, &r), r)) return rc;
+  static const char* kname = s3_kname(r);
+  vx_note_kernel(kname);
+  hipLaunchKernelGGL(prenorm_split_kernel<FOLD>, dim3(r.grid_x, r.grid_y), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, r.pieces, scale,
+                     stat_src(stsrc));
+  VX_CHECK_LAUNCH(who);
   return VX_OK;
 }
-
+extern "C" int vx_prenorm_split(float* x, const float* mean, const float* rstd, int N, int64_t nvox, float scale, vx_stream_t stream) {
+  return launch_split<false>("vx_prenorm_split", x, mean, rstd, nullptr, N, nvox, scale, stream);
+}
 extern "C" int vx_prenorm_split_stats(float* x, const vx_stat_src* stsrc, int N, int64_t nvox, float scale, vx_stream_t stream) {
-  if (!x) VX_FAIL(VX_E_NULL, "vx_prenorm_split_stats: null pointer");
-  if (N <= 0 || N >= 65536 || nvox <= 0 || nvox >= (1ll << 30)) VX_FAIL(VX_E_SHAPE, "vx_prenorm_split_stats: empty / too large");
-  if (!vx_aligned16(x)) VX_FAIL(VX_E_ALIGN, "vx_prenorm_split_stats: alignment");
-  StatSrc st;
-  const int rc = vx_stat_src_check(stsrc, 8, "vx_prenorm_split_stats", &st);
-  if (rc != VX_OK) return rc;
-  const unsigned pieces = (unsigned)(nvox * 2);
-  unsigned bx = (pieces + 255u) / 256u;
-  if (bx > 128u) bx = 128u;       // (longer-lived workgroups than the plain pass: each reduces the partials once)
-  vx_note_kernel("prenorm_split_kernel<true>");
-  hipLaunchKernelGGL(prenorm_split_kernel<true>, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr, pieces, scale, st);
-  VX_CHECK_LAUNCH("vx_prenorm_split_stats");
-  return VX_OK;
+  return launch_split<true>("vx_prenorm_split_stats", x, nullptr, nullptr, stsrc, N, nvox, scale, stream);
 }
 
 extern "C" int vx_pool_finish(const float* pool_raw, const uint32_t* pool_flags, const float* mean, const float* rstd,
                               float* out, int out_pitch, int N, int64_t voxels_per_sample, int drop_scale2,
                               vx_stream_t stream) {
-  if (!pool_raw || !pool_flags || !mean || !rstd || !out) VX_FAIL(VX_E_NULL, "vx_pool_finish: null pointer");
-  if (N <= 0 || voxels_per_sample <= 0 || voxels_per_sample >= (1ll << 30)) VX_FAIL(VX_E_SHAPE, "vx_pool_finish: empty / too large");
-  if (out_pitch < 8 || out_pitch % 4 || !vx_aligned16(pool_raw) || !vx_aligned16(out))
-    VX_FAIL(VX_E_ALIGN, "vx_pool_finish: pitch %d / alignment", out_pitch);
-  const unsigned pieces = (unsigned)(voxels_per_sample * 2);
-  unsigned bx = (pieces + 255u) / 256u;
-  if (bx > 64u) bx = 64u;
-  if (N >= 65536) VX_FAIL(VX_E_SHAPE, "vx_pool_finish: N");
-  vx_note_kernel("pool_finish_kernel");
-  hipLaunchKernelGGL(pool_finish_kernel, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, pool_raw, pool_flags, mean,
-                     rstd, out, out_pitch, pieces, drop_scale2 ? 2.f : 1.f);
+  Stream3dRoute r;
+  if (const int rc = routed(stream3d_finish_route(pool_raw, pool_flags, mean, rstd, out, out_pitch, N, voxels_per_sample, &r), r)) return rc;
+  static const char* kname = s3_kname(r);
+  vx_note_kernel(kname);
+  hipLaunchKernelGGL(pool_finish_kernel, dim3(r.grid_x, r.grid_y), dim3(256), 0, (hipStream_t)stream, pool_raw, pool_flags, mean,
+                     rstd, out, out_pitch, r.pieces, drop_scale2 ? 2.f : 1.f);
   VX_CHECK_LAUNCH("vx_pool_finish");
   return VX_OK;
 }
 
+template <bool FOLD>
+static int launch_finish_z(const char* who, const float* pool_raw, const uint32_t* pool_flags, const float* mean, const float* rstd,
+                           const vx_stat_src* stsrc, float* out, int out_pitch, int N, int Dp, int64_t plane_voxels, int drop_scale2,
+                           vx_stream_t stream) {
+  Stream3dRoute r;
+  if (const int rc = routed(stream3d_finish_z_route(who, pool_raw, pool_flags, mean, rstd, FOLD, stsrc, out, out_pitch, N, Dp, plane_voxels, &r), r))
+    return rc;
+  static const char* kname = s3_kname(r);
+  vx_note_kernel(kname);
+  hipLaunchKernelGGL(pool_finish_z_kernel<FOLD>, dim3(r.grid_x, r.grid_y), dim3(256), 0, (hipStream_t)stream, pool_raw, pool_flags, mean,
+                     rstd, out, out_pitch, (unsigned)Dp, (unsigned)plane_voxels, drop_scale2 ? 2.f : 1.f, stat_src(stsrc));
+  VX_CHECK_LAUNCH(who);
+  return VX_OK;
+}
 extern "C" int vx_pool_finish_z(const float* pool_raw, const uint32_t* pool_flags, const float* mean, const float* rstd,
                                 float* out, int out_pitch, int N, int Dp, int64_t plane_voxels, int drop_scale2,
                                 vx_stream_t stream) {
-  if (!pool_raw || !pool_flags || !mean || !rstd || !out) VX_FAIL(VX_E_NULL, "vx_pool_finish_z: null pointer");
-  if (N <= 0 || Dp <= 0 || plane_voxels <= 0 || (int64_t)Dp * plane_voxels >= (1ll << 28)) VX_FAIL(VX_E_SHAPE, "vx_pool_finish_z: empty / too large");
-  if (out_pitch < 16 || out_pitch % 4 || !vx_aligned16(pool_raw) || !vx_aligned16(out))
-    VX_FAIL(VX_E_ALIGN, "vx_pool_finish_z: pitch %d / alignment", out_pitch);
-  if (N >= 65536) VX_FAIL(VX_E_SHAPE, "vx_pool_finish_z: N");
-  const unsigned pieces = (unsigned)(Dp * plane_voxels * 4);
-  unsigned bx = (pieces + 255u) / 256u;
-  if (bx > 64u) bx = 64u;
-  vx_note_kernel("pool_finish_z_kernel<false>");
-  hipLaunchKernelGGL(pool_finish_z_kernel<false>, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, pool_raw, pool_flags, mean,
-                     rstd, out, out_pitch, (unsigned)Dp, (unsigned)plane_voxels, drop_scale2 ? 2.f : 1.f, StatSrc{});
-  VX_CHECK_LAUNCH("vx_pool_finish_z");
-  return VX_OK;
+  return launch_finish_z<false>("vx_pool_finish_z", pool_raw, pool_flags, mean, rstd, nullptr, out, out_pitch, N, Dp, plane_voxels, drop_scale2, stream);
 }
-
 extern "C" int vx_pool_finish_z_stats(const float* pool_raw, const uint32_t* pool_flags, const vx_stat_src* stsrc, float* out,
                                       int out_pitch, int N, int Dp, int64_t plane_voxels, int drop_scale2, vx_stream_t stream) {
-  if (!pool_raw || !pool_flags || !out) VX_FAIL(VX_E_NULL, "vx_pool_finish_z_stats: null pointer");
-  if (N <= 0 || Dp <= 0 || plane_voxels <= 0 || (int64_t)Dp * plane_voxels >= (1ll << 28)) VX_FAIL(VX_E_SHAPE, "vx_pool_finish_z_stats: empty / too large");
-  if (out_pitch < 16 || out_pitch % 4 || !vx_aligned16(pool_raw) || !vx_aligned16(out))
-    VX_FAIL(VX_E_ALIGN, "vx_pool_finish_z_stats: pitch %d / alignment", out_pitch);
-  if (N >= 65536) VX_FAIL(VX_E_SHAPE, "vx_pool_finish_z_stats: N");
-  StatSrc st;
-  const int rc = vx_stat_src_check(stsrc, 16, "vx_pool_finish_z_stats", &st);
-  if (rc != VX_OK) return rc;
-  const unsigned pieces = (unsigned)(Dp * plane_voxels * 4);
-  unsigned bx = (pieces + 255u) / 256u;
-  if (bx > 16u) bx = 16u;
-  vx_note_kernel("pool_finish_z_kernel<true>");
-  hipLaunchKernelGGL(pool_finish_z_kernel<true>, dim3(bx, (unsigned)N), dim3(256), 0, (hipStream_t)stream, pool_raw, pool_flags,
-                     (const float*)nullptr, (const float*)nullptr, out, out_pitch, (unsigned)Dp, (unsigned)plane_voxels, drop_scale2 ? 2.f : 1.f, st);
-  VX_CHECK_LAUNCH("vx_pool_finish_z_stats");
-  return VX_OK;
+  return launch_finish_z<true>("vx_pool_finish_z_stats", pool_raw, pool_flags, nullptr, nullptr, stsrc, out, out_pitch, N, Dp, plane_voxels, drop_scale2,
+                               stream);
 }
-
 
 extern "C" int vx_zero(void* p, int64_t bytes, vx_stream_t stream) {
   if (bytes < 0 || (!p && bytes > 0)) VX_FAIL(VX_E_NULL, "vx_zero: null pointer / negative size");

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"
 
 #define P2D_THREADS 256
 #define P2D_PER_LANE 4                                   // consecutive output pixels of a lane in one step
@@ -43,8 +44,6 @@ struct p2d_plan {
   char err[200] = {0};
 };
 
-static inline size_t p2d_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // size / k rounded half to even on the exact quotient: cv2.resize's saturate_cast<int>(size * fx) at fx = 1 / k
 static inline int p2d_out_size(int size, int k) {
   if (size < 1 || k < 1 || (k & 1)) return 0;
@@ -54,50 +53,43 @@ static inline int p2d_out_size(int size, int k) {
   return q + (q & 1);
 }
 
-#define P2D_REFUSE(plan, c, ...)                                \
-  do {                                                          \
-    snprintf((plan)->err, sizeof((plan)->err), __VA_ARGS__);    \
-    (plan)->code = (c);                                         \
-    return (c);                                                 \
-  } while (0)
-
 static inline int p2d_plan_items(const vx_p2d_item* items, int n_items, const vx_p2d_tables* tables, p2d_plan* p) {
   const char* who = "vx_crop_resize_batched";
-  if (n_items < 0 || n_items > VX_SELECT_MAX_ITEMS) P2D_REFUSE(p, VX_E_SHAPE, "%s: n_items %d outside 0..%d", who, n_items, VX_SELECT_MAX_ITEMS);
+  if (n_items < 0 || n_items > VX_SELECT_MAX_ITEMS) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: n_items %d outside 0..%d", who, n_items, VX_SELECT_MAX_ITEMS);
   if (n_items == 0) return VX_OK;
-  if (!items) P2D_REFUSE(p, VX_E_NULL, "%s: null items", who);
+  if (!items) VX_REFUSE_CODE(p, VX_E_NULL, "%s: null items", who);
   p->items.reserve((size_t)n_items);
   for (int i = 0; i < n_items; ++i) {
     const vx_p2d_item& it = items[i];
-    if (it.bpp != 1 && it.bpp != 3 && it.bpp != 4) P2D_REFUSE(p, VX_E_DTYPE, "%s: item %d: bpp %d (1, 3 or 4)", who, i, it.bpp);
+    if (it.bpp != 1 && it.bpp != 3 && it.bpp != 4) VX_REFUSE_CODE(p, VX_E_DTYPE, "%s: item %d: bpp %d (1, 3 or 4)", who, i, it.bpp);
     if (it.mode != VX_P2D_IMAGE && it.mode != VX_P2D_LABEL_IDS && it.mode != VX_P2D_LABEL_COLOR)
-      P2D_REFUSE(p, VX_E_DTYPE, "%s: item %d: mode %d", who, i, it.mode);
-    if (it.palette && it.bpp != 1) P2D_REFUSE(p, VX_E_DTYPE, "%s: item %d: a palette with bpp %d", who, i, it.bpp);
+      VX_REFUSE_CODE(p, VX_E_DTYPE, "%s: item %d: mode %d", who, i, it.mode);
+    if (it.palette && it.bpp != 1) VX_REFUSE_CODE(p, VX_E_DTYPE, "%s: item %d: a palette with bpp %d", who, i, it.bpp);
     if (it.mode == VX_P2D_LABEL_IDS) {
-      if (it.bpp != 1 || it.palette) P2D_REFUSE(p, VX_E_DTYPE, "%s: item %d: label ids are a grey image (bpp 1, no palette)", who, i);
+      if (it.bpp != 1 || it.palette) VX_REFUSE_CODE(p, VX_E_DTYPE, "%s: item %d: label ids are a grey image (bpp 1, no palette)", who, i);
     } else if (it.bpp == 1 && !it.palette) {
-      P2D_REFUSE(p, VX_E_DTYPE, "%s: item %d: bpp 1 without a palette where a colour image is expected", who, i);
+      VX_REFUSE_CODE(p, VX_E_DTYPE, "%s: item %d: bpp 1 without a palette where a colour image is expected", who, i);
     }
-    if (it.H < 1 || it.W < 1) P2D_REFUSE(p, VX_E_SHAPE, "%s: item %d: H=%d W=%d", who, i, it.H, it.W);
-    if ((int64_t)it.H * it.W * it.bpp > 0x7FFFFFFF) P2D_REFUSE(p, VX_E_SHAPE, "%s: item %d: H W bpp >= 2^31", who, i);
-    if (it.factor < 1 || (it.factor & 1)) P2D_REFUSE(p, VX_E_SHAPE, "%s: item %d: factor %d is not a positive even integer", who, i, it.factor);
+    if (it.H < 1 || it.W < 1) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: item %d: H=%d W=%d", who, i, it.H, it.W);
+    if ((int64_t)it.H * it.W * it.bpp > 0x7FFFFFFF) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: item %d: H W bpp >= 2^31", who, i);
+    if (it.factor < 1 || (it.factor & 1)) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: item %d: factor %d is not a positive even integer", who, i, it.factor);
     if (it.crop_h < 1 || it.crop_w < 1 || it.y0 < 0 || it.x0 < 0 || (int64_t)it.y0 + it.crop_h > it.H || (int64_t)it.x0 + it.crop_w > it.W)
-      P2D_REFUSE(p, VX_E_SHAPE, "%s: item %d: crop %d x %d at (%d, %d) outside the %d x %d image", who, i, it.crop_h, it.crop_w, it.y0,
+      VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: item %d: crop %d x %d at (%d, %d) outside the %d x %d image", who, i, it.crop_h, it.crop_w, it.y0,
                  it.x0, it.H, it.W);
     const int oh = p2d_out_size(it.crop_h, it.factor), ow = p2d_out_size(it.crop_w, it.factor);
-    if (oh < 1 || ow < 1) P2D_REFUSE(p, VX_E_SHAPE, "%s: item %d: a %d x %d crop at factor %d has no output", who, i, it.crop_h, it.crop_w, it.factor);
-    if (!it.src || !it.out_rgb) P2D_REFUSE(p, VX_E_NULL, "%s: item %d: null src or out_rgb", who, i);
+    if (oh < 1 || ow < 1) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: item %d: a %d x %d crop at factor %d has no output", who, i, it.crop_h, it.crop_w, it.factor);
+    if (!it.src || !it.out_rgb) VX_REFUSE_CODE(p, VX_E_NULL, "%s: item %d: null src or out_rgb", who, i);
     if (it.mode != VX_P2D_IMAGE) {
-      if (!it.out_ids) P2D_REFUSE(p, VX_E_NULL, "%s: item %d: null out_ids", who, i);
-      if (!tables) P2D_REFUSE(p, VX_E_NULL, "%s: item %d: null tables", who, i);
+      if (!it.out_ids) VX_REFUSE_CODE(p, VX_E_NULL, "%s: item %d: null out_ids", who, i);
+      if (!tables) VX_REFUSE_CODE(p, VX_E_NULL, "%s: item %d: null tables", who, i);
     }
     if (it.mode == VX_P2D_LABEL_IDS && (!tables->id2trainid || !tables->trainid2color))
-      P2D_REFUSE(p, VX_E_NULL, "%s: item %d: null id2trainid or trainid2color", who, i);
+      VX_REFUSE_CODE(p, VX_E_NULL, "%s: item %d: null id2trainid or trainid2color", who, i);
     if (it.mode == VX_P2D_LABEL_COLOR) {
-      if (tables->n_color < 0 || tables->n_color > P2D_MAX_COLORS) P2D_REFUSE(p, VX_E_SHAPE, "%s: n_color=%d (0..%d)", who, tables->n_color, P2D_MAX_COLORS);
-      if (tables->default_id < 0 || tables->default_id > 255) P2D_REFUSE(p, VX_E_DTYPE, "%s: default_id=%d", who, tables->default_id);
-      if (tables->n_color > 0 && !tables->color2trainid) P2D_REFUSE(p, VX_E_NULL, "%s: item %d: null color2trainid", who, i);
-      if ((uintptr_t)it.out_ids & 7) P2D_REFUSE(p, VX_E_ALIGN, "%s: item %d: int64 out_ids not aligned to 8 bytes", who, i);
+      if (tables->n_color < 0 || tables->n_color > P2D_MAX_COLORS) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: n_color=%d (0..%d)", who, tables->n_color, P2D_MAX_COLORS);
+      if (tables->default_id < 0 || tables->default_id > 255) VX_REFUSE_CODE(p, VX_E_DTYPE, "%s: default_id=%d", who, tables->default_id);
+      if (tables->n_color > 0 && !tables->color2trainid) VX_REFUSE_CODE(p, VX_E_NULL, "%s: item %d: null color2trainid", who, i);
+      if ((uintptr_t)it.out_ids & 7) VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: item %d: int64 out_ids not aligned to 8 bytes", who, i);
     }
     p2d_item_dev d;
     d.src = it.src; d.palette = it.palette; d.out_rgb = it.out_rgb; d.out_ids = it.mode == VX_P2D_IMAGE ? nullptr : it.out_ids;
@@ -109,6 +101,6 @@ static inline int p2d_plan_items(const vx_p2d_item* items, int n_items, const vx
     p->items.push_back(d);
     p->n_blocks += d.n_blocks;
   }
-  p->bytes = p2d_align256((size_t)n_items * sizeof(p2d_item_dev));
+  p->bytes = vx_align256((size_t)n_items * sizeof(p2d_item_dev));
   return VX_OK;
 }

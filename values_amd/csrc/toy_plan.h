@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"
 
 #ifdef __HIPCC__
 #define TOY_HD __host__ __device__ __forceinline__
@@ -35,15 +36,6 @@ TOY_HD int toy_reflect(int64_t i, int n) {
   return (int)(m < n ? m : p - 1 - m);
 }
 
-#define TOY_REFUSE(plan, c, ...)                                \
-  do {                                                          \
-    snprintf((plan)->err, sizeof((plan)->err), __VA_ARGS__);    \
-    (plan)->code = (c);                                         \
-    return (c);                                                 \
-  } while (0)
-
-static inline size_t toy_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // ---------------------------------------------------------------------------------------------------------------
 // vx_toy_embed: the object's box clipped to the image, in image coordinates BEFORE the flips
 struct toy_embed_plan {
@@ -56,20 +48,20 @@ struct toy_embed_plan {
 static inline int toy_plan_embed(const void* obj, const int32_t* obj_dims, const int32_t* offset, const void* image,
                                  const int32_t* dims, toy_embed_plan* p) {
   const char* who = "vx_toy_embed";
-  if (!obj || !obj_dims || !offset || !image || !dims) TOY_REFUSE(p, VX_E_NULL, "%s: null pointer", who);
+  if (!obj || !obj_dims || !offset || !image || !dims) VX_REFUSE_CODE(p, VX_E_NULL, "%s: null pointer", who);
   int64_t n = 1;
   for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || obj_dims[a] < 1) TOY_REFUSE(p, VX_E_SHAPE, "%s: axis %d: image %d, object %d voxels", who, a, dims[a], obj_dims[a]);
+    if (dims[a] < 1 || obj_dims[a] < 1) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: axis %d: image %d, object %d voxels", who, a, dims[a], obj_dims[a]);
     n *= dims[a];
-    if (n > TOY_MAX_N) TOY_REFUSE(p, VX_E_SHAPE, "%s: more than 2^40 voxels", who);
+    if (n > TOY_MAX_N) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: more than 2^40 voxels", who);
     const int64_t lo = offset[a] > 0 ? offset[a] : 0;
     const int64_t end = (int64_t)offset[a] + obj_dims[a];
     const int64_t hi = end < dims[a] ? end : dims[a];
     p->lo[a] = (int32_t)(lo < dims[a] ? lo : dims[a]);
     p->hi[a] = (int32_t)(hi > 0 ? hi : 0);
   }
-  if ((uintptr_t)obj & 3) TOY_REFUSE(p, VX_E_ALIGN, "%s: obj not aligned to its 4-byte elements", who);
-  if ((uintptr_t)image & 7) TOY_REFUSE(p, VX_E_ALIGN, "%s: image not aligned to its 8-byte elements", who);
+  if ((uintptr_t)obj & 3) VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: obj not aligned to its 4-byte elements", who);
+  if ((uintptr_t)image & 7) VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: image not aligned to its 8-byte elements", who);
   p->n = n;
   return VX_OK;
 }
@@ -94,19 +86,19 @@ static inline int toy_strided_step(int tw) { return TOY_STRIDED_ROWS * (TOY_THRE
 static inline int toy_plan_blur(const void* src, const void* dst, const int32_t* dims, int axis, const void* weights, int radius,
                                 toy_blur_plan* p) {
   const char* who = "vx_gauss_blur_axis_f64";
-  if (!src || !dst || !dims || !weights) TOY_REFUSE(p, VX_E_NULL, "%s: null pointer", who);
-  if (axis < 0 || axis > 2) TOY_REFUSE(p, VX_E_SHAPE, "%s: axis %d", who, axis);
-  if (radius < 0 || radius > TOY_MAX_RADIUS) TOY_REFUSE(p, VX_E_SHAPE, "%s: radius %d outside 0..%d", who, radius, TOY_MAX_RADIUS);
+  if (!src || !dst || !dims || !weights) VX_REFUSE_CODE(p, VX_E_NULL, "%s: null pointer", who);
+  if (axis < 0 || axis > 2) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: axis %d", who, axis);
+  if (radius < 0 || radius > TOY_MAX_RADIUS) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: radius %d outside 0..%d", who, radius, TOY_MAX_RADIUS);
   int64_t n = 1;
   for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1) TOY_REFUSE(p, VX_E_SHAPE, "%s: axis %d: %d voxels", who, a, dims[a]);
+    if (dims[a] < 1) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: axis %d: %d voxels", who, a, dims[a]);
     n *= dims[a];
-    if (n > TOY_MAX_N) TOY_REFUSE(p, VX_E_SHAPE, "%s: more than 2^40 voxels", who);
+    if (n > TOY_MAX_N) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: more than 2^40 voxels", who);
   }
   if (((uintptr_t)src & 7) || ((uintptr_t)dst & 7) || ((uintptr_t)weights & 7))
-    TOY_REFUSE(p, VX_E_ALIGN, "%s: src, dst or weights not aligned to its 8-byte elements", who);
+    VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: src, dst or weights not aligned to its 8-byte elements", who);
   const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (uintptr_t)n * 8, d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)n * 8;
-  if (s0 < d1 && d0 < s1) TOY_REFUSE(p, VX_E_SHAPE, "%s: src and dst overlap (a pass never runs in place)", who);
+  if (s0 < d1 && d0 < s1) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: src and dst overlap (a pass never runs in place)", who);
   const bool al16 = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
   if (axis == 2) {
     p->outer = (int64_t)dims[0] * dims[1]; p->len = dims[2]; p->inner = 1;
@@ -127,8 +119,8 @@ static inline int toy_plan_blur(const void* src, const void* dst, const int32_t*
     p->blocks = p->outer * p->slabs;
     p->vec = al16 && p->inner % 2 == 0;
   }
-  if (p->lds > TOY_LDS_BYTES) TOY_REFUSE(p, VX_E_SHAPE, "%s: radius %d: no tile fits the LDS", who, radius);
-  if (p->blocks > 0x7fffffffLL) TOY_REFUSE(p, VX_E_SHAPE, "%s: %lld workgroups", who, (long long)p->blocks);
+  if (p->lds > TOY_LDS_BYTES) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: radius %d: no tile fits the LDS", who, radius);
+  if (p->blocks > 0x7fffffffLL) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: %lld workgroups", who, (long long)p->blocks);
   return VX_OK;
 }
 
@@ -146,25 +138,25 @@ struct toy_os_plan {
 };
 
 static inline size_t toy_os_bytes() {
-  return toy_align256(2 * TOY_OS_CHUNK * 8) + toy_align256((size_t)TOY_OS_CHUNK * 256 * 8) + toy_align256(2 * TOY_OS_MAX_K * 8);
+  return vx_align256(2 * TOY_OS_CHUNK * 8) + vx_align256((size_t)TOY_OS_CHUNK * 256 * 8) + vx_align256(2 * TOY_OS_MAX_K * 8);
 }
 
 static inline int toy_plan_order_stats(const void* x, int64_t n, const int64_t* ks, int n_k, const void* out, const void* status,
                                        const void* workspace, int64_t ws_bytes, toy_os_plan* p) {
   const char* who = "vx_order_stats_f64";
-  if (n_k < 1 || n_k > TOY_OS_MAX_K) TOY_REFUSE(p, VX_E_SHAPE, "%s: n_k %d outside 1..%d", who, n_k, TOY_OS_MAX_K);
-  if (n < 1 || n > TOY_MAX_N) TOY_REFUSE(p, VX_E_SHAPE, "%s: n=%lld outside 1..2^40", who, (long long)n);
-  if (!x || !ks || !out || !status || !workspace) TOY_REFUSE(p, VX_E_NULL, "%s: null pointer", who);
+  if (n_k < 1 || n_k > TOY_OS_MAX_K) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: n_k %d outside 1..%d", who, n_k, TOY_OS_MAX_K);
+  if (n < 1 || n > TOY_MAX_N) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: n=%lld outside 1..2^40", who, (long long)n);
+  if (!x || !ks || !out || !status || !workspace) VX_REFUSE_CODE(p, VX_E_NULL, "%s: null pointer", who);
   for (int i = 0; i < n_k; ++i)
-    if (ks[i] < 0 || ks[i] >= n) TOY_REFUSE(p, VX_E_SHAPE, "%s: rank %d: k=%lld outside [0, %lld)", who, i, (long long)ks[i], (long long)n);
+    if (ks[i] < 0 || ks[i] >= n) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: rank %d: k=%lld outside [0, %lld)", who, i, (long long)ks[i], (long long)n);
   if (((uintptr_t)x & 7) || ((uintptr_t)out & 7) || ((uintptr_t)status & 3))
-    TOY_REFUSE(p, VX_E_ALIGN, "%s: x, out or status not aligned to its elements", who);
-  if ((uintptr_t)workspace & 15) TOY_REFUSE(p, VX_E_ALIGN, "%s: workspace not 16-byte aligned", who);
+    VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: x, out or status not aligned to its elements", who);
+  if ((uintptr_t)workspace & 15) VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: workspace not 16-byte aligned", who);
   p->off_krem = TOY_OS_CHUNK * 8;
-  p->off_hist = toy_align256(2 * TOY_OS_CHUNK * 8);
-  p->off_vals = p->off_hist + toy_align256((size_t)TOY_OS_CHUNK * 256 * 8);
+  p->off_hist = vx_align256(2 * TOY_OS_CHUNK * 8);
+  p->off_vals = p->off_hist + vx_align256((size_t)TOY_OS_CHUNK * 256 * 8);
   p->bytes = toy_os_bytes();
-  if (ws_bytes < (int64_t)p->bytes) TOY_REFUSE(p, VX_E_WORKSPACE, "%s: workspace needs %lld bytes", who, (long long)p->bytes);
+  if (ws_bytes < (int64_t)p->bytes) VX_REFUSE_CODE(p, VX_E_WORKSPACE, "%s: workspace needs %lld bytes", who, (long long)p->bytes);
   // insertion into the sorted list of distinct ranks (at most 64)
   for (int i = 0; i < n_k; ++i) {
     for (int h = 0; h < 2; ++h) {

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "../../include/values_amd.h"
+#include "host_checks.h"
 
 // A workgroup is four waves on ONE row of 64 columns.  The voxeliser is bound by the latency of a wave's walk over its list,
 // not by throughput: the volumes are small against the machine, so a tile one sample high gives the most
@@ -32,32 +33,25 @@ struct vox_plan {
   char err[160] = {0};
 };
 
-#define VOX_REFUSE(plan, c, ...)                                \
-  do {                                                          \
-    snprintf((plan)->err, sizeof((plan)->err), __VA_ARGS__);    \
-    (plan)->code = (c);                                         \
-    return (c);                                                 \
-  } while (0)
-
 static inline int vox_plan_meshes(const void* tris, const int64_t* mesh_offsets, int n_meshes, const double* origin, double h,
                                   const int32_t* dims, const void* out, const void* odd_columns, vox_plan* p) {
   const char* who = "vx_voxelize_meshes";
-  if (!tris || !mesh_offsets || !origin || !dims || !out || !odd_columns) VOX_REFUSE(p, VX_E_NULL, "%s: null pointer", who);
-  if (n_meshes < 1 || n_meshes > VOX_MAX_MESHES) VOX_REFUSE(p, VX_E_SHAPE, "%s: n_meshes %d outside 1..%d", who, n_meshes, VOX_MAX_MESHES);
+  if (!tris || !mesh_offsets || !origin || !dims || !out || !odd_columns) VX_REFUSE_CODE(p, VX_E_NULL, "%s: null pointer", who);
+  if (n_meshes < 1 || n_meshes > VOX_MAX_MESHES) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: n_meshes %d outside 1..%d", who, n_meshes, VOX_MAX_MESHES);
   for (int a = 0; a < 3; ++a)
-    if (dims[a] < 1 || dims[a] > VOX_MAX_DIM) VOX_REFUSE(p, VX_E_SHAPE, "%s: dims[%d] = %d outside 1..%d", who, a, dims[a], VOX_MAX_DIM);
-  if (mesh_offsets[0] != 0) VOX_REFUSE(p, VX_E_SHAPE, "%s: mesh_offsets[0] = %lld, not 0", who, (long long)mesh_offsets[0]);
+    if (dims[a] < 1 || dims[a] > VOX_MAX_DIM) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: dims[%d] = %d outside 1..%d", who, a, dims[a], VOX_MAX_DIM);
+  if (mesh_offsets[0] != 0) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: mesh_offsets[0] = %lld, not 0", who, (long long)mesh_offsets[0]);
   int64_t chunks = 0;
   for (int m = 0; m < n_meshes; ++m) {
     if (mesh_offsets[m + 1] <= mesh_offsets[m] || mesh_offsets[m + 1] > VOX_MAX_TRIS)
-      VOX_REFUSE(p, VX_E_SHAPE, "%s: mesh_offsets[%d] = %lld: offsets increase from 0 to n_tri <= 2^20", who, m + 1, (long long)mesh_offsets[m + 1]);
+      VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: mesh_offsets[%d] = %lld: offsets increase from 0 to n_tri <= 2^20", who, m + 1, (long long)mesh_offsets[m + 1]);
     chunks += (mesh_offsets[m + 1] - mesh_offsets[m] + VOX_CHUNK - 1) / VOX_CHUNK;
   }
-  if (!(h > 0) || !isfinite(h)) VOX_REFUSE(p, VX_E_SHAPE, "%s: h = %g is not finite and positive", who, h);
+  if (!(h > 0) || !isfinite(h)) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: h = %g is not finite and positive", who, h);
   for (int a = 0; a < 3; ++a)
-    if (!isfinite(origin[a])) VOX_REFUSE(p, VX_E_SHAPE, "%s: origin[%d] is not finite", who, a);
-  if (((uintptr_t)tris & 3) || ((uintptr_t)out & 3)) VOX_REFUSE(p, VX_E_ALIGN, "%s: tris or out not aligned to its 4-byte elements", who);
-  if ((uintptr_t)odd_columns & 7) VOX_REFUSE(p, VX_E_ALIGN, "%s: odd_columns not aligned to its 8-byte element", who);
+    if (!isfinite(origin[a])) VX_REFUSE_CODE(p, VX_E_SHAPE, "%s: origin[%d] is not finite", who, a);
+  if (((uintptr_t)tris & 3) || ((uintptr_t)out & 3)) VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: tris or out not aligned to its 4-byte elements", who);
+  if ((uintptr_t)odd_columns & 7) VX_REFUSE_CODE(p, VX_E_ALIGN, "%s: odd_columns not aligned to its 8-byte element", who);
   p->nz = dims[0]; p->ny = dims[1]; p->nx = dims[2];
   p->tiles_x = (p->nx + VOX_TILE_X - 1) / VOX_TILE_X;
   p->tiles_y = (p->ny + VOX_TILE_Y - 1) / VOX_TILE_Y;
