@@ -18,6 +18,10 @@
 // epilogue runs once per tile.
 // LDS: two images [hi | lo][1080 positions][8 halves] (67.5 KB), two weight chunks [step 7][row tile 2][hi | lo][lane][8
 // halves] (56 KB), statistics slots and the bias vector.
+//
+// Grid: one persistent workgroup per CU, pairs vb, vb + G, ...  The pairs of the last, partly filled round are each shared by 2 / 4
+// of the workgroups that would idle (deep_tail, conv3d_route.h): all stage the whole pair, each multiplies and stores the column
+// tiles of 4 / 2 of the multiplying waves -- the same accumulation chain per stored value as in a whole pair.
 #include "s16_common.h"
 #include "conv3d_internal.h"
 
@@ -29,9 +33,12 @@ struct DeepArgs {
   int tiles_x, tiles_y, tiles_z;
   int npos;                       // halo positions of a tile: ts (tx + 2)(ty + 2)(tz + 2)
   int nchunks, ncg;               // 8-channel input chunks; 32-row output groups
-  int npairs;                     // (tile, output group) pairs in the launch
   unsigned m_cg, m_tx, m_ty, m_tz;   // multiply-high magics of the pair decode
-  int stat_epc;                   // statistics entries per tile in stats_partial (entry 0 real, the rest zero)
+  int stat_epc;                   // statistics entries per tile in stats_partial (the first stat_parts real, the rest zero)
+  int stat_parts;                 // wave groups a tile's statistics are written by: 8 / stat_parts waves per entry, in wave order
+  // the last, partly filled round (deep_tail, conv3d_route.h): a workgroup runs nfull whole pairs, then -- the first tail_wgs
+  // workgroups -- the multiplying waves' share `vb & (2^ltail - 1)` of pair tail0 + (vb >> ltail)
+  int nfull, tail0, tail_wgs, ltail;
   unsigned long long* stamps;
   int abl;
 };
@@ -82,12 +89,14 @@ __global__ __launch_bounds__(768) void conv3d_deep_kernel(DeepArgs ka) {
   int vb = blockIdx.x;
   const int G = (int)gridDim.x;
   if ((G & 7) == 0) vb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);   // one XCD: neighbouring pairs (the groups of one tile)
-  const int npair_wg = vb < ka.npairs ? (ka.npairs - vb + G - 1) / G : 0;
+  const int nfull = ka.nfull;
+  const int npair_wg = nfull + (vb < ka.tail_wgs ? 1 : 0);      // whole pairs, then at most one (share of a) pair of the last round
 
   struct Cur { int ci, c; };      // pair number of this workgroup, chunk
   auto advance = [&](Cur& x) { if (++x.c == NCH) { x.c = 0; ++x.ci; } };
   auto pair_of = [&](int ci, int& n0, int& tzi, int& tyi, int& txi, int& cg) {
     unsigned t = (unsigned)(vb + ci * G), q;
+    if (ci >= nfull) { const auto kp = kernarg(); t = (unsigned)(kp->tail0 + (vb >> kp->ltail)); }      // (once per pair: re-read)
     q = ka.ncg == 1 ? t : __umulhi(t, ka.m_cg); cg = (int)(t - q * (unsigned)ka.ncg); t = q;
     q = ka.tiles_x == 1 ? t : __umulhi(t, ka.m_tx); txi = (int)(t - q * (unsigned)ka.tiles_x); t = q;
     q = ka.tiles_y == 1 ? t : __umulhi(t, ka.m_ty); tyi = (int)(t - q * (unsigned)ka.tiles_y); t = q;
@@ -478,7 +487,7 @@ __global__ __launch_bounds__(768) void conv3d_deep_kernel(DeepArgs ka) {
       }
     };
 
-    // statistics of a complete tile: entry 0 of the tile's block is real, the other stat_epc - 1 are zero
+    // statistics of a complete tile: the first stat_parts entries of the tile's block are real, the others of its stat_epc are zero
     // (vx_instnorm_finalize sums vx_conv3d_k3_tiles_for entries per sample)
     auto flush_tile = [&](int ci) {
       const float* red = s_red + (ci & 1) * (NW * 32 * 2);
@@ -489,23 +498,37 @@ __global__ __launch_bounds__(768) void conv3d_deep_kernel(DeepArgs ka) {
       const int tps = ka.tiles_x * ka.tiles_y * ka.tiles_z;
       const int tile = (tzi * ka.tiles_y + tyi) * ka.tiles_x + txi;
       float* dst = kp->a.stats_partial + (((size_t)n0 * tps + tile) * epc * a.Cout + cg * 32) * 2;
-      if (tid < 32) {
+      // Entry p is the sum over the waves of group p, in wave order -- for EVERY tile, so that a sample's statistics are the same
+      // bits whether its tile ran whole or as a shared pair of the last round.  Of a shared pair this workgroup holds the sums of
+      // its own waves only: it writes their entries (the launch's 2^ltail parts are whole groups: ltail <= log2 stat_parts).
+      const int parts = kp->stat_parts, wpp = NW / parts;
+      const int ltail = kp->ltail;
+      const bool shared = ci >= nfull && ltail > 0;
+      const int p = tid >> 5, ch = tid & 31;          // (waves 0..3: tid < 256 -- up to eight groups)
+      if (p < parts && (!shared || (p * wpp) >> (3 - ltail) == (vb & ((1 << ltail) - 1)))) {
         float s = 0.f, qq = 0.f;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          s += red[(w * 32 + tid) * 2 + 0];
-          qq += red[(w * 32 + tid) * 2 + 1];
+        for (int i = 0; i < NW; ++i) {                // (all eight reads in flight at once; the group's own are added, in wave order)
+          const int w = (p * wpp + i) & (NW - 1);
+          const float rs = red[(w * 32 + ch) * 2 + 0], rq = red[(w * 32 + ch) * 2 + 1];
+          s = i < wpp ? s + rs : s;
+          qq = i < wpp ? qq + rq : qq;
         }
-        dst[tid * 2 + 0] = s;
-        dst[tid * 2 + 1] = qq;
+        dst[(size_t)p * a.Cout * 2 + ch * 2 + 0] = s;
+        dst[(size_t)p * a.Cout * 2 + ch * 2 + 1] = qq;
       }
-      for (int e = 1; e < epc; ++e)
-        if (tid < 64) dst[(size_t)e * a.Cout * 2 + tid] = 0.f;
+      if (!shared || (vb & ((1 << ltail) - 1)) == 0)
+        for (int e = parts; e < epc; ++e)
+          if (tid < 64) dst[(size_t)e * a.Cout * 2 + tid] = 0.f;
     };
 
     // waves 0..3 multiply(j) then store a finished tile; waves 4..7 store the tile they finished in the previous iteration FIRST,
     // then multiply(j): the partner wave of a SIMD multiplies while the other runs the tile's epilogue
     const bool late = wave >= NW / 2;
+    // the pair of the last round is shared by 2^ltail workgroups: this one's waves [part 8 / S, (part + 1) 8 / S) multiply and store
+    // their column tiles of it (with wave w and w + 4 on one SIMD, a part is one wave on each of four / two SIMDs); the others
+    // only keep the barrier cadence.  Wave-uniform.
+    const bool tail_mine = (wave >> (3 - ka.ltail)) == (vb & ((1 << ka.ltail) - 1));
     Cur cx = {0, 0};
     int j = 0;
     int prev_ci = -1;                             // waves 4..7: the tile still to store
@@ -519,7 +542,8 @@ __global__ __launch_bounds__(768) void conv3d_deep_kernel(DeepArgs ka) {
         prev_ci = -1;
       }
       DP_STAMP(2);
-      if (cx.c == 0) {
+      const bool mine = cx.ci < nfull || tail_mine;
+      if (cx.c == 0 && mine) {
         int n0, tzi, tyi, txi, cg;
         pair_of(cx.ci, n0, tzi, tyi, txi, cg);
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -530,11 +554,13 @@ __global__ __launch_bounds__(768) void conv3d_deep_kernel(DeepArgs ka) {
           for (int r = 0; r < R; ++r) { acc[r][nt] = b4; accx[r][nt] = zero; }
         }
       }
-      if (!(DP_ABL & 1)) multiply(j & 1);
+      if (mine && !(DP_ABL & 1)) multiply(j & 1);
       DP_STAMP(1);
       if (cx.c == NCH - 1) {
-        if (late) prev_ci = cx.ci;
-        else if (!(DP_ABL & 2)) epilogue(cx.ci);
+        if (mine) {
+          if (late) prev_ci = cx.ci;
+          else if (!(DP_ABL & 2)) epilogue(cx.ci);
+        }
         if (STATS) { fl_ci = cx.ci; fl_at = j + 2; }
       }
       DP_STAMP(2);
@@ -595,7 +621,7 @@ int vx_pack_conv3d_deep(const float* w_torch, float* w_packed, int Cin, int Cout
 }
 
 template <int R, int EPI, int PRE>
-static int launch_deep(const DeepArgs& ka, const Conv3dRoute& r, hipStream_t s) {
+static int launch_deep(const DeepArgs& ka, const Conv3dRoute& r, int grid, hipStream_t s) {
   constexpr size_t lds = 2 * (size_t)DEEP_IMG_B + 2 * (size_t)DEEP_W_B + 2 * 8 * 32 * 2 * 4 + DEEP_MAXC * 4;
   static_assert(lds <= 160 * 1024, "LDS budget");
   auto kern = conv3d_deep_kernel<R, EPI, PRE>;
@@ -605,11 +631,9 @@ static int launch_deep(const DeepArgs& ka, const Conv3dRoute& r, hipStream_t s) 
     if (e != hipSuccess) VX_FAIL((int)e, "vx_conv3d_k3(deep): hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
     attr = true;
   }
-  int gx = vx_cu_count();      // one persistent workgroup per CU
-  if (gx > ka.npairs) gx = ka.npairs;
   static const char* kname = vx_conv3d_kname(r);
   vx_note_kernel(kname);
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(768), lds, s, ka);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(768), lds, s, ka);
   VX_CHECK_LAUNCH("vx_conv3d_k3(deep)");
   return VX_OK;
 }
@@ -624,12 +648,15 @@ int vx_conv3d_deep_launch(const Conv3dRoute& r, const vx_conv3d_args& a, const f
   ka.npos = r.npos;
   ka.nchunks = r.nchunks;
   ka.ncg = r.ncg;
-  ka.npairs = r.nitems;
   ka.m_cg = r.m_cg; ka.m_tx = r.mx; ka.m_ty = r.my; ka.m_tz = r.mz;
   ka.stat_epc = r.stat_epc;
+  ka.stat_parts = r.stat_parts;
+  // one persistent workgroup per CU; the pairs of the last, partly filled round go to 2 / 4 workgroups each where that many idle
+  const DeepTail t = deep_tail(r.nitems, vx_cu_count(), r.tail_cap);
+  ka.nfull = t.full; ka.tail0 = t.tail0; ka.tail_wgs = t.rest * t.split; ka.ltail = __builtin_ctz((unsigned)t.split);
   vx_conv_diag(VX_DIAG_XP_ABL, &ka.stamps, &ka.abl);
   switch (conv3d_key_of(r.p, r.np)) {
-#define DEEP_CASE(...) case conv3d_key(__VA_ARGS__): return launch_deep<__VA_ARGS__>(ka, r, s);
+#define DEEP_CASE(...) case conv3d_key(__VA_ARGS__): return launch_deep<__VA_ARGS__>(ka, r, t.grid, s);
     DEEP_INSTANCES(DEEP_CASE)
 #undef DEEP_CASE
   }

@@ -3,7 +3,8 @@
 // walks it under ASan / UBSan).  vx_conv3d_k3 is: conv3d_route(), then the family's launcher with the descriptor.
 //
 //   shape / channel rules   conv_config, s16_config, tile_config, vx_conv3d_s16_tile, conv3d_*_applies / _packs, deep_geo / deep_pick,
-//                           the family numbering, the packed sizes and the tile counts -- each stated once, here
+//                           deep_tail (how the deep kernel's last round is shared; tests/deep_tail_host.cpp), the family numbering,
+//                           the packed sizes and the tile counts -- each stated once, here
 //   instance lists          one X-macro per family (MFMA_ / C8_ / S16_ / XP8W_ / ZC16_ / DEEP_INSTANCES): the route asks "does this
 //                           instance exist?", the family's .hip file instantiates launch_X<...> from the same list
 //   conv3d_route()          every argument check of vx_conv3d_k3 in one order; the families are tried xp8w -> zc16 -> deep -> tile
@@ -106,7 +107,9 @@ struct Conv3dRoute {
   int nitems;                      // z-column kernels: columns in the launch; deep: (tile, output group) pairs
   unsigned mcps;                   // z-column kernels: magic of columns per sample
   int rep; unsigned mrep;          // xp8w: in_repeat as the column order's inner factor, and its magic
-  int stat_epc;                    // statistics entries per column / tile in stats_partial (entry 0 real, the rest zero)
+  int stat_epc;                    // statistics entries per column / tile in stats_partial (entry 0 real, the rest zero; deep: the
+                                   //   first stat_parts)
+  int stat_parts, tail_cap;        // deep: wave groups a tile's statistics are written by; largest split of a last-round pair
   int tx, ty, tz, ts, npos, ncg;   // deep: tile voxels along x, y, z; samples per tile; halo positions; 32-row output groups
   unsigned m_cg;                   // deep: magic of ncg
   char err[400];                   // the refusal's message (vx_last_error_string) when conv3d_route returns < 0
@@ -192,6 +195,28 @@ static inline int deep_pick(int D, int H, int W, DeepGeo* o) {
   if (deep_geo(D, H, W, 4, o)) return 4;
   return deep_geo(D, H, W, 2, o) ? 2 : 0;
 }
+// The last, partly filled round of the deep kernel's persistent grid: P (tile, output group) pairs on G workgroups are `full` whole
+// rounds (workgroup vb runs pairs vb + i G) and `rest` pairs from `tail0` on.  Where split * rest <= G, each of those goes to `split`
+// workgroups (4, else 2), which all stage the whole pair and multiply 8 / split of its eight multiplying waves' column tiles each --
+// the tile and every stored value's accumulation chain stay what they are, so a sample's bits do not depend on where it stands in
+// the batch.  cap: the largest split the launch admits (statistics: deep_stat_parts).  grid: workgroups to launch.
+struct DeepTail { int full, rest, split, tail0, grid; };
+static inline DeepTail deep_tail(int P, int G, int cap) {
+  DeepTail t;
+  if (G < 1) G = 1;
+  t.full = P / G;
+  t.tail0 = t.full * G;
+  t.rest = P - t.tail0;
+  t.split = 1;
+  for (int s = 4; s >= 2; s >>= 1)
+    if (t.split == 1 && s <= cap && t.rest > 0 && (int64_t)t.rest * s <= G) t.split = s;
+  t.grid = t.full > 0 ? G : t.rest * t.split;
+  return t;
+}
+// Statistics of a tile are written as per-wave-group entries -- by every tile, shared or not, so that the sums InstanceNorm reads are
+// the same bits either way: as many groups (4, 2) as the tile's block of the partials buffer holds entries, a function of the
+// layer's shape only.  One entry: one group, and statistics launches share no pair.
+static inline int deep_stat_parts(int stat_epc) { return stat_epc >= 4 ? 4 : (stat_epc >= 2 ? 2 : 1); }
 static inline bool conv3d_deep_applies(int D, int H, int W, int Cin, int Cout, const vx_config& cfg) {
   if (cfg.conv_fp32 != 0 || cfg.s16_no_deep) return false;
   if (!conv3d_deep_packs(Cin, Cout)) return false;
@@ -502,12 +527,15 @@ static inline int route_deep(const vx_conv3d_args& a, int stat_tiles, Conv3dRout
   r->nitems = (int)npairs;
   r->m_cg = vx_magic_raw(r->ncg); r->mx = vx_magic_raw(g.tiles_x); r->my = vx_magic_raw(g.tiles_y); r->mz = vx_magic_raw(g.tiles_z);
   r->stat_epc = 0;
+  r->stat_parts = 1;
+  r->tail_cap = 4;
   if (a.stats_partial) {
     // the caller's partials buffer holds stat_tiles entries per sample (the tile kernel's count): this kernel's tiles must divide it,
     // else the tile kernel takes the launch (D % 4 == 2 volumes give 3 tiles against 4 entries)
     if (stat_tiles % tps) return ROUTE_DECLINED;
     if (a.act != VX_ACT_NONE || a.drop_mode != VX_DROP_NONE) VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(deep): statistics go with a plain epilogue");
     r->stat_epc = stat_tiles / tps;
+    r->tail_cap = r->stat_parts = deep_stat_parts(r->stat_epc);
   }
   if ((vx_wide)g.ts * a.D * a.H * a.W * a.out_pitch * 4 >= CONV3D_2GIB)
     VX_REFUSE(r, VX_E_SHAPE, "vx_conv3d_k3(deep): one tile's samples must stay below 2 GiB");
