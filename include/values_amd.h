@@ -1052,6 +1052,88 @@ int vx_label_switch_batched(const vx_lswitch_item* items /* host */, int n_items
                             const float* var_table /* host [256], or null */, int32_t* status /* device [n_items] */,
                             void* workspace, int64_t ws_bytes, vx_stream_t stream);
 
+/* The 3D test split on the device (patches3d.hip; values_amd.sliding.run_test_3d): three batched streaming
+ * passes whose batches mix cases.  Common to all three: lanes run along z, a lane takes four consecutive z positions of a
+ * row and moves them in one access of up to 16 bytes where they lie inside the row and the address is aligned to the
+ * access, element by element elsewhere; no byte outside a crop, a destination box or an output array is touched; an
+ * item's result does not depend on its batch mates; the host item tables go up through a pinned staging buffer inside
+ * the call (no wait on the stream, not capturable into a hipGraph); every check below runs before any device call;
+ * workspace: the call's *_workspace_bytes(...) bytes (0 for counts the call refuses), 16-byte aligned.
+ *
+ * vx_gather_patches_3d: out [n_items][P0][P1][P2] float32; out[i] is the crop [origin, origin + P) of item i's volume
+ *   src [dims0][dims1][dims2] of kind VX_PREP_*, converted as numpy's astype(float32) converts (round to nearest even from
+ *   float64 and the 32-bit integers, exact from the narrower kinds).  Traffic: P0*P1*P2 * (esize + 4) bytes per item.
+ *   Refused: a null table, out, workspace or src (VX_E_NULL); n_items outside [1, VX_SELECT_MAX_ITEMS], P or a dimension
+ *   below 1, a crop not inside its volume (VX_E_SHAPE); an unknown kind (VX_E_DTYPE); src off its element alignment, out
+ *   off 4 bytes, a workspace off 16 (VX_E_ALIGN); a short workspace (VX_E_WORKSPACE).
+ *
+ * vx_softmax_accumulate_cases: vx_softmax_accumulate with the destination taken per patch.  logits [B][T][C][P0][P1][P2]
+ *   float32; patch b adds softmax_c(logits[b][t]) into items[b].sum [T][C][X][Y][Z] at origin and 1 into items[b].count
+ *   [X][Y][Z] (t == 0), dims = {X, Y, Z}.  Per voxel the expressions of vx_softmax_accumulate in their order (running
+ *   maximum, expf, one reciprocal): with sum_overlap == 0 (plain read-modify-write) the result is bit-equal to that call
+ *   made image by image; with sum_overlap != 0 sums and counts go through float atomics (overlapping patches of one
+ *   image: the order of the additions is not fixed).  A voxel of a patch outside its image is skipped.  2 <= C <= 8.
+ *   Traffic: B*T*C*P^3 * 4 bytes read, twice that read and written in the sums.
+ *   Refused: null logits, table, workspace, sum or count (VX_E_NULL); B outside [1, VX_SELECT_MAX_ITEMS], T or P below 1,
+ *   C outside [2, 8], a dimension below 1, a negative origin, or -- with sum_overlap == 0 -- two items that name the same
+ *   sum with boxes (cut to the image) that share a voxel (VX_E_SHAPE); a pointer off 4 bytes or a workspace off 16
+ *   (VX_E_ALIGN); a short workspace (VX_E_WORKSPACE).
+ *
+ * vx_case_composite: the composites DataCarrier3D keeps beside the predictions (concat_data / save_data,
+ *   data_carrier_3D.py:130-153, 173-179, 209-214; calculate_metrics, test_3D.py:555-562), from the case's resident file
+ *   payloads and the count map the accumulation left, n = X*Y*Z voxels, in float64 with true divisions:
+ *     data   [n] float64      = (0 + x + ... + x, count[v] additions of double(image[v])) / max(count[v], 1)
+ *     gt_seg [R][n] float64   = double(intc sum of count[v] additions of the label) / max(count[v], 1)
+ *     gt     [R][n] uint8     = (intc) of that, narrowed
+ *   A voxel under no patch (count 0) is 0 in all three.  Any of the three outputs may be null (image may be null when
+ *   data is).  The R raters of item i are labels[first_label .. first_label + R): device arrays of n integers of 1 / 2 /
+ *   4 / 8 bytes (kind VX_COUNT_B1 .. B8) where the reader left them; the value used is the one astype(intc) gives, and a
+ *   label outside 0..255 is counted in status[i] (device, zeroed by the call; integer atomics): the host turns a
+ *   non-zero count into its error.  Traffic per voxel: esize + 4 + 8 + R * (label bytes + 9).
+ *   Refused: a null item table, label table (n_labels > 0), count, status, workspace, label pointer, or data without an
+ *   image (VX_E_NULL); n_items outside [1, VX_SELECT_MAX_ITEMS], n_labels outside [0, VX_COMPOSITE_MAX_LABELS], a
+ *   dimension below 1, more than 2^40 voxels, R < 0 or a label range outside the table (VX_E_SHAPE); an unknown image or
+ *   label kind (VX_E_DTYPE); a pointer off its element alignment or a workspace off 16 (VX_E_ALIGN); a short workspace
+ *   (VX_E_WORKSPACE). */
+#define VX_COMPOSITE_MAX_LABELS (1 << 20)
+typedef struct vx_gather3d_item {
+  const void* src;    /* device [dims[0]][dims[1]][dims[2]] */
+  int32_t kind;       /* VX_PREP_* */
+  int32_t dims[3];
+  int32_t origin[3];  /* first voxel of the crop */
+  int32_t reserved;
+} vx_gather3d_item;
+typedef struct vx_acc3d_item {
+  float* sum;         /* device [T][C][X][Y][Z] */
+  float* count;       /* device [X][Y][Z] */
+  int32_t dims[3];    /* X, Y, Z */
+  int32_t origin[3];  /* where the patch lands */
+} vx_acc3d_item;
+typedef struct vx_composite_label {
+  const void* ptr;    /* device, n integers */
+  int32_t kind;       /* VX_COUNT_B1 | B2 | B4 | B8 */
+  int32_t reserved;
+} vx_composite_label;
+typedef struct vx_composite_item {
+  const void* image;  /* device [X][Y][Z] of image_kind (null allowed when data is null) */
+  const float* count; /* device [X][Y][Z]: patches per voxel */
+  double* data;       /* device [X][Y][Z], or null */
+  double* gt_seg;     /* device [R][X][Y][Z], or null */
+  uint8_t* gt;        /* device [R][X][Y][Z], or null */
+  int32_t image_kind; /* VX_PREP_* */
+  int32_t first_label, R; /* labels[first_label .. first_label + R) */
+  int32_t dims[3];
+} vx_composite_item;
+int64_t vx_gather_patches_3d_workspace_bytes(int n_items);
+int vx_gather_patches_3d(const vx_gather3d_item* items /* host */, int n_items, float* out, int P0, int P1, int P2, void* workspace,
+                         int64_t ws_bytes, vx_stream_t stream);
+int64_t vx_softmax_accumulate_cases_workspace_bytes(int B);
+int vx_softmax_accumulate_cases(const float* logits, int B, int T, int C, int P0, int P1, int P2, const vx_acc3d_item* items /* host */,
+                                int sum_overlap, void* workspace, int64_t ws_bytes, vx_stream_t stream);
+int64_t vx_case_composite_workspace_bytes(int n_items, int n_labels);
+int vx_case_composite(const vx_composite_item* items /* host */, int n_items, const vx_composite_label* labels /* host */, int n_labels,
+                      int32_t* status /* device [n_items] */, void* workspace, int64_t ws_bytes, vx_stream_t stream);
+
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),
  *   counts[i][j][c] = #{v: mask_i(v) == c and mask_j(v) == c}.  M <= 32, C <= 8.

@@ -6,7 +6,7 @@ from .uncertainty import (calculate_one_minus_msr, calculate_uncertainty, one_mi
 from .predict import (GraphedPredictor, HostPipeline, crop_indices, noise_view_device, predict_logits,  # noqa: F401
                       predict_uncertainty)
 from .io import load_models_from_checkpoint, instantiate  # noqa: F401
-from .sliding import predict_image_sliding  # noqa: F401
+from .sliding import predict_image_sliding, run_test_3d  # noqa: F401
 from .preprocess import load_cases_device, preprocess_dataset  # noqa: F401
 from .preprocess2d import preprocess_dataset_2d, preprocess_images_device  # noqa: F401
 from .toydata import generate_toy_dataset  # noqa: F401

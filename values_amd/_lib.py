@@ -306,6 +306,32 @@ class LswitchRow(C.Structure):
     _fields_ = [("from_", _i32), ("to", _i32), ("thr", _u32)]
 
 
+VX_COMPOSITE_MAX_LABELS = 1 << 20
+
+
+class Gather3dItem(C.Structure):
+    """vx_gather3d_item: one crop of vx_gather_patches_3d: the volume src [dims] of kind VX_PREP_* and the crop's origin."""
+    _fields_ = [("src", _p), ("kind", _i32), ("dims", _i32 * 3), ("origin", _i32 * 3), ("reserved", _i32)]
+
+
+class Acc3dItem(C.Structure):
+    """vx_acc3d_item: the destination of one patch of vx_softmax_accumulate_cases: sum [T][C][X][Y][Z], count [X][Y][Z],
+    dims = (X, Y, Z) and where the patch lands."""
+    _fields_ = [("sum", _p), ("count", _p), ("dims", _i32 * 3), ("origin", _i32 * 3)]
+
+
+class CompositeLabel(C.Structure):
+    """vx_composite_label: one rater file's payload on the device, kind VX_COUNT_B1 .. B8."""
+    _fields_ = [("ptr", _p), ("kind", _i32), ("reserved", _i32)]
+
+
+class CompositeItem(C.Structure):
+    """vx_composite_item: one case of vx_case_composite: image (VX_PREP_*), count map, its raters
+    labels[first_label .. first_label + R) and the outputs data f64 / gt_seg f64 [R] / gt u8 [R] (each may be null)."""
+    _fields_ = [("image", _p), ("count", _p), ("data", _p), ("gt_seg", _p), ("gt", _p), ("image_kind", _i32),
+                ("first_label", _i32), ("R", _i32), ("dims", _i32 * 3)]
+
+
 VX_MSR_MAX_ITEMS, VX_MSR_MAX_PLANES = 65536, 1 << 22
 
 
@@ -401,6 +427,12 @@ SIGNATURES = {
     "vx_label_switch_batched_workspace_bytes": (_i64, [_i, _i]),
     "vx_label_switch_batched": (_i, [C.POINTER(LswitchItem), _i, _i, C.POINTER(LswitchRow), _i, _p, _u32, C.POINTER(C.c_float), _p,
                                      _p, _i64, _p]),
+    "vx_gather_patches_3d_workspace_bytes": (_i64, [_i]),
+    "vx_gather_patches_3d": (_i, [C.POINTER(Gather3dItem), _i, _p, _i, _i, _i, _p, _i64, _p]),
+    "vx_softmax_accumulate_cases_workspace_bytes": (_i64, [_i]),
+    "vx_softmax_accumulate_cases": (_i, [_p, _i, _i, _i, _i, _i, _i, C.POINTER(Acc3dItem), _i, _p, _i64, _p]),
+    "vx_case_composite_workspace_bytes": (_i64, [_i, _i]),
+    "vx_case_composite": (_i, [C.POINTER(CompositeItem), _i, C.POINTER(CompositeLabel), _i, _p, _p, _i64, _p]),
     "vx_toy_embed": (_i, [_p, C.POINTER(_i32), C.POINTER(_i32), C.c_double, _i, _i, _p, C.POINTER(_i32), _p]),
     "vx_gauss_blur_axis_f64": (_i, [_p, _p, C.POINTER(_i32), _i, _p, _i, _p]),
     "vx_count_ge_f64": (_i, [_p, _i64, C.c_double, _p, _p]),

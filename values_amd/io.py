@@ -30,6 +30,11 @@ TARGET_MAP = {
     "data.torch_dataloader.BaseDataModule": "values_amd.dataset2d.TestDataModule2D",
     "uncertainty_modeling.data.cityscapes_dataset.Cityscapes_dataset": "values_amd.dataset2d.CityscapesTestSet",
     "data.cityscapes_dataset.Cityscapes_dataset": "values_amd.dataset2d.CityscapesTestSet",
+    # the 3D test split's listing (test_3D.py:640-650 calls the datamodule's get_val_test_data_samples), both datamodules
+    "uncertainty_modeling.toy_datamodule_3D.get_val_test_data_samples": "values_amd.dataset3d.get_val_test_data_samples_toy",
+    "toy_datamodule_3D.get_val_test_data_samples": "values_amd.dataset3d.get_val_test_data_samples_toy",
+    "uncertainty_modeling.lidc_idri_datamodule_3D.get_val_test_data_samples": "values_amd.dataset3d.get_val_test_data_samples_lidc",
+    "lidc_idri_datamodule_3D.get_val_test_data_samples": "values_amd.dataset3d.get_val_test_data_samples_lidc",
 }
 
 
