@@ -1205,8 +1205,11 @@ int vx_ssn2d_add_diag(float* out, const float* diag, const float* eps_d, uint32_
  *                          The host iterates (Newton).  Two launches.
  *   vx_calib_bins_batched  (ace.py:44-90) platt_scale_confid + calib_stats' 20-bin statistics: bins63 [n_items][63]
  *                          (device) = bin_sums[21], bin_true[21], bin_total[21] per item for the bin edges edges21 (a
- *                          HOST array: np.linspace(0, 1 + 1e-8, 21)); ab: HOST [n_items][2] = (A, B) per item.  Two
- *                          launches.
+ *                          HOST array: np.linspace(0, 1 + 1e-8, 21)); ab: HOST [n_items][2] = (A, B) per item.  A voxel
+ *                          lies in bin np.digitize(prob, edges21) - 1: the last edge <= prob.  A NaN prob (a NaN in
+ *                          the map) counts in bin 20 as np.digitize puts it: its correctness goes to bin_true[20], 1
+ *                          to bin_total[20], and bin_sums[20] becomes NaN, so the ACE of such an image is NaN as the
+ *                          reference's.  Two launches.
  * Every argument check (VX_E_NULL / VX_E_SHAPE / VX_E_DTYPE, the message names the item; VX_E_WORKSPACE / VX_E_ALIGN)
  * returns before any device call.  workspace: caller-owned, of vx_*_batched_workspace_bytes(the same items) bytes --
  * the descriptor table and 512 partial rows per item -- 0 for arguments the call refuses.  The descriptor table goes up

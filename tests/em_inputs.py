@@ -1,5 +1,6 @@
-"""Inputs shared by tests/test_evalmetrics_batched_cpu.py and tests/test_gpu_evalmetrics_batched.py: a numpy stand-in for
-the Platt sums, images whose Platt fits finish in different rounds, rater label stacks, host restatements of the device
+"""Inputs shared by tests/test_evalmetrics_batched_cpu.py, tests/test_gpu_evalmetrics_batched.py and the matrix tests
+(tests/test_em_ref_cpu.py, tests/test_gpu_evalmetrics_matrix.py): numpy stand-ins for the Platt sums and the calibration
+bins, images whose Platt fits finish in different rounds, rater label stacks, host restatements of the device
 arithmetic (the rater variance, the five NCC sums in the documented association), and a datamodule stub for a results tree whose reference segmentations come from a dataloader."""
 import os
 
@@ -18,6 +19,30 @@ def platt_sums_numpy(unc, correct, A, B, t_pos, t_neg):
     d, w = T - P, P * (1.0 - P)
     return [float(len(F)), float(np.sum(correct)), float(loss.sum()), float((d * F).sum()), float(d.sum()),
             float((w * F * F).sum()), float((w * F).sum()), float(w.sum())]
+
+
+def platt_sums_raters_numpy(ref, pred, unc, A, B, t_pos, t_neg, ignore=None):
+    """platt_sums_numpy for R reference segmentations ref [R][nvox] against pred [nvox] and the map unc [nvox], as
+    ace.py:24-31 lays them out (prediction and map repeated per rater, rater-voxels with ref == ignore dropped)"""
+    valid = np.ones(ref.shape, dtype=bool) if ignore is None else ref != ignore
+    return platt_sums_numpy(np.broadcast_to(unc[None], ref.shape)[valid], (ref == pred[None])[valid], A, B, t_pos, t_neg)
+
+
+def calib_bins_numpy(ref, pred, unc, A, B, ignore=None):
+    """(bin_sums, bin_true, bin_total, bin ids) of one item of vx_calib_bins_batched as ace.py:46 and :67-73 form them:
+    numpy's 1 / (1 + np.exp(...)), np.digitize and np.bincount in float64.  bin_sums alone are added per bin with numpy's
+    pairwise sum, not with np.bincount(weights=...): bincount adds a bin's members one after the other, a chain of additions
+    as long as the bin (1.4e-8 off on 131072 values near 1), where the bound of tests/em_ref.py allows for the 523 to 532
+    of the device's association"""
+    valid = np.ones(ref.shape, dtype=bool) if ignore is None else ref != ignore
+    conf = -np.broadcast_to(np.asarray(unc, dtype=np.float64)[None], ref.shape)[valid]
+    with np.errstate(over="ignore", invalid="ignore"):
+        prob = 1 / (1 + np.exp(conf * A + B))
+    bins = np.linspace(0.0, 1.0 + 1e-8, 21)
+    binids = np.digitize(prob, bins) - 1
+    correct = (ref == pred[None])[valid].astype(np.float64)
+    return (np.array([prob[binids == k].sum() for k in range(21)]), np.bincount(binids, weights=correct, minlength=21),
+            np.bincount(binids, minlength=21).astype(np.float64), binids)
 
 
 def platt_items():

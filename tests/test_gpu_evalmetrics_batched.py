@@ -101,6 +101,9 @@ def _rater_case(rng, R, nvox, dtype):
 
 @pytest.mark.parametrize("ignore", [None, 2])
 def test_platt_sums_and_bins_batched_equal_the_per_image_calls(ignore):
+    """pins batch independence: an item's 8 + 63 numbers are the same bits alone, first, last, and among other parameters
+    (the per-image functions are a batch of one through the same entry point, so this compares the kernel with itself).
+    The VALUES are pinned in tests/test_gpu_evalmetrics_matrix.py, against the long double reference of tests/em_ref.py"""
     from values_amd import _lib, evalmetrics as vm
     lib = _lib.load()
     rng = np.random.default_rng(29)

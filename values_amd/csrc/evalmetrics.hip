@@ -182,6 +182,7 @@ __device__ __forceinline__ void em_bins_body(const BinItem& a, const BinEdges& e
     int bin = -1;                                                     // np.digitize(prob, bins) - 1
 #pragma unroll
     for (int k = 0; k < NB; ++k) bin += (edges.e[k] <= prob) ? 1 : 0;
+    if (prob != prob) bin = NB - 1;   // np.digitize(nan, bins) = len(bins): a NaN map value counts in bin 20, whose sum is NaN
     const double corr = ref == a.x.pred[vx] ? 1.0 : 0.0;
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
