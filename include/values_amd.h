@@ -1164,6 +1164,51 @@ int64_t vx_soft_metric_batched_workspace_bytes(int B, int C, int R, int64_t nvox
 int vx_soft_metric_sums_batched(const float* prob, const uint8_t* gt, int B, int C, int R, int64_t nvox, double* sums,
                                 void* workspace, vx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * The validation step's reductions (LightningExperiment.validation_step and forward_ssn(val=True),
+ * lightning_experiment.py:175-219, 278-377), see valstep.hip: what turns a model's output and a label volume into
+ * validation/val_loss and validation/val_dice.  The head is read once, no sample is written.
+ *
+ * labels [B][nvox] uint8.  ignore_label is -1 (none) or 0..255: a voxel whose label equals it takes no log term; a label
+ *   >= C other than ignore_label belongs to no class, takes no log term and is counted as INVALID (torch raises there, and
+ *   so does values_amd.validation).  Arg-max ties go to the lowest class index.
+ * Arithmetic: the sample logits are float32, formed with vx_aleatoric_sample's y = fmaf(exp(s / 2), eps, mu) and
+ *   vx_ssn_sample's y = (mean + sum_r factor_r eps_w) + sqrt(exp(logd) + epsilon) eps_d; everything after them -- the
+ *   maximum, exp, log and every sum -- is float64 (the exact order is in valstep.hip's header and restated by
+ *   tests/valstep_ref.py).  Span partials, a fixed shuffle tree, a finalize launch in span order, no atomics: an item's
+ *   numbers are bit-equal whether it is submitted alone or with batch mates.  Two launches on the stream, no
+ *   synchronisation: capturable into a hipGraph.
+ *
+ * vx_val_sums_batched (the deterministic branch; any layout [B][C][nvox], 3D or NCHW): logits float32, 1 <= C <= 32,
+ *   1 <= nvox <= 2^39.  sums [B][5C + 3] float64: per class c  sum softmax_c [t = c],  sum [t = c],  sum softmax_c,
+ *   tp_c = #{argmax = c and t = c},  pred_c = #{argmax = c};  then  sum log_softmax_t  over the voxels that take a log
+ *   term, the count of those voxels, and the invalid count.
+ * vx_val_aleatoric_sums_batched: mu_s [B][2C][nvox] (mu | s), eps [B][T][C][nvox] injected or NULL (generated from
+ *   `seed`), 2 <= C <= 8, 1 <= T <= 32, C * nvox < 2^32.  Per voxel and sample the log-softmax over classes of y_t, then
+ *   lavg_c = logsumexp_t - log T; sums as above with p = exp(lavg), the log term lavg_t and the arg-max of lavg.
+ * vx_val_ssn_sums_batched: head [B][(2 + R)C][nvox] in vx_ssn_sample's layout (R = 0: the mean_only pretraining branch),
+ *   eps_w [S][B][R] and eps_d [S][B][C * nvox] injected or NULL (generated), 2 <= C <= 8, 1 <= S <= 32, 0 <= R <= 32,
+ *   C * nvox < 2^32.  sample_sums [B][S][1 + 2C]: sum_v log_softmax(y_s)[t], tp_c, pred_c of sample s;
+ *   target_sums [B][C + 2]: sum [t = c], the count of voxels that take a log term, the invalid count.
+ * Generated normals are keyed by the GLOBAL item index item0 + b: with item0 = 0 they are the streams vx_aleatoric_sample /
+ *   vx_ssn_sample draw for the same seed (slot (item0 + b) * T + t, resp. * S + s), and for any item0 an item's result does
+ *   not depend on how a set of items is cut into calls.  Injected normals are indexed by the call's own b.
+ * Refused before any launch: B outside [1, 65535], C, T, S, R, nvox or ignore_label out of range (VX_E_SHAPE); a null
+ *   logits / head / labels / output / workspace (VX_E_NULL); workspace_bytes below *_workspace_bytes(...) (VX_E_WORKSPACE;
+ *   the companions return 0 for shapes the call refuses). */
+int64_t vx_val_sums_workspace_bytes(int B, int C, int64_t nvox);
+int vx_val_sums_batched(const float* logits, const uint8_t* labels, int B, int C, int64_t nvox, int ignore_label, double* sums,
+                        void* workspace, int64_t workspace_bytes, vx_stream_t stream);
+int64_t vx_val_aleatoric_sums_workspace_bytes(int B, int C, int64_t nvox);
+int vx_val_aleatoric_sums_batched(const float* mu_s, const float* eps, uint32_t seed, uint32_t item0, const uint8_t* labels, int B,
+                                  int T, int C, int64_t nvox, int ignore_label, double* sums, void* workspace,
+                                  int64_t workspace_bytes, vx_stream_t stream);
+int64_t vx_val_ssn_sums_workspace_bytes(int B, int S, int C, int64_t nvox);
+int vx_val_ssn_sums_batched(const float* head, const float* eps_w, const float* eps_d, uint32_t seed, uint32_t item0,
+                            const uint8_t* labels, int B, int S, int C, int R, int64_t nvox, float epsilon, int ignore_label,
+                            double* sample_sums, double* target_sums, void* workspace, int64_t workspace_bytes,
+                            vx_stream_t stream);
+
 /* 2D SSN head (HighResolutionNet.hrnet_ssn, hrnet_module.py:559-595), see accumulate.hip:
  * vx_ssn2d_lowres: channels-last head outputs at the head's resolution -- mean [B*pix][mean_pitch] (C used),
  *   factor [B*pix][factor_pitch] (channel r*C + c) -- and eps_w [S][B][R] (nullable: generated) ->

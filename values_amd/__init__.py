@@ -11,3 +11,5 @@ from .preprocess import load_cases_device, preprocess_dataset  # noqa: F401
 from .preprocess2d import preprocess_dataset_2d, preprocess_images_device  # noqa: F401
 from .toydata import generate_toy_dataset  # noqa: F401
 from .stl import generate_toy_dataset_from_config  # noqa: F401
+from . import validation  # noqa: F401
+from .validation import validate, validation_step  # noqa: F401

@@ -28,6 +28,11 @@ class LowRankNormal:
         self._draws = 0
 
     @property
+    def head(self) -> torch.Tensor:
+        """the planar head the kernels read: (B, (2 + rank) * C, D, H, W), mean | log_cov_diag | cov_factor"""
+        return self._head
+
+    @property
     def batch_shape(self):
         return torch.Size([self._head.shape[0]])
 
