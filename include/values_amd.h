@@ -1004,7 +1004,8 @@ int vx_crop_resize_batched(const vx_p2d_item* items /* host */, int n_items, con
  * left them (label_switch.hip).
  * vx_label_switch_batched: per item, a label map [H][W] (device; kind VX_COUNT_B1 / B2 / B4 / B8: an integer of 1 / 2 /
  *   4 / 8 bytes; H, W >= 1 and H * W < 2^31; sizes may differ within a batch; pointers need only the alignment of their
- *   elements) gives
+ *   elements; VX_COUNT_B1 labels are read as UNSIGNED bytes -- a caller holding signed bytes widens them to 2 bytes first,
+ *   as values_amd.dataset2d does, or a negative label passes as 128..255 uncounted) gives
  *     refs     [R][H * W] uint8 (or null): refs[r][i] = rows[k].to where label[i] == rows[k].from and decision(item, r, k),
  *              else (uint8)label[i] -- 255 (ignore) and every class without a row pass through;
  *     variance [W][H] float32 (or null), THE FIRST TWO AXES SWAPPED as gta.py:34 returns it: var_table[label[y][x]] at
@@ -1089,13 +1090,17 @@ int vx_label_switch_batched(const vx_lswitch_item* items /* host */, int n_items
  *   data is).  The R raters of item i are labels[first_label .. first_label + R): device arrays of n integers of 1 / 2 /
  *   4 / 8 bytes (kind VX_COUNT_B1 .. B8) where the reader left them; the value used is the one astype(intc) gives, and a
  *   label outside 0..255 is counted in status[i] (device, zeroed by the call; integer atomics): the host turns a
- *   non-zero count into its error.  Traffic per voxel: esize + 4 + 8 + R * (label bytes + 9).
+ *   non-zero count into its error.  A label array is read as UNSIGNED integers unless its flags hold VX_LABEL_SIGNED:
+ *   without the flag a signed byte -1 passes as 255, uncounted, and a signed 2-byte -1 is counted but used as 65535; a
+ *   caller holding signed elements sets the flag (values_amd.dataset3d.composite_device does) and negative labels are then
+ *   counted and used as astype(intc) gives them.  Traffic per voxel: esize + 4 + 8 + R * (label bytes + 9).
  *   Refused: a null item table, label table (n_labels > 0), count, status, workspace, label pointer, or data without an
  *   image (VX_E_NULL); n_items outside [1, VX_SELECT_MAX_ITEMS], n_labels outside [0, VX_COMPOSITE_MAX_LABELS], a
  *   dimension below 1, more than 2^40 voxels, R < 0 or a label range outside the table (VX_E_SHAPE); an unknown image or
  *   label kind (VX_E_DTYPE); a pointer off its element alignment or a workspace off 16 (VX_E_ALIGN); a short workspace
  *   (VX_E_WORKSPACE). */
 #define VX_COMPOSITE_MAX_LABELS (1 << 20)
+#define VX_LABEL_SIGNED 1
 typedef struct vx_gather3d_item {
   const void* src;    /* device [dims[0]][dims[1]][dims[2]] */
   int32_t kind;       /* VX_PREP_* */
@@ -1112,7 +1117,7 @@ typedef struct vx_acc3d_item {
 typedef struct vx_composite_label {
   const void* ptr;    /* device, n integers */
   int32_t kind;       /* VX_COUNT_B1 | B2 | B4 | B8 */
-  int32_t reserved;
+  int32_t flags;      /* 0 (unsigned elements) or VX_LABEL_SIGNED; any other bit: VX_E_DTYPE */
 } vx_composite_label;
 typedef struct vx_composite_item {
   const void* image;  /* device [X][Y][Z] of image_kind (null allowed when data is null) */

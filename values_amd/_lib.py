@@ -307,6 +307,7 @@ class LswitchRow(C.Structure):
 
 
 VX_COMPOSITE_MAX_LABELS = 1 << 20
+VX_LABEL_SIGNED = 1
 
 
 class Gather3dItem(C.Structure):
@@ -321,8 +322,8 @@ class Acc3dItem(C.Structure):
 
 
 class CompositeLabel(C.Structure):
-    """vx_composite_label: one rater file's payload on the device, kind VX_COUNT_B1 .. B8."""
-    _fields_ = [("ptr", _p), ("kind", _i32), ("reserved", _i32)]
+    """vx_composite_label: one rater file's payload on the device, kind VX_COUNT_B1 .. B8, flags 0 or VX_LABEL_SIGNED."""
+    _fields_ = [("ptr", _p), ("kind", _i32), ("flags", _i32)]
 
 
 class CompositeItem(C.Structure):

@@ -80,24 +80,30 @@ __device__ __forceinline__ void vx4_load_kind(const void* base, int kind, int64_
   }
 }
 
-// labels [e, e + n) of 1 << esl bytes each as (the value numpy's astype(intc) gives, anything outside 0..255)
+// labels [e, e + n) of 1 << esl bytes each, signed when sgn, as (the value numpy's astype(intc) gives: the low 32 bits of
+// the sign- or zero-extended element; anything outside 0..255)
 template <typename S>
 __device__ __forceinline__ void vx4_load_label_t(const void* base, int64_t e, int n, int32_t lab[4], bool bad[4]) {
   S v[4];
   vx4_load<S>(reinterpret_cast<const S*>(base) + e, n, v);
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    lab[u] = (int32_t)(uint32_t)v[u];
-    bad[u] = u < n && v[u] > (S)255;
+    const unsigned long long w = (unsigned long long)(long long)v[u];   // a negative value extends to one above 255
+    lab[u] = (int32_t)(uint32_t)w;
+    bad[u] = u < n && w > 255ull;
   }
 }
 
-__device__ __forceinline__ void vx4_load_label(const void* base, int esl, int64_t e, int n, int32_t lab[4], bool bad[4]) {
-  switch (esl) {
+__device__ __forceinline__ void vx4_load_label(const void* base, int esl, int sgn, int64_t e, int n, int32_t lab[4], bool bad[4]) {
+  switch (esl | (sgn << 2)) {
     case 0: vx4_load_label_t<uint8_t>(base, e, n, lab, bad); break;
     case 1: vx4_load_label_t<uint16_t>(base, e, n, lab, bad); break;
     case 2: vx4_load_label_t<uint32_t>(base, e, n, lab, bad); break;
-    default: vx4_load_label_t<unsigned long long>(base, e, n, lab, bad); break;
+    case 3: vx4_load_label_t<unsigned long long>(base, e, n, lab, bad); break;
+    case 4: vx4_load_label_t<int8_t>(base, e, n, lab, bad); break;
+    case 5: vx4_load_label_t<int16_t>(base, e, n, lab, bad); break;
+    case 6: vx4_load_label_t<int32_t>(base, e, n, lab, bad); break;
+    default: vx4_load_label_t<long long>(base, e, n, lab, bad); break;
   }
 }
 
@@ -364,7 +370,7 @@ struct p3_comp_item {
 
 struct p3_comp_label {
   const void* p;
-  int32_t esl, reserved;
+  int32_t esl, sgn;   // log2 of the label's bytes; 1: signed elements
 };
 
 // the last entry whose block0 is not after blk (same for every thread of a workgroup)
@@ -405,7 +411,7 @@ __global__ __launch_bounds__(P3_THREADS) void case_composite_kernel(const p3_com
         const p3_comp_label lb = labels[it.first_label + r];
         int32_t lab[4];
         bool bad[4];
-        vx4_load_label(lb.p, lb.esl, e, n, lab, bad);
+        vx4_load_label(lb.p, lb.esl, lb.sgn, e, n, lab, bad);
         double g[4];
         uint8_t g8[4];
 #pragma unroll
@@ -447,7 +453,8 @@ extern "C" int vx_case_composite(const vx_composite_item* items, int n_items, co
     if (labels[l].kind < VX_COUNT_B1 || labels[l].kind > VX_COUNT_B8) VX_FAIL(VX_E_DTYPE, "%s: label %d: kind %d", who, l, labels[l].kind);
     if (!labels[l].ptr) VX_FAIL(VX_E_NULL, "%s: label %d: null pointer", who, l);
     if ((uintptr_t)labels[l].ptr % (1u << labels[l].kind)) VX_FAIL(VX_E_ALIGN, "%s: label %d: not aligned to its %d-byte elements", who, l, 1 << labels[l].kind);
-    ltab[(size_t)l].p = labels[l].ptr; ltab[(size_t)l].esl = labels[l].kind; ltab[(size_t)l].reserved = 0;
+    if (labels[l].flags & ~VX_LABEL_SIGNED) VX_FAIL(VX_E_DTYPE, "%s: label %d: flags %d", who, l, labels[l].flags);
+    ltab[(size_t)l].p = labels[l].ptr; ltab[(size_t)l].esl = labels[l].kind; ltab[(size_t)l].sgn = labels[l].flags & VX_LABEL_SIGNED;
   }
   int64_t n_blocks = 0;
   for (int i = 0; i < n_items; ++i) {

@@ -274,7 +274,8 @@ def label_switch_device(labels, indices, R: int, seed: int = 0, decisions=None, 
                         names=None):
     """The raters and / or variance maps of a batch of label maps: labels a list of (H, W) integer device tensors (1 / 2 /
     4 / 8-byte; sizes may differ), indices their split positions.  -> ([(R, H, W) uint8] or None, [(W, H) float32] or
-    None), device tensors.  A label outside 0..255 raises ValueError naming the item (names[i], default its number)."""
+    None), device tensors.  A label outside 0..255 raises ValueError naming the item (names[i], default its number); an
+    int8 map goes in widened to int16, so its negative labels are among them."""
     import torch
     _lib.require_gpu()
     n = len(labels)
@@ -286,7 +287,8 @@ def label_switch_device(labels, indices, R: int, seed: int = 0, decisions=None, 
     for i, (lab, index) in enumerate(zip(labels, indices)):
         if lab.dim() != 2 or lab.dtype.is_floating_point or lab.element_size() not in _KIND:
             raise ValueError("label_switch_device: (H, W) integer label maps expected")
-        lab = lab.contiguous()
+        # VX_COUNT_B1 is read as unsigned bytes: signed bytes go up as int16, whose negatives the kernel counts
+        lab = lab.to(torch.int16).contiguous() if lab.dtype == torch.int8 else lab.contiguous()
         keep.append(lab)
         H, W = int(lab.shape[0]), int(lab.shape[1])
         it = arr[i]
@@ -390,10 +392,14 @@ class DeviceTestLoader2D(_devio.PipelinedReader):
         seg = torch.empty((B, R, H, W), dtype=torch.uint8, device=device)
         status = torch.empty(B, dtype=torch.int32, device=device)
         arr = (_lib.LswitchItem * B)()
+        wide = []
         for b in range(B):
             it, (shape, dtype, _) = arr[b], heads[B + b]
             it.labels, it.refs = buf.data_ptr() + offs[B + b], seg[b].data_ptr()
             it.H, it.W, it.kind, it.index = H, W, _KIND[dtype.itemsize], first + b
+            if dtype == np.int8:   # VX_COUNT_B1 is read as unsigned bytes: signed bytes go in as int16
+                wide.append(buf[offs[B + b]:offs[B + b] + sizes[B + b]].view(torch.int8).to(torch.int16))
+                it.labels, it.kind = wide[-1].data_ptr(), _KIND[2]
         label_switch_call(arr, B, R, status, self.seed)
         check_label_status(status.cpu().tolist(), names[B:])
         out = {"data": views, "seg": seg, "image_id": [ds.image_ids[first + b] for b in range(B)],

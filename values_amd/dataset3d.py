@@ -323,6 +323,7 @@ def composite_device(group, counts, want_data: bool = True, want_gt_seg: bool = 
                 raise ValueError(f"composite_device: {c['image_path']}: integer label maps of shape {shape} expected")
             keep.append(lab.contiguous())
             labels[k].ptr, labels[k].kind = keep[-1].data_ptr(), _LABEL_KIND[lab.element_size()]
+            labels[k].flags = _lib.VX_LABEL_SIGNED if lab.dtype.is_signed else 0     # a negative label is counted, at any width
             k += 1
         out.append(o)
     status = torch.empty(n, dtype=torch.int32, device=dev)
