@@ -1214,6 +1214,27 @@ int vx_val_ssn_sums_batched(const float* head, const float* eps_w, const float* 
                             double* sample_sums, double* target_sums, void* workspace, int64_t workspace_bytes,
                             vx_stream_t stream);
 
+/* vx_val_ssn2d_sums_batched: the same sums for the 2D SSN head (HighResolutionNet.hrnet_ssn), whose mean and factor live
+ *   at the head's resolution h0 x w0, channels-last, exactly as vx_ssn2d_lowres takes them (mean_lo [B*h0*w0][mean_pitch],
+ *   factor_lo [B*h0*w0][factor_pitch], channel r*C + c; R = 0 is mean_only and factor_lo may be NULL).  The samples of the
+ *   H x W image are the ones vx_ssn2d_lowres -> vx_bilinear_nchw -> vx_ssn2d_add_diag write, bit for bit:
+ *       y_s,c = interp(mean + sum_r factor_r eps_w)_c + sqrtf(interp(expf(mean))_c + epsilon) * eps_d
+ *   with interp the bilinear upsample of F.interpolate(align_corners=False) -- but no full-resolution value is written.
+ *   eps_w [S][B][R], eps_d [S][B][C*H*W] injected or NULL: generated, eps_d = vx_gauss(seed, c*H*W + pixel, (item0 + b)*S + s),
+ *   eps_w = vx_gauss(seed ^ 0x5bd1e995, r, (item0 + b)*S + s) -- with item0 = 0 the streams of the three calls above.
+ *   labels [B][H*W]; sample_sums [B][S][1 + 2C], target_sums [B][C + 2] and the float64 arithmetic as vx_val_ssn_sums_batched.
+ *   2 <= C <= 32, 1 <= S <= 32, 0 <= R <= 32, 1 <= B <= 65535, every side in 1..65536, C*H*W < 2^32, B*h0*w0 < 2^32,
+ *   mean_pitch >= C, factor_pitch >= R*C (R > 0), ignore_label in -1..255: anything else VX_E_SHAPE; a null mean_lo, labels,
+ *   output or workspace (or factor_lo with R > 0) VX_E_NULL; a short workspace VX_E_WORKSPACE -- all before any launch.
+ *   The workspace holds the low-resolution combination ([S + 1][B*h0*w0][C] float32) and the span partials.  Three launches
+ *   on the stream, no synchronisation; counts are integer sums, the float64 sums go through the fixed tree: an item's rows
+ *   are bit-equal alone (item0 = k) and as row k of a batch. */
+int64_t vx_val_ssn2d_sums_workspace_bytes(int B, int S, int C, int h0, int w0, int H, int W);
+int vx_val_ssn2d_sums_batched(const float* mean_lo, int mean_pitch, const float* factor_lo, int factor_pitch, const float* eps_w,
+                              const float* eps_d, uint32_t seed, uint32_t item0, const uint8_t* labels, int B, int S, int C, int R,
+                              int h0, int w0, int H, int W, float epsilon, int ignore_label, double* sample_sums,
+                              double* target_sums, void* workspace, int64_t workspace_bytes, vx_stream_t stream);
+
 /* 2D SSN head (HighResolutionNet.hrnet_ssn, hrnet_module.py:559-595), see accumulate.hip:
  * vx_ssn2d_lowres: channels-last head outputs at the head's resolution -- mean [B*pix][mean_pitch] (C used),
  *   factor [B*pix][factor_pitch] (channel r*C + c) -- and eps_w [S][B][R] (nullable: generated) ->

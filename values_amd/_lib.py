@@ -455,6 +455,9 @@ SIGNATURES = {
     "vx_val_aleatoric_sums_batched": (_i, [_p, _p, _u32, _u32, _p, _i, _i, _i, _i64, _i, _p, _p, _i64, _p]),
     "vx_val_ssn_sums_workspace_bytes": (_i64, [_i, _i, _i, _i64]),
     "vx_val_ssn_sums_batched": (_i, [_p, _p, _p, _u32, _u32, _p, _i, _i, _i, _i, _i64, C.c_float, _i, _p, _p, _p, _i64, _p]),
+    "vx_val_ssn2d_sums_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "vx_val_ssn2d_sums_batched": (_i, [_p, _i, _p, _i, _p, _p, _u32, _u32, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p,
+                                       _p, _i64, _p]),
     "vx_ssn2d_lowres": (_i, [_p, _i, _p, _i, _p, _u32, _i, _i64, _i, _i, _i, _p, _p, _p]),
     "vx_ssn2d_add_diag": (_i, [_p, _p, _p, _u32, _i, _i, _i64, C.c_float, _p]),
     "vx_softmax_variance": (_i, [_p, _i, _i, _i, _i, _i64, _p, _p]),

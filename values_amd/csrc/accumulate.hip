@@ -6,6 +6,7 @@
 // patch_overlap = 1 every voxel is written once and plain stores are used (bit-reproducible).
 #include "common.h"
 #include "gauss.h"
+#include "ssn2d_internal.h"
 
 template <int C>
 __global__ __launch_bounds__(256) void softmax_accumulate_kernel(const float* __restrict__ logits, int B, int T, int P0,
@@ -167,8 +168,8 @@ extern "C" int vx_ssn_sample(const float* head, const float* eps_w, const float*
 //                         -> comb [S][P][C] = mean + sum_r factor_r * eps_w[s][b][r],  expm [P][C] = exp(mean)
 //   ssn2d_add_diag_kernel: out [S][B][C][HW] += sqrt(diag [B][C][HW] + epsilon) * eps_d (injected or generated)
 __global__ __launch_bounds__(256) void ssn2d_lowres_kernel(const float* __restrict__ mean, int pm, const float* __restrict__ fac,
-                                                           int pf, const float* __restrict__ eps_w, uint32_t seed, int B,
-                                                           int64_t pix_per_image, int S, int C, int R,
+                                                           int pf, const float* __restrict__ eps_w, uint32_t seed,
+                                                           uint32_t item0, int B, int64_t pix_per_image, int S, int C, int R,
                                                            float* __restrict__ comb, float* __restrict__ expm) {
   const int64_t P = (int64_t)B * pix_per_image;
   const int64_t total = P * C;
@@ -182,12 +183,26 @@ __global__ __launch_bounds__(256) void ssn2d_lowres_kernel(const float* __restri
       float low = 0.f;
       for (int k = 0; k < R; ++k) {
         const float ew = eps_w ? eps_w[((size_t)s * B + b) * R + k]
-                               : vx_gauss(seed ^ 0x5bd1e995u, (uint32_t)k, (uint32_t)(b * S + s));
+                               : vx_gauss(seed ^ 0x5bd1e995u, (uint32_t)k, (item0 + (uint32_t)b) * (uint32_t)S + (uint32_t)s);
         low = fmaf(fac[pix * pf + k * C + c], ew, low);
       }
       comb[((size_t)s * P + pix) * C + c] = m + low;
     }
   }
+}
+
+// the launch itself, shared with vx_val_ssn2d_sums_batched (valstep.hip, through ssn2d_internal.h): image b of the call draws the
+// generated eps_w of the global item item0 + b (slot (item0 + b) * S + s).  vx_ssn2d_lowres passes item0 = 0.
+int vx_ssn2d_lowres_launch(const float* mean, int mean_pitch, const float* factor, int factor_pitch, const float* eps_w, uint32_t seed,
+                           uint32_t item0, int B, int64_t pix_per_image, int S, int C, int R, float* comb, float* expm, hipStream_t s,
+                           const char* who) {
+  const int64_t total = (int64_t)B * pix_per_image * C;
+  int bx = (int)((total + 255) / 256);
+  if (bx > 8192) bx = 8192;
+  hipLaunchKernelGGL(ssn2d_lowres_kernel, dim3(bx), dim3(256), 0, s, mean, mean_pitch, factor, factor_pitch, eps_w, seed, item0, B,
+                     pix_per_image, S, C, R, comb, expm);
+  VX_CHECK_LAUNCH(who);
+  return VX_OK;
 }
 
 extern "C" int vx_ssn2d_lowres(const float* mean, int mean_pitch, const float* factor, int factor_pitch, const float* eps_w,
@@ -200,13 +215,8 @@ extern "C" int vx_ssn2d_lowres(const float* mean, int mean_pitch, const float* f
   if ((int64_t)B * pix_per_image >= (1ll << 32) || (int64_t)B * S >= (1ll << 31))
     VX_FAIL(VX_E_SHAPE, "vx_ssn2d_lowres: batch too large");
   if (!mean || !comb || (R > 0 && !factor)) VX_FAIL(VX_E_NULL, "vx_ssn2d_lowres: null pointer");
-  const int64_t total = (int64_t)B * pix_per_image * C;
-  int bx = (int)((total + 255) / 256);
-  if (bx > 8192) bx = 8192;
-  hipLaunchKernelGGL(ssn2d_lowres_kernel, dim3(bx), dim3(256), 0, (hipStream_t)stream, mean, mean_pitch, factor, factor_pitch,
-                     eps_w, seed, B, pix_per_image, S, C, R, comb, expm);
-  VX_CHECK_LAUNCH("vx_ssn2d_lowres");
-  return VX_OK;
+  return vx_ssn2d_lowres_launch(mean, mean_pitch, factor, factor_pitch, eps_w, seed, 0u, B, pix_per_image, S, C, R, comb, expm,
+                                (hipStream_t)stream, "vx_ssn2d_lowres");
 }
 
 __global__ __launch_bounds__(256) void ssn2d_add_diag_kernel(float* __restrict__ out, const float* __restrict__ diag,

@@ -11,6 +11,7 @@
 //   vx_bilinear_nchw    final upsample of the class logits to the input size, written in the reference's NCHW layout
 //                       into the pred_idx slot (hrnet_module.py:667-669; test_2D.py:302-316).
 #include "common.h"
+#include "bil_coord.h"   // bil_coord: the bilinear source coordinate, shared with valstep.hip
 
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partial, int ntiles, int C,
                                                           double inv_count, float eps, const float* __restrict__ gamma,
@@ -94,16 +95,6 @@ extern "C" int vx_bn_running_affine(const vx_bn_affine_item* items, int n_items,
   hipLaunchKernelGGL(bn_running_affine_kernel, dim3((unsigned)n_items), dim3(256), 0, (hipStream_t)stream, items, eps);
   VX_CHECK_LAUNCH("vx_bn_running_affine");
   return VX_OK;
-}
-
-// bilinear source coordinates of F.interpolate(align_corners=False): src = (dst + 0.5) * in/out - 0.5, clamped at 0
-__device__ __forceinline__ void bil_coord(int d, int in, float ratio, int& i0, int& i1, float& l1) {
-  float s = ((float)d + 0.5f) * ratio - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
 }
 
 // Index scheme of the two streaming kernels below (round 5): grid = (pieces of an output row / 256, OH, N) -- image and row are

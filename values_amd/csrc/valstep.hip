@@ -5,6 +5,9 @@
 //                                    lavg_c = logsumexp_t - log T, p = exp(lavg)
 //   * vx_val_ssn_sums_batched        SSN head: S samples of the low-rank normal, per sample sum_v log_softmax(y_s)[t] and the
 //                                    arg-max counts
+//   * vx_val_ssn2d_sums_batched      the same sums for the 2D SSN head (HighResolutionNet.hrnet_ssn), whose mean and factor live at
+//                                    1/4 resolution: the samples are formed per full-resolution pixel inside the reduction
+//                                    (val_ssn2d_kernel, further down, with its own notes)
 // The reference materialises S x B x C x voxels samples and runs cross_entropy, S arg-maxes and S dice calls over them; here the
 // head is read once and a few hundred bytes per item are written.  No sample is written.
 //
@@ -31,6 +34,8 @@
 // then the same butterfly.  No atomics, no data-dependent order.
 #include "common.h"
 #include "gauss.h"
+#include "bil_coord.h"
+#include "ssn2d_internal.h"
 
 constexpr int VS_SPAN = 256;
 constexpr int VS_MAXC = 32;                   // plain kernel
@@ -351,6 +356,140 @@ __global__ __launch_bounds__(256) void val_ssn_kernel(const float* __restrict__ 
   }
 }
 
+// ---- the 2D SSN head (HighResolutionNet.hrnet_ssn) ---------------------------------------------------------------------------------
+// The head lives at 1/4 resolution, channels-last.  ssn2d_lowres_kernel (accumulate.hip) has left comb [S][B * h0 * w0][C] and
+// expm [B * h0 * w0][C] in the workspace; a thread owns one FULL-resolution pixel and forms its S x C sample logits as
+// LowRankNormal2D.sample_images does, expression for expression (bilinear_nchw_kernel's interpolation, ssn2d_add_diag_kernel's
+// diagonal term), so the very float32 values that route writes are reduced here without being written:
+//     sd_c = sqrtf(interp(expm)_c + epsilon),   y_s,c = interp(comb_s)_c + sd_c * eps_d
+// The four low-resolution pixels of a thread are shared with its neighbours (16 full-resolution pixels per source pixel at the
+// shipped 1/4) and stay in L1 / L2.  CT > 0: the class count is a template constant and a pixel's C logits and C standard
+// deviations are register arrays.  CT == 0 (any C up to 32): two sweeps over the classes per sample -- maximum, arg-max and
+// the label's logit, then the sum of exponentials -- each re-evaluating y_s,c from the four source pixels, so nothing is
+// indexed by a runtime class and nothing lands in scratch (bn2d.hip records what a 32-wide register array cost).
+// Accumulation: lane s keeps sample s's float64 log-term sum (butterfly, as above).  The counts do not go through
+// per-class registers (2 C of them per lane, 38 at the shipped C = 19): a wave walks the DISTINCT arg-max classes of its 64
+// pixels (ballot, popcount) and lane 0 adds each count into the workgroup's LDS table with an integer atomic -- integer adds
+// commute, so the table does not depend on the order.  Partial row as val_ssn_kernel's.
+template <int CT>
+__global__ __launch_bounds__(256) void val_ssn2d_kernel(const float* __restrict__ comb, const float* __restrict__ expm,
+                                                        const float* __restrict__ eps_d, uint32_t seed, uint32_t item0,
+                                                        const uint8_t* __restrict__ labels, int B, int S, int Crt, int h0, int w0, int H,
+                                                        int W, float epsilon, int ignore, int64_t nspan, double* __restrict__ part) {
+  const int C = CT ? CT : Crt;
+  __shared__ double sll[4 * VS_MAXS];                                // [wave][s]
+  __shared__ unsigned cnt[VS_MAXS * 2 * VS_MAXC + VS_MAXC + 2];      // [s][tp_c | pred_c], then #[t = c] | valid | invalid
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, PS = 1 + 2 * C, K = S * PS + C + 2, NC = S * 2 * C + C + 2;
+  const uint32_t nvox = (uint32_t)H * (uint32_t)W;                   // C * nvox < 2^32 (host check)
+  const size_t per = (size_t)C * nvox;
+  const size_t pix = (size_t)h0 * w0, PC = (size_t)B * pix * C;      // floats of one sample's comb
+  const float ry = (float)h0 / (float)H, rx = (float)w0 / (float)W;
+  const uint8_t* g = labels + (size_t)b * nvox;
+  const uint32_t slot0 = (item0 + (uint32_t)b) * (uint32_t)S;
+  for (int64_t sp = blockIdx.x; sp < nspan; sp += gridDim.x) {
+    for (int i = tid; i < NC; i += 256) cnt[i] = 0u;
+    __syncthreads();
+    double aLL = 0.0;
+    const int64_t v0 = sp * VS_SPAN + wave * 64;
+    if (v0 < (int64_t)nvox) {   // else the whole wave is past the end
+      const int64_t v = v0 + lane;
+      const bool act = v < (int64_t)nvox;
+      const uint32_t vv = act ? (uint32_t)v : nvox - 1u;
+      const vs_label l = vs_load_label(g, v, nvox, C, ignore);
+      if (act && l.lab < C) atomicAdd(&cnt[S * 2 * C + l.lab], 1u);
+      const int nv = vs_pop(__ballot(l.take)), ni = vs_pop(__ballot(l.inv));
+      if (lane == 0) {
+        atomicAdd(&cnt[S * 2 * C + C], (unsigned)nv);
+        atomicAdd(&cnt[S * 2 * C + C + 1], (unsigned)ni);
+      }
+      const int oy = (int)(vv / (uint32_t)W), ox = (int)(vv - (uint32_t)oy * (uint32_t)W);
+      int y0, y1, x0, x1;
+      float ly, lx;
+      bil_coord(oy, h0, ry, y0, y1, ly);
+      bil_coord(ox, w0, rx, x0, x1, lx);
+      const float hy = 1.f - ly, hx = 1.f - lx;
+      const size_t o00 = ((size_t)b * pix + (size_t)y0 * w0 + x0) * C, o01 = ((size_t)b * pix + (size_t)y0 * w0 + x1) * C;
+      const size_t o10 = ((size_t)b * pix + (size_t)y1 * w0 + x0) * C, o11 = ((size_t)b * pix + (size_t)y1 * w0 + x1) * C;
+      // bilinear_nchw_kernel's expression on the four source pixels at p + o00 .. p + o11
+      auto interp = [&](const float* p, int c) {
+        return hy * (hx * p[o00 + c] + lx * p[o01 + c]) + ly * (hx * p[o10 + c] + lx * p[o11 + c]);
+      };
+      auto sdev = [&](int c) { return sqrtf(interp(expm, c) + epsilon); };
+      float sd[CT ? CT : 1];
+      if constexpr (CT > 0) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) sd[c] = sdev(c);
+      }
+      for (int s = 0; s < S; ++s) {
+        const float* cs = comb + (size_t)s * PC;
+        const float* ed = eps_d ? eps_d + ((size_t)s * B + b) * per + vv : nullptr;
+        const uint32_t slot = slot0 + (uint32_t)s;
+        // ssn2d_add_diag_kernel's expression: the upsampled combination + sd * eps_d
+        auto logit = [&](int c, float sdc) {
+          const float e = ed ? ed[(size_t)c * nvox] : vx_gauss(seed, (uint32_t)c * nvox + vv, slot);
+          return interp(cs, c) + sdc * e;
+        };
+        float mx, yt = 0.f;
+        int a = 0;
+        double se = 0.0;
+        if constexpr (CT > 0) {
+          float y[CT];
+#pragma unroll
+          for (int c = 0; c < CT; ++c) y[c] = logit(c, sd[c]);
+          mx = y[0];
+#pragma unroll
+          for (int c = 1; c < CT; ++c)
+            if (y[c] > mx) { mx = y[c]; a = c; }
+          const double m = (double)mx;
+#pragma unroll
+          for (int c = 0; c < CT; ++c) {
+            se += exp((double)y[c] - m);
+            if (l.lab == c) yt = y[c];
+          }
+        } else {
+          mx = logit(0, sdev(0));
+          if (l.lab == 0) yt = mx;
+          for (int c = 1; c < C; ++c) {
+            const float yc = logit(c, sdev(c));
+            if (yc > mx) { mx = yc; a = c; }
+            if (l.lab == c) yt = yc;
+          }
+          const double m = (double)mx;
+          for (int c = 0; c < C; ++c) se += exp((double)logit(c, sdev(c)) - m);
+        }
+        const double lt = l.take ? ((double)yt - (double)mx) - log(se) : 0.0;
+        const double tot = vs_wave_all(lt);
+        if (lane == s) aLL += tot;
+        // the distinct arg-max classes of the wave's pixels
+        const bool hit = a == l.lab;
+        unsigned long long rem = __ballot(act);
+        while (rem) {
+          const int c = __builtin_amdgcn_readlane(a, __ffsll((long long)rem) - 1);
+          const unsigned long long ba = __ballot(act && a == c), bh = __ballot(act && a == c && hit);
+          if (lane == 0) {
+            atomicAdd(&cnt[s * 2 * C + C + c], (unsigned)vs_pop(ba));
+            if (bh) atomicAdd(&cnt[s * 2 * C + c], (unsigned)vs_pop(bh));
+          }
+          rem &= ~ba;
+        }
+      }
+    }
+    if (lane < S) sll[wave * VS_MAXS + lane] = aLL;
+    __syncthreads();
+    double* row = part + ((size_t)b * nspan + sp) * K;
+    for (int k = tid; k < K; k += 256) {
+      if (k < S * PS) {
+        const int s = k / PS, j = k - s * PS;
+        row[k] = j == 0 ? ((sll[s] + sll[VS_MAXS + s]) + sll[2 * VS_MAXS + s]) + sll[3 * VS_MAXS + s] : (double)cnt[s * 2 * C + j - 1];
+      } else {
+        row[k] = (double)cnt[S * 2 * C + (k - S * PS)];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // out[b][k] = the span partials of item b: a wave per output, lane l adds the spans l, l + 64, ... in ascending order, the lanes
 // meet in the butterfly; row entries k >= K1 go to out2[b][k - K1]
 __global__ __launch_bounds__(256) void val_final_kernel(const double* __restrict__ part, int64_t n, int K, int K1, int64_t nspan,
@@ -468,4 +607,66 @@ extern "C" int vx_val_ssn_sums_batched(const float* head, const float* eps_w, co
 #undef VS_SSN
   const int K = S * (1 + 2 * C) + C + 2;
   return vs_finalize((const double*)workspace, B, K, S * (1 + 2 * C), nspan, sample_sums, target_sums, s, "vx_val_ssn_sums_batched");
+}
+
+// ---- vx_val_ssn2d_sums_batched ---------------------------------------------------------------------------------------------------
+constexpr int VS_MAXSIDE = 65536;   // h0, w0, H, W: a float32 holds (side + 0.5) exactly, as bil_coord needs
+static bool vs_ssn2d_ok(int B, int S, int C, int h0, int w0, int H, int W) {
+  if (B < 1 || B > VS_MAXB || S < 1 || S > VS_MAXS || C < 2 || C > VS_MAXC) return false;
+  if (h0 < 1 || w0 < 1 || H < 1 || W < 1 || h0 > VS_MAXSIDE || w0 > VS_MAXSIDE || H > VS_MAXSIDE || W > VS_MAXSIDE) return false;
+  // the guards of the calls this one stands for: vx_ssn2d_add_diag (C * H * W indexes the generator in 32 bits) and
+  // vx_ssn2d_lowres (B * pix pixels index in 32 bits; B * S < 2^31 holds with B < 2^16, S <= 32)
+  return (int64_t)C * H * W < ((int64_t)1 << 32) && (int64_t)B * h0 * w0 < ((int64_t)1 << 32);
+}
+// the workspace: [comb (S) | expm] floats of the low-resolution head, rounded up to 16 bytes, then the span partial rows
+static int64_t vs_ssn2d_lowres_bytes(int B, int S, int C, int h0, int w0) {
+  const int64_t fl = (int64_t)(S + 1) * B * h0 * w0 * C;   // 33 * 2^32 * 32 < 2^43
+  return (fl * 4 + 15) / 16 * 16;
+}
+
+extern "C" int64_t vx_val_ssn2d_sums_workspace_bytes(int B, int S, int C, int h0, int w0, int H, int W) {
+  if (!vs_ssn2d_ok(B, S, C, h0, w0, H, W)) return 0;
+  return vs_ssn2d_lowres_bytes(B, S, C, h0, w0) + vs_workspace(B, (int64_t)S * (1 + 2 * C) + C + 2, (int64_t)H * W);
+}
+
+extern "C" int vx_val_ssn2d_sums_batched(const float* mean_lo, int mean_pitch, const float* factor_lo, int factor_pitch,
+                                         const float* eps_w, const float* eps_d, uint32_t seed, uint32_t item0, const uint8_t* labels,
+                                         int B, int S, int C, int R, int h0, int w0, int H, int W, float epsilon, int ignore_label,
+                                         double* sample_sums, double* target_sums, void* workspace, int64_t workspace_bytes,
+                                         vx_stream_t stream) {
+  if (!vs_ssn2d_ok(B, S, C, h0, w0, H, W) || ignore_label < -1 || ignore_label > 255 || R < 0 || R > VS_MAXR || mean_pitch < C ||
+      (R > 0 && (int64_t)factor_pitch < (int64_t)R * C))
+    VX_FAIL(VX_E_SHAPE,
+            "vx_val_ssn2d_sums_batched: B=%d (1..%d) S=%d (1..%d) C=%d (2..%d) R=%d (0..%d) %dx%d -> %dx%d (sides 1..%d, C * H * W < 2^32, "
+            "B * h0 * w0 < 2^32) mean_pitch=%d (>= C) factor_pitch=%d (>= R * C) ignore_label=%d (-1..255)",
+            B, VS_MAXB, S, VS_MAXS, C, VS_MAXC, R, VS_MAXR, h0, w0, H, W, VS_MAXSIDE, mean_pitch, factor_pitch, ignore_label);
+  if (!mean_lo || (R > 0 && !factor_lo) || !labels || !sample_sums || !target_sums || !workspace)
+    VX_FAIL(VX_E_NULL, "vx_val_ssn2d_sums_batched: null pointer");
+  const int64_t need = vx_val_ssn2d_sums_workspace_bytes(B, S, C, h0, w0, H, W);
+  if (workspace_bytes < need)
+    VX_FAIL(VX_E_WORKSPACE, "vx_val_ssn2d_sums_batched: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t pix = (int64_t)h0 * w0, nvox = (int64_t)H * W;
+  float* comb = (float*)workspace;
+  float* expm = comb + (size_t)S * B * pix * C;
+  double* part = (double*)((char*)workspace + vs_ssn2d_lowres_bytes(B, S, C, h0, w0));
+  const int rc = vx_ssn2d_lowres_launch(mean_lo, mean_pitch, factor_lo, factor_pitch, R > 0 ? eps_w : nullptr, seed, item0, B, pix, S, C, R,
+                                        comb, expm, s, "vx_val_ssn2d_sums_batched (low-resolution combination)");
+  if (rc != VX_OK) return rc;
+  const int64_t nspan = (nvox + VS_SPAN - 1) / VS_SPAN;
+  const dim3 grid((unsigned)(nspan < VS_MAXGRID ? nspan : VS_MAXGRID), (unsigned)B);
+#define VS_SSN2D(CC)                                                                                                                   \
+  hipLaunchKernelGGL(val_ssn2d_kernel<CC>, grid, dim3(256), 0, s, comb, expm, eps_d, seed, item0, labels, B, S, C, h0, w0, H, W, epsilon, \
+                     ignore_label, nspan, part)
+  switch (C) {
+    case 2: VS_SSN2D(2); break;
+    case 3: VS_SSN2D(3); break;
+    case 4: VS_SSN2D(4); break;
+    case 19: VS_SSN2D(19); break;   // the shipped head (hrnet_config_ssn.yaml)
+    default: VS_SSN2D(0); break;    // any other count: the two-sweep form
+  }
+#undef VS_SSN2D
+  VX_CHECK_LAUNCH("vx_val_ssn2d_sums_batched");
+  const int K = S * (1 + 2 * C) + C + 2;
+  return vs_finalize(part, B, K, S * (1 + 2 * C), nspan, sample_sums, target_sums, s, "vx_val_ssn2d_sums_batched");
 }

@@ -26,7 +26,9 @@ checkpoint's running statistics leave, and nothing guards it: a checkpoint whose
 native-fp32 kernels (vx_config.conv_fp32 = 1, where eval mode takes the raw conv + vx_affine_gather route).
 
 HIP path limits: every branch width and the stem/bottleneck widths must be multiples of 16 (true for the shipped W48
-config: 48/96/192/384, 64/256, 720).  The SSN head (hrnet_config_ssn.yaml) returns a LowRankNormal2D.
+config: 48/96/192/384, 64/256, 720).  The SSN head (hrnet_config_ssn.yaml) returns a LowRankNormal2D: `sample` /
+`sample_images` for the test split, and `lowres()` for values_amd.validation, which reduces the validation sums from the
+1/4-resolution head without writing a sample (val_sums_ssn2d).
 """
 from __future__ import annotations
 
@@ -200,6 +202,36 @@ class LowRankNormal2D:
         self._up(self._m.t, self._m.pitch, B, out, None)
         return out.reshape(B, -1)
 
+    @classmethod
+    def from_lowres(cls, mean: torch.Tensor, factor: Optional[torch.Tensor], num_classes: int, rank: int, epsilon: float, size,
+                    seed: int = 0) -> "LowRankNormal2D":
+        """the distribution of a head given as channels-last float32 device tensors: mean (B, h0, w0, pitch >= C), factor
+        (B, h0, w0, pitch >= rank * C; channel r * C + c; None at rank 0), for the full-resolution size (H, W)"""
+        if mean.dim() != 4 or mean.shape[3] < num_classes or mean.dtype != torch.float32 or not mean.is_contiguous():
+            raise ValueError(f"LowRankNormal2D.from_lowres: mean (B, h0, w0, >= {num_classes}) contiguous float32 expected")
+        if rank:
+            if (factor is None or factor.dim() != 4 or tuple(factor.shape[:3]) != tuple(mean.shape[:3]) or factor.shape[3] < rank * num_classes
+                    or factor.dtype != torch.float32 or not factor.is_contiguous()):
+                raise ValueError(f"LowRankNormal2D.from_lowres: factor {tuple(mean.shape[:3])} + (>= {rank * num_classes},) contiguous float32 expected")
+        return cls(_Act(mean, num_classes), _Act(factor, rank * num_classes) if rank else None, num_classes, rank, epsilon,
+                   (int(size[0]), int(size[1])), seed)
+
+    def next_seed(self) -> int:
+        """the seed of this distribution's next draw (sample_images and validation.val_sums_ssn2d take it when none is
+        given, so the materialised and the fused route see the same normals)"""
+        seed = (self._seed * 7919 + self._draws) & 0xFFFFFFFF
+        self._draws += 1
+        return seed
+
+    def lowres(self) -> dict:
+        """the head at its own resolution, as vx_ssn2d_lowres / vx_val_ssn2d_sums_batched take it: channels-last tensors
+        "mean" (B, h0, w0, mean_pitch) and "factor" (B, h0, w0, factor_pitch; channel r * C + c; None at rank 0), their
+        pitches, and the sizes B, h0, w0, H, W"""
+        R = self.rank
+        return {"mean": self._m.t, "mean_pitch": self._m.pitch, "factor": self._f.t if R else None,
+                "factor_pitch": self._f.pitch if R else 0, "B": self._m.N, "h0": self._m.H, "w0": self._m.W,
+                "H": int(self.size[0]), "W": int(self.size[1])}
+
     def sample_images(self, n: int, eps_w=None, eps_d=None, seed: Optional[int] = None) -> torch.Tensor:
         """(B, n, C, H, W) logit samples (per-image stacks, the layout process_output_2d reads)."""
         lib = _lib.load()
@@ -209,8 +241,7 @@ class LowRankNormal2D:
         H, W = self.size
         pix = h0 * w0
         if seed is None:
-            seed = (self._seed * 7919 + self._draws) & 0xFFFFFFFF
-            self._draws += 1
+            seed = self.next_seed()
         hold = []
         pw = pd = None
         if eps_w is not None:

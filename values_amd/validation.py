@@ -1,6 +1,6 @@
-"""The validation step on MI355X: validation/val_loss and validation/val_dice for all three 3D model kinds (and any model
-that returns logits), as LightningExperiment.validation_step and forward_ssn(val=True) compute them
-(lightning_experiment.py:175-219, 278-377).
+"""The validation step on MI355X: validation/val_loss and validation/val_dice for all three 3D model kinds, the 2D
+HighResolutionNet with the SSN head (and any model that returns logits), as LightningExperiment.validation_step and
+forward_ssn(val=True) compute them (lightning_experiment.py:175-219, 278-377).
 
 The reference materialises S x B x C x voxels logit samples and runs cross_entropy, S arg-maxes and S dice calls over
 them.  Here one fused reduction per branch (valstep.hip) reads the model's output once and returns a few hundred bytes of
@@ -8,13 +8,17 @@ float64 sums and integer counts; every ratio is formed on the host from those:
     val_sums            logits (B, C, *spatial)                 -> (B, 5C + 3)      vx_val_sums_batched
     val_sums_aleatoric  mu_s   (B, 2C, *spatial), T samples     -> (B, 5C + 3)      vx_val_aleatoric_sums_batched
     val_sums_ssn        head   (B, (2 + R)C, *spatial), S       -> (B, S, 1 + 2C), (B, C + 2)   vx_val_ssn_sums_batched
+    val_sums_ssn2d      a LowRankNormal2D (head at 1/4 res.), S -> (B, S, 1 + 2C), (B, C + 2)   vx_val_ssn2d_sums_batched
+The 2D SSN head's samples are formed per full-resolution pixel from the low-resolution head inside the reduction (the
+bits LowRankNormal2D.sample_images writes): neither the S x B x C x H x W samples nor the reference's (B, C*H*W, R) factor
+tensor exist.
 The host arithmetic follows the reference, its ignore_index quirk included: with ignore_index == 0 (the 3D default) the
 cross-entropy ignores NOTHING and the loss is SoftDice + CE; with ignore_index != 0 the loss is CE(ignore_index) alone;
 the aleatoric branch is SoftDice + NLL either way; `dice` always deletes the ignore_index column (torchmetrics 0.11.4,
 average='micro', mdmc_average='global' -- the counting metrics.py does).
 
-Not here: the 2D SSN head's validation branch, the validation data loader (the caller supplies
-batches), training / gradients, the visualisation sample and TensorBoard grids.
+Not here: the validation data loader (the caller supplies batches), training / gradients, the
+visualisation sample and TensorBoard grids.
 """
 from __future__ import annotations
 
@@ -148,6 +152,45 @@ def val_sums_ssn(head: torch.Tensor, target, num_classes: int, rank: int, n_samp
     return ss, ts
 
 
+def val_sums_ssn2d(dist, target, n_samples: int = 10, eps_w: Optional[torch.Tensor] = None, eps_d: Optional[torch.Tensor] = None,
+                   seed: Optional[int] = None, item0: int = 0, ignore_label: Optional[int] = None, raise_invalid: bool = True):
+    """dist: the LowRankNormal2D of an SSN HighResolutionNet (head at h0 x w0, image H x W); target (B, H, W) or (B, 1, H, W)
+    integer labels; eps_w (S, B, R) / eps_d (S, B, C * H * W) injected normals or None (generated from seed, keyed by
+    item0 + b; seed None: the distribution's next draw seed, the one sample_images would take)
+    -> sample_sums (B, S, 1 + 2C), target_sums (B, C + 2) as val_sums_ssn, over the samples dist.sample_images(S) writes."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    ig = _check_ignore(ignore_label)
+    lo = dist.lowres()
+    C, R, S = int(dist.num_classes), int(dist.rank), int(n_samples)
+    B, h0, w0, H, W = (int(lo[k]) for k in ("B", "h0", "w0", "H", "W"))
+    mean, fac = lo["mean"], lo["factor"]
+    dev = mean.device
+    if seed is None:
+        seed = dist.next_seed()
+    g = _labels_u8(target, dev, B, H * W, ig)
+    ew = ed = None
+    if eps_w is not None and R:
+        ew = eps_w.to(device=dev, dtype=torch.float32).contiguous()
+        if ew.numel() != S * B * R:
+            raise ValueError(f"val_sums_ssn2d: eps_w of {tuple(eps_w.shape)} for (S, B, R) = {(S, B, R)}")
+    if eps_d is not None:
+        ed = eps_d.to(device=dev, dtype=torch.float32).contiguous()
+        if ed.numel() != S * B * C * H * W:
+            raise ValueError(f"val_sums_ssn2d: eps_d of {tuple(eps_d.shape)} for (S, B, C * H * W) = {(S, B, C * H * W)}")
+    ss = torch.empty((B, S, 1 + 2 * C), dtype=torch.float64, device=dev)
+    ts = torch.empty((B, C + 2), dtype=torch.float64, device=dev)
+    ws = _lib.workspace(dev, int(lib.vx_val_ssn2d_sums_workspace_bytes(B, S, C, h0, w0, H, W)))
+    _lib.check(lib.vx_val_ssn2d_sums_batched(mean.data_ptr(), int(lo["mean_pitch"]), _lib.ptr(fac), int(lo["factor_pitch"]), _lib.ptr(ew),
+                                             _lib.ptr(ed), int(seed) & 0xFFFFFFFF, int(item0) & 0xFFFFFFFF, g.data_ptr(), B, S, C, R, h0, w0,
+                                             H, W, float(dist.epsilon), ig, ss.data_ptr(), ts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             _lib.stream_ptr()), "vx_val_ssn2d_sums_batched")
+    ss, ts = ss.cpu().numpy(), ts.cpu().numpy()
+    if raise_invalid:
+        _raise_invalid(ts[:, C + 1].sum(), "val_sums_ssn2d")
+    return ss, ts
+
+
 # ---- host arithmetic --------------------------------------------------------------------------------------------------------------
 def ce_ignore_label(ignore_index: int) -> int:
     """the label the cross-entropy ignores: the reference calls it WITHOUT ignore_index when ignore_index == 0"""
@@ -196,10 +239,12 @@ def validation_step(model, data: torch.Tensor, seg, n_aleatoric_samples: int = 1
                     mean_only: bool = False, seed: Optional[int] = None, eps=None) -> Dict[str, float]:
     """LightningExperiment.validation_step for one batch: data (B, Cin, *spatial), seg (B, 1, *spatial) or (B, *spatial)
     integer labels -> {"validation/val_loss", "validation/val_dice"}.  Dispatch as the reference (:290-330): an SsnUNet3D
-    takes the SSN branch (mean_only: the pretraining epochs' rank-0 distribution), a model with aleatoric_loss the
-    aleatoric one, anything else that returns logits (B, C, *spatial) the plain one.
+    or a model with `ssn` set (the 2D HighResolutionNet, which returns a LowRankNormal2D) takes the SSN branch (mean_only:
+    the pretraining epochs' rank-0 distribution), a model with aleatoric_loss the aleatoric one, anything else that returns
+    logits (B, C, *spatial) the plain one.
     eps: the standard normals, for parity -- aleatoric: (B, T, C, *spatial); SSN: (eps_w (S, B, R), eps_d (S, B, C * voxels))
-    (either may be None); None: generated on the device from seed (None: the model's next seed)."""
+    (either may be None; 2D: eps_d (S, B, C * H * W)); None: generated on the device from seed (None: the model's next
+    seed; 2D: the distribution's)."""
     from .ssn import SsnUNet3D
     _lib.require_gpu()
     ignore_index = int(ignore_index)
@@ -212,8 +257,14 @@ def validation_step(model, data: torch.Tensor, seg, n_aleatoric_samples: int = 1
         ss, ts = val_sums_ssn(dist.head, seg, dist.num_classes, dist.rank, n_aleatoric_samples, ew, ed, seed, 0, dist.epsilon, ce_ig)
         loss, dice = ssn_loss_dice_from_sums(ss, ts, dist.num_classes, ignore_index)
     elif getattr(model, "ssn", False):
-        raise NotImplementedError("validation_step: the 2D SSN head's validation branch forms its samples at 1/4 resolution "
-                                  "and is not on the device path")
+        from .hrnet import LowRankNormal2D
+        dist = model(data, mean_only=mean_only)
+        if not isinstance(dist, LowRankNormal2D):
+            raise NotImplementedError("validation_step: a model with `ssn` set must return a values_amd.hrnet.LowRankNormal2D (the 2D "
+                                      f"HighResolutionNet's SSN head), got {type(dist).__name__}")
+        ew, ed = eps if eps is not None else (None, None)
+        ss, ts = val_sums_ssn2d(dist, seg, n_aleatoric_samples, ew, ed, seed, 0, ce_ig)
+        loss, dice = ssn_loss_dice_from_sums(ss, ts, dist.num_classes, ignore_index)
     elif getattr(model, "aleatoric_loss", False):
         mu, s = model(data)
         if seed is None:
