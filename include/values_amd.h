@@ -1139,6 +1139,52 @@ int64_t vx_case_composite_workspace_bytes(int n_items, int n_labels);
 int vx_case_composite(const vx_composite_item* items /* host */, int n_items, const vx_composite_label* labels /* host */, int n_labels,
                       int32_t* status /* device [n_items] */, void* workspace, int64_t ws_bytes, vx_stream_t stream);
 
+/* A whole training (or validation) batch of the 3D datamodules from resident file payloads, in ONE launch
+ * (train_patches3d.hip; values_amd.datamodule3d.DeviceLoader3D): per item the crop of NumpyDataLoader
+ * (toy_datamodule_3D.py:479-499), batchgenerators' MirrorTransform and GaussianNoiseTransform and the float cast of
+ * NumpyToTensor, for the image and the drawn rater's label in the same pass.  Items mix cases, shapes and stored dtypes.
+ *   data[i][x][y][z] = float32(image[o0 + m0(x)][o1 + m1(y)][o2 + m2(z)]),  m_a(t) = P_a - 1 - t when bit a of flags is
+ *   set and t otherwise; the conversion is vx_gather_patches_3d's (numpy's astype(float32)).  With bit 3 set the value
+ *   becomes fmaf(sigma_i, vx_gauss(seed', r, index), value): r the flat index in the output patch, seed' = seed +
+ *   *seed_dev (nullable device word), sigma_i what vx_noise_view_3d derives for volume `index` from (var_lo, var_hi,
+ *   sigma_law) -- the same field, bit for bit, as vx_noise_view_3d over the noise-free patch with index0 = index.
+ *   THE REFERENCE ADDS ITS NOISE IN FLOAT64 BEFORE THE CAST TO FLOAT32; THIS CALL ADDS IT IN FLOAT32 AFTER THE CAST: at
+ *   most one float32 rounding apart.  The distribution is the reference's, the stream this project's.
+ *   seg[i] (nullable) = the same crop and mirror of the label as astype(intc) gives it, stored as float32 (seg_u8 == 0:
+ *   what NumpyToTensor(cast_to="float") leaves) or as its low byte (seg_u8 != 0); a label outside 0..255 is counted in
+ *   status[i] (device, zeroed by the call; integer atomics), read as vx_case_composite reads it (label_flags 0 |
+ *   VX_LABEL_SIGNED).  An item without a label (null) gets zeros in seg.  Without seg no label is read.
+ *   sigma_out (nullable, device [n_items]): sigma_i of the items with bit 3, 0 for the others.
+ *   Lanes run along z, four consecutive z per lane, one access of up to 16 bytes where the four elements lie inside the
+ *   row and the address is aligned to the access, element by element elsewhere; a z-mirror loads forward from the
+ *   mirrored source address and reverses the four elements in registers.  Plain C++ stores.  No byte outside a crop or
+ *   an output array is touched.  AN ITEM'S OUTPUT BYTES ARE EQUAL WHETHER IT IS SUBMITTED ALONE OR IN ANY BATCH, AT ANY
+ *   POSITION.  Traffic per item: P0*P1*P2 * (esize + 4) bytes, plus P0*P1*P2 * (label bytes + 4 or 1) with seg.
+ *   Refused before any device call: a null table, data, status, workspace or image (VX_E_NULL); n_items outside
+ *   [1, VX_SELECT_MAX_ITEMS], P or a dimension below 1, a crop not inside its volume, P0*P1*P2 >= 2^32, var_lo < 0 or
+ *   var_hi < var_lo (VX_E_SHAPE); an unknown image or label kind, flag bits above 3, label_flags other than 0 or
+ *   VX_LABEL_SIGNED, another sigma_law (VX_E_DTYPE); a pointer off its element alignment or a workspace off 16
+ *   (VX_E_ALIGN); a short workspace (VX_E_WORKSPACE).  A refused call writes nothing.  workspace:
+ *   vx_train_patches_3d_workspace_bytes(n_items) bytes, 0 for counts the call refuses.  The item table goes up through a
+ *   pinned staging buffer: no wait on the stream, not capturable into a hipGraph. */
+enum { VX_TRAIN3D_MIRROR0 = 1, VX_TRAIN3D_MIRROR1 = 2, VX_TRAIN3D_MIRROR2 = 4, VX_TRAIN3D_NOISE = 8 };
+typedef struct vx_train3d_item {
+  const void* image;   /* device [dims[0]][dims[1]][dims[2]] of image_kind VX_PREP_* */
+  const void* label;   /* device, same dims, or null */
+  int32_t image_kind;
+  int32_t label_kind;  /* VX_COUNT_B1 | B2 | B4 | B8 */
+  int32_t label_flags; /* 0 | VX_LABEL_SIGNED */
+  int32_t dims[3];
+  int32_t origin[3];
+  int32_t flags;       /* bits 0-2: mirror axis 0 / 1 / 2; bit 3: add noise */
+  uint32_t index;      /* global sample index: keys the noise stream */
+} vx_train3d_item;
+int64_t vx_train_patches_3d_workspace_bytes(int n_items);
+int vx_train_patches_3d(const vx_train3d_item* items /* host */, int n_items, int P0, int P1, int P2, float* data,
+                        void* seg /* nullable */, int seg_u8, uint32_t seed, const uint32_t* seed_dev, float var_lo, float var_hi,
+                        int sigma_law, float* sigma_out /* nullable [n_items] */, int32_t* status /* device [n_items] */,
+                        void* workspace, int64_t ws_bytes, vx_stream_t stream);
+
 /* Metric reductions behind calculate_test_metrics / calculate_ged (test_3D.py:250-358): see metrics.hip.
  * vx_mask_agreement: masks [M][nvox] uint8 labels < C; counts [M][M][C] uint64 (zeroed here),
  *   counts[i][j][c] = #{v: mask_i(v) == c and mask_j(v) == c}.  M <= 32, C <= 8.

@@ -12,4 +12,6 @@ from .preprocess2d import preprocess_dataset_2d, preprocess_images_device  # noq
 from .toydata import generate_toy_dataset  # noqa: F401
 from .stl import generate_toy_dataset_from_config  # noqa: F401
 from . import validation  # noqa: F401
-from .validation import validate, validation_step  # noqa: F401
+from .validation import validate, validate_split, validation_step  # noqa: F401
+from . import datamodule3d  # noqa: F401
+from .datamodule3d import DeviceLoader3D, HostLoader3D, LIDCDataModule3D, ToyDataModule3D  # noqa: F401

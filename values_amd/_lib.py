@@ -315,6 +315,17 @@ class Gather3dItem(C.Structure):
     _fields_ = [("src", _p), ("kind", _i32), ("dims", _i32 * 3), ("origin", _i32 * 3), ("reserved", _i32)]
 
 
+VX_TRAIN3D_MIRROR0, VX_TRAIN3D_MIRROR1, VX_TRAIN3D_MIRROR2, VX_TRAIN3D_NOISE = 1, 2, 4, 8
+
+
+class Train3dItem(C.Structure):
+    """vx_train3d_item: one sample of vx_train_patches_3d: image (VX_PREP_*) and label (VX_COUNT_B1 .. B8, flags 0 or
+    VX_LABEL_SIGNED; null: none) of one case, the crop's origin, flags (bits 0-2 mirror axis 0 / 1 / 2, bit 3 noise) and the
+    global sample index that keys the noise stream."""
+    _fields_ = [("image", _p), ("label", _p), ("image_kind", _i32), ("label_kind", _i32), ("label_flags", _i32),
+                ("dims", _i32 * 3), ("origin", _i32 * 3), ("flags", _i32), ("index", _u32)]
+
+
 class Acc3dItem(C.Structure):
     """vx_acc3d_item: the destination of one patch of vx_softmax_accumulate_cases: sum [T][C][X][Y][Z], count [X][Y][Z],
     dims = (X, Y, Z) and where the patch lands."""
@@ -430,6 +441,9 @@ SIGNATURES = {
                                      _p, _i64, _p]),
     "vx_gather_patches_3d_workspace_bytes": (_i64, [_i]),
     "vx_gather_patches_3d": (_i, [C.POINTER(Gather3dItem), _i, _p, _i, _i, _i, _p, _i64, _p]),
+    "vx_train_patches_3d_workspace_bytes": (_i64, [_i]),
+    "vx_train_patches_3d": (_i, [C.POINTER(Train3dItem), _i, _i, _i, _i, _p, _p, _i, _u32, _p, C.c_float, C.c_float, _i, _p, _p, _p,
+                                 _i64, _p]),
     "vx_softmax_accumulate_cases_workspace_bytes": (_i64, [_i]),
     "vx_softmax_accumulate_cases": (_i, [_p, _i, _i, _i, _i, _i, _i, C.POINTER(Acc3dItem), _i, _p, _i64, _p]),
     "vx_case_composite_workspace_bytes": (_i64, [_i, _i]),

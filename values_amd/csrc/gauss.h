@@ -28,6 +28,12 @@ __device__ __forceinline__ float vx_noise_var(uint32_t seed, uint32_t b, float l
   const float u2 = (float)(h2 >> 8) * (1.0f / 16777216.0f);           // [0, 1)
   return lo + (hi - lo) * u2;
 }
+// The scale itself, as vx_noise_view_3d (noise.hip) and vx_train_patches_3d (train_patches3d.hip) apply it to stream b:
+// sigma_law 0: sqrt(var), 1: var
+__device__ __forceinline__ float vx_noise_sigma(uint32_t seed, uint32_t b, float lo, float hi, int sigma_law) {
+  const float var = vx_noise_var(seed, b, lo, hi);
+  return sigma_law ? var : sqrtf(var);
+}
 
 // The label-switch decisions of the 2D test split (label_switch.hip): the h1 word of element r * n_switch + k of stream
 // `image index` of seed ^ VX_LSWITCH_XOR -- the same idiom, a constant of its own: no stream is shared with the dropout,

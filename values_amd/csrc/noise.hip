@@ -22,8 +22,7 @@ __global__ __launch_bounds__(256) void noise_view_3d_kernel(const float* x, floa
     const int v = (int)(i / per);
     const int64_t r = i - (int64_t)v * per;
     if (v != last) {            // one scale per volume: a thread meets a new volume once per `per` elements of its stride
-      const float var = vx_noise_var(s, index0 + (uint32_t)v, lo, hi);
-      sg = sigma_law ? var : sqrtf(var);
+      sg = vx_noise_sigma(s, index0 + (uint32_t)v, lo, hi, sigma_law);
       last = v;
     }
     if (sigma_out && r == 0) sigma_out[v] = sg;

@@ -35,6 +35,12 @@ TARGET_MAP = {
     "toy_datamodule_3D.get_val_test_data_samples": "values_amd.dataset3d.get_val_test_data_samples_toy",
     "uncertainty_modeling.lidc_idri_datamodule_3D.get_val_test_data_samples": "values_amd.dataset3d.get_val_test_data_samples_lidc",
     "lidc_idri_datamodule_3D.get_val_test_data_samples": "values_amd.dataset3d.get_val_test_data_samples_lidc",
+    # the 3D datamodules (uncertainty_modeling/configs/datamodule/case*_config.yaml, lidc_idri_config.yaml): train and
+    # validation loaders, host or device
+    "uncertainty_modeling.toy_datamodule_3D.ToyDataModule3D": "values_amd.datamodule3d.ToyDataModule3D",
+    "toy_datamodule_3D.ToyDataModule3D": "values_amd.datamodule3d.ToyDataModule3D",
+    "uncertainty_modeling.lidc_idri_datamodule_3D.LidcIdriDataModule3D": "values_amd.datamodule3d.LIDCDataModule3D",
+    "lidc_idri_datamodule_3D.LidcIdriDataModule3D": "values_amd.datamodule3d.LIDCDataModule3D",
 }
 
 

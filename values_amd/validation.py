@@ -296,3 +296,18 @@ def validate(model, batches: Iterable, **kw) -> Dict:
     for k in ("validation/val_loss", "validation/val_dice"):
         out[k] = float((np.array([p[k] for p in per]) * w).sum() / w.sum()) if per else float("nan")
     return out
+
+
+def validate_split(model, datamodule_or_loader, **kw) -> Dict:
+    """The validation epoch from a directory: validate() over the validation loader of a values_amd.datamodule3d
+    datamodule (its val_dataloader(); setup() must have run) or over a loader given as such.  A host loader's numpy
+    batches go to the model's device first."""
+    loader = datamodule_or_loader.val_dataloader() if hasattr(datamodule_or_loader, "val_dataloader") else datamodule_or_loader
+    dev = next(model.parameters()).device
+
+    def batches():
+        for b in loader:
+            data = b["data"] if isinstance(b["data"], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(b["data"])).to(dev)
+            yield data, b["seg"]
+
+    return validate(model, batches(), **kw)
