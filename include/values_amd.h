@@ -472,7 +472,10 @@ typedef struct vx_convT_args {
   int32_t N, D, H, W, Cin, Cout; /* input dims; output is 2D x 2H x 2W */
   int32_t act, drop_mode; uint32_t drop_seed, drop_layer; const uint8_t* drop_mask; /* mask [N][2D][2H][2W][Cout] */
   int32_t out_xblk, out_half; /* as in vx_norm_args: write half out_half of a concat buffer */
-  uint32_t* range_flag;       /* nullable: as in vx_conv3d_args (matrix-core kernels only: Cin in {16,32,64,128}) */
+  uint32_t* range_flag;       /* nullable: as in vx_conv3d_args.  Recorded by the matrix-core kernels (Cin in {16,32,64,128}) and
+                                 by the row-streaming kernel that takes Cin 16 / 32 past their decode bound; a launch that
+                                 vx_convT_k2s2_route sends to the generic kernel (any other Cin, or Cin 16 / 32 past the bound
+                                 with a Cout outside {8,16,32,64,128}) leaves the word alone */
   const uint32_t* seed_dev;   /* as in vx_conv3d_args */
 } vx_convT_args;
 int vx_convT_k2s2(const vx_convT_args* a, vx_stream_t stream);

@@ -411,8 +411,8 @@ def test_convT_split_fp16_reports_weights_and_outputs_past_the_fp16_range(vxcfg)
     big = wt.clone(); big[3, 5, 0, 1, 1] = 1.0e5                   # one weight past the fp16 range
     _, fl, _ = run(big, x)
     assert fl == float("inf"), fl
-    _, fl, _ = run(wt, x * 3.0e4)                                   # outputs past 32768, weights and inputs in range
-    assert 32768.0 <= fl < float("inf"), fl
+    out, fl, _ = run(wt, x * 3.0e4)                                 # outputs past 32768, weights and inputs in range
+    assert 32768.0 <= fl < float("inf") and fl == out.abs().max().item(), fl      # exactly the largest stored magnitude
     vxcfg.set(conv_fp32=1)
     out32, fl, kn = run(big, x)
     assert kn.startswith("convT_k2s2_mfma_kernel<64,"), kn

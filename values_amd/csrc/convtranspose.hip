@@ -101,6 +101,7 @@ __global__ __launch_bounds__(256) void convT_k2s2_rows_kernel(vx_convT_args a, i
     for (int ci = 0; ci < CIN; ++ci) wreg[ci] = *reinterpret_cast<const f32x4*>(wp + (size_t)ci * 2 * a.Cout);
   }
   const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bias + cq * 4);
+  float rmax = 0.f;   // range guard of the split-fp16 consumer (vx_convT_args.range_flag), as the tile kernels record it
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + tid; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     int64_t r = i;
     const int p = (int)(r % PW); r /= PW;
@@ -139,6 +140,12 @@ __global__ __launch_bounds__(256) void convT_k2s2_rows_kernel(vx_convT_args a, i
       for (int j = 0; j < 4; ++j) acc[j] = ((mk >> (8 * j)) & 0xFFu) ? 2.f * acc[j] : 0.f;
     }
     *reinterpret_cast<f32x4*>(convT_out_ptr(a, (size_t)(n * OD + oz) * OH + oy, ox, OW, cq * 4)) = acc;
+    rmax = fmaxf(fmaxf(rmax, fmaxf(fabsf(acc[0]), fabsf(acc[1]))), fmaxf(fabsf(acc[2]), fabsf(acc[3])));
+  }
+  if (a.range_flag) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, off, 64));
+    if ((tid & 63) == 0 && !(rmax < 32768.f)) atomicMax(a.range_flag, __float_as_uint(rmax));
   }
 }
 
